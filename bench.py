@@ -487,7 +487,12 @@ def main():
                     help="initialise the RCCL process group even at world size 1 (exercises the N>1 code path on one GPU)")
     ap.add_argument("--selftest-gloo", action="store_true",
                     help="CPU-only check of the multi-process harness (gloo, no model): each rank's step sleeps 10 ms x (rank+1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits of the last timed step as DIR/logits.npy (float32; rank r > 0: "
+                         "DIR/logits_rank<r>.npy); the inputs are seeded, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process becomes the PARENT -- it never touches the device -- and starts the N
@@ -561,6 +566,11 @@ def main():
         assert torch.equal(out[0], ref), "forward_async and model(x) disagree"
     assert torch.isfinite(out[0]).all()
     model.check_status()        # what only the device knows (the fused Mlp's stream-K hand-over record) fails the run here, not silently
+    if a.dump_outputs:          # what a caller of the timed path received from its last step: the logits [BATCH, 1000], 1 MB per rank
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "logits.npy" if rank == 0 else f"logits_rank{rank}.npy"),
+                out[0].detach().float().cpu().numpy())
     one_ms = 1e3 * timed_steps(step, a.steps, 2, dist, torch.cuda.synchronize, dev) / a.steps if IN_FLIGHT > 1 else None
     eager_ms = None
     if rank == 0 and not a.no_extra:          # the same forward as plain launches (model.use_graph = False): what the graph replay saves

@@ -1,11 +1,13 @@
 """The N>1 path of bench.py on CPU: world_size 2 over gloo through torch.distributed.run, exactly as the driver launches it
 (no model, no GPU: `--selftest-gloo` swaps the step for a rank-dependent sleep).  Checks the barrier + MAX-over-ranks timing and
-the whole-job aggregation of `value`."""
+the whole-job aggregation of `value`.  One GPU test: the `--dump-outputs` record of the headline path."""
 import json
 import os
 import socket
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -64,3 +66,22 @@ def test_self_launch_relays_a_failing_rank_as_a_non_zero_exit():
                          capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert out.returncode != 0
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")], out.stdout
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_step_logits_and_repeats(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's logits as float32 .npy, bit-identical across runs of the same seeded inputs whatever
+    --steps says (two builds are compared output for output on this file)."""
+    import numpy as np
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / f"s{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--no-extra", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert r["steps"] == steps
+        assert sorted(p.name for p in d.iterdir()) == ["logits.npy"]
+        dumps.append(np.load(d / "logits.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (256, 1000) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
