@@ -164,10 +164,13 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
   }
 }
 
-// Long sequences (256 < N <= 640: the 384^2 inputs, N = 577): K^T and V of a head no longer fit the LDS as fp32 (2 x 164 KB), so
+// Long sequences (256 < N <= 1088: the 384^2, 448^2 and 512^2 inputs, N = 577, 785, 1025): K^T and V of a head no longer fit the LDS as fp32 (2 x 164 KB), so
 // the same wave-per-query scheme reads K rows and V rows straight from global memory (they stay in L2: 2 x 148 KB per head).
-// Only the softmax row lives in LDS.  Same arithmetic and summation order as attention_f32_kernel.
+// Only the softmax row lives in LDS.  Same arithmetic and summation order as attention_f32_kernel.  CHUNKS = 64-key chunks per
+// lane: F32_LONG_CHUNKS up to 640 keys, F32_XL_CHUNKS up to 1088 (the 448^2 and 512^2 inputs, N = 785 and 1025).
 constexpr int F32_LONG_CHUNKS = 10;
+constexpr int F32_XL_CHUNKS = 17;
+template <int CHUNKS>
 __global__ __launch_bounds__(256) void attention_f32_long_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                  float* __restrict__ cls_rows, const float* __restrict__ size,
                                                                  float* __restrict__ colsum_part, int N, int H) {
@@ -181,16 +184,16 @@ __global__ __launch_bounds__(256) void attention_f32_long_kernel(const float* __
   const float* base = qkv + (size_t)b * N * ldq;
   const int qcol = h * 64, kcol = H * 64 + h * 64, vcol = 2 * H * 64 + h * 64;
   const int nkc = NP >> 6;
-  float colacc[F32_LONG_CHUNKS];
+  float colacc[CHUNKS];
 #pragma unroll
-  for (int c = 0; c < F32_LONG_CHUNKS; ++c) colacc[c] = 0.f;
+  for (int c = 0; c < CHUNKS; ++c) colacc[c] = 0.f;
   for (int q = wave; q < N; q += 4) {
     sQ[wave * 64 + lane] = base[(size_t)q * ldq + qcol + lane];
     __builtin_amdgcn_wave_barrier();
-    float s[F32_LONG_CHUNKS];
+    float s[CHUNKS];
     float mx = -INFINITY;
 #pragma unroll
-    for (int c = 0; c < F32_LONG_CHUNKS; ++c) {
+    for (int c = 0; c < CHUNKS; ++c) {
       s[c] = -INFINITY;
       if (c < nkc) {
         const int key = c * 64 + lane;
@@ -207,14 +210,14 @@ __global__ __launch_bounds__(256) void attention_f32_long_kernel(const float* __
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     float l = 0.f;
 #pragma unroll
-    for (int c = 0; c < F32_LONG_CHUNKS; ++c) {
+    for (int c = 0; c < CHUNKS; ++c) {
       s[c] = expf(s[c] - mx);
       l += s[c];
     }
     l = wave_sum(l);
     const float inv = 1.0f / l;
 #pragma unroll
-    for (int c = 0; c < F32_LONG_CHUNKS; ++c)
+    for (int c = 0; c < CHUNKS; ++c)
       if (c < nkc) {
         sP[wave * NP + c * 64 + lane] = s[c] * inv;
         colacc[c] += s[c] * inv;
@@ -225,7 +228,7 @@ __global__ __launch_bounds__(256) void attention_f32_long_kernel(const float* __
     out[((size_t)b * N + q) * (H * 64) + h * 64 + lane] = o;
     if (cls_rows != nullptr && q == 0) {
 #pragma unroll
-      for (int c = 0; c < F32_LONG_CHUNKS; ++c) {
+      for (int c = 0; c < CHUNKS; ++c) {
         const int key = c * 64 + lane;
         if (c < nkc && key < N) cls_rows[((size_t)b * H + h) * N + key] = s[c] * inv;
       }
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(256) void attention_f32_long_kernel(const float* __
   }
   if (colsum_part != nullptr) {
 #pragma unroll
-    for (int c = 0; c < F32_LONG_CHUNKS; ++c) {
+    for (int c = 0; c < CHUNKS; ++c) {
       const int key = c * 64 + lane;
       if (c < nkc && key < N) colsum_part[(((size_t)b * H + h) * 4 + wave) * N + key] = colacc[c];
     }
@@ -265,12 +268,18 @@ extern "C" int tr_gemm_f32(const float* A, const float* W, const float* bias, fl
 extern "C" int tr_attention_f32(const float* qkv, float* out, float* cls_rows, const float* size, float* colsum_part, int B, int N,
                                 int H, tr_stream_t s) {
   TR_REQUIRE(qkv && out, TR_ERR_NULL, "tr_attention_f32: null pointer");
-  TR_REQUIRE(B > 0 && H > 0 && N >= 1 && N <= 64 * F32_LONG_CHUNKS, TR_ERR_SHAPE, "tr_attention_f32: need 1 <= N <= %d (N=%d)", 64 * F32_LONG_CHUNKS, N);
+  TR_REQUIRE(B > 0 && H > 0 && N >= 1 && N <= 64 * F32_XL_CHUNKS, TR_ERR_SHAPE, "tr_attention_f32: need 1 <= N <= %d (N=%d)", 64 * F32_XL_CHUNKS, N);
   const int NP = (N + 63) & ~63;
   hipStream_t st = static_cast<hipStream_t>(s);
+  if (N > 64 * F32_LONG_CHUNKS) {
+    const size_t lds_xl = (size_t)(4 * 64 + 4 * NP) * sizeof(float);     // 19 KB at N = 1088
+    hipLaunchKernelGGL(attention_f32_long_kernel<F32_XL_CHUNKS>, dim3(B * H), dim3(256), lds_xl, st, qkv, out, cls_rows, size, colsum_part, N, H);
+    TR_CHECK_LAUNCH("tr_attention_f32_long");
+    return TR_OK;
+  }
   if (N > 256) {
     const size_t lds_long = (size_t)(4 * 64 + 4 * NP) * sizeof(float);
-    hipLaunchKernelGGL(attention_f32_long_kernel, dim3(B * H), dim3(256), lds_long, st, qkv, out, cls_rows, size, colsum_part, N, H);
+    hipLaunchKernelGGL(attention_f32_long_kernel<F32_LONG_CHUNKS>, dim3(B * H), dim3(256), lds_long, st, qkv, out, cls_rows, size, colsum_part, N, H);
     TR_CHECK_LAUNCH("tr_attention_f32");
     return TR_OK;
   }

@@ -502,7 +502,8 @@ __global__ __launch_bounds__(SKT) void sinkhorn_kernel(const float* __restrict__
 // per image with one thread walking all tokens of a centre: 1384 us at B = 64, K = 144, P = 576 -- a quarter of the 384^2 forward.
 constexpr int SGT = 1024;
 constexpr int SG_KMAX = 640;                 // centres the wide instantiation holds per token row (K = 518 at 384 x 384, keep_rate 0.9)
-// KC: 64-centre groups a lane holds of one token row in the v-step (4: K <= 256, every registered model; 10: K <= 640)
+constexpr int SG_XL_KMAX = 1024;             // the widest (K = 921 at 512 x 512, keep_rate 0.9); one u-step segment: nseg = SGT / KW = 1
+// KC: 64-centre groups a lane holds of one token row in the v-step (4: K <= 256, every registered model; 10: K <= 640; 16: K <= 1024)
 template <int KC>
 __global__ __launch_bounds__(SGT) void sinkhorn_global_kernel(const float* __restrict__ scores, int ldl, float eps, int iters,
                                                               float* __restrict__ wt, float* __restrict__ soft, int N, int K) {
@@ -561,18 +562,19 @@ __global__ __launch_bounds__(SGT) void sinkhorn_global_kernel(const float* __res
       s_u[kc] = norm - (m + logf(tt));
     }
     __syncthreads();
-    // ---- v = log_nu - logsumexp_k(Z + u): wave per token row, four rows per step
-    for (int p0 = wave * 4; p0 < P; p0 += (SGT / 64) * 4) {
-      float z[4][KC];
+    // ---- v = log_nu - logsumexp_k(Z + u): wave per token row, RW rows per step (four; two at KC = 16, which spilled with four)
+    constexpr int RW = KC > 10 ? 2 : 4;
+    for (int p0 = wave * RW; p0 < P; p0 += (SGT / 64) * RW) {
+      float z[RW][KC];
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < RW; ++r)
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
           const int k = lane + 64 * c;
           z[r][c] = sc[(size_t)min(p0 + r, P - 1) * ldl + min(k, K - 1)];
         }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < RW; ++r) {
         float mm = -INFINITY;
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
@@ -845,9 +847,14 @@ extern "C" int tr_sinkhorn(const float* scores, int ldl, float eps, int iters, f
       TR_CHECK_LAUNCH("tr_sinkhorn");
       return TR_OK;
     }
-    TR_REQUIRE(K <= SG_KMAX, TR_ERR_SHAPE, "tr_sinkhorn: K=%d > %d centres with K*P beyond the LDS is not supported", K, SG_KMAX);
+    TR_REQUIRE(K <= SG_XL_KMAX, TR_ERR_SHAPE, "tr_sinkhorn: K=%d > %d centres with K*P beyond the LDS is not supported", K, SG_XL_KMAX);
     const int kw = (K + 63) & ~63;
     const size_t lds_g = ((size_t)K + (N - 1) + (size_t)(SGT / kw) * kw) * sizeof(float);
+    if (K > SG_KMAX) {
+      hipLaunchKernelGGL(sinkhorn_global_kernel<SG_XL_KMAX / 64>, dim3(B), dim3(SGT), lds_g, st, scores, ldl, eps, iters, wt, soft, N, K);
+      TR_CHECK_LAUNCH("tr_sinkhorn_xl");
+      return TR_OK;
+    }
     if (K <= 256) hipLaunchKernelGGL(sinkhorn_global_kernel<4>, dim3(B), dim3(SGT), lds_g, st, scores, ldl, eps, iters, wt, soft, N, K);
     else hipLaunchKernelGGL(sinkhorn_global_kernel<SG_KMAX / 64>, dim3(B), dim3(SGT), lds_g, st, scores, ldl, eps, iters, wt, soft, N, K);
     TR_CHECK_LAUNCH("tr_sinkhorn");

@@ -3,7 +3,7 @@
 //   tr_tome_match             bipartite_soft_matching (tome.py:230-277, class_token=True) on metric = k.mean(1) (tome.py:58):
 //                             cosine scores between even- and odd-position tokens, row max/argmax, descending rank of the
 //                             row maxima, split into merged (src -> dst) and unmerged tokens.  One workgroup per image; the
-//                             whole problem (<= 113 x 112 x 64 MACs) lives in LDS, scores in 4x4 register tiles.  Integer outputs; ties: row argmax ->
+//                             whole problem lives in LDS up to 600 tokens (above: the odd rows in LDS, the even rows streamed), scores in 4x4 register tiles.  Integer outputs; ties: row argmax ->
 //                             first index (torch CPU max), rank -> lowest index first (torch's argsort order is unspecified).
 //   tr_tome_merge_layernorm   merge_wavg (tome.py:309-323): x = merge(x*size) / merge(size), size = merge(size), with the
 //                             pending residual add (x + attn.proj output, tome.py:84) in front and norm2 (tome.py:101) behind,
@@ -17,6 +17,8 @@
 namespace {
 
 constexpr int TOME_MAX_N = 600;      // tokens incl. CLS: 197 at 224^2 inputs, 577 at 384^2 (metric rows live in LDS: N*65 floats)
+constexpr int TOME_LONG_MAX_N = 1025;   // 1024 patch tokens + CLS (512^2): only the odd rows stay in LDS, the even rows stream through
+constexpr int TOME_LONG_ACH = 64;       // even (a) rows per streamed chunk: (512 + 64) * 65 floats + 6.7 KB of keys = 153 KB at N = 1025
 constexpr int MST = 65;              // metric row stride in floats (odd: conflict-free column walks)
 
 // order-preserving map float -> uint32 (a < b  <=>  key(a) < key(b)), so (score, lowest j) maxima reduce with one ds_max_u64
@@ -43,22 +45,25 @@ __device__ __forceinline__ void head_sum_bf16(const uint16_t* kp, int H, float* 
 }
 
 constexpr int TMT = 1024;   // 16 waves per image: the kernel is a chain of short latency-bound phases, one workgroup per CU
-template <bool F32>
+// LONG = false: all N metric rows in LDS (N <= TOME_MAX_N).  LONG = true (N <= TOME_LONG_MAX_N): the nb odd rows in LDS, the even rows
+// computed TOME_LONG_ACH at a time into a chunk behind them; each pair's score is the same arithmetic on the same metric values.
+template <bool F32, bool LONG>
 __global__ __launch_bounds__(TMT) void tome_match_kernel(const void* __restrict__ qkv, int32_t* __restrict__ unm_idx,
                                                          int32_t* __restrict__ src_idx, int32_t* __restrict__ dst_idx, int N, int H,
                                                          int r) {
   extern __shared__ __attribute__((aligned(16))) float s_m[];      // [N][MST], dynamic: 50 KB at N = 197, 150 KB at N = 577
-  __shared__ unsigned long long s_key[(TOME_MAX_N + 1) / 2];
-  __shared__ int s_edge[(TOME_MAX_N + 1) / 2];
-  __shared__ unsigned char s_unm[(TOME_MAX_N + 1) / 2];
+                                                                   // LONG: [nb + TOME_LONG_ACH][MST], odd rows then the even chunk
+  constexpr int KMAX = ((LONG ? TOME_LONG_MAX_N : TOME_MAX_N) + 1) / 2;
+  __shared__ unsigned long long s_key[KMAX];
+  __shared__ int s_edge[KMAX];
+  __shared__ unsigned char s_unm[KMAX];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int na = (N + 1) >> 1, nb = N >> 1;
   const int ldq = 3 * H * 64;
   // metric = mean over heads of K (post-bias), then metric / metric.norm(dim=-1)  (tome.py:58, :255).  One 8-wide chunk of a
   // token per lane (16-B loads for bf16), head sum sequential in fp32 like a strided torch mean; the 8 lanes of a token
   // share the sum of squares through the wave.
-  for (int item = tid; item < N * 8; item += TMT) {
-    const int n = item >> 3, c = item & 7;
+  auto metric = [&](int n, int c, float* dst) {
     float m[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) m[k] = 0.f;
@@ -107,10 +112,18 @@ __global__ __launch_bounds__(TMT) void tome_match_kernel(const void* __restrict_
       nrm = sqrtf(ss);
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s_m[n * MST + c * 8 + k] = m[k] / nrm;
+    for (int k = 0; k < 8; ++k) dst[c * 8 + k] = m[k] / nrm;
+  };
+  if constexpr (!LONG) {
+    for (int item = tid; item < N * 8; item += TMT) metric(item >> 3, item & 7, s_m + (item >> 3) * MST);
+  } else {
+    for (int item = tid; item < nb * 8; item += TMT) metric(2 * (item >> 3) + 1, item & 7, s_m + (item >> 3) * MST);
   }
   for (int i = tid; i < na; i += TMT) s_key[i] = score_key(-INFINITY, 0);    // row 0 (CLS) stays -inf: never merged (tome.py:259)
   __syncthreads();
+  // b row j; a rows ia0 <= i < ia1 through arow(i)
+  auto brow = [&](int j) -> const float* { return LONG ? s_m + (size_t)j * MST : s_m + (size_t)(2 * j + 1) * MST; };
+  auto scores = [&](int ia0, int ia1, auto arow) {
   if (!F32) {
     // scores[i][j] = a_i . b_j (a = even tokens, b = odd tokens) on the matrix cores with FP32 OPERANDS (v_mfma_f32_16x16x4_f32: exact
     // fp32 products, fp32 accumulation -- the precision class of the fmaf chain it replaces, NOT a bf16 product): one 16 x 16 tile of the
@@ -120,11 +133,11 @@ __global__ __launch_bounds__(TMT) void tome_match_kernel(const void* __restrict_
     // order-preserving (score, lowest j) key with DPP, one ds_max_u64 per row and tile.
     const int lane = tid & 63, wave = tid >> 6;
     const int il = lane & 15, kq = lane >> 4;
-    const int nbi = (na + 15) >> 4, nbj = (nb + 15) >> 4;
+    const int nbi = (ia1 - ia0 + 15) >> 4, nbj = (nb + 15) >> 4;
     for (int t = wave; t < nbi * nbj; t += TMT / 64) {
-      const int i0 = (t / nbj) * 16, j0 = (t % nbj) * 16;
-      const float* ap = s_m + (size_t)(2 * min(i0 + il, na - 1)) * MST + kq;          // MFMA A: row i0 + il, k = 4 ks + kq
-      const float* bp = s_m + (size_t)(2 * min(j0 + il, nb - 1) + 1) * MST + kq;      // MFMA B: column j0 + il
+      const int i0 = ia0 + (t / nbj) * 16, j0 = (t % nbj) * 16;
+      const float* ap = arow(min(i0 + il, ia1 - 1)) + kq;          // MFMA A: row i0 + il, k = 4 ks + kq
+      const float* bp = brow(min(j0 + il, nb - 1)) + kq;           // MFMA B: column j0 + il
       // all 32 fragment values first (one LDS round trip per tile, not one per MFMA), then two independent accumulator chains
       float av[16], bv[16];
 #pragma unroll
@@ -155,22 +168,22 @@ __global__ __launch_bounds__(TMT) void tome_match_kernel(const void* __restrict_
           key = other > key ? other : key;
         }
         const int i = i0 + 4 * kq + e;
-        if (il == 0 && i > 0 && i < na) atomicMax(&s_key[i], key);
+        if (il == 0 && i > 0 && i < ia1) atomicMax(&s_key[i], key);
       }
     }
   } else {
   // scores[i][j] = a_i . b_j (a = even tokens, b = odd tokens) in 4x4 register tiles, rows/columns STRIDED over the tile grid
     // (i = ti + nti*ii, j = tj + ntj*jj) so the lanes of a wave read consecutive b rows (conflict-free, a rows broadcast);
     // row max/argmax (ties -> lowest j, torch's CPU max) through ds_max_u64 on an order-preserving (score, ~j) key
-    const int nti = (na + 3) >> 2, ntj = (nb + 3) >> 2;
+    const int nti = (ia1 - ia0 + 3) >> 2, ntj = (nb + 3) >> 2;
     for (int t = tid; t < nti * ntj; t += TMT) {
       const int ti = t / ntj, tj = t - ti * ntj;
       const float* ap[4];
       const float* bp[4];
   #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        ap[q] = s_m + (size_t)(2 * min(ti + nti * q, na - 1)) * MST;
-        bp[q] = s_m + (size_t)(2 * min(tj + ntj * q, nb - 1) + 1) * MST;
+        ap[q] = arow(min(ia0 + ti + nti * q, ia1 - 1));
+        bp[q] = brow(min(tj + ntj * q, nb - 1));
       }
       float best[4];
       int arg[4];
@@ -227,9 +240,22 @@ __global__ __launch_bounds__(TMT) void tome_match_kernel(const void* __restrict_
       }
   #pragma unroll
       for (int ii = 0; ii < 4; ++ii) {
-        const int i = ti + nti * ii;
-        if (i > 0 && i < na) atomicMax(&s_key[i], score_key(best[ii], arg[ii]));
+        const int i = ia0 + ti + nti * ii;
+        if (i > 0 && i < ia1) atomicMax(&s_key[i], score_key(best[ii], arg[ii]));
       }
+    }
+  }
+  };
+  if constexpr (!LONG) {
+    scores(0, na, [&](int i) -> const float* { return s_m + (size_t)(2 * i) * MST; });
+  } else {
+    float* s_a = s_m + (size_t)nb * MST;
+    for (int ia0 = 0; ia0 < na; ia0 += TOME_LONG_ACH) {
+      const int ia1 = min(na, ia0 + TOME_LONG_ACH);
+      for (int item = tid; item < (ia1 - ia0) * 8; item += TMT) metric(2 * (ia0 + (item >> 3)), item & 7, s_a + (item >> 3) * MST);
+      __syncthreads();
+      scores(ia0, ia1, [&](int i) -> const float* { return s_a + (size_t)(i - ia0) * MST; });
+      __syncthreads();                                                // the next chunk overwrites s_a
     }
   }
   __syncthreads();
@@ -369,17 +395,29 @@ __global__ __launch_bounds__(256) void tome_merge_layernorm_kernel(const float* 
 extern "C" int tr_tome_match(const void* qkv, int qkv_is_f32, int32_t* unm_idx, int32_t* src_idx, int32_t* dst_idx, int B, int N,
                              int H, int r, tr_stream_t s) {
   TR_REQUIRE(qkv && unm_idx && src_idx && dst_idx, TR_ERR_NULL, "tr_tome_match: null pointer");
-  TR_REQUIRE(B > 0 && H > 0 && N >= 3 && N <= TOME_MAX_N, TR_ERR_SHAPE, "tr_tome_match: need 3 <= N <= %d (N=%d)", TOME_MAX_N, N);
+  TR_REQUIRE(B > 0 && H > 0 && N >= 3 && N <= TOME_LONG_MAX_N, TR_ERR_SHAPE, "tr_tome_match: need 3 <= N <= %d (N=%d)", TOME_LONG_MAX_N, N);
   TR_REQUIRE(r >= 1 && r <= (N - 1) / 2, TR_ERR_SHAPE, "tr_tome_match: r=%d must be in [1, (N-1)/2] for N=%d (tome.py:253)", r, N);
   TR_REQUIRE(tr_aligned16(qkv), TR_ERR_ALIGN, "tr_tome_match: qkv must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(s);
+  if (N > TOME_MAX_N) {
+    const size_t lds = (size_t)(N / 2 + TOME_LONG_ACH) * MST * sizeof(float);
+    if (qkv_is_f32) {
+      TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<true, true>), lds, "tr_tome_match");
+      hipLaunchKernelGGL((tome_match_kernel<true, true>), dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
+    } else {
+      TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<false, true>), lds, "tr_tome_match");
+      hipLaunchKernelGGL((tome_match_kernel<false, true>), dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
+    }
+    TR_CHECK_LAUNCH("tr_tome_match_long");
+    return TR_OK;
+  }
   const size_t lds = (size_t)N * MST * sizeof(float);
   if (qkv_is_f32) {
-    TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<true>), lds, "tr_tome_match");
-    hipLaunchKernelGGL(tome_match_kernel<true>, dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
+    TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<true, false>), lds, "tr_tome_match");
+    hipLaunchKernelGGL((tome_match_kernel<true, false>), dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
   } else {
-    TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<false>), lds, "tr_tome_match");
-    hipLaunchKernelGGL(tome_match_kernel<false>, dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
+    TR_RESERVE_LDS(reinterpret_cast<const void*>(tome_match_kernel<false, false>), lds, "tr_tome_match");
+    hipLaunchKernelGGL((tome_match_kernel<false, false>), dim3(B), dim3(TMT), lds, st, qkv, unm_idx, src_idx, dst_idx, N, H, r);
   }
   TR_CHECK_LAUNCH("tr_tome_match");
   return TR_OK;

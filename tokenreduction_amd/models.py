@@ -13,7 +13,8 @@ them: it hands the image batch to the gfx950 executor (csrc/tr_vit.hip) through 
 There is no CPU path: forward() on a CPU tensor raises.  In train mode forward() runs the training executor
 (activations kept on a tape) and `loss.backward()` runs the HIP backward executor (training.py) -- every family and
 every factory width, 224 x 224 and 384 x 384; what the training path refuses (attn_drop_rate, the distillation token,
-more than 640 tokens) raises there.
+more than 640 tokens) raises there.  In eval mode every family runs at up to 1024 patch tokens + CLS (448 x 448 and 512 x 512
+inputs) in all three precisions; more tokens raise.
 """
 from __future__ import annotations
 
