@@ -9,8 +9,13 @@
 A "step" = one pass of the hot path (model.forward through the native executor) over one synthetic batch of
 256 images already resident in HBM (BASELINE.json configs[1]).  Data-parallel inference shards images over
 ranks with no data-path collective: every rank runs its own batch of 256 -> weak scaling.
-Rank 0 prints ONE JSON line.  Extra legs (rank 0, N=1 only, outside the timed region):
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm up, time the K steps,
+write --dump-outputs, print.  --full adds the extra legs, all outside the timed region:
+  the forward_async == model(x) check, the same forward one at a time and as plain launches
+  finetune      fwd + bwd + AdamW through the HIP training path (every rank: the legs contain the gradient collectives)
+and at N=1 on rank 0:
   roofline      per-launch HIP-event timing of the same forward, kernel by kernel, on the launch stream
+  other_configs, per_config, drift_vs_fp32_path, drift_trained, bf16x3_mode
   cpu_baseline  the oracle (fp32 torch-CPU restatement of the reference) timed on this box's host cores
 """
 import argparse
@@ -482,7 +487,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-extra", action="store_true", help="skip the roofline / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the extra legs (one-at-a-time and plain-launch timings, forward_async check, fine-tune, "
+                         "roofline, other configs, drift, cpu_baseline); a plain run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs even with --full (a run without --full has none)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even at world size 1 (exercises the N>1 code path on one GPU)")
     ap.add_argument("--selftest-gloo", action="store_true",
@@ -493,6 +501,7 @@ def main():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    extra = a.full and not a.no_extra
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process becomes the PARENT -- it never touches the device -- and starts the N
@@ -562,8 +571,9 @@ def main():
     el = timed_steps(step_in_flight if IN_FLIGHT > 1 else step, a.steps, a.warmup, dist, torch.cuda.synchronize, dev)
     if pend:
         out[0] = pend[-1].result()
-        ref = model(x)                       # the same batch, one forward at a time: the pipelined steps computed the same bits
-        assert torch.equal(out[0], ref), "forward_async and model(x) disagree"
+        if extra:
+            ref = model(x)                   # the same batch, one forward at a time: the pipelined steps computed the same bits
+            assert torch.equal(out[0], ref), "forward_async and model(x) disagree"
     assert torch.isfinite(out[0]).all()
     model.check_status()        # what only the device knows (the fused Mlp's stream-K hand-over record) fails the run here, not silently
     if a.dump_outputs:          # what a caller of the timed path received from its last step: the logits [BATCH, 1000], 1 MB per rank
@@ -571,9 +581,9 @@ def main():
         os.makedirs(a.dump_outputs, exist_ok=True)
         np.save(os.path.join(a.dump_outputs, "logits.npy" if rank == 0 else f"logits_rank{rank}.npy"),
                 out[0].detach().float().cpu().numpy())
-    one_ms = 1e3 * timed_steps(step, a.steps, 2, dist, torch.cuda.synchronize, dev) / a.steps if IN_FLIGHT > 1 else None
+    one_ms = 1e3 * timed_steps(step, a.steps, 2, dist, torch.cuda.synchronize, dev) / a.steps if IN_FLIGHT > 1 and extra else None
     eager_ms = None
-    if rank == 0 and not a.no_extra:          # the same forward as plain launches (model.use_graph = False): what the graph replay saves
+    if rank == 0 and extra:                   # the same forward as plain launches (model.use_graph = False): what the graph replay saves
         model.use_graph = False
         eager_ms = 1e3 * timed_steps(step, a.steps, 2, None, torch.cuda.synchronize, dev) / a.steps
         model.use_graph = True
@@ -590,7 +600,7 @@ def main():
         dist.all_gather(seen, me)
         headline["dp"] = {"world": dist.get_world_size(), "backend": dist.get_backend(),
                           "cuda_device_by_rank": {str(int(v[0])): int(v[1]) for v in seen}}
-    if not a.no_extra:
+    if extra:
         import threading
         done = threading.Event()
 
@@ -623,7 +633,7 @@ def main():
         rec = headline_record(a, world, headline, eager_ms)
         if finetune is not None:
             rec["finetune"] = finetune
-        if world == 1 and not a.no_extra:
+        if world == 1 and extra:
             for label, name, kr, loc, bsz in (("deit_small dense B=256 (fwd+bwd+AdamW)", "deit_small_patch16_224_local", [1.0], [], 256),
                                               ("evit_small kr0.7 B=256 (fwd+bwd+AdamW)", "evit_small_patch16_224", [0.7], [3, 6, 9], 256),
                                               ("tome_small r16 B=256 (fwd+bwd+AdamW)", "tome_small_patch16_224",

@@ -85,3 +85,21 @@ def test_dump_outputs_writes_the_last_step_logits_and_repeats(tmp_path):
         dumps.append(np.load(d / "logits.npy"))
     assert dumps[0].dtype == np.float32 and dumps[0].shape == (256, 1000) and np.isfinite(dumps[0]).all()
     assert np.array_equal(dumps[0], dumps[1])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_without_the_extra_legs():
+    """Without --full the run only sets up, warms up, times the steps and prints: the headline fields are there, the legs of --full are
+    not (they would cost minutes outside the timed steps)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["unit"] == "images/s" and r["higher_is_better"] is True and r["dtype"] == "bf16" and r["steps"] == 2, r
+    assert r["value"] > 0 and abs(r["value"] - 256 / (r["ms_per_step"] * 1e-3)) / r["value"] < 0.01, r
+    extras = ("finetune", "roofline", "kernels", "cpu_baseline", "other_configs", "per_config", "drift_vs_fp32_path", "drift_trained",
+              "bf16x3_mode", "dense_deit_s_images_per_s")
+    assert not [k for k in extras if k in r], r
+    assert r["ms_per_step_one_in_flight"] is None and r["ms_per_step_plain_launches"] is None, r

@@ -77,7 +77,7 @@ def test_two_ranks_average_their_hip_gradients(tmp_path, case, algo, comm):
 
 @pytest.mark.gpu
 def test_bench_runs_its_two_rank_path_on_one_gpu(tmp_path):
-    """`python bench.py --gpus 2` (self-launching; the watchdog test below uses the driver's torch.distributed.run form) with both ranks on the box's one GPU
+    """`python bench.py --gpus 2 --full` (self-launching; the watchdog test below uses the driver's torch.distributed.run form) with both ranks on the box's one GPU
     (TR_BENCH_SHARE_GPU=1: gloo collectives): the headline line and all three data-parallel fine-tune legs must come out."""
     import json
     import torch
@@ -87,7 +87,7 @@ def test_bench_runs_its_two_rank_path_on_one_gpu(tmp_path):
     # GPU) starts the ranks itself and relays rank 0's line
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TR_BENCH_SHARE_GPU="1", TR_BENCH_FINETUNE_STEPS="2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -116,7 +116,8 @@ def test_bench_watchdog_ends_a_hung_run_non_zero():
         pytest.skip("needs a GPU")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", TR_BENCH_SHARE_GPU="1", TR_BENCH_FINETUNE_STEPS="2", TR_BENCH_FINETUNE_TIMEOUT="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29647", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                          "--master-port", "29647", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                          "--full"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode != 0, out.stdout[-1500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
