@@ -163,6 +163,12 @@ int tr_layernorm_bf16_to(const float* x, long ldx, float* x_out, long ldxo, cons
  * tr_layernorm_bf16 calls, 22 instead of 24 bytes per element and block. */
 int tr_layernorm2_bf16(const float* x, long ldx, float* x_out, long ldxo, const uint16_t* delta, long ldd, const uint16_t* delta2, long ldd2,
                        const float* gamma, const float* beta, uint16_t* y, int M, int D, float eps, tr_stream_t s);
+/* The three bf16-path norms above with the output stored as fp32 rows y [M,D]: y = LayerNorm((x + delta) + delta2), delta and delta2
+ * nullable (delta2 needs delta), the sum written to x_out (x_out == x: in place; NULL: not written).  Same statistics, same summation order,
+ * same arithmetic -- only the final store differs, so bf16(y) is bit for bit what tr_layernorm_bf16 / _bf16_to / tr_layernorm2_bf16 store.
+ * The final norm of a headless model (tr_vit_config.num_classes == 0), whose fp32 CLS features are the output. */
+int tr_layernorm_bf16_f32(const float* x, long ldx, float* x_out, long ldxo, const uint16_t* delta, long ldd, const uint16_t* delta2,
+                          long ldd2, const float* gamma, const float* beta, float* y, int M, int D, float eps, tr_stream_t s);
 
 /* out[i] = x[i] + delta[i] for n elements (delta nullable; bf16, fp32 when delta_is_f32): the residual stream after a block as
  * the reference's viz_data["Features"] records it (topk.py:197) -- x itself absorbs the pending mlp output only in the next norm. */
@@ -536,7 +542,7 @@ typedef struct {
   const void* patch_w; const float* patch_b;     /* [D, C*p*p], [D] */
   const float* cls_token; const float* pos_embed;/* [D], [(P+1), D] fp32 */
   const float* norm_g; const float* norm_b;
-  const void* head_w; const float* head_b;       /* [classes, D], [classes] */
+  const void* head_w; const float* head_b;       /* [classes, D], [classes]; NULL (not read) when num_classes == 0 */
   tr_block_weights blocks[TR_MAX_DEPTH];
   tr_stage_weights stage[TR_MAX_DEPTH];          /* indexed by BLOCK; read only where keep[blk] > 0 (DyViT, SiT) */
 } tr_vit_weights;
@@ -544,7 +550,8 @@ typedef struct {
 typedef struct {
   int family;                 /* TR_FAMILY_* */
   int img_size, patch, in_chans;
-  int embed_dim, depth, num_heads, mlp_hidden, num_classes;
+  int embed_dim, depth, num_heads, mlp_hidden, num_classes;   /* num_classes == 0: headless (no classifier; the output is the
+                                                                  final-normed CLS row, see tr_vit_forward) */
   float ln_eps;
   int keep[TR_MAX_DEPTH];     /* per block, 0 = plain block.  Top-K/EViT/DyViT: K patch tokens kept; ToMe: r tokens merged
                                  away; SiT: K output tokens of the slimming module */
@@ -579,7 +586,10 @@ size_t tr_vit_workspace_bytes(const tr_vit_config* cfg, int B);
  * it where the logits are consumed. */
 int tr_vit_forward_status(const tr_vit_config* cfg, void* workspace, size_t workspace_bytes, int B, tr_stream_t s);
 
-/* img fp32 [B,C,S,S] -> logits fp32 [B,classes].  kept_idx (nullable): device int32 slab of depth*B*(P+1) entries;
+/* img fp32 [B,C,S,S] -> logits fp32 [B,classes].  Headless (num_classes == 0, deit_viz.py:142,182: head = nn.Identity()): `logits` is
+ * fp32 [B,D] and receives pre_logits(norm(x)[:, 0]), the final-normed CLS row; no classifier GEMM runs and w->head_w / head_b may be NULL.
+ * In bf16 the row is the final norm's output before its bf16 rounding (tr_layernorm_bf16_f32): bf16(features) is the classifier's operand.
+ * kept_idx (nullable): device int32 slab of depth*B*(P+1) entries;
  * reduction block blk writes its contiguous [B,K_blk] idx array at offset blk*B*(P+1) (Kept_Tokens, topk.py:196); ToMe
  * writes [unm_idx | src_idx | dst_idx] there ([B,na-r], [B,r], [B,r] back to back).  The slab holds depth*B*(P+1) entries.
  * compl_idx (nullable, EViT): same slab shape, block blk writes [B,P_in-K_blk] at offset blk*B*(P+1)
@@ -602,7 +612,8 @@ int tr_vit_forward(const tr_vit_config* cfg, const tr_vit_weights* w, const floa
  *   bytes, caller-owned; 0 = family / precision without a training path).  drop_scale (nullable, both calls get the same): DropPath
  *   (timm 0.4.12 drop_path, topk.py:78,87,95) as fp32 [2*depth, B]: entry [2i][b] / [2i+1][b] = the scale (0 or 1/keep_prob) of
  *   image b's attention / MLP branch in block i -- the random draw is the caller's.  Dropout: see below.
- * tr_vit_backward: dlogits fp32 [B,classes] -> parameter gradients.  `w` = the forward's weights; `wt` = same struct with the block
+ * tr_vit_backward: dlogits fp32 [B,classes] -> parameter gradients.  Headless (num_classes == 0): the forward's `logits` are the CLS features
+ *   fp32 [B,D], `dlogits` is their gradient fp32 [B,D], no classifier gradient is computed and grads->head_w / head_b may be NULL.  `w` = the forward's weights; `wt` = same struct with the block
  *   matrices TRANSPOSED (bf16: qkv_w [D,3D], proj_w [D,D], fc1_w [D,Hd], fc2_w [Hd,D]); `grads` = same struct, every pointer an
  *   fp32 buffer of the parameter's shape (written; added to when accumulate != 0).  workspace: tr_vit_backward_workspace_bytes.
  *   [blk_hi .. blk_lo]: the blocks this call walks, in reverse; blk_hi == depth-1 runs the classifier + final norm first, blk_lo == 0

@@ -17,7 +17,9 @@ namespace {
 // written back.  Together they let the eval executor skip the stream write of a norm2 that no reduction follows: norm2 reads
 // x + d_attn without storing it, the next norm1 reads x + d_attn + d_mlp (same fp32 additions in the same order: bit-identical) and
 // writes the stream once -- 22 instead of 24 bytes per element and block.
-template <bool F32, int NCH>
+// OUT32 (with F32 == false): the bf16 path's arithmetic, y stored as fp32 rows -- the final norm of a headless model (num_classes == 0),
+// whose features are the output; bf16(y) is bit for bit what the bf16 form stores.
+template <bool F32, int NCH, bool OUT32 = F32>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, long ldx, float* x_out, long ldxo, const void* __restrict__ delta, long ldd,
                                                         const uint16_t* __restrict__ delta2, long ldd2, int write_x,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -58,18 +60,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, long ldx
         if (write_x) ln_nt_store4(v[c], xo + 4 * (lane + 64 * c));
       }
   }
-  ln_row_store<F32, NCH>(v, nchunks, lane, D, eps, gamma, beta,
-                    F32 ? (void*)(reinterpret_cast<float*>(y) + (size_t)row * D) : (void*)(reinterpret_cast<uint16_t*>(y) + (size_t)row * D));
+  ln_row_store<F32, NCH, OUT32>(v, nchunks, lane, D, eps, gamma, beta,
+                    OUT32 ? (void*)(reinterpret_cast<float*>(y) + (size_t)row * D) : (void*)(reinterpret_cast<uint16_t*>(y) + (size_t)row * D));
 }
 
 // D = 128 * CPL <= 512 (DeiT-S: 384): HALF a wave per row, CPL float4 chunks per lane -- every lane busy (the one-wave-per-row
 // kernel above leaves a quarter of the lanes idle at D = 384 and splits a row's 1.5 KiB into a full and a half request).
-// Same arithmetic as ln_row_store (two-pass statistics, sums over the row's 32 lanes by xor-shuffles 16..1).
-template <int CPL>
+// Same arithmetic as ln_row_store (two-pass statistics, sums over the row's 32 lanes by xor-shuffles 16..1).  OutT = float: the same
+// values stored unrounded (headless final norm, see layernorm_kernel).
+template <int CPL, typename OutT = uint16_t>
 __global__ __launch_bounds__(256) void layernorm_half_kernel(const float* x, long ldx, float* x_out, long ldxo, const uint16_t* __restrict__ delta, long ldd,
                                                              const uint16_t* __restrict__ delta2, long ldd2, int write_x,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             uint16_t* __restrict__ y, int M, float eps) {
+                                                             OutT* __restrict__ y, int M, float eps) {
   constexpr int D = 128 * CPL;
   const int sub = threadIdx.x & 31;
   const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 5);      // two rows per wave, any number of waves per workgroup
@@ -124,16 +127,23 @@ __global__ __launch_bounds__(256) void layernorm_half_kernel(const float* x, lon
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
   const float rstd = rsqrtf(q / (float)D + eps);
-  u2* yr = reinterpret_cast<u2*>(y + (size_t)row * D);
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int ch = sub + 32 * c;
     const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * ch);
     const f4 b = *reinterpret_cast<const f4*>(beta + 4 * ch);
-    u2 pk;
-    pk[0] = pack_bf16x2((v[c][0] - mean) * rstd * g[0] + b[0], (v[c][1] - mean) * rstd * g[1] + b[1]);
-    pk[1] = pack_bf16x2((v[c][2] - mean) * rstd * g[2] + b[2], (v[c][3] - mean) * rstd * g[3] + b[3]);
-    yr[ch] = pk;
+    const float o0 = (v[c][0] - mean) * rstd * g[0] + b[0], o1 = (v[c][1] - mean) * rstd * g[1] + b[1];
+    const float o2 = (v[c][2] - mean) * rstd * g[2] + b[2], o3 = (v[c][3] - mean) * rstd * g[3] + b[3];
+    if constexpr (sizeof(OutT) == 4) {
+      f4 o;
+      o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3;
+      reinterpret_cast<f4*>(y + (size_t)row * D)[ch] = o;
+    } else {
+      u2 pk;
+      pk[0] = pack_bf16x2(o0, o1);
+      pk[1] = pack_bf16x2(o2, o3);
+      reinterpret_cast<u2*>(y + (size_t)row * D)[ch] = pk;
+    }
   }
 }
 
@@ -294,8 +304,10 @@ __global__ __launch_bounds__(256) void cls_pos_kernel(const float* __restrict__ 
 
 }  // namespace
 
+// out32 (bf16 path only): y as fp32 rows, same arithmetic (tr_layernorm_bf16_f32)
 static int layernorm_impl(bool f32, const float* x, long ldx, float* x_out, long ldxo, const void* delta, long ldd, const float* gamma,
-                          const float* beta, void* y, int M, int D, float eps, tr_stream_t s, const uint16_t* delta2 = nullptr, long ldd2 = 0) {
+                          const float* beta, void* y, int M, int D, float eps, tr_stream_t s, const uint16_t* delta2 = nullptr, long ldd2 = 0,
+                          bool out32 = false) {
   TR_REQUIRE(x && gamma && beta && y, TR_ERR_NULL, "tr_layernorm: null pointer");
   const int write_x = x_out != nullptr;           // tr_layernorm2_bf16: no stream write
   if (!write_x) { x_out = const_cast<float*>(x); ldxo = ldx; }
@@ -308,19 +320,24 @@ static int layernorm_impl(bool f32, const float* x, long ldx, float* x_out, long
   TR_REQUIRE(tr_aligned16(x) && tr_aligned16(gamma) && tr_aligned16(beta) && tr_aligned16(y), TR_ERR_ALIGN,
              "tr_layernorm: pointers must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(s);
-  tr_prof_note("layernorm_kernel", 0.0, (double)M * D * (f32 ? 4.0 : 2.0) + (double)M * D * 4.0 + (delta ? (double)M * D * (f32 ? 4.0 : 2.0) : 0.0) +
+  tr_prof_note("layernorm_kernel", 0.0, (double)M * D * ((f32 || out32) ? 4.0 : 2.0) + (double)M * D * 4.0 + (delta ? (double)M * D * (f32 ? 4.0 : 2.0) : 0.0) +
                                             (delta2 ? (double)M * D * 2.0 : 0.0) + ((delta && write_x) ? (double)M * D * 4.0 : 0.0));
 #ifndef TR_LN_NO_HALF
   if (!f32 && D == 384) {
     static const int lnb = [] { const char* e = getenv("TR_LN_BLOCK"); const int b = e ? atoi(e) : 0; return (b == 64 || b == 128) ? b : 256; }();   // lab: waves per workgroup
     const int rpb = lnb / 32;
-    hipLaunchKernelGGL(layernorm_half_kernel<3>, dim3((M + rpb - 1) / rpb), dim3(lnb), 0, st, x, ldx, x_out, ldxo, static_cast<const uint16_t*>(delta), ldd,
-                       delta2, ldd2, write_x, gamma, beta, static_cast<uint16_t*>(y), M, eps);
+    if (out32)
+      hipLaunchKernelGGL((layernorm_half_kernel<3, float>), dim3((M + rpb - 1) / rpb), dim3(lnb), 0, st, x, ldx, x_out, ldxo,
+                         static_cast<const uint16_t*>(delta), ldd, delta2, ldd2, write_x, gamma, beta, static_cast<float*>(y), M, eps);
+    else
+      hipLaunchKernelGGL(layernorm_half_kernel<3>, dim3((M + rpb - 1) / rpb), dim3(lnb), 0, st, x, ldx, x_out, ldxo, static_cast<const uint16_t*>(delta), ldd,
+                         delta2, ldd2, write_x, gamma, beta, static_cast<uint16_t*>(y), M, eps);
     TR_CHECK_LAUNCH("tr_layernorm");
     return TR_OK;
   }
 #endif
   if (f32) TR_DISPATCH_NCH(D, hipLaunchKernelGGL((layernorm_kernel<true, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, ldx, x_out, ldxo, delta, ldd, delta2, ldd2, write_x, gamma, beta, y, M, D, eps));
+  else if (out32) TR_DISPATCH_NCH(D, hipLaunchKernelGGL((layernorm_kernel<false, NCH, true>), dim3((M + 3) / 4), dim3(256), 0, st, x, ldx, x_out, ldxo, delta, ldd, delta2, ldd2, write_x, gamma, beta, y, M, D, eps));
   else TR_DISPATCH_NCH(D, hipLaunchKernelGGL((layernorm_kernel<false, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, ldx, x_out, ldxo, delta, ldd, delta2, ldd2, write_x, gamma, beta, y, M, D, eps));
   TR_CHECK_LAUNCH("tr_layernorm");
   return TR_OK;
@@ -339,6 +356,12 @@ extern "C" int tr_layernorm2_bf16(const float* x, long ldx, float* x_out, long l
                                   long ldd2, const float* gamma, const float* beta, uint16_t* y, int M, int D, float eps, tr_stream_t s) {
   TR_REQUIRE(delta != nullptr, TR_ERR_NULL, "tr_layernorm2_bf16: needs a pending residual");
   return layernorm_impl(false, x, ldx, x_out, ldxo, delta, ldd, gamma, beta, y, M, D, eps, s, delta2, ldd2);
+}
+// the bf16 path's LayerNorm with fp32 output: y = LayerNorm((x + delta) + delta2), both residuals nullable (delta2 needs delta); x_out: the sum
+// (x_out == x: in place, NULL: not written).  bf16(y) == what tr_layernorm_bf16 / _bf16_to / tr_layernorm2_bf16 store, bit for bit.
+extern "C" int tr_layernorm_bf16_f32(const float* x, long ldx, float* x_out, long ldxo, const uint16_t* delta, long ldd, const uint16_t* delta2,
+                                     long ldd2, const float* gamma, const float* beta, float* y, int M, int D, float eps, tr_stream_t s) {
+  return layernorm_impl(false, x, ldx, x_out, ldxo, delta, ldd, gamma, beta, y, M, D, eps, s, delta2, ldd2, true);
 }
 extern "C" int tr_layernorm_f32(float* x, long ldx, const float* delta, long ldd, const float* gamma, const float* beta, float* y,
                                 int M, int D, float eps, tr_stream_t s) {

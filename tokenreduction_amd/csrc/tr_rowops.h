@@ -21,7 +21,9 @@ constexpr int LN_MAX_CHUNKS = 4;  // float4 chunks per lane -> D <= 1024
 // Normalise one row held as `nch` float4 chunks per lane; two-pass (mean, then centred variance) in registers.
 // NCH = 64-lane chunks the row actually spans (ceil(D / 256)): the callers instantiate per NCH so that no lane issues loads
 // for chunks the row does not have (the branch-free loads clamp the chunk index instead of predicating).
-template <bool F32, int NCH>
+// OUT32 = the output type only (fp32 rows, else bf16); F32 also picks the arithmetic (1/sqrtf vs rsqrtf).  <false, NCH, true> is the bf16
+// path's normalisation stored unrounded: its bf16 rounding is bit for bit what <false, NCH> stores.
+template <bool F32, int NCH, bool OUT32 = F32>
 __device__ __forceinline__ void ln_row_store(float4 (&v)[NCH], int nchunks, int lane, int D, float eps,
                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                              void* __restrict__ yrow_) {
@@ -54,7 +56,7 @@ __device__ __forceinline__ void ln_row_store(float4 (&v)[NCH], int nchunks, int 
       const float4 g = gm[c], b = bt[c];
       const float o0 = (v[c].x - mean) * rstd * g.x + b.x, o1 = (v[c].y - mean) * rstd * g.y + b.y;
       const float o2 = (v[c].z - mean) * rstd * g.z + b.z, o3 = (v[c].w - mean) * rstd * g.w + b.w;
-      if (F32) {
+      if (OUT32) {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(yrow_) + 4 * ch) = make_float4(o0, o1, o2, o3);
       } else {
         uint2 pk;

@@ -53,7 +53,7 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
   upd(tr_colsum_workspace_floats((int)T, (int)(3 * D)));
   upd(tr_colsum_workspace_floats((int)T, (int)Hd));
   upd(tr_layernorm_bwd_workspace_floats((int)T, (int)D));
-  upd(tr_wgrad_workspace_floats(B, c->num_classes, (int)D));
+  if (c->num_classes > 0) upd(tr_wgrad_workspace_floats(B, c->num_classes, (int)D));      // the classifier's weight gradient (none headless)
   upd((size_t)(8 * B + 1) * (D + 4));          // tr_cluster_merge_bwd: eight workgroups per image
   upd(tr_dyvit_decide_bwd_workspace_floats(B, t.N0, (int)(D / 4)));
   upd(tr_wgrad_workspace_floats((int)T, (int)(D / 2), (int)D));
@@ -81,7 +81,7 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
   p->gfused = take((size_t)B * D * 4);
   p->invmap = take(T * 4);
   p->dxcls = take((size_t)B * D * 2);
-  p->dl16 = take((size_t)B * c->num_classes * 2);
+  p->dl16 = c->num_classes > 0 ? take((size_t)B * c->num_classes * 2) : 0;
   p->dpol = take(T * 4);
   p->dprev = take(T * 4);
   p->dpolpart = take(T * c->num_heads * 4);
@@ -126,6 +126,8 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 // accumulate != 0: gradients are added to the buffers (engine.py:41 grad accumulation), else overwritten.
 // [blk_hi .. blk_lo] (blk_hi >= blk_lo): the blocks this call walks, in reverse.  blk_hi == depth-1 also runs the classifier and
 // the final norm first; blk_lo == 0 also runs the embedding gradients last.
+// Headless (num_classes == 0): dlogits is the gradient of the CLS features fp32 [B,D]; it enters the final norm's backward rounded to bf16
+// (what the classifier's data gradient hands it), and w->head_* / grads->head_* are not read.
 // DyViT only: dpred (nullable) fp32 [stages, B, P]: gradient wrt each stage's out_pred_prob (the ratio loss, losses.py:113-118), stages in
 // block order; dfeat (nullable) fp32 [B, N0, D]: gradient wrt the final-norm token features (distillation, losses.py:134-156; row 0 = 0).  The gradient of the residual stream stays in the
 // workspace between calls, so a backward pass is the calls (depth-1 .. a), (a-1 .. b), ..., (c .. 0) in this order.
@@ -194,8 +196,11 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
     TR_REQUIRE(hipMemsetAsync(zeros, 0, zmax * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
     // ---- classifier + final norm (topk.py:201-203): gradient enters the CLS rows of the last block's output stream
     const int Nl = t.n_mlp[cfg->depth - 1];
-    TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
-                       reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
+    if (C == 0)
+      TR_TRY(tr_f32_to_bf16(dlogits, dxcls, (size_t)B * D, s));
+    else
+      TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
+                         reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
     TR_REQUIRE(hipMemsetAsync(g, 0, (size_t)B * Nl * D * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
     TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, g, (long)Nl * D, nullptr, nullptr, 0, 0,
                             0, nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));

@@ -158,7 +158,8 @@ bool make_plan(const tr_vit_config* c, int B, Plan* p) {
   p->Hd = c->mlp_hidden;
   p->C = c->num_classes;
   p->kcols = c->in_chans * c->patch * c->patch;
-  if (p->kcols % 64 || p->D % 64 || p->Hd % 64 || p->C % 4 || p->Hd <= 0 || p->C <= 0) return false;
+  // C == 0: headless (deit_viz.py:142,182 -- head = nn.Identity()): the final-normed CLS rows are the output, no classifier runs
+  if (p->kcols % 64 || p->D % 64 || p->Hd % 64 || p->C % 4 || p->Hd <= 0 || p->C < 0) return false;
   const size_t T = (size_t)B * p->N0;  // max tokens
   size_t o = 0;
   p->off_x0 = o;     o += align_up(T * p->D * 4);
@@ -221,12 +222,16 @@ inline int op_ln(bool f32, float* x, long ldx, const void* d, long ldd, const fl
              : tr_layernorm_bf16(x, ldx, static_cast<const uint16_t*>(d), ldd, g, b, static_cast<uint16_t*>(y), M, D, eps, s);
 }
 // norm over x + pending residual(s): the plain norm1 of a block and the final norm.  d_attn != nullptr: the previous block's norm2 did
-// not write the stream back (lazy norm2 below), so BOTH of its residuals are still pending -- (x + d_attn) + d, the reference's order
+// not write the stream back (lazy norm2 below), so BOTH of its residuals are still pending -- (x + d_attn) + d, the reference's order.
+// y_f32 (the final norm of a headless model): y is fp32 on every path -- on the bf16 path the same arithmetic stored unrounded
+// (tr_layernorm_bf16_f32), so bf16(y) is what the bf16 forms store
 inline int op_ln_pending(bool f32, float* x, long ldx, const void* d, const void* d_attn, long ldd, const float* g, const float* b, void* y,
-                         int M, int D, float eps, tr_stream_t s) {
+                         int M, int D, float eps, tr_stream_t s, bool y_f32 = false) {
+  const uint16_t* d1 = static_cast<const uint16_t*>(d_attn != nullptr ? d_attn : d);     // first residual added
+  const uint16_t* d2 = d_attn != nullptr ? static_cast<const uint16_t*>(d) : nullptr;     // second (lazy norm2 only)
+  if (y_f32 && !f32) return tr_layernorm_bf16_f32(x, ldx, x, ldx, d1, ldd, d2, ldd, g, b, static_cast<float*>(y), M, D, eps, s);
   if (d_attn == nullptr) return op_ln(f32, x, ldx, d, ldd, g, b, y, M, D, eps, s);
-  return tr_layernorm2_bf16(x, ldx, x, ldx, static_cast<const uint16_t*>(d_attn), ldd, static_cast<const uint16_t*>(d), ldd, g, b,
-                            static_cast<uint16_t*>(y), M, D, eps, s);
+  return tr_layernorm2_bf16(x, ldx, x, ldx, d1, ldd, d2, ldd, g, b, static_cast<uint16_t*>(y), M, D, eps, s);
 }
 inline int op_attn(int prec, const void* qkv, void* out, float* cls_rows, const float* size, float* colsum, int B, int N, int H,
                    tr_stream_t s) {
@@ -268,7 +273,7 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   const bool train = tape != nullptr;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
-             "tr_vit_forward: invalid config (need embed_dim == 64*heads, dims %% 64 == 0, classes %% 4 == 0, depth <= %d)",
+             "tr_vit_forward: invalid config (need embed_dim == 64*heads, dims %% 64 == 0, classes >= 0 and %% 4 == 0, depth <= %d)",
              TR_MAX_DEPTH);
   TR_REQUIRE(workspace_bytes >= p.total, TR_ERR_SHAPE, "tr_vit_forward: workspace too small (%zu < %zu)", workspace_bytes, p.total);
   TR_REQUIRE(tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_forward: workspace must be 16-byte aligned");
@@ -829,7 +834,9 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
     }
     if (tokens_out) tokens_out[i] = N;
   }
-  // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier
+  // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier -- or, headless (C == 0), the
+  // normed CLS rows themselves are the output (deit_viz.py:209-212 with head = nn.Identity()): the norm writes fp32 straight into `logits`
+  const bool headless = p.C == 0;
   if (train && features_out != nullptr) {
     // DyViT distillation (dyvit.py:252-258): the final norm of EVERY row is an output; the whole stream stays for its backward
     float* xfa = reinterpret_cast<float*>(tape + tp->xfin_all);
@@ -839,10 +846,17 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
     x = xfa;
     pending = nullptr;
   }
+  if (train && headless) {          // the CLS rows entering the norm stay on the tape (xfinal) for the backward; the tape's xcls is not needed
+    TR_TRY(tr_layernorm_bf16_f32(x, (long)N * D, reinterpret_cast<float*>(tape + tp->xfinal), D, static_cast<const uint16_t*>(pending), (long)N * D,
+                                 nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s));
+    return TR_OK;
+  }
   if (train) {
     xcls = tape + tp->xcls;
     TR_TRY(tr_layernorm_bf16_to(x, (long)N * D, reinterpret_cast<float*>(tape + tp->xfinal), D, static_cast<const uint16_t*>(pending), (long)N * D,
                                 w->norm_g, w->norm_b, static_cast<uint16_t*>(xcls), B, D, cfg->ln_eps, s));
+  } else if (headless) {
+    return op_ln_pending(f32, x, (long)N * D, pending, pending_attn, (long)N * D, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
   } else {
     TR_TRY(op_ln_pending(f32, x, (long)N * D, pending, pending_attn, (long)N * D, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
   }

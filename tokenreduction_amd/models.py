@@ -15,6 +15,8 @@ There is no CPU path: forward() on a CPU tensor raises.  In train mode forward()
 every factory width, 224 x 224 and 384 x 384; what the training path refuses (attn_drop_rate, the distillation token,
 more than 640 tokens) raises there.  In eval mode every family runs at up to 1024 patch tokens + CLS (448 x 448 and 512 x 512
 inputs) in all three precisions; more tokens raise.
+A headless model (num_classes=0 or reset_classifier(0): head = nn.Identity(), deit_viz.py:142,182) returns the fp32 final-normed CLS row
+[B, embed_dim] wherever a classifier returns logits -- eval in all three precisions, viz_mode, forward_async, training and its backward.
 """
 from __future__ import annotations
 
@@ -217,6 +219,17 @@ class VisionTransformer(nn.Module):
         NUS-WIDE 81, train.py:334); the padded logits columns are cut off again before anything is returned."""
         return (self.num_classes + 7) // 8 * 8
 
+    @property
+    def _out_width(self):
+        """Columns of the executor's output buffer: the padded classifier, or -- headless (num_classes == 0, head = nn.Identity()) -- the
+        final-normed CLS features [B, embed_dim] (deit_viz.py:142,182, :209-212)."""
+        return self._classes_padded if self.num_classes > 0 else self.embed_dim
+
+    @property
+    def _out_cols(self):
+        """Columns returned to the caller: the logits, or the CLS features of a headless model."""
+        return self.num_classes if self.num_classes > 0 else self.embed_dim
+
     def get_new_module_names(self):
         return []
 
@@ -266,8 +279,9 @@ class VisionTransformer(nn.Module):
         dev = self.pos_embed.device
         if dev.type != "cuda":
             raise RuntimeError(f"model is on {dev}: tokenreduction_amd runs on MI355X only (no CPU path); call .cuda()")
-        if not isinstance(self.head, nn.Linear):
-            raise NotImplementedError("num_classes == 0 (headless) is not supported by the executor")
+        headless = not isinstance(self.head, nn.Linear)
+        if headless != (self.num_classes <= 0):
+            raise RuntimeError(f"num_classes = {self.num_classes} but head is {type(self.head).__name__}: use reset_classifier() to change the head")
         keep_alive = []
         wdt = torch.bfloat16 if self.precision == "bf16" else torch.float32
         slots = self.__dict__.setdefault("_pack_slots", {})          # persistent operand buffers: {(call index, kind): tensor}
@@ -334,8 +348,9 @@ class VisionTransformer(nn.Module):
         W.pos_embed = f32(self.pos_embed.reshape(-1, D))
         W.norm_g, W.norm_b = f32(self.norm.weight), f32(self.norm.bias)
         cpad = self._classes_padded
-        W.head_w = w16(self.head.weight if cpad == self.num_classes else _pad_rows(self.head.weight, cpad))
-        W.head_b = f32(self.head.bias if cpad == self.num_classes else _pad_vec(self.head.bias, cpad))
+        if not headless:             # headless: no classifier operands (tr_vit_weights.head_* stay NULL)
+            W.head_w = w16(self.head.weight if cpad == self.num_classes else _pad_rows(self.head.weight, cpad))
+            W.head_b = f32(self.head.bias if cpad == self.num_classes else _pad_vec(self.head.bias, cpad))
         tblocks = []
         for i, blk in enumerate(self.blocks):
             b = W.blocks[i]
@@ -576,7 +591,7 @@ class VisionTransformer(nn.Module):
                 # conversion above, a loader without a static buffer, K-Medoids --equal_weight with its per-forward draws) would
                 # re-capture on every call -- slower than not using a graph at all: after GRAPH_MISS_LIMIT misses in a row the
                 # workspace goes back to plain launches (at batch 256 within 0.5 % of the replay; bench.py ms_per_step_plain_launches).
-                key = (x.data_ptr(), bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws)
+                key = (x.data_ptr(), bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width)
                 graphs = ws.setdefault("graphs", {})
                 ent = graphs.get(key)
                 if ent is None:
@@ -587,13 +602,13 @@ class VisionTransformer(nn.Module):
                         warnings.warn(f"{type(self).__name__}: {self.GRAPH_MISS_LIMIT} forwards in a row came with a new input address (or new "
                                       "per-forward draws); hipGraph replay is off for this batch size -- keep the input in one static "
                                       "buffer to get it back (model.use_graph = False silences this)", RuntimeWarning, stacklevel=3)
-                        logits = torch.empty(B, self._classes_padded, dtype=torch.float32, device=x.device)
+                        logits = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
                         tokens = launch(logits)
-                        if self._classes_padded != self.num_classes:
-                            logits = logits[:, :self.num_classes].contiguous()
+                        if self._out_width != self._out_cols:
+                            logits = logits[:, :self._out_cols].contiguous()
                         ent = False
                     else:
-                        out = torch.empty(B, self._classes_padded, dtype=torch.float32, device=x.device)
+                        out = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
                         if not ws.get("warm"):
                             launch(out)                                   # eager once per workspace: first touch, lazy module load
                             ws["warm"] = True
@@ -608,12 +623,12 @@ class VisionTransformer(nn.Module):
                 if ent:
                     g, out, toks = ent
                     g.replay()
-                    logits, tokens = out[:, :self.num_classes].clone(), toks
+                    logits, tokens = out[:, :self._out_cols].clone(), toks
             else:
-                logits = torch.empty(B, self._classes_padded, dtype=torch.float32, device=x.device)
+                logits = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
                 tokens = launch(logits)
-                if self._classes_padded != self.num_classes:
-                    logits = logits[:, :self.num_classes].contiguous()
+                if self._out_width != self._out_cols:
+                    logits = logits[:, :self._out_cols].contiguous()
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
         self._last_tokens = list(tokens)
         self._last_ws = ws

@@ -100,7 +100,8 @@ class TrainState:
         G.patch_w, G.patch_b = ptr("patch_embed.proj.weight"), ptr("patch_embed.proj.bias")
         G.cls_token, G.pos_embed = ptr("cls_token"), ptr("pos_embed")
         G.norm_g, G.norm_b = ptr("norm.weight"), ptr("norm.bias")
-        G.head_w, G.head_b = ptr("head.weight"), ptr("head.bias")
+        if "head.weight" in v:       # headless models (num_classes == 0) have no classifier slices: the head pointers stay NULL
+            G.head_w, G.head_b = ptr("head.weight"), ptr("head.bias")
         for i in range(model.depth):
             b, pre = G.blocks[i], f"blocks.{i}."
             b.ln1_g, b.ln1_b = ptr(pre + "norm1.weight"), ptr(pre + "norm1.bias")
@@ -243,7 +244,7 @@ class _VitTrainFn(torch.autograd.Function):
         st.gen += 1
         ctx.gen = st.gen
         ws = model._workspace(B, x.device)
-        logits = torch.empty(B, model._classes_padded, dtype=torch.float32, device=x.device)
+        logits = torch.empty(B, model._out_width, dtype=torch.float32, device=x.device)      # headless: the CLS features [B, D]
         tokens = (C.c_int * model.depth)()
         dyvit = model._family == _lib.TR_FAMILY_DYVIT
         distill = dyvit and bool(getattr(model, "dyvit_distillation", False))
@@ -262,8 +263,8 @@ class _VitTrainFn(torch.autograd.Function):
         ctx.model, ctx.B, ctx.pk = model, B, pk
         ctx.keep = x
         ctx.n_pred, ctx.distill = 0, distill
-        if model._classes_padded != model.num_classes:          # the padded classifier columns never leave the executor
-            logits = logits[:, :model.num_classes].contiguous()
+        if model._out_width != model._out_cols:          # the padded classifier columns never leave the executor
+            logits = logits[:, :model._out_cols].contiguous()
         if not dyvit:
             return logits
         preds = []
@@ -291,11 +292,11 @@ class _VitTrainFn(torch.autograd.Function):
                 "use model.eval() / torch.no_grad() for the forwards that need no gradient.")
         dev = st.flat.device
         if dlogits is None:
-            dlogits = torch.zeros(B, model.num_classes, dtype=torch.float32, device=dev)
+            dlogits = torch.zeros(B, model._out_cols, dtype=torch.float32, device=dev)
         dl = dlogits.detach().to(torch.float32).contiguous()
-        if model._classes_padded != model.num_classes:          # zero gradient on the padded classifier columns
-            dlp = torch.zeros(B, model._classes_padded, dtype=torch.float32, device=dev)
-            dlp[:, :model.num_classes] = dl
+        if model._out_width != model._out_cols:          # zero gradient on the padded classifier columns
+            dlp = torch.zeros(B, model._out_width, dtype=torch.float32, device=dev)
+            dlp[:, :model._out_cols] = dl
             dl = dlp
         dpred = dfeat = None
         if ctx.n_pred:
