@@ -70,6 +70,17 @@ int tr_patch_embed_supported(int C, int HW, int patch, int D);
 int tr_patch_embed_bf16(const float* img, const uint16_t* W, const float* bias, const float* cls_token, const float* pos_embed, float* x,
                         int B, int C, int HW, int patch, int D, tr_stream_t s);
 
+/* Raw uint8 pixels: img uint8 [B,C,H,W] (layout TR_LAYOUT_NCHW) or [B,H,W,C] (TR_LAYOUT_NHWC), 16-byte aligned; lut fp32 [C][256] is the
+ * normalized value of every pixel value, lut[c][v] = (v / 255 - mean[c]) / std[c] computed by the host (torchvision's ToTensor + Normalize
+ * order).  The kernels only gather from it: their output is bitwise what the fp32 entry points give for the normalized image.
+ * tr_im2col_u8_*: as tr_im2col_bf16 / _f32.  tr_patch_embed_u8_bf16: as tr_patch_embed_bf16 (same shapes; NHWC with C = 1 or 3). */
+#define TR_LAYOUT_NCHW 0
+#define TR_LAYOUT_NHWC 1
+int tr_im2col_u8_bf16(const uint8_t* img, const float* lut, int layout, uint16_t* cols, int B, int C, int H, int W, int patch, tr_stream_t s);
+int tr_im2col_u8_f32(const uint8_t* img, const float* lut, int layout, float* cols, int B, int C, int H, int W, int patch, tr_stream_t s);
+int tr_patch_embed_u8_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls_token,
+                           const float* pos_embed, float* x, int B, int C, int HW, int patch, int D, tr_stream_t s);
+
 /* a3/a4 Linear layers (nn.Linear: y = x W^T + b, W is [N,K] row-major like the state dict).
  * A bf16 [M,K], W bf16 [N,K], bias fp32 [N]; K % 64 == 0, N % 4 == 0.  `out` dtype/meaning per epilogue;
  * aux/aux_i only for TR_EPI_PATCH_F32. */
@@ -602,6 +613,18 @@ int tr_vit_forward(const tr_vit_config* cfg, const tr_vit_weights* w, const floa
                    void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                    const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s);
 
+/* tr_vit_forward / tr_vit_forward_train with the image in another format: input_format TR_INPUT_F32 = fp32 [B,C,S,S] (the calls above),
+ * TR_INPUT_U8_NCHW = uint8 [B,C,S,S], TR_INPUT_U8_NHWC = uint8 [B,S,S,C] (NHWC: C = 1 or 3 where the fused patch embedding runs).  For the
+ * uint8 formats pixel_lut is the fp32 [C][256] table of tr_patch_embed_u8_bf16 and the patch embedding normalizes on the way in: outputs
+ * and the training tape are bitwise those of the fp32 call on the normalized image.  Any other format, or a uint8 format without a LUT,
+ * is TR_ERR_CONFIG.  (Separate entry points rather than fields of tr_vit_config / tr_vit_weights: those layouts are part of the ABI.) */
+#define TR_INPUT_F32 0
+#define TR_INPUT_U8_NCHW 1
+#define TR_INPUT_U8_NHWC 2
+int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                          float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
+                          const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s);
+
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
  * gradients), up to 640 tokens (224 x 224 and 384 x 384 inputs).  DyViT (dyvit.py:221-229): noise_in = the Gumbel noise of every stage, fp32 [B,P,2] back to back (torch's
@@ -624,6 +647,10 @@ size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B);
 int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
                          size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,
                          const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate);
+int tr_vit_forward_train_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                                float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
+                                float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
+                                float drop_rate);
 /* Dropout (timm's drop_rate, train.py:46 --drop: pos_drop topk.py:186, proj_drop :53, the Mlp's two nn.Dropout): dropout_keep (nullable
  * = drop_rate 0; both calls get the same) is the caller's keep mask, 1 byte per element (non-zero = keep), tr_vit_dropout_mask_bytes()
  * bytes in the order the forward consumes them -- the embedded tokens [B,N0,D], then per block proj's output rows, the Mlp's hidden

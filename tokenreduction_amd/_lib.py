@@ -18,6 +18,8 @@ TR_FAMILY_DEIT, TR_FAMILY_TOPK, TR_FAMILY_EVIT, TR_FAMILY_TOME, TR_FAMILY_DYVIT,
     TR_FAMILY_DPCKNN, TR_FAMILY_ATS, TR_FAMILY_SINKHORN, TR_FAMILY_KMEDOIDS, \
     TR_FAMILY_PATCHMERGER, TR_FAMILY_HEURISTIC = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 TR_PREC_BF16, TR_PREC_FP32, TR_PREC_BF16X3 = 0, 1, 2
+TR_LAYOUT_NCHW, TR_LAYOUT_NHWC = 0, 1
+TR_INPUT_F32, TR_INPUT_U8_NCHW, TR_INPUT_U8_NHWC = 0, 1, 2
 
 _vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -81,6 +83,9 @@ SIGNATURES = {
     "tr_cls_pos_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tr_patch_embed_supported": (_i, [_i, _i, _i, _i]),
     "tr_patch_embed_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_im2col_u8_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_im2col_u8_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_patch_embed_u8_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_gemm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_mlp_fused_supported": (_i, [_i, _i]),
     "tr_set_mlp_fused": (_i, [_i]),
@@ -179,6 +184,10 @@ SIGNATURES = {
     "tr_add_patch_rows": (_i, [_vp, _vp, _i, _i, _vp]),
     "tr_vit_forward": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                             C.POINTER(_i), _i, _vp]),
+    "tr_vit_forward_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(_i), _i, _vp]),
+    "tr_vit_forward_train_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
+                                         C.POINTER(_i), _i, _vp, _vp, _f]),
 }
 
 _lib = None

@@ -294,6 +294,49 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
   }
 }
 
+// raw uint8 pixels: the same unfold, every pixel through lut[c][v] (the value the normalized fp32 image holds) and then the same rounding
+// as im2col_kernel, so the columns are bitwise those of the normalized image.  NCHW: one 8-byte load; NHWC: 8 bytes C apart.
+template <bool F32, bool NHWC>
+__global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ lut, void* __restrict__ cols,
+                                                        int B, int C, int H, int W, int patch, long total) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int per_row = patch >> 3;
+  const int kcols = C * patch * patch;
+  const int groups_per_row = kcols >> 3;
+  const long rowid = t / groups_per_row;
+  const int g = (int)(t - rowid * groups_per_row);
+  const int gw = W / patch, gh = H / patch;
+  const int b = (int)(rowid / (gh * gw));
+  const int pp = (int)(rowid - (long)b * gh * gw);
+  const int py = pp / gw, px = pp - py * gw;
+  const int c = g / (patch * per_row);
+  const int rem = g - c * patch * per_row;
+  const int iy = rem / per_row, ixg = rem - iy * per_row;
+  const size_t y = (size_t)py * patch + iy, x0 = (size_t)px * patch + ixg * 8;
+  const float* lc = lut + c * 256;
+  float v[8];
+  if (NHWC) {
+    const uint8_t* src = img + (((size_t)b * H + y) * W + x0) * C + c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = lc[src[(size_t)k * C]];
+  } else {
+    const uint2 u = *reinterpret_cast<const uint2*>(img + (((size_t)b * C + c) * H + y) * W + x0);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = lc[((k < 4 ? u.x : u.y) >> (8 * (k & 3))) & 0xffu];
+  }
+  if (F32) {
+    float* o = reinterpret_cast<float*>(cols) + rowid * kcols + (size_t)g * 8;
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  } else {
+    uint4 pk;
+    pk.x = pack_bf16x2(v[0], v[1]); pk.y = pack_bf16x2(v[2], v[3]);
+    pk.z = pack_bf16x2(v[4], v[5]); pk.w = pack_bf16x2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(cols) + rowid * kcols + (size_t)g * 8) = pk;
+  }
+}
+
 __global__ __launch_bounds__(256) void cls_pos_kernel(const float* __restrict__ cls, const float* __restrict__ pos, float* __restrict__ x,
                                                       int B, int N, int D) {
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -474,6 +517,36 @@ extern "C" int tr_im2col_bf16(const float* img, uint16_t* cols, int B, int C, in
 }
 extern "C" int tr_im2col_f32(const float* img, float* cols, int B, int C, int H, int W, int patch, tr_stream_t s) {
   return im2col_impl(true, img, cols, B, C, H, W, patch, s);
+}
+
+static int im2col_u8_impl(bool f32, const uint8_t* img, const float* lut, int layout, void* cols, int B, int C, int H, int W, int patch,
+                          tr_stream_t s) {
+  TR_REQUIRE(img && lut && cols, TR_ERR_NULL, "tr_im2col_u8: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_SHAPE, "tr_im2col_u8: layout %d is neither NCHW (0) nor NHWC (1)",
+             layout);
+  TR_REQUIRE(B > 0 && C > 0 && patch >= 8 && patch % 8 == 0 && H % patch == 0 && W % patch == 0, TR_ERR_SHAPE,
+             "tr_im2col_u8: need patch %% 8 == 0 and H,W multiples of patch (H=%d W=%d patch=%d)", H, W, patch);
+  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(cols), TR_ERR_ALIGN, "tr_im2col_u8: pointers must be 16-byte aligned");
+  const long total = (long)B * C * H * W / 8;
+  tr_prof_note("im2col_u8_kernel", 0.0, (double)B * C * H * W * (f32 ? 5.0 : 3.0));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  const bool nhwc = layout == TR_LAYOUT_NHWC;
+  if (f32 && nhwc) hipLaunchKernelGGL((im2col_u8_kernel<true, true>), grid, dim3(256), 0, st, img, lut, cols, B, C, H, W, patch, total);
+  else if (f32) hipLaunchKernelGGL((im2col_u8_kernel<true, false>), grid, dim3(256), 0, st, img, lut, cols, B, C, H, W, patch, total);
+  else if (nhwc) hipLaunchKernelGGL((im2col_u8_kernel<false, true>), grid, dim3(256), 0, st, img, lut, cols, B, C, H, W, patch, total);
+  else hipLaunchKernelGGL((im2col_u8_kernel<false, false>), grid, dim3(256), 0, st, img, lut, cols, B, C, H, W, patch, total);
+  TR_CHECK_LAUNCH("tr_im2col_u8");
+  return TR_OK;
+}
+
+extern "C" int tr_im2col_u8_bf16(const uint8_t* img, const float* lut, int layout, uint16_t* cols, int B, int C, int H, int W, int patch,
+                                 tr_stream_t s) {
+  return im2col_u8_impl(false, img, lut, layout, cols, B, C, H, W, patch, s);
+}
+extern "C" int tr_im2col_u8_f32(const uint8_t* img, const float* lut, int layout, float* cols, int B, int C, int H, int W, int patch,
+                                tr_stream_t s) {
+  return im2col_u8_impl(true, img, lut, layout, cols, B, C, H, W, patch, s);
 }
 
 extern "C" int tr_cls_pos_rows(const float* cls_token, const float* pos_embed, float* x, int B, int N, int D, tr_stream_t s) {

@@ -205,6 +205,11 @@ inline int op_im2col(bool f32, const float* img, void* cols, int B, int C, int H
   return f32 ? tr_im2col_f32(img, static_cast<float*>(cols), B, C, H, W, patch, s)
              : tr_im2col_bf16(img, static_cast<uint16_t*>(cols), B, C, H, W, patch, s);
 }
+inline int op_im2col_u8(bool f32, const uint8_t* img, const float* lut, int layout, void* cols, int B, int C, int H, int W, int patch,
+                        tr_stream_t s) {
+  return f32 ? tr_im2col_u8_f32(img, lut, layout, static_cast<float*>(cols), B, C, H, W, patch, s)
+             : tr_im2col_u8_bf16(img, lut, layout, static_cast<uint16_t*>(cols), B, C, H, W, patch, s);
+}
 inline int op_gemm(int prec, const void* A, const void* W, const float* bias, void* out, const float* aux, int aux_i, int M, int N,
                    int K, int epi, tr_stream_t s) {
   if (prec == TR_PREC_BF16)
@@ -265,7 +270,9 @@ extern "C" size_t tr_vit_workspace_bytes(const tr_vit_config* cfg, int B) {
 // tape != nullptr: TRAINING forward -- every activation the backward pass needs goes to its own slot of the tape (tr_plan.h)
 // instead of the shared scratch, the residual stream is written out of place (the inputs of norm1 / norm2 of every block stay),
 // fc1 keeps its pre-activation (GELU as a separate kernel), and the decisions (kept ids, sizes) are kept per block.
-static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
+// img: fp32 [B,C,S,S] (input_format TR_INPUT_F32) or uint8 pixels normalized through pixel_lut by the patch embedding
+static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                            float* logits, void* workspace,
                             size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f) {
@@ -277,6 +284,9 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
              TR_MAX_DEPTH);
   TR_REQUIRE(workspace_bytes >= p.total, TR_ERR_SHAPE, "tr_vit_forward: workspace too small (%zu < %zu)", workspace_bytes, p.total);
   TR_REQUIRE(tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_forward: workspace must be 16-byte aligned");
+  TR_REQUIRE(input_format == TR_INPUT_F32 || input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
+             "tr_vit_forward: input_format %d is not a TR_INPUT_* format", input_format);
+  TR_REQUIRE(input_format == TR_INPUT_F32 || pixel_lut != nullptr, TR_ERR_CONFIG, "tr_vit_forward: a uint8 input needs the pixel LUT");
 
   tr_prof_restart();
   char* ws = static_cast<char*>(workspace);
@@ -330,14 +340,25 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   const bool rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
   const void* xn1_ready = nullptr;         // norm1 of the block about to start, written by the previous block's fused tail
   // a1 + a2: patch embedding, CLS token, position embedding
+  // uint8 pixels: the same choice of path, each with its uint8 loader (normalization through the LUT; same columns, same bits)
+  const bool pixels = input_format != TR_INPUT_F32;
+  const uint8_t* u8img = static_cast<const uint8_t*>(img);
+  const int layout = input_format == TR_INPUT_U8_NHWC ? TR_LAYOUT_NHWC : TR_LAYOUT_NCHW;
   static const bool unfused_patch = [] { const char* e = getenv("TR_PATCH_UNFUSED"); return e && atoi(e) != 0; }();   // lab: the three-launch path
   if (!train && !f32 && !unfused_patch && tr_patch_embed_supported(cfg->in_chans, cfg->img_size, cfg->patch, D)) {
     // eval: unfold + GEMM + cls/pos in one launch (tr_patch.hip), at every batch size (the two paths differ in the last bit: an image's
     // tokens must not depend on its batch); training keeps the column matrix (PatchEmbed's weight-gradient operand)
-    TR_TRY(tr_patch_embed_bf16(img, static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, cfg->in_chans,
-                               cfg->img_size, cfg->patch, D, s));
+    if (pixels)
+      TR_TRY(tr_patch_embed_u8_bf16(u8img, pixel_lut, layout, static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x,
+                                    B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
+    else
+      TR_TRY(tr_patch_embed_bf16(static_cast<const float*>(img), static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token,
+                                 w->pos_embed, x, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
   } else {
-    TR_TRY(op_im2col(f32, img, cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
+    if (pixels)
+      TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
+    else
+      TR_TRY(op_im2col(f32, static_cast<const float*>(img), cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
     TR_TRY(op_gemm(prec, cols, w->patch_w, w->patch_b, x, w->pos_embed, p.P, B * p.P, D, p.kcols, TR_EPI_PATCH_F32, s));
     TR_TRY(tr_cls_pos_rows(w->cls_token, w->pos_embed, x, B, p.N0, D, s));
   }
@@ -881,8 +902,15 @@ extern "C" int tr_vit_forward_status(const tr_vit_config* cfg, void* workspace, 
 extern "C" int tr_vit_forward(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
                               size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                               const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s) {
-  return vit_forward_impl(cfg, w, img, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in, features_out, tokens_out,
-                          B, s, nullptr, nullptr);
+  return vit_forward_impl(cfg, w, img, TR_INPUT_F32, nullptr, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
+                          features_out, tokens_out, B, s, nullptr, nullptr);
+}
+
+extern "C" int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                                     float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx,
+                                     float* soft_out, const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s) {
+  return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
+                          features_out, tokens_out, B, s, nullptr, nullptr);
 }
 
 extern "C" size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B) {
@@ -914,9 +942,10 @@ extern "C" int tr_vit_tape_layout(const tr_vit_config* cfg, int B, int blk, size
   return TR_OK;
 }
 
-extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
-                                    size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,
-                                    const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                                  float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
+                                  float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
+                                  float drop_rate) {
   TR_REQUIRE(cfg && tape, TR_ERR_NULL, "tr_vit_forward_train: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_forward_train: dropout needs a keep mask AND 0 < drop_rate < 1 (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
@@ -930,8 +959,23 @@ extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weigh
   for (int i = 0; i < cfg->depth; ++i)
     TR_REQUIRE(t.n_att[i] <= 640, TR_ERR_SHAPE, "tr_vit_forward_train: %d tokens in block %d (the training path holds 640)", t.n_att[i], i);
   TR_REQUIRE(features_out == nullptr || cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_forward_train: features_out is DyViT's distillation output");
-  return vit_forward_impl(cfg, w, img, logits, workspace, workspace_bytes, nullptr, nullptr, nullptr, noise_in, features_out, tokens_out, B, s,
-                          static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate);
+  return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, nullptr, noise_in,
+                          features_out, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate);
+}
+
+extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
+                                    size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,
+                                    const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+  return vit_forward_train_impl(cfg, w, img, TR_INPUT_F32, nullptr, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in, features_out,
+                                drop_scale, tokens_out, B, s, dropout_keep, drop_rate);
+}
+
+extern "C" int tr_vit_forward_train_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format,
+                                           const float* pixel_lut, float* logits, void* workspace, size_t workspace_bytes, void* tape,
+                                           size_t tape_bytes, const float* noise_in, float* features_out, const float* drop_scale, int* tokens_out,
+                                           int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+  return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in,
+                                features_out, drop_scale, tokens_out, B, s, dropout_keep, drop_rate);
 }
 
 // Bytes of the dropout keep mask of one training forward (1 byte per element, 1 = keep), in the order the forward consumes it:

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, pixels
 
 
 def _pair(v):
@@ -172,7 +172,7 @@ class VisionTransformer(nn.Module):
     # torch.cuda.CUDAGraph objects cannot be deep-copied at all, and a copied workspace would not belong to the copy's own packed weights.
     _EXECUTOR_CACHES = {"_packed": None, "_ws": None, "_last_ws": None, "_tstate": None, "_grad_reducer": None, "_noise_buf": None,
                         "_gumbel_buf": None, "_kmed_draws": None, "_pack_slots": None, "_pack_table": None, "_mlp_pack_items": None,
-                        "_pipe_streams": None, "_pipe_next": None, "_noise_bufs": None}
+                        "_pipe_streams": None, "_pipe_next": None, "_noise_bufs": None, "_pixel_luts": None}
 
     def __deepcopy__(self, memo):
         new = self.__class__.__new__(self.__class__)
@@ -498,6 +498,36 @@ class VisionTransformer(nn.Module):
             self._ws[wkey] = ws
         return ws
 
+    # ---- raw uint8 pixels (pixels.py) ---------------------------------------------------------------
+    @property
+    def pixel_input(self):
+        """None, or the (mean, std) with which uint8 inputs are normalized on the device (set_pixel_input)."""
+        return self.__dict__.get("_pixel_input")
+
+    def set_pixel_input(self, mean=pixels.IMAGENET_DEFAULT_MEAN, std=pixels.IMAGENET_DEFAULT_STD):
+        """Opt-in: a uint8 input [B, C, S, S] -- contiguous (NCHW) or torch.channels_last (NHWC), read in place -- is taken as raw pixels and
+        normalized inside the kernels that read the image, bitwise as if the fp32 tensor of torchvision's ToTensor() + Normalize(mean, std)
+        had been passed.  Float inputs are unaffected.  set_pixel_input(None) turns it off (a uint8 tensor is then cast to fp32 as before).
+        mean and std have in_chans entries.  Not a buffer: state_dict() stays the reference's; copy.deepcopy keeps the setting."""
+        new = None if mean is None else pixels.check_mean_std(mean, std, self.patch_embed.proj.in_channels)
+        if new != self.pixel_input:
+            self.sync_pipeline()          # the old table may still be read by forwards in flight on forward_async's side streams
+            self._pixel_luts = None
+        self._pixel_input = new
+        return self
+
+    def _executor_input(self, x: torch.Tensor):
+        """(image tensor, TR_INPUT_* format, LUT pointer or None) of the executor for input x."""
+        if self.pixel_input is None or x.dtype != torch.uint8:
+            return x.detach().to(torch.float32).contiguous(), _lib.TR_INPUT_F32, None
+        x, fmt = pixels.as_executor_input(x, self.patch_embed.proj.in_channels)
+        luts = self.__dict__.get("_pixel_luts")
+        if luts is None:
+            luts = self._pixel_luts = {}
+        if x.device not in luts:                       # one table per device, built at its first uint8 forward
+            luts[x.device] = pixels.pixel_lut(*self.pixel_input).to(x.device)
+        return x, fmt, luts[x.device].data_ptr()
+
     # ---- training state (flat gradient buffer, tape, workspaces): training.py -----------------------
     def _train_state(self):
         st = getattr(self, "_tstate", None)
@@ -556,7 +586,7 @@ class VisionTransformer(nn.Module):
         B, Cc, Hh, Ww = x.shape
         if (Cc, Hh, Ww) != (cfg.in_chans, cfg.img_size, cfg.img_size):
             raise ValueError(f"expected [B,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(x.shape)}")
-        x = x.detach().to(torch.float32).contiguous()
+        x, fmt, lut = self._executor_input(x)
         ws = self._workspace(B, x.device, slot)
         if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
             ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
@@ -573,11 +603,13 @@ class VisionTransformer(nn.Module):
 
         def launch(out):
             tokens = (C.c_int * self.depth)()
-            rc = lib.tr_vit_forward(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), out.data_ptr(), ws["buf"].data_ptr(),
-                                    ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
-                                    None if ws.get("soft") is None else ws["soft"].data_ptr(), noise_ptr,
-                                    ws["feat"].data_ptr() if want_feat else None, tokens, B,
-                                    torch.cuda.current_stream().cuda_stream)
+            rest = (out.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
+                    None if ws.get("soft") is None else ws["soft"].data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
+                    torch.cuda.current_stream().cuda_stream)
+            if fmt == _lib.TR_INPUT_F32:
+                rc = lib.tr_vit_forward(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest)
+            else:
+                rc = lib.tr_vit_forward_pixels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest)
             _lib.check(rc, "tr_vit_forward")
             return list(tokens)
 
@@ -591,7 +623,7 @@ class VisionTransformer(nn.Module):
                 # conversion above, a loader without a static buffer, K-Medoids --equal_weight with its per-forward draws) would
                 # re-capture on every call -- slower than not using a graph at all: after GRAPH_MISS_LIMIT misses in a row the
                 # workspace goes back to plain launches (at batch 256 within 0.5 % of the replay; bench.py ms_per_step_plain_launches).
-                key = (x.data_ptr(), bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width)
+                key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width)
                 graphs = ws.setdefault("graphs", {})
                 ent = graphs.get(key)
                 if ent is None:

@@ -63,6 +63,43 @@ def patch_embed(img: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cls_toke
     return x
 
 
+def _pixels(img: torch.Tensor, lut: torch.Tensor, C: int):
+    """(image pointer, layout, LUT pointer) of uint8 pixels [B,C,H,W] (contiguous or channels_last) and their fp32 LUT [C,256]."""
+    if not img.is_cuda:
+        raise RuntimeError(f"img: tensor is on {img.device}; tokenreduction_amd has no CPU path (HIP kernels only)")
+    if img.dtype != torch.uint8:
+        raise TypeError(f"img: expected torch.uint8, got {img.dtype}")
+    if tuple(lut.shape) != (C, 256):
+        raise ValueError(f"lut: expected [{C}, 256], got {tuple(lut.shape)}")
+    _same_device(img, lut)
+    from .pixels import layout
+    return img.data_ptr(), layout(img), _dev(lut, torch.float32, "lut")
+
+
+def im2col_u8(img: torch.Tensor, lut: torch.Tensor, patch: int, f32: bool = False) -> torch.Tensor:
+    """im2col of raw uint8 pixels (contiguous or channels_last) normalized through `lut` (pixels.pixel_lut): bf16 (f32=True: fp32)
+    [B*P, C*p*p], bitwise the columns of the normalized fp32 image."""
+    B, Cc, H, W = img.shape
+    ptr, lay, lp = _pixels(img, lut, Cc)
+    cols = torch.empty(B * (H // patch) * (W // patch), Cc * patch * patch, dtype=torch.float32 if f32 else torch.bfloat16, device=img.device)
+    fn = _lib.load().tr_im2col_u8_f32 if f32 else _lib.load().tr_im2col_u8_bf16
+    _lib.check(fn(ptr, lp, lay, cols.data_ptr(), B, Cc, H, W, patch, _stream(img)), "tr_im2col_u8")
+    return cols
+
+
+def patch_embed_u8(img: torch.Tensor, lut: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cls_token: torch.Tensor,
+                   pos_embed: torch.Tensor, patch: int = 16) -> torch.Tensor:
+    """patch_embed of raw uint8 pixels (contiguous or channels_last) normalized through `lut`: bitwise patch_embed of the normalized image."""
+    B, Cc, H, _ = img.shape
+    D = w.shape[0]
+    ptr, lay, lp = _pixels(img, lut, Cc)
+    x = torch.empty(B, (H // patch) ** 2 + 1, D, dtype=torch.float32, device=img.device)
+    _lib.check(_lib.load().tr_patch_embed_u8_bf16(ptr, lp, lay, _dev(w, torch.bfloat16, "w"), _dev(bias, torch.float32, "bias"),
+                                                  _dev(cls_token, torch.float32, "cls_token"), _dev(pos_embed, torch.float32, "pos_embed"),
+                                                  x.data_ptr(), B, Cc, H, patch, D, _stream(img)), "tr_patch_embed_u8_bf16")
+    return x
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, epilogue: int, out: torch.Tensor = None,
          aux: torch.Tensor = None, aux_i: int = 0) -> torch.Tensor:
     """nn.Linear on MFMA: epilogue(a[M,K] @ w[N,K]^T + bias).  For RESID/PATCH `out` is required (updated in place)."""
