@@ -200,6 +200,15 @@ int tr_broadcast_rows(const float* src, float* dst, int B, int N, tr_stream_t s)
  * through the LDS in chunks of 128 with an online softmax; column sums together with a key bias need N <= 608. */
 int tr_attention_bf16(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B, int N,
                       int H, tr_stream_t s);
+/* The same attention where only the CLS query's output is read (the last block of the eval forward): out bf16 [B, H*64] (compact) = row 0
+ * of every image of what tr_attention_bf16 writes into [B*N, H*64], bit for bit (same kernels, same instruction sequence for that query
+ * block).  K and V of all N rows are read; only the first query block of every (image, head) is computed.  size as above. */
+int tr_attention_cls_bf16(const uint16_t* qkv, uint16_t* out, const float* size, int B, int N, int H, tr_stream_t s);
+/* CLS tail of the eval executor (bf16): in the LAST block, where nothing reduces from the attention onward and no `Features` are asked for,
+ * tr_vit_forward runs tr_attention_cls_bf16 and then proj, norm2, fc1, fc2 on the B CLS rows only -- the only rows the final norm and the
+ * head read (topk.py:201-203).  1 (default) / 0: the full-width block; the logits are bit-identical.  TR_PREC_FP32 / TR_PREC_BF16X3
+ * always run the full-width block.  Process-wide, read when the launches are enqueued; returns the previous setting. */
+int tr_set_cls_tail(int on);
 /* fp32 validation path (N <= 640; K/V of a head in LDS up to N = 256, read from L2 beyond): same contract in the reference's
  * arithmetic (expf softmax, fp32 everywhere). */
 int tr_attention_f32(const float* qkv, float* out, float* cls_rows, const float* size, float* colsum_part, int B, int N, int H,

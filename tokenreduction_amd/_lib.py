@@ -96,6 +96,8 @@ SIGNATURES = {
     "tr_set_mlp_poll_max": (_i, [_i]),
     "tr_mlp_fused_status": (_i, [_vp, _sz, _i, _i, _vp]),
     "tr_set_mlp_ln": (_i, [_i]),
+    "tr_set_cls_tail": (_i, [_i]),
+    "tr_attention_cls_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tr_mlp_fused_ln_bf16": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "tr_gemm_clock_probe_read": (_i, [_vp]),
     "tr_mlp_clock_probe_read": (_i, [_vp]),

@@ -389,7 +389,9 @@ __device__ __forceinline__ float quad_rows_sum(float v) {
 #define TR_ATT16_SB 3
 #endif
 constexpr int A16_NW = TR_ATT16_WAVES, A16_NT = 64 * A16_NW;     // waves / threads per workgroup
-template <int NP, bool COLSUM, bool POLICY, bool BIAS>
+// CLS (tr_attention_cls_bf16: the last block of the eval forward, whose other rows nobody reads): all waves stage K and V as always, then
+// wave 0 alone runs query block 0 -- the same instructions as in the full launch -- and stores only query 0, into a compact [B, H*64] buffer
+template <int NP, bool COLSUM, bool POLICY, bool BIAS, bool CLS = false>
 __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention16_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                              float* __restrict__ cls_rows, const float* __restrict__ size,
                                                              float* __restrict__ colsum_part, int N, int H) {
@@ -409,7 +411,7 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
   const int ldq = 3 * H * 64;
   const uint16_t* base = qkv + (size_t)b * N * ldq;
   const int qcol = h * 64, kcol = H * 64 + h * 64, vcol = 2 * H * 64 + h * 64;
-  const int nqb = (N + 15) >> 4;
+  const int nqb = CLS ? 1 : (N + 15) >> 4;
 
   // ---- stage K and V (all loads issued before the first LDS write); the first query block's fragments are requested alongside
   constexpr int NIT = (NP * 256 + A16_NT - 1) / A16_NT;     // 16-byte chunks per thread and matrix
@@ -572,8 +574,8 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (q < N) {
-      uint16_t* orow = out + ((size_t)b * N + q) * (H * 64) + h * 64 + 8 * g;
+    if (CLS ? q == 0 : q < N) {
+      uint16_t* orow = out + ((size_t)b * (CLS ? 1 : N) + q) * (H * 64) + h * 64 + 8 * g;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         uint4 pk;
@@ -834,7 +836,9 @@ constexpr int FRS = FKB * 64 + 16;           // V^T row stride in bytes
 //   a = e * pi (pi = policy[key], 1 on the diagonal): out = (sum_k a_k v_k + eps/N sum_k v_k) / (sum_k a_k + eps).  eps is relative to the
 //   TRUE row maximum, the accumulators to the integer reference point m >= max: eps' = eps 2^(max - m); sum_k v_k (all valid keys) is
 //   collected once per workgroup on the vector ALUs while the chunks pass through the LDS.
-template <bool POLICY>
+// CLS (tr_attention_cls_bf16): launched with nqg = 1, query group 0 only; wave 0 computes query block 0, the other waves only stage; query 0
+// alone is stored, into a compact [B, H*64] buffer
+template <bool POLICY, bool CLS = false>
 __global__ __launch_bounds__(256, TR_FLASH_WGS) void attention_flash_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                                  float* __restrict__ cls_rows, const float* __restrict__ size,
                                                                  float* __restrict__ stats, int N, int H, int nqg) {
@@ -855,7 +859,7 @@ __global__ __launch_bounds__(256, TR_FLASH_WGS) void attention_flash_kernel(cons
   const int nqb = (N + 31) >> 5;
   const int qb = qg * 4 + wave;                      // this wave's query block (may lie past the end: it still helps staging)
   const int q = qb * 32 + ql;
-  const bool live = qb < nqb;
+  const bool live = CLS ? wave == 0 : qb < nqb;
   const float c_exp = 0.125f * 1.44269504088896340736f;
 
   bf16x8 qf[4];
@@ -1017,8 +1021,8 @@ __global__ __launch_bounds__(256, TR_FLASH_WGS) void attention_flash_kernel(cons
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[db][r] += add * sVsum[db * 32 + 8 * (r >> 2) + 4 * hh + (r & 3)];
   }
-  if (q < N) {
-    uint16_t* orow = out + ((size_t)b * N + q) * (H * 64) + h * 64 + 4 * hh;
+  if (CLS ? q == 0 : q < N) {
+    uint16_t* orow = out + ((size_t)b * (CLS ? 1 : N) + q) * (H * 64) + h * 64 + 4 * hh;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -1150,6 +1154,18 @@ int launch_attention16(const uint16_t* qkv, uint16_t* out, float* cls_rows, cons
   return 0;
 }
 
+template <int NP>
+int launch_attention16_cls(const uint16_t* qkv, uint16_t* out, const float* size, int B, int N, int H, hipStream_t st) {
+  const int R = ((N + 15) >> 4) << 4;
+  const size_t lds = (size_t)R * 256 + (size ? (size_t)R * 4 : 0);
+  float* const none = nullptr;
+  if (size)
+    hipLaunchKernelGGL((attention16_kernel<NP, false, false, true, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
+  else
+    hipLaunchKernelGGL((attention16_kernel<NP, false, false, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
+  return 0;
+}
+
 template <int NKB>
 int launch_attention(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B, int N, int H,
                      hipStream_t st, bool policy = false) {
@@ -1167,7 +1183,46 @@ int launch_attention(const uint16_t* qkv, uint16_t* out, float* cls_rows, const 
   return 0;
 }
 
+bool att_use_old() {
+  static const bool use_old = [] { const char* e = getenv("TR_ATT_OLD"); return e && atoi(e) != 0; }();   // lab: the 32-query kernel
+  return use_old;
+}
+
 }  // namespace
+
+// 0 where tr_attention_bf16 runs a kernel that has no CLS-only form (the lab's 32-query kernel): the executor keeps the full launch there
+int tr_attention_cls_available() { return att_use_old() ? 0 : 1; }
+
+// The attention of a block whose output is read on the CLS rows only: out bf16 [B, H*64] = row 0 of every image of what tr_attention_bf16
+// writes, bit for bit.  K and V of all N rows are read as always; q and the output of the first query block only.
+extern "C" int tr_attention_cls_bf16(const uint16_t* qkv, uint16_t* out, const float* size, int B, int N, int H, tr_stream_t s) {
+  TR_REQUIRE(qkv && out, TR_ERR_NULL, "tr_attention_cls_bf16: null pointer");
+  TR_REQUIRE(B > 0 && H > 0 && N >= 1, TR_ERR_SHAPE, "tr_attention_cls_bf16: bad shape B=%d N=%d H=%d", B, N, H);
+  TR_REQUIRE(tr_aligned16(qkv) && tr_aligned16(out), TR_ERR_ALIGN, "tr_attention_cls_bf16: pointers must be 16-byte aligned");
+  TR_REQUIRE(tr_attention_cls_available(), TR_ERR_CONFIG, "tr_attention_cls_bf16: not available beside TR_ATT_OLD");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  // one query block per (image, head): 16 (N <= 224) or 32 queries against all keys; K, V and the block's q rows in, B rows out
+  const double qrows = N <= 224 ? 16.0 : 32.0;
+  tr_prof_note(N <= 224 ? "attention_kernel<cls>" : "attention_flash_kernel<cls>", 4.0 * B * H * qrows * N * 64,
+               2.0 * B * H * 64 * (2.0 * N + (N < qrows ? N : qrows) + 1.0));
+  if (N > 224) {
+    hipLaunchKernelGGL((attention_flash_kernel<false, true>), dim3(B * H), dim3(256), 0, st, qkv, out, static_cast<float*>(nullptr), size,
+                       static_cast<float*>(nullptr), N, H, 1);
+    TR_CHECK_LAUNCH("tr_attention_cls_bf16");
+    return TR_OK;
+  }
+  switch ((N + 31) / 32) {
+    case 1: launch_attention16_cls<1>(qkv, out, size, B, N, H, st); break;
+    case 2: launch_attention16_cls<2>(qkv, out, size, B, N, H, st); break;
+    case 3: launch_attention16_cls<3>(qkv, out, size, B, N, H, st); break;
+    case 4: launch_attention16_cls<4>(qkv, out, size, B, N, H, st); break;
+    case 5: launch_attention16_cls<5>(qkv, out, size, B, N, H, st); break;
+    case 6: launch_attention16_cls<6>(qkv, out, size, B, N, H, st); break;
+    default: launch_attention16_cls<7>(qkv, out, size, B, N, H, st); break;
+  }
+  TR_CHECK_LAUNCH("tr_attention_cls_bf16");
+  return TR_OK;
+}
 
 extern "C" int tr_attention_bf16(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B,
                                  int N, int H, tr_stream_t s) {
@@ -1212,8 +1267,7 @@ extern "C" int tr_attention_bf16(const uint16_t* qkv, uint16_t* out, float* cls_
     TR_CHECK_LAUNCH("tr_attention_bf16");
     return TR_OK;
   }
-  static const bool use_old = [] { const char* e = getenv("TR_ATT_OLD"); return e && atoi(e) != 0; }();   // lab: the 32-query kernel
-  if (!use_old) {
+  if (!att_use_old()) {
     switch ((N + 31) / 32) {
       case 1: launch_attention16<1>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
       case 2: launch_attention16<2>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;

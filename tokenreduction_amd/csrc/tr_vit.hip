@@ -132,6 +132,13 @@ int tr_mlp_fused_resid_ln_bf16_set(const uint16_t* xn, const void* packed, const
                                    const float* next_b, float eps, uint16_t* xn_next, void* scratch, size_t scratch_bytes, int M, int D, int Hd,
                                    int cset, tr_stream_t s);
 int tr_mlp_ln_wanted(int M, int D, int Hd, int have_scratch, int concurrent);         // tr_mlp_fused.hip: ... with the norm2 in front of it inside the launch (tr_set_mlp_ln)
+int tr_attention_cls_available();                                     // tr_attention.hip: tr_attention_bf16 has its CLS-only form (tr_attention_cls_bf16)
+
+// CLS tail (eval, bf16): after the last block's attention no row mixes with another one again, and the forward returns head(norm(x)[:, 0]) --
+// so from that attention's output onward only the B CLS rows are computed (see vit_forward_impl).  1 (default) / 0: today's full-width block.
+// Bit-identical either way; process-wide, read when the launches are enqueued (a captured hipGraph keeps the form it was captured with).
+static std::atomic<int> g_cls_tail{1};
+extern "C" int tr_set_cls_tail(int on) { return g_cls_tail.exchange(on != 0 ? 1 : 0); }
 
 namespace {
 
@@ -383,6 +390,7 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   if (one_memset) TR_TRY(tr_mlp_fused_zero_counters(ws + p.off_mlp_sk, p.mlp_sk_bytes, D, p.Hd, cfg->depth, s));
   int N = p.N0;
   const void* pending = nullptr;   // residual not yet added to x (the previous block's fc2 output)
+  long pending_ld = 0;             // row stride of the pending residuals at the final norm's CLS rows; 0: N * D (full-width last block)
   const float* policy_cur = nullptr;      // DyViT training: the keep policy every block attends under (all ones before the first stage)
   if (train && cfg->family == TR_FAMILY_DYVIT) {
     float* ones = reinterpret_cast<float*>(tape + tp->ones);
@@ -666,6 +674,13 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
       r = cfg->keep[i] < (N - 1) / 2 ? cfg->keep[i] : (N - 1) / 2;
     }
     const int M = B * N;
+    // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features).
+    // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
+    // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
+    // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
+    const bool cls_tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && K == 0 && r == 0 && Ks == 0 &&
+                          drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr &&
+                          g_cls_tail.load(std::memory_order_relaxed) != 0 && tr_attention_cls_available() != 0;
     if (train) {          // this block's tape slots replace the shared scratch
       const trplan::BlockTape& bt = tp->blk[i];
       xn = tape + bt.xn1; qkv = tape + bt.qkv; hbuf = tape + bt.h;
@@ -691,6 +706,26 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
     // K-Medoids: the NEXT block's clustering is seeded by the column sums of THIS block's attention (kmedoids.py:240)
     const bool want_colsum = cfg->family == TR_FAMILY_KMEDOIDS && i + 1 < cfg->depth && cfg->keep[i + 1] > 0;
     const bool masked = ats || cfg->family == TR_FAMILY_HEURISTIC;
+    if (cls_tail) {
+      // every buffer below holds B compact rows [B, D] (or [B, Hd]); the stream keeps its row stride N * D
+      uint16_t* const ao_c = static_cast<uint16_t*>(ao);
+      uint16_t* const xn_c = static_cast<uint16_t*>(xn);
+      uint16_t* const h_c = static_cast<uint16_t*>(hbuf);
+      uint16_t* const d_attn = static_cast<uint16_t*>(dbuf_shared);
+      uint16_t* const d_mlp = static_cast<uint16_t*>(dbuf2);
+      TR_TRY(tr_attention_cls_bf16(static_cast<const uint16_t*>(qkv), ao_c, (tome || masked) ? size_cur : nullptr, B, N, H, s));
+      TR_TRY(tr_gemm_bf16(ao_c, static_cast<const uint16_t*>(bw->proj_w), bw->proj_b, d_attn, nullptr, 0, B, D, D, TR_EPI_BF16, s));
+      // norm2 of x + d_attn without a stream write (lazy, as above): the final norm adds both residuals in the reference's order
+      TR_TRY(tr_layernorm2_bf16(x, (long)N * D, nullptr, 0, d_attn, D, nullptr, 0, bw->ln2_g, bw->ln2_b, xn_c, B, D, cfg->ln_eps, s));
+      // the GEMM pair, not the fused Mlp: two workgroups of that kernel would be one long latency chain (same bits: tr_mlp_fused.hip)
+      TR_TRY(tr_gemm_bf16(xn_c, static_cast<const uint16_t*>(bw->fc1_w), bw->fc1_b, h_c, nullptr, 0, B, p.Hd, D, TR_EPI_GELU_BF16, s));
+      TR_TRY(tr_gemm_bf16(h_c, static_cast<const uint16_t*>(bw->fc2_w), bw->fc2_b, d_mlp, nullptr, 0, B, D, p.Hd, TR_EPI_BF16, s));
+      pending_attn = d_attn;
+      pending = d_mlp;
+      pending_ld = D;
+      if (tokens_out) tokens_out[i] = N;
+      break;
+    }
     if (policy_cur != nullptr)       // DyViT training: softmax_with_policy in every block (dyvit.py:245-246)
       TR_TRY(tr_attention_policy_bf16(static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(ao), policy_cur, B, N, H, s));
     else
@@ -858,6 +893,7 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier -- or, headless (C == 0), the
   // normed CLS rows themselves are the output (deit_viz.py:209-212 with head = nn.Identity()): the norm writes fp32 straight into `logits`
   const bool headless = p.C == 0;
+  const long ldd_cls = pending_ld > 0 ? pending_ld : (long)N * D;
   if (train && features_out != nullptr) {
     // DyViT distillation (dyvit.py:252-258): the final norm of EVERY row is an output; the whole stream stays for its backward
     float* xfa = reinterpret_cast<float*>(tape + tp->xfin_all);
@@ -877,9 +913,9 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
     TR_TRY(tr_layernorm_bf16_to(x, (long)N * D, reinterpret_cast<float*>(tape + tp->xfinal), D, static_cast<const uint16_t*>(pending), (long)N * D,
                                 w->norm_g, w->norm_b, static_cast<uint16_t*>(xcls), B, D, cfg->ln_eps, s));
   } else if (headless) {
-    return op_ln_pending(f32, x, (long)N * D, pending, pending_attn, (long)N * D, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
+    return op_ln_pending(f32, x, (long)N * D, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
   } else {
-    TR_TRY(op_ln_pending(f32, x, (long)N * D, pending, pending_attn, (long)N * D, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
+    TR_TRY(op_ln_pending(f32, x, (long)N * D, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
   }
   TR_TRY(op_gemm(prec, xcls, w->head_w, w->head_b, logits, nullptr, 0, B, p.C, D, TR_EPI_F32, s));
   return TR_OK;

@@ -197,6 +197,23 @@ def set_mlp_ln(mode: int) -> int:
     return int(_lib.load().tr_set_mlp_ln(int(mode)))
 
 
+def set_cls_tail(on: bool) -> bool:
+    """Whether the eval executor (bf16) runs the LAST block's work after its attention -- proj, norm2, fc1, fc2 -- on the B CLS rows only, with
+    the attention computing the CLS query alone (attention_cls): the only rows the final norm and the head read.  On by default; off: the
+    full-width block.  Bit-identical.  Blocks that reduce from the attention onward, viz_mode and the fp32 / bf16x3 executors always run
+    full width.  Process-wide, read when the launches are enqueued: a captured hipGraph keeps the form it was captured with (drop
+    `model._ws` to re-capture).  Returns the previous setting."""
+    return bool(_lib.load().tr_set_cls_tail(1 if on else 0))
+
+
+def attention_cls(qkv: torch.Tensor, B: int, N: int, H: int, size: torch.Tensor = None) -> torch.Tensor:
+    """Row 0 of every image of attention(qkv, B, N, H, size=size)[0], bit for bit, computing the first query block only -> bf16 [B, H*64]."""
+    out = torch.empty(B, H * 64, dtype=torch.bfloat16, device=qkv.device)
+    _lib.check(_lib.load().tr_attention_cls_bf16(_dev(qkv, torch.bfloat16, "qkv"), out.data_ptr(), _opt(size, torch.float32, "size"), B, N, H,
+                                                 _stream()), "tr_attention_cls_bf16")
+    return out
+
+
 def mlp_fused_ln(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, packed: torch.Tensor,
                  fc1_b: torch.Tensor, out: torch.Tensor = None, streamk: bool = True) -> torch.Tensor:
     """topk.py:95's `self.mlp(self.norm2(x))` in one launch: Mlp(LayerNorm(x + delta)) with x the fp32 stream [M,D] and delta the pending
