@@ -472,7 +472,7 @@ int tr_rownorm_bwd(const float* x, const float* da, const uint16_t* db, float* d
 int tr_add_into_bf16(const float* a, uint16_t* y, size_t n, tr_stream_t s);
 
 int tr_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* scale, int B, int rows, int D, tr_stream_t s);   /* dst[b,r,:] = src[b,r,:] * scale[b] */
-int tr_reduce_partials_f32(const float* part, int S, size_t count, float* dst, int accumulate, tr_stream_t s);   /* dst (+)= sum_s part[s] */
+int tr_reduce_partials_f32(const float* part, int S, size_t count, float* dst, int accumulate, tr_stream_t s);   /* dst (+)= sum_s part[s], in a fixed order that is not sequential in s: four interleaved lanes, see csrc/tr_backward.hip */
 /* ---- DyViT training pieces (csrc/tr_dyvit_train.hip, csrc/tr_attention_bwd.hip): see the file headers.  policy / prev / outputs are
  * fp32 [B,N] with entry 0 = the CLS token (always 1); gumbel fp32 [B,N-1,2]. */
 int tr_pool_policy(uint16_t* h, const float* policy, int B, int N, int C, float eps, tr_stream_t s);

@@ -157,6 +157,22 @@ def test_argument_validation_without_gpu():
     assert lib.tr_adamw_step(None, None, 1, 1, 0.9, 0.999, 1e-8, 0.1, 0.03, z8, z8, 0, None) == -3                    # null item table
     assert lib.tr_adamw_step(p, p, 0, 0, 0.9, 0.999, 1e-8, 0.1, 0.03, z8, z8, 0, None) == -1                          # nothing to update
     assert lib.tr_adamw_step(p, p, 1, 1, 0.9, 0.999, 1e-8, 0.0, 0.03, z8, z8, 0, None) == -1                          # bias correction 0: a step count of 0
+    # the training glue: policy-gradient sums and dropout check their arguments before the launch
+    assert lib.tr_head_sum(None, p, 1, 1, 1, None) == -3 and lib.tr_head_sum(p, None, 1, 1, 1, None) == -3
+    assert lib.tr_head_sum(p, p, 0, 6, 197, None) == -1 and lib.tr_head_sum(p, p, 2, 0, 197, None) == -1 and lib.tr_head_sum(p, p, 2, 6, -1, None) == -1
+    assert lib.tr_fill_f32(None, 1.0, 4, None) == -3 and lib.tr_fill_f32(p, 1.0, 0, None) == -1                       # n = 0: a zero-sized grid
+    assert lib.tr_add_patch_rows(None, p, 1, 2, None) == -3 and lib.tr_add_patch_rows(p, None, 1, 2, None) == -3
+    assert lib.tr_add_patch_rows(p, p, 0, 197, None) == -1 and lib.tr_add_patch_rows(p, p, 2, 1, None) == -1          # N = 1: no patch row
+    assert lib.tr_dropout_bf16(None, p, p, 1.0, 8, None) == -3 and lib.tr_dropout_f32(p, p, None, 1.0, 4, None) == -3
+    assert lib.tr_dropout_bf16(p, p, p, 1.0, 12, None) == -1 and lib.tr_dropout_bf16(p, p, p, 1.0, 0, None) == -1      # n % 8
+    assert lib.tr_dropout_f32(p, p, p, 1.0, 6, None) == -1                                                            # n % 4
+    assert lib.tr_dropout_bf16(p + 8, p, p, 1.0, 8, None) == -2 and lib.tr_dropout_bf16(p, p + 8, p, 1.0, 8, None) == -2   # data off 16 bytes
+    assert lib.tr_dropout_bf16(p, p, p + 4, 1.0, 8, None) == -2                                                       # mask off 8 bytes
+    assert lib.tr_dropout_f32(p + 4, p, p, 1.0, 4, None) == -2 and lib.tr_dropout_f32(p, p, p + 2, 1.0, 4, None) == -2     # mask off 4 bytes
+    assert lib.tr_rowscale_bf16(p, p, p, 2, 3, 12, None) == -1                                                        # D % 8
+    need = lib.tr_dyvit_decide_bwd_workspace_floats(2, 50, 48)
+    assert need == ((2 * 50 + 15) // 16 + 1) * (2 * 48 + 4) == 800
+    assert lib.tr_dyvit_decide_bwd(p, p, p, p, p, p, 48, p, p, p, p, p, 0, p, need - 1, 2, 50, 48, None) == -1          # workspace one float short
 
 
 def test_fused_adamw_refuses_what_it_does_not_build():

@@ -1464,6 +1464,9 @@ extern "C" int tr_ats_scatter(const float* g, const uint16_t* dao_s, const int32
 }
 
 // dst[e] = (accumulate ? dst[e] : 0) + sum_{s < S} part[s][e]: the deterministic second stage of the two-stage reductions
+// The order is fixed but NOT sequential in s (partial_reduce_kernel): lane y of four adds partials y, y + 4, y + 8, ... -- for whole groups of
+// four elements sixteen partials at a time as (v0 + v1) + (v2 + v3), for the ragged last group one by one --, the result is
+// ((lane0 + lane1) + lane2) + lane3, and the destination is added LAST when accumulating.
 extern "C" int tr_reduce_partials_f32(const float* part, int S, size_t count, float* dst, int accumulate, tr_stream_t s) {
   TR_REQUIRE(part && dst && S >= 1 && count >= 1, TR_ERR_NULL, "tr_reduce_partials_f32: bad arguments");
   reduce_partials(part, S, count, dst, accumulate, static_cast<hipStream_t>(s));

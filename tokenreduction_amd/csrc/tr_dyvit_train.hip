@@ -47,6 +47,9 @@ __global__ __launch_bounds__(256) void pool_policy_kernel(uint16_t* __restrict__
 //   the CLS row included in the forward's layout but its gradient is zero by construction)
 //   d h0[p,c] = G_c pol_p / S;   d pol_p = sum_c G_c (h0[p,c] - glob_c + eps) / S
 // h0's global half was overwritten by the broadcast, so it is recomputed from the saved pre-activation (same GELU fit as the forward).
+// The recomputed value stays in fp32: it is NOT rounded to bf16 as the rows the forward pooled were, so d policy differs from the gradient
+// of the forward as computed by that rounding -- 0.2-0.4 % relative L2 per image (tests/test_hip_dyvit_train_ops.py); whether that matters
+// to training has not been measured.
 // One workgroup per image; phase 1: G_c (thread per channel pair), phase 2: one wave per row.
 __global__ __launch_bounds__(256) void pool_policy_bwd_kernel(const uint16_t* __restrict__ dcat, const uint16_t* __restrict__ pre0,
                                                               const uint16_t* __restrict__ cat, const float* __restrict__ policy,
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(256) void pool_policy_bwd_kernel(const uint16_t* __
       dh[e + Ch + c] = (uint16_t)(pack_bf16x2(n == 0 ? 0.f : g * p * invS, 0.f) & 0xffffu);
       if (n > 0) {
         const f32x2 hv = gelu2(f32x2{bf16_bits_to_f32(pre0[e + Ch + c]), 0.f});
-        dp += g * (hv[0] - sGl[c]);                      // sGl = glob + eps (1e-6: below the bf16 resolution of the broadcast value)
+        dp += g * (hv[0] - sGl[c]);                      // hv: fp32, not bf16-rounded; sGl = glob + eps (1e-6: below the bf16 resolution of the broadcast value)
       }
     }
     dp = wave_sum(dp);
@@ -328,6 +331,7 @@ extern "C" int tr_dyvit_decide_bwd(const float* dkeep, const float* prev, const 
 // dst[b][n] += sum_h part[b][h][n]  (the per-head policy gradients of tr_attention_policy_bwd_bf16)
 extern "C" int tr_head_sum(const float* part, float* dst, int B, int H, int N, tr_stream_t s) {
   TR_REQUIRE(part && dst, TR_ERR_NULL, "tr_head_sum: null pointer");
+  TR_REQUIRE(B > 0 && H > 0 && N > 0, TR_ERR_SHAPE, "tr_head_sum: bad shape B=%d H=%d N=%d", B, H, N);
   hipLaunchKernelGGL(head_sum_kernel, dim3((B * N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(s), part, dst, B, H, N);
   TR_CHECK_LAUNCH("tr_head_sum");
   return TR_OK;
@@ -335,6 +339,7 @@ extern "C" int tr_head_sum(const float* part, float* dst, int B, int H, int N, t
 
 extern "C" int tr_fill_f32(float* p, float v, size_t n, tr_stream_t s) {
   TR_REQUIRE(p, TR_ERR_NULL, "tr_fill_f32: null pointer");
+  TR_REQUIRE(n > 0, TR_ERR_SHAPE, "tr_fill_f32: nothing to fill");
   hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(s), p, v, n);
   TR_CHECK_LAUNCH("tr_fill_f32");
   return TR_OK;
@@ -342,6 +347,7 @@ extern "C" int tr_fill_f32(float* p, float v, size_t n, tr_stream_t s) {
 
 extern "C" int tr_add_patch_rows(float* dst, const float* src, int B, int N, tr_stream_t s) {
   TR_REQUIRE(dst && src, TR_ERR_NULL, "tr_add_patch_rows: null pointer");
+  TR_REQUIRE(B > 0 && N >= 2, TR_ERR_SHAPE, "tr_add_patch_rows: bad shape B=%d N=%d", B, N);
   hipLaunchKernelGGL(add_rows_kernel, dim3((B * N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(s), dst, src, B, N);
   TR_CHECK_LAUNCH("tr_add_patch_rows");
   return TR_OK;

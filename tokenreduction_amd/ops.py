@@ -6,6 +6,8 @@ on a ROCm device -- there is no CPU path.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -974,7 +976,6 @@ def linear_bwd_group(layers, accumulate: bool = False, outs=None):
     """Weight and bias gradients of up to four Linear layers in ONE weight-gradient launch + one reduce (tr_linear_bwd_group).
     layers: [(dy bf16 [M_i, N_i], x bf16 [M_i, K_i]), ...]; returns [(dW_i fp32 [N_i, K_i], db_i fp32 [N_i]), ...]; outs: the same list
     of destination tensors when accumulating."""
-    import ctypes
     lib = _lib.load()
     n = len(layers)
     if not 1 <= n <= 4:
@@ -991,3 +992,222 @@ def linear_bwd_group(layers, accumulate: bool = False, outs=None):
     ws = _ws(lib.tr_linear_bwd_group_workspace_floats(ctypes.cast(arr, ctypes.c_void_p), n), dev)
     _lib.check(lib.tr_linear_bwd_group(ctypes.cast(arr, ctypes.c_void_p), n, int(accumulate), ws.data_ptr(), ws.numel(), _stream()), "tr_linear_bwd_group")
     return outs
+
+
+# ---------------------------------------------------------------------------------------- DyViT training pieces (csrc/tr_dyvit_train.hip)
+def pool_policy(h: torch.Tensor, policy: torch.Tensor, B: int, N: int, eps: float = 1e-6) -> torch.Tensor:
+    """PredictorLG global feature under a policy (dyvit.py:115-118), in place on h bf16 [B*N, C]: channels C/2.. of every row :=
+    sum_p h[p] policy[p] / sum_p policy[p] + eps over the image's patch rows.  policy fp32 [B,N] (entry 0 = CLS, not read)."""
+    C_ = h.shape[-1]
+    _same_device(h, policy)
+    _lib.check(_lib.load().tr_pool_policy(_dev(h, torch.bfloat16, "h"), _dev(policy, torch.float32, "policy"), B, N, C_, float(eps), _stream(h)),
+               "tr_pool_policy")
+    return h
+
+
+def _view_ptr(t: torch.Tensor, dtype, name: str) -> int:
+    """Pointer of a dense tensor that may start anywhere inside a larger buffer (a view): for the entry points that choose a kernel by
+    the alignment of their operands."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; tokenreduction_amd has no CPU path (HIP kernels only)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: tensor must be contiguous")
+    return t.data_ptr()
+
+
+def pool_policy_bwd(dcat: torch.Tensor, pre0: torch.Tensor, cat: torch.Tensor, policy: torch.Tensor, dpolicy: torch.Tensor, B: int, N: int,
+                    dh: torch.Tensor = None) -> torch.Tensor:
+    """Backward of pool_policy: dcat bf16 [B*N, C] (gradient wrt [local | global]), pre0 the saved pre-activation, cat the forward's
+    output -> dh bf16 [B*N, C] (wrt the GELU output); dpolicy fp32 [B,N] += (entry 0 untouched)."""
+    C_ = dcat.shape[-1]
+    _same_device(dcat, pre0, cat, policy, dpolicy, dh)
+    if dh is None:
+        dh = torch.empty(B * N, C_, dtype=torch.bfloat16, device=dcat.device)
+    _lib.check(_lib.load().tr_pool_policy_bwd(_view_ptr(dcat, torch.bfloat16, "dcat"), _view_ptr(pre0, torch.bfloat16, "pre0"),
+                                              _view_ptr(cat, torch.bfloat16, "cat"), _dev(policy, torch.float32, "policy"),
+                                              _view_ptr(dh, torch.bfloat16, "dh"), _dev(dpolicy, torch.float32, "dpolicy"), B, N, C_, _stream(dcat)),
+               "tr_pool_policy_bwd")
+    return dh
+
+
+def dyvit_decide(h2: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, gumbel: torch.Tensor, prev: torch.Tensor, B: int, N: int, C: int,
+                 outs=None):
+    """out_conv.4 + LogSoftmax + F.gumbel_softmax(hard=True)[..., 0] * prev_decision (dyvit.py:108-109, 223-224): h2 bf16 [B*N, ldh]
+    (first C columns), w fp32 [2,C], gumbel fp32 [B,N-1,2], prev fp32 [B,N] -> (policy_out, ysoft0, sm0, hard0) fp32 [B,N]; CLS entries:
+    policy_out 1, the others not written.  outs: the four destinations (tests prefill them)."""
+    ldh = h2.shape[-1]
+    _same_device(h2, w, bias, gumbel, prev)
+    if outs is None:
+        outs = tuple(torch.zeros(B, N, dtype=torch.float32, device=h2.device) for _ in range(4))
+    _lib.check(_lib.load().tr_dyvit_decide(_dev(h2, torch.bfloat16, "h2"), ldh, _dev(w, torch.float32, "w"), _dev(bias, torch.float32, "bias"),
+                                           _dev(gumbel, torch.float32, "gumbel"), _dev(prev, torch.float32, "prev"),
+                                           *(_dev(t, torch.float32, "out") for t in outs), B, N, C, _stream(h2)), "tr_dyvit_decide")
+    return outs
+
+
+def dyvit_decide_bwd(dkeep, prev, hard0, ysoft0, sm0, h2, w, dprev, B: int, N: int, C: int, dw=None, db=None, accumulate: bool = False,
+                     ws: torch.Tensor = None):
+    """Backward of dyvit_decide: dkeep fp32 [B,N] -> (dh2 bf16 [B*N, ldh], dW3 fp32 [2,C], db3 fp32 [2]); dprev fp32 [B,N] += dkeep * hard0
+    (CLS entries untouched).  ws: the workspace (tr_dyvit_decide_bwd_workspace_floats), allocated when None."""
+    ldh = h2.shape[-1]
+    _same_device(dkeep, prev, hard0, ysoft0, sm0, h2, w, dprev, dw, db, ws)
+    lib = _lib.load()
+    dev = h2.device
+    dh2 = torch.empty(B * N, ldh, dtype=torch.bfloat16, device=dev)
+    dw = torch.empty(2, C, dtype=torch.float32, device=dev) if dw is None else dw
+    db = torch.empty(2, dtype=torch.float32, device=dev) if db is None else db
+    if ws is None:
+        ws = torch.empty(lib.tr_dyvit_decide_bwd_workspace_floats(B, N, C), dtype=torch.float32, device=dev)
+    _lib.check(lib.tr_dyvit_decide_bwd(_dev(dkeep, torch.float32, "dkeep"), _dev(prev, torch.float32, "prev"), _dev(hard0, torch.float32, "hard0"),
+                                       _dev(ysoft0, torch.float32, "ysoft0"), _dev(sm0, torch.float32, "sm0"), _dev(h2, torch.bfloat16, "h2"), ldh,
+                                       _dev(w, torch.float32, "w"), dh2.data_ptr(), _dev(dprev, torch.float32, "dprev"),
+                                       _dev(dw, torch.float32, "dw"), _dev(db, torch.float32, "db"), int(accumulate), ws.data_ptr(), ws.numel(),
+                                       B, N, C, _stream(h2)), "tr_dyvit_decide_bwd")
+    return dh2, dw, db
+
+
+def head_sum(part: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """dst fp32 [B,N] += sum over the heads (in index order) of part fp32 [B,H,N]."""
+    B, H, N = part.shape
+    _same_device(part, dst)
+    _lib.check(_lib.load().tr_head_sum(_dev(part, torch.float32, "part"), _dev(dst, torch.float32, "dst"), B, H, N, _stream(part)), "tr_head_sum")
+    return dst
+
+
+def add_patch_rows(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    """dst fp32 [B,N][:, 1:] += src fp32 [B,N-1]; column 0 (the CLS entry) untouched."""
+    B, N = dst.shape
+    _same_device(dst, src)
+    _lib.check(_lib.load().tr_add_patch_rows(_dev(dst, torch.float32, "dst"), _dev(src, torch.float32, "src"), B, N, _stream(dst)),
+               "tr_add_patch_rows")
+    return dst
+
+
+def fill_f32(t: torch.Tensor, value: float, n: int = None) -> torch.Tensor:
+    """The first n (default: all) elements of fp32 t := value."""
+    _lib.check(_lib.load().tr_fill_f32(_dev(t, torch.float32, "t"), float(value), t.numel() if n is None else int(n), _stream(t)), "tr_fill_f32")
+    return t
+
+
+# ---------------------------------------------------------------------------------------- training glue (csrc/tr_backward.hip, csrc/tr_norm.hip)
+def dropout(src: torch.Tensor, keep: torch.Tensor, mul: float, dst: torch.Tensor = None, n: int = None) -> torch.Tensor:
+    """nn.Dropout with the caller's keep mask (uint8, non-zero = keep): dst = keep ? src * mul : 0 on the first n elements; bf16 or fp32;
+    dst may be src (the executor's form)."""
+    if src.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("src must be bf16 or fp32")
+    dst = torch.empty_like(src) if dst is None else dst
+    _same_device(src, keep, dst)
+    lib = _lib.load()
+    fn = lib.tr_dropout_f32 if src.dtype == torch.float32 else lib.tr_dropout_bf16
+    _lib.check(fn(_view_ptr(src, src.dtype, "src"), _view_ptr(dst, src.dtype, "dst"), _view_ptr(keep, torch.uint8, "keep"), float(mul),
+                  src.numel() if n is None else int(n), _stream(src)), "tr_dropout")
+    return dst
+
+
+def rowscale(src: torch.Tensor, scale: torch.Tensor, dst: torch.Tensor = None) -> torch.Tensor:
+    """DropPath's per-image scaling: dst[b, r, :] = src[b, r, :] * scale[b], bf16 [B, rows, D]; dst may be src."""
+    B, rows, D = src.shape
+    dst = torch.empty_like(src) if dst is None else dst
+    _same_device(src, dst, scale)
+    _lib.check(_lib.load().tr_rowscale_bf16(_dev(src, torch.bfloat16, "src"), _dev(dst, torch.bfloat16, "dst"), _dev(scale, torch.float32, "scale"),
+                                            B, rows, D, _stream(src)), "tr_rowscale_bf16")
+    return dst
+
+
+def f32_to_bf16(src: torch.Tensor) -> torch.Tensor:
+    dst = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+    _lib.check(_lib.load().tr_f32_to_bf16(_dev(src, torch.float32, "src"), dst.data_ptr(), src.numel(), _stream(src)), "tr_f32_to_bf16")
+    return dst
+
+
+def reduce_partials(part: torch.Tensor, dst: torch.Tensor = None, accumulate: bool = False) -> torch.Tensor:
+    """dst fp32 [count] (+)= sum_s part fp32 [S, count], in the kernel's fixed order."""
+    S, count = part.shape
+    dst = torch.empty(count, dtype=torch.float32, device=part.device) if dst is None else dst
+    _same_device(part, dst)
+    _lib.check(_lib.load().tr_reduce_partials_f32(_dev(part, torch.float32, "part"), S, count, _dev(dst, torch.float32, "dst"), int(accumulate),
+                                                  _stream(part)), "tr_reduce_partials_f32")
+    return dst
+
+
+def _rows2d(t, dtype, name):
+    """(pointer, row stride) of a 2-D operand that may be a column slice of a wider tensor (unit column stride)."""
+    if t.dim() != 2 or t.stride(1) != 1 or not t.is_cuda or t.dtype != dtype:
+        raise ValueError(f"{name}: expected a 2-D {dtype} device tensor with unit column stride")
+    return t.data_ptr(), t.stride(0)
+
+
+def layernorm_to(x: torch.Tensor, x_out: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None) -> torch.Tensor:
+    """layernorm out of place (tr_layernorm_bf16_to): x_out = x + delta, y = LayerNorm(x_out) -> bf16 [M,D]; x is not written.  x, x_out
+    (fp32) and delta (bf16) are [M,D] rows, possibly column slices of wider tensors."""
+    M, D = x.shape
+    _same_device(x, x_out, gamma, beta, delta)
+    (px, ldx), (po, ldo) = _rows2d(x, torch.float32, "x"), _rows2d(x_out, torch.float32, "x_out")
+    pd, ldd = _rows2d(delta, torch.bfloat16, "delta") if delta is not None else (None, D)
+    y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().tr_layernorm_bf16_to(px, ldx, po, ldo, pd, ldd, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+                                                y.data_ptr(), M, D, eps, _stream(x)), "tr_layernorm_bf16_to")
+    return y
+
+
+def layernorm_bf16_f32(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None, delta2: torch.Tensor = None,
+                       x_out: torch.Tensor = None) -> torch.Tensor:
+    """The bf16 path's LayerNorm with fp32 output (tr_layernorm_bf16_f32): y fp32 [M,D] = LayerNorm((x + delta) + delta2); the sum goes to
+    x_out (x itself: in place; None: not written)."""
+    M, D = x.shape
+    _same_device(x, gamma, beta, delta, delta2, x_out)
+    y = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().tr_layernorm_bf16_f32(_dev(x, torch.float32, "x"), D, _opt(x_out, torch.float32, "x_out"), D,
+                                                 _opt(delta, torch.bfloat16, "delta"), D, _opt(delta2, torch.bfloat16, "delta2"), D,
+                                                 _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps,
+                                                 _stream(x)), "tr_layernorm_bf16_f32")
+    return y
+
+
+def residual_snapshot(x: torch.Tensor, delta: torch.Tensor = None) -> torch.Tensor:
+    """out fp32 = x + delta (bf16 or fp32, or None: a copy)."""
+    out = torch.empty_like(x)
+    _same_device(x, delta)
+    if delta is not None and delta.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("delta must be bf16 or fp32")
+    _lib.check(_lib.load().tr_residual_snapshot(_dev(x, torch.float32, "x"), None if delta is None else _dev(delta, delta.dtype, "delta"),
+                                                int(delta is not None and delta.dtype == torch.float32), out.data_ptr(), x.numel(), _stream(x)),
+               "tr_residual_snapshot")
+    return out
+
+
+def broadcast_rows(src: torch.Tensor, B: int) -> torch.Tensor:
+    """dst fp32 [B,N] = src fp32 [N] in every row."""
+    N = src.numel()
+    dst = torch.empty(B, N, dtype=torch.float32, device=src.device)
+    _lib.check(_lib.load().tr_broadcast_rows(_dev(src, torch.float32, "src"), dst.data_ptr(), B, N, _stream(src)), "tr_broadcast_rows")
+    return dst
+
+
+class _CastItem(ctypes.Structure):          # tr_cast_item
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("dst_t", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int)]
+
+
+def cast_pack(items) -> None:
+    """fp32 master weights -> bf16 operand copies, every item in ONE launch (tr_cast_pack_bf16).  items: [(src fp32 [rows, cols],
+    dst bf16 [rows, cols] | None, dst_t bf16 [cols, rows] | None), ...]; the tensors may be views that start anywhere in a buffer.
+    For tests: the item table is built and uploaded per call and the stream is synchronised before it is freed (the models keep a
+    persistent table, models.py)."""
+    n = len(items)
+    arr = (_CastItem * n)()
+    first = [0]
+    for i, (src, dst, dst_t) in enumerate(items):
+        rows, cols = src.shape
+        _same_device(src, dst, dst_t, items[0][0])
+        if dst is not None and tuple(dst.shape) != (rows, cols) or dst_t is not None and tuple(dst_t.shape) != (cols, rows):
+            raise ValueError(f"cast_pack: item {i}: destinations do not fit a [{rows}, {cols}] source")
+        arr[i] = _CastItem(_view_ptr(src, torch.float32, "src"), None if dst is None else _view_ptr(dst, torch.bfloat16, "dst"),
+                           None if dst_t is None else _view_ptr(dst_t, torch.bfloat16, "dst_t"), rows, cols)
+        first.append(first[-1] + ((rows + 63) // 64) * ((cols + 63) // 64))
+    dev = items[0][0].device
+    d_items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    d_first = torch.tensor(first, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tr_cast_pack_bf16(d_items.data_ptr(), d_first.data_ptr(), n, first[-1], _stream(items[0][0])), "tr_cast_pack_bf16")
+    torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch
