@@ -81,6 +81,33 @@ int tr_im2col_u8_f32(const uint8_t* img, const float* lut, int layout, float* co
 int tr_patch_embed_u8_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls_token,
                            const float* pos_embed, float* x, int B, int C, int HW, int patch, int D, tr_stream_t s);
 
+/* Train-time augmentation of a uint8 batch on the device: RandomErasing (datasets.py:93-95, per image, before mixing) and timm's Mixup
+ * (mixup / cutmix, engine.py:47-48), applied to the normalized values while the image is unfolded.  The batch B is even and image b's
+ * partner is j = B - 1 - b (timm's x.flip(0)).  One record per image, a DEVICE array of B records, 16-byte aligned:
+ *   src(i,c,y,x) = noise[noise_off_i + (c*eh_i + (y - ey_i))*ew_i + (x - ex_i)]  if erased_i and (y,x) inside [ey_i, ey_i+eh_i) x [ex_i, ex_i+ew_i)
+ *                = lut[c][img[i,c,y,x]]                                          otherwise
+ *   kind 0: out = src(b)    kind 1: out = rn(rn(src(b)*lam) + rn(src(j)*oml))  (fp32; two roundings and an add, never an fma; lam and oml
+ *   are independent numbers)    kind 2: out = src(j) inside [yl,yh) x [xl,xh), src(b) outside.
+ * noise: one packed fp32 device buffer of noise_len floats; an erased image owns a [C, eh, ew] block at noise_off (NULL allowed when
+ * noise_len == 0).  Boxes are clamped to the image and a noise index outside [0, noise_len) reads as 0.0f: a wrong table gives wrong
+ * pixels, never a read outside the buffers.  A table of all-zero records gives the bits of tr_im2col_u8_bf16.
+ * tr_im2col_u8_aug_bf16: the columns of tr_im2col_u8_bf16 for the augmented image.  tr_pixels_augment_f32: the augmented image itself,
+ * fp32 [B,C,H,W] (NCHW whatever the input layout) -- what the float pipeline would hold.  Both refuse the shapes tr_im2col_u8_* refuses
+ * and an odd B (TR_ERR_SHAPE). */
+typedef struct tr_augment_rec {
+  int32_t kind;                 /* 0 none, 1 blend (mixup), 2 paste (cutmix) */
+  float lam, oml;               /* kind 1: the two fp32 factors */
+  int32_t yl, yh, xl, xh;       /* kind 2: the box pasted from the partner */
+  int32_t erased;               /* non-zero: this image has an erase box */
+  int32_t ey, eh, ex, ew;       /* erase box: top, height, left, width */
+  int64_t noise_off;            /* first float of this image's [C, eh, ew] block in `noise` */
+  int32_t reserved_[2];         /* pads the record to 64 bytes (one cache line per image) */
+} tr_augment_rec;
+int tr_im2col_u8_aug_bf16(const uint8_t* img, const float* lut, int layout, const tr_augment_rec* aug, const float* noise, long noise_len,
+                          uint16_t* cols, int B, int C, int H, int W, int patch, tr_stream_t s);
+int tr_pixels_augment_f32(const uint8_t* img, const float* lut, int layout, const tr_augment_rec* aug, const float* noise, long noise_len,
+                          float* out, int B, int C, int H, int W, int patch, tr_stream_t s);
+
 /* a3/a4 Linear layers (nn.Linear: y = x W^T + b, W is [N,K] row-major like the state dict).
  * A bf16 [M,K], W bf16 [N,K], bias fp32 [N]; K % 64 == 0, N % 4 == 0.  `out` dtype/meaning per epilogue;
  * aux/aux_i only for TR_EPI_PATCH_F32. */
@@ -660,6 +687,13 @@ int tr_vit_forward_train_pixels(const tr_vit_config* cfg, const tr_vit_weights* 
                                 float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
                                 float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
                                 float drop_rate);
+/* tr_vit_forward_train_pixels with the device-side augmentation of tr_im2col_u8_aug_bf16: input_format is one of the uint8 formats, B is
+ * even, aug / aug_noise / aug_noise_len are that call's table and noise.  The tape's column matrix (the patch GEMM's operand and
+ * PatchEmbed's weight-gradient operand) is that of the augmented image, so tr_vit_backward needs nothing else. */
+int tr_vit_forward_train_aug(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                             const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len, float* logits, void* workspace,
+                             size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,
+                             const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate);
 /* Dropout (timm's drop_rate, train.py:46 --drop: pos_drop topk.py:186, proj_drop :53, the Mlp's two nn.Dropout): dropout_keep (nullable
  * = drop_rate 0; both calls get the same) is the caller's keep mask, 1 byte per element (non-zero = keep), tr_vit_dropout_mask_bytes()
  * bytes in the order the forward consumes them -- the embedded tokens [B,N0,D], then per block proj's output rows, the Mlp's hidden

@@ -47,6 +47,12 @@ class TrVitConfig(C.Structure):
                 ("kmed_init", _i * TR_MAX_DEPTH), ("ats_dynamic", _i), ("concurrent", _i)]
 
 
+class TrAugmentRec(C.Structure):     # tr_augment_rec: one image of the device-side erase / mixup / cutmix table (64 bytes)
+    _fields_ = [("kind", C.c_int32), ("lam", _f), ("oml", _f), ("yl", C.c_int32), ("yh", C.c_int32), ("xl", C.c_int32), ("xh", C.c_int32),
+                ("erased", C.c_int32), ("ey", C.c_int32), ("eh", C.c_int32), ("ex", C.c_int32), ("ew", C.c_int32), ("noise_off", C.c_int64),
+                ("reserved_", C.c_int32 * 2)]
+
+
 class TrLinearGrad(C.Structure):     # tr_linear_grad: one layer of tr_linear_bwd_group
     _fields_ = [("dY", _vp), ("ldy", _l), ("X", _vp), ("ldx", _l), ("dW", _vp), ("db", _vp), ("M", _i), ("N", _i), ("K", _i)]
 
@@ -85,6 +91,8 @@ SIGNATURES = {
     "tr_patch_embed_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_im2col_u8_aug_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_pixels_augment_f32": (_i, [_vp, _vp, _i, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_patch_embed_u8_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_gemm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_mlp_fused_supported": (_i, [_i, _i]),
@@ -190,6 +198,8 @@ SIGNATURES = {
                                    C.POINTER(_i), _i, _vp]),
     "tr_vit_forward_train_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
                                          C.POINTER(_i), _i, _vp, _vp, _f]),
+    "tr_vit_forward_train_aug": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,
+                                      _vp, _vp, C.POINTER(_i), _i, _vp, _vp, _f]),
 }
 
 _lib = None

@@ -337,6 +337,104 @@ __global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restric
   }
 }
 
+// ---- device-side RandomErasing + mixup / cutmix on raw uint8 pixels (tr_augment_rec, one record per image) ----
+// src(i, c, y, x0 .. x0+7): image i's normalized pixels (the LUT gather of im2col_u8_kernel), with image i's erase box pasted over them
+// from its [C, eh, ew] block of `noise`.  Every comparison is against the pixel's own coordinates, which lie inside the image, so a box that
+// sticks out of the image is clamped by construction; the noise index is formed in unsigned 64-bit arithmetic (no signed overflow on a wild
+// record) and anything outside [0, noise_len) reads as 0.0f.
+template <bool NHWC>
+__device__ __forceinline__ void aug_src8(const uint8_t* __restrict__ img, const float* __restrict__ lc, const tr_augment_rec* __restrict__ r,
+                                         const float* __restrict__ noise, unsigned long long noise_len, int i, int c, int C, int H, int W,
+                                         int y, int x0, float (&v)[8]) {
+  if (NHWC) {
+    const uint8_t* src = img + (((size_t)i * H + y) * W + x0) * C + c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = lc[src[(size_t)k * C]];
+  } else {
+    const uint2 u = *reinterpret_cast<const uint2*>(img + (((size_t)i * C + c) * H + y) * W + x0);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = lc[((k < 4 ? u.x : u.y) >> (8 * (k & 3))) & 0xffu];
+  }
+  if (r->erased == 0) return;
+  const long long ey = r->ey, eh = r->eh, ex = r->ex, ew = r->ew;
+  if (eh <= 0 || ew <= 0 || y < ey || y >= ey + eh || x0 + 8 <= ex || x0 >= ex + ew) return;
+  const unsigned long long row = (unsigned long long)r->noise_off +
+                                 ((unsigned long long)c * (unsigned long long)eh + (unsigned long long)(y - ey)) * (unsigned long long)ew;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const long long x = x0 + k;
+    if (x >= ex && x < ex + ew) {
+      const unsigned long long idx = row + (unsigned long long)(x - ex);
+      v[k] = idx < noise_len ? noise[idx] : 0.0f;
+    }
+  }
+}
+
+// a * b rounded to fp32 on its own: the library is built with -ffp-contract=fast, under which a plain product (and __fmul_rn, which is one)
+// fuses with the add that follows; the multiply as an instruction the compiler does not look into cannot.
+__device__ __forceinline__ float mul_rn_unfused(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// The unfold of im2col_u8_kernel (one thread = 8 consecutive pixels of one patch row) over the augmented source: image b with its partner
+// j = B - 1 - b (timm's x.flip(0)).  kind 1: rn(rn(src(b) * lam) + rn(src(j) * oml)), two roundings and an add, never an fma; kind 2: src(j)
+// inside [yl,yh) x [xl,xh).  The partner's run is read only where the output needs it.  IMG: the fp32 [B,C,H,W] image instead of columns.
+template <bool IMG, bool NHWC>
+__global__ __launch_bounds__(256) void im2col_u8_aug_kernel(const uint8_t* __restrict__ img, const float* __restrict__ lut,
+                                                            const tr_augment_rec* __restrict__ recs, const float* __restrict__ noise,
+                                                            unsigned long long noise_len, void* __restrict__ out, int B, int C, int H, int W,
+                                                            int patch, long total) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int per_row = patch >> 3;
+  const int kcols = C * patch * patch;
+  const int groups_per_row = kcols >> 3;
+  const long rowid = t / groups_per_row;
+  const int g = (int)(t - rowid * groups_per_row);
+  const int gw = W / patch, gh = H / patch;
+  const int b = (int)(rowid / (gh * gw));
+  const int pp = (int)(rowid - (long)b * gh * gw);
+  const int py = pp / gw, px = pp - py * gw;
+  const int c = g / (patch * per_row);
+  const int rem = g - c * patch * per_row;
+  const int iy = rem / per_row, ixg = rem - iy * per_row;
+  const int y = py * patch + iy, x0 = px * patch + ixg * 8;
+  const float* lc = lut + c * 256;
+  const tr_augment_rec* rb = recs + b;
+  const int j = B - 1 - b;
+  float v[8];
+  aug_src8<NHWC>(img, lc, rb, noise, noise_len, b, c, C, H, W, y, x0, v);
+  const int kind = rb->kind;
+  if (kind == 1) {
+    const float lam = rb->lam, oml = rb->oml;
+    float u[8];
+    aug_src8<NHWC>(img, lc, recs + j, noise, noise_len, j, c, C, H, W, y, x0, u);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = mul_rn_unfused(v[k], lam) + mul_rn_unfused(u[k], oml);
+  } else if (kind == 2) {
+    const int yl = rb->yl, yh = rb->yh, xl = rb->xl, xh = rb->xh;
+    if (y >= yl && y < yh && x0 + 8 > xl && x0 < xh) {
+      float u[8];
+      aug_src8<NHWC>(img, lc, recs + j, noise, noise_len, j, c, C, H, W, y, x0, u);
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (x0 + k >= xl && x0 + k < xh) v[k] = u[k];
+    }
+  }
+  if (IMG) {
+    float* o = reinterpret_cast<float*>(out) + (((size_t)b * C + c) * H + y) * W + x0;
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  } else {
+    uint4 pk;
+    pk.x = pack_bf16x2(v[0], v[1]); pk.y = pack_bf16x2(v[2], v[3]);
+    pk.z = pack_bf16x2(v[4], v[5]); pk.w = pack_bf16x2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(out) + rowid * kcols + (size_t)g * 8) = pk;
+  }
+}
+
 __global__ __launch_bounds__(256) void cls_pos_kernel(const float* __restrict__ cls, const float* __restrict__ pos, float* __restrict__ x,
                                                       int B, int N, int D) {
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -547,6 +645,47 @@ extern "C" int tr_im2col_u8_bf16(const uint8_t* img, const float* lut, int layou
 extern "C" int tr_im2col_u8_f32(const uint8_t* img, const float* lut, int layout, float* cols, int B, int C, int H, int W, int patch,
                                 tr_stream_t s) {
   return im2col_u8_impl(true, img, lut, layout, cols, B, C, H, W, patch, s);
+}
+
+static int im2col_u8_aug_impl(bool image, const uint8_t* img, const float* lut, int layout, const tr_augment_rec* aug, const float* noise,
+                              long noise_len, void* out, int B, int C, int H, int W, int patch, tr_stream_t s) {
+  const char* what = image ? "tr_pixels_augment_f32" : "tr_im2col_u8_aug_bf16";
+  TR_REQUIRE(img && lut && aug && out && (noise || noise_len == 0), TR_ERR_NULL, "%s: null pointer", what);
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_SHAPE, "%s: layout %d is neither NCHW (0) nor NHWC (1)", what, layout);
+  TR_REQUIRE(B > 0 && C > 0 && patch >= 8 && patch % 8 == 0 && H % patch == 0 && W % patch == 0, TR_ERR_SHAPE,
+             "%s: need patch %% 8 == 0 and H,W multiples of patch (H=%d W=%d patch=%d)", what, H, W, patch);
+  TR_REQUIRE(B % 2 == 0, TR_ERR_SHAPE, "%s: the batch must be even (image b mixes with image B - 1 - b), got B = %d", what, B);
+  TR_REQUIRE(noise_len >= 0, TR_ERR_SHAPE, "%s: noise_len %ld is negative", what, noise_len);
+  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(out) && tr_aligned16(aug), TR_ERR_ALIGN, "%s: img, the table and the output must be 16-byte aligned",
+             what);
+  TR_REQUIRE((reinterpret_cast<uintptr_t>(lut) & 3) == 0 && (reinterpret_cast<uintptr_t>(noise) & 3) == 0, TR_ERR_ALIGN,
+             "%s: lut and noise must be 4-byte aligned", what);
+  const long total = (long)B * C * H * W / 8;
+  // bytes: both images' pixels at most + the table + the output (the noise blocks are a fraction of an image)
+  tr_prof_note(image ? "pixels_augment_kernel" : "im2col_u8_aug_kernel", 0.0, (double)B * C * H * W * (image ? 6.0 : 4.0) + 64.0 * B);
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  const bool nhwc = layout == TR_LAYOUT_NHWC;
+  const unsigned long long nl = (unsigned long long)noise_len;
+  if (image && nhwc)
+    hipLaunchKernelGGL((im2col_u8_aug_kernel<true, true>), grid, dim3(256), 0, st, img, lut, aug, noise, nl, out, B, C, H, W, patch, total);
+  else if (image)
+    hipLaunchKernelGGL((im2col_u8_aug_kernel<true, false>), grid, dim3(256), 0, st, img, lut, aug, noise, nl, out, B, C, H, W, patch, total);
+  else if (nhwc)
+    hipLaunchKernelGGL((im2col_u8_aug_kernel<false, true>), grid, dim3(256), 0, st, img, lut, aug, noise, nl, out, B, C, H, W, patch, total);
+  else
+    hipLaunchKernelGGL((im2col_u8_aug_kernel<false, false>), grid, dim3(256), 0, st, img, lut, aug, noise, nl, out, B, C, H, W, patch, total);
+  TR_CHECK_LAUNCH(what);
+  return TR_OK;
+}
+
+extern "C" int tr_im2col_u8_aug_bf16(const uint8_t* img, const float* lut, int layout, const tr_augment_rec* aug, const float* noise,
+                                     long noise_len, uint16_t* cols, int B, int C, int H, int W, int patch, tr_stream_t s) {
+  return im2col_u8_aug_impl(false, img, lut, layout, aug, noise, noise_len, cols, B, C, H, W, patch, s);
+}
+extern "C" int tr_pixels_augment_f32(const uint8_t* img, const float* lut, int layout, const tr_augment_rec* aug, const float* noise,
+                                     long noise_len, float* out, int B, int C, int H, int W, int patch, tr_stream_t s) {
+  return im2col_u8_aug_impl(true, img, lut, layout, aug, noise, noise_len, out, B, C, H, W, patch, s);
 }
 
 extern "C" int tr_cls_pos_rows(const float* cls_token, const float* pos_embed, float* x, int B, int N, int D, tr_stream_t s) {

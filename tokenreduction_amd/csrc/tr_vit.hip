@@ -282,7 +282,8 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
                             float* logits, void* workspace,
                             size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
-                            const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f) {
+                            const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
+                            const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0) {
   Plan p;
   const bool train = tape != nullptr;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
@@ -362,7 +363,10 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
       TR_TRY(tr_patch_embed_bf16(static_cast<const float*>(img), static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token,
                                  w->pos_embed, x, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
   } else {
-    if (pixels)
+    if (pixels && aug != nullptr)      // training on uint8 pixels with the device-side erase / mixup / cutmix: the same columns, of the augmented image
+      TR_TRY(tr_im2col_u8_aug_bf16(u8img, pixel_lut, layout, aug, aug_noise, aug_noise_len, static_cast<uint16_t*>(cols), B, cfg->in_chans,
+                                   cfg->img_size, cfg->img_size, cfg->patch, s));
+    else if (pixels)
       TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
     else
       TR_TRY(op_im2col(f32, static_cast<const float*>(img), cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
@@ -981,7 +985,7 @@ extern "C" int tr_vit_tape_layout(const tr_vit_config* cfg, int B, int blk, size
 static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
                                   float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
                                   float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
-                                  float drop_rate) {
+                                  float drop_rate, const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0) {
   TR_REQUIRE(cfg && tape, TR_ERR_NULL, "tr_vit_forward_train: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_forward_train: dropout needs a keep mask AND 0 < drop_rate < 1 (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
@@ -996,7 +1000,8 @@ static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights
     TR_REQUIRE(t.n_att[i] <= 640, TR_ERR_SHAPE, "tr_vit_forward_train: %d tokens in block %d (the training path holds 640)", t.n_att[i], i);
   TR_REQUIRE(features_out == nullptr || cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_forward_train: features_out is DyViT's distillation output");
   return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, nullptr, noise_in,
-                          features_out, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate);
+                          features_out, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate, aug, aug_noise,
+                          aug_noise_len);
 }
 
 extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
@@ -1012,6 +1017,19 @@ extern "C" int tr_vit_forward_train_pixels(const tr_vit_config* cfg, const tr_vi
                                            int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
   return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in,
                                 features_out, drop_scale, tokens_out, B, s, dropout_keep, drop_rate);
+}
+
+extern "C" int tr_vit_forward_train_aug(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format,
+                                        const float* pixel_lut, const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len,
+                                        float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes,
+                                        const float* noise_in, float* features_out, const float* drop_scale, int* tokens_out, int B,
+                                        tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+  TR_REQUIRE(aug != nullptr, TR_ERR_NULL, "tr_vit_forward_train_aug: null augmentation table");
+  TR_REQUIRE(input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
+             "tr_vit_forward_train_aug: the augmentation runs on uint8 pixels (input_format %d)", input_format);
+  TR_REQUIRE(B > 0 && B % 2 == 0, TR_ERR_SHAPE, "tr_vit_forward_train_aug: the batch must be even, got B = %d", B);
+  return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in,
+                                features_out, drop_scale, tokens_out, B, s, dropout_keep, drop_rate, aug, aug_noise, aug_noise_len);
 }
 
 // Bytes of the dropout keep mask of one training forward (1 byte per element, 1 = keep), in the order the forward consumes it:

@@ -31,6 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, pixels
+from .augment import AugmentedBatch
 
 
 def _pair(v):
@@ -538,6 +539,8 @@ class VisionTransformer(nn.Module):
 
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
+        if isinstance(x, AugmentedBatch) and not (self.training and self.pixel_input is not None):
+            x = x.float()         # eval, the teacher, pixel input off: the augmented fp32 image, then the float path
         if self.training:
             # engine.py:50-51 `output = model(samples)` in train mode: logits with the HIP backward behind them (training.py)
             from . import training
@@ -553,6 +556,8 @@ class VisionTransformer(nn.Module):
         forward runs 2.65 -> 2.44 ms per batch of 256 with two in flight (tools/lab/two_stream_full.py).  A data loop uses it with one batch
         of lookahead (harness.evaluate_multiclass does): launch batch k + 1, then consume batch k.  Same kernels, same bits as `model(x)`.
         Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete)."""
+        if isinstance(x, AugmentedBatch):
+            x = x.float()
         if self.training or self.viz_mode or getattr(self, "dynamic_width", False) or not x.is_cuda:
             return _Pending(self(x), None)
         depth = max(1, int(getattr(self, "pipeline_depth", 2)))

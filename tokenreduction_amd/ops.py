@@ -89,6 +89,41 @@ def im2col_u8(img: torch.Tensor, lut: torch.Tensor, patch: int, f32: bool = Fals
     return cols
 
 
+def _augment(img: torch.Tensor, table: torch.Tensor, noise: torch.Tensor):
+    """(table pointer, noise pointer or None, noise length) of an augmentation table (uint8, 64 bytes per image: augment.REC_DTYPE) and
+    its packed fp32 noise."""
+    if table.numel() != 64 * img.shape[0]:
+        raise ValueError(f"table: expected {64 * img.shape[0]} bytes (one 64-byte record per image), got {table.numel()}")
+    _same_device(img, table, noise)
+    return _dev(table, torch.uint8, "table"), (_dev(noise, torch.float32, "noise") if noise.numel() else None), noise.numel()
+
+
+def im2col_u8_aug(img: torch.Tensor, lut: torch.Tensor, table: torch.Tensor, noise: torch.Tensor, patch: int, layout=None) -> torch.Tensor:
+    """im2col_u8 with the device-side erase / mixup / cutmix of `table` (augment.py): bf16 [B*P, C*p*p], bitwise the columns of the
+    augmented normalized image.  `layout` (TR_LAYOUT_*) overrides the one read off the strides (one channel: both describe the same bytes)."""
+    B, Cc, H, W = img.shape
+    ptr, lay, lp = _pixels(img, lut, Cc)
+    lay = lay if layout is None else layout
+    tp, npz, nl = _augment(img, table, noise)
+    cols = torch.empty(B * (H // patch) * (W // patch), Cc * patch * patch, dtype=torch.bfloat16, device=img.device)
+    _lib.check(_lib.load().tr_im2col_u8_aug_bf16(ptr, lp, lay, tp, npz, nl, cols.data_ptr(), B, Cc, H, W, patch, _stream(img)),
+               "tr_im2col_u8_aug_bf16")
+    return cols
+
+
+def pixels_augment(img: torch.Tensor, lut: torch.Tensor, table: torch.Tensor, noise: torch.Tensor, patch: int = 8, layout=None) -> torch.Tensor:
+    """The augmented, normalized image itself: uint8 pixels (contiguous or channels_last) -> fp32 [B,C,H,W] contiguous.  `patch` only
+    shapes the launch (any multiple of 8 that divides H and W); `layout` as in im2col_u8_aug."""
+    B, Cc, H, W = img.shape
+    ptr, lay, lp = _pixels(img, lut, Cc)
+    lay = lay if layout is None else layout
+    tp, npz, nl = _augment(img, table, noise)
+    out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=img.device)
+    _lib.check(_lib.load().tr_pixels_augment_f32(ptr, lp, lay, tp, npz, nl, out.data_ptr(), B, Cc, H, W, patch, _stream(img)),
+               "tr_pixels_augment_f32")
+    return out
+
+
 def patch_embed_u8(img: torch.Tensor, lut: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cls_token: torch.Tensor,
                    pos_embed: torch.Tensor, patch: int = 16) -> torch.Tensor:
     """patch_embed of raw uint8 pixels (contiguous or channels_last) normalized through `lut`: bitwise patch_embed of the normalized image."""

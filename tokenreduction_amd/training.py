@@ -18,6 +18,7 @@ from typing import List, Tuple
 import torch
 
 from . import _lib
+from .augment import AugmentedBatch
 
 
 def _align4(n: int) -> int:
@@ -234,7 +235,7 @@ class _VitTrainFn(torch.autograd.Function):
     [B,P] (straight-through differentiable, dyvit.py:223-225), features = the final norm of the patch tokens [B,P,D]."""
 
     @staticmethod
-    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None):
+    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None):
         lib = _lib.load()
         pk = model._pack(need_transposed=True)
         cfg = pk["cfg"]
@@ -258,14 +259,18 @@ class _VitTrainFn(torch.autograd.Function):
                     None if feats is None else feats.data_ptr(), None if ctx.drop is None else ctx.drop.data_ptr(), tokens, B,
                     torch.cuda.current_stream().cuda_stream, None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(),
                     float(model.drop_rate or 0.0))
-            if fmt == _lib.TR_INPUT_F32:
+            if aug is not None:      # uint8 pixels + the device-side erase / mixup / cutmix table (augment.py): the columns of the augmented image
+                table, aug_noise = aug
+                rc = lib.tr_vit_forward_train_aug(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, table.data_ptr(),
+                                                  aug_noise.data_ptr() if aug_noise.numel() else None, aug_noise.numel(), *rest)
+            elif fmt == _lib.TR_INPUT_F32:
                 rc = lib.tr_vit_forward_train(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest)
             else:      # uint8 pixels: the patch embedding normalizes them; the tape's column matrix is the one the fp32 image gives
                 rc = lib.tr_vit_forward_train_pixels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest)
         _lib.check(rc, "tr_vit_forward_train")
         model._last_tokens = list(tokens)
         ctx.model, ctx.B, ctx.pk = model, B, pk
-        ctx.keep = x
+        ctx.keep = (x, aug)
         ctx.n_pred, ctx.distill = 0, distill
         if model._out_width != model._out_cols:          # the padded classifier columns never leave the executor
             logits = logits[:, :model._out_cols].contiguous()
@@ -350,7 +355,7 @@ class _VitTrainFn(torch.autograd.Function):
         was_dirty = bool(getattr(model, "_weights_dirty", False))
         model.weights_changed()          # an optimizer step follows; fused optimizers do not bump the version counters the pack cache reads
         model._dirty_by_backward = not was_dirty      # dirt that was there before this backward is somebody else's: only a full repack clears it
-        return None, None, None, None, None
+        return None, None, None, None, None, None
 
 
 def train_forward(model, x: torch.Tensor) -> torch.Tensor:
@@ -362,9 +367,15 @@ def train_forward(model, x: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError("attn_drop_rate (dropout on the attention probabilities, topk.py:49) is not built in the HIP training path; "
                                   "the reference's command line cannot set it either (train.py:46 exposes --drop only, which IS supported, "
                                   "as is --drop-path)")
+    aug = None
+    if isinstance(x, AugmentedBatch):       # (models.forward has materialized the batch unless pixel input is on)
+        if x.mean_std != model.pixel_input:
+            raise ValueError(f"the batch normalizes with (mean, std) = {x.mean_std}, the model with {model.pixel_input}: "
+                             "give DeviceAugment the mean and std of model.set_pixel_input")
+        aug, x = (x.table, x.noise), x.pixels
     x, fmt, lut = model._executor_input(x)
     anchor = torch.empty(0, dtype=torch.float32, device=x.device, requires_grad=True)
-    out = _VitTrainFn.apply(anchor, x, model, fmt, lut)
+    out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug)
     if model._family != _lib.TR_FAMILY_DYVIT:
         return out
     # dyvit.py:257-261: (x, features, prev_decision.detach(), out_pred_prob) with the DyViT distillation scheme, else (x, out_pred_prob)
