@@ -104,6 +104,99 @@ def _init_vit_weights(m: nn.Module):
         nn.init.ones_(m.weight)
 
 
+def _pad8(n):
+    """Rows of a matrix whose row count the kernels pad with zeros: the classifier, the K outputs of a soft-assignment stage."""
+    return (n + 7) // 8 * 8
+
+
+def _pad64(n):
+    """Widths the bf16 GEMMs reduce over (K-step 64): hidden layers of the reduction modules, leading dimensions of their transposed copies."""
+    return (n + 63) // 64 * 64
+
+
+def _expand_schedule(values, locs, expand, what):
+    """The per-stage values of a (keep_rate, reduction_loc) pair: ONE value is expanded to a geometric schedule by the family's own rule
+    `expand(value, stage index)`, a list is taken as given and must name one value per location (`what` = the two nouns of the reference's
+    assertion message)."""
+    values, locs = list(values), list(locs)
+    if len(values) == 1:
+        values = [expand(values[0], idx) for idx in range(len(locs))]
+    assert len(values) == len(locs), f"Mismatch between the {what[0]} location ({locs}) and {what[1]} ({values})"
+    return values
+
+
+class _Packer:
+    """The operand copies of one _pack() call: w16(t) / f32(t) return the device address the executor reads parameter t through.  A LIVE
+    parameter storage (fp32, contiguous, on the device) is passed through as it is -- always current, never copied; everything else goes
+    into a persistent slot of `model._pack_slots`, keyed (call index, kind), so the ORDER of the calls is the identity of a slot: a repack
+    rewrites the same buffers in place and addresses, workspaces and captured graphs survive."""
+
+    def __init__(self, model, dev, wdt, want_t):
+        self.dev, self.wdt, self.want_t = dev, wdt, want_t
+        self.slots = model._pack_slots
+        self.own = {p.untyped_storage().data_ptr() for p in model.parameters()}      # storages that ARE parameters
+        self.calls = 0
+        self.fused = []                  # (fp32 source, bf16 slot, transposed bf16 slot or None): one tr_cast_pack_bf16 launch for all
+        self.keep_alive = []
+        self.moved = False               # a slot was (re)allocated: addresses changed
+        self.copied = False              # an operand copy the fused table does not cover (optim.FusedAdamW then leaves the refresh to _pack)
+
+    def _live(self, t):
+        return t.dtype == torch.float32 and t.is_contiguous() and t.device == self.dev and t.untyped_storage().data_ptr() in self.own
+
+    def _slot(self, kind, shape, dtype):
+        k = (self.calls, kind)
+        t = self.slots.get(k)
+        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype or t.device != self.dev:
+            t = self.slots[k] = torch.zeros(shape, dtype=dtype, device=self.dev)
+            self.moved = True
+        return t
+
+    def buffer(self, kind, shape, dtype):
+        """A persistent buffer that is no parameter copy (the fragment-major Mlp pack): counts as a call of its own."""
+        self.calls += 1
+        return self._slot(kind, shape, dtype)
+
+    def w16(self, t, transposed=False):
+        """Weight matrix in the executor's operand type.  transposed=True: returns (address, slot of its [cols, rows] bf16 copy or None --
+        the copies exist once training asked for them, in bf16 only)."""
+        self.calls += 1
+        t = t.detach()
+        ct = None
+        if self.wdt == torch.float32:
+            if self._live(t):
+                self.keep_alive.append(t)
+                ptr = t.data_ptr()
+            else:
+                c = self._slot("w", t.shape, torch.float32)
+                c.copy_(t)
+                ptr = c.data_ptr()
+            return (ptr, None) if transposed else ptr
+        c = self._slot("w", t.shape, torch.bfloat16)
+        if transposed and self.want_t:
+            ct = self._slot("t", (t.shape[1], t.shape[0]), torch.bfloat16)
+        # the fused cast kernel moves 16-byte vectors: rows must be whole vectors and start on one
+        if (t.dim() == 2 and self._live(t) and t.numel() >= 4096 and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0
+                and (ct is None or t.shape[0] % 4 == 0)):
+            self.fused.append((t, c, ct))
+        else:
+            c.copy_(t)
+            self.copied = True
+            if ct is not None:
+                ct.copy_(t.t())
+        return (c.data_ptr(), ct) if transposed else c.data_ptr()
+
+    def f32(self, t):
+        self.calls += 1
+        t = t.detach()
+        if self._live(t):
+            self.keep_alive.append(t)
+            return t.data_ptr()
+        c = self._slot("f", t.shape, torch.float32)
+        c.copy_(t)
+        return c.data_ptr()
+
+
 class VisionTransformer(nn.Module):
     """DeiT trunk, no reduction (deit_viz.py:75-212); also the base class of the reduction models."""
 
@@ -113,6 +206,9 @@ class VisionTransformer(nn.Module):
     # consecutive forwards with a never-seen input address before a workspace stops capturing hipGraphs: one more than the cache holds, so
     # that a caller rotating up to GRAPH_CACHE static input buffers (prefetch ring, multi-crop eval) gets through its first pass
     GRAPH_MISS_LIMIT = GRAPH_CACHE + 1
+    pipeline_depth = 2           # side streams (and workspaces) of forward_async
+    dynamic_width = False        # ATS only (ATSVisionTransformer)
+    _always_features = False     # the residual stream after every block is recorded outside viz_mode too (VisionTransformerTeacher)
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
@@ -161,29 +257,59 @@ class VisionTransformer(nn.Module):
         # with its Linears and attention on the matrix cores as split-bf16 products (3 MFMAs per product, ~1e-5 relative per Linear)
         self.precision = "bf16"
         self.use_graph = True        # eval forward replays a captured hipGraph (False: plain launches)
-        self._packed = None
-        self._ws = {}
+        self._pixel_input = None     # set_pixel_input(): a setting, not executor state
+        self._reset_executor_state()
         nn.init.trunc_normal_(self.pos_embed, std=.02)
         nn.init.trunc_normal_(self.cls_token, std=.02)
         self.apply(_init_vit_weights)
 
-    # ---- copies -----------------------------------------------------------------------------------
-    # executor caches (ctypes structs, GPU workspaces with captured hipGraphs, the tape / flat gradient buffer, noise buffers): state of
-    # THIS object's executor, rebuilt on demand.  A copy (copy.deepcopy: ModelEma, torch's swa_utils) starts without them: captured
-    # torch.cuda.CUDAGraph objects cannot be deep-copied at all, and a copied workspace would not belong to the copy's own packed weights.
-    _EXECUTOR_CACHES = {"_packed": None, "_ws": None, "_last_ws": None, "_tstate": None, "_grad_reducer": None, "_noise_buf": None,
-                        "_gumbel_buf": None, "_kmed_draws": None, "_pack_slots": None, "_pack_table": None, "_mlp_pack_items": None,
-                        "_pipe_streams": None, "_pipe_next": None, "_noise_bufs": None, "_pixel_luts": None}
+    # ---- executor state ---------------------------------------------------------------------------
+    def _reset_executor_state(self):
+        """Every attribute the executor owns (ctypes structs, GPU workspaces with captured hipGraphs, operand copies, the tape / flat
+        gradient buffer, noise buffers, side streams), at its empty value: state of THIS object's executor, rebuilt on demand.  This is
+        their one declaration -- __init__ starts from it and a copy does (__deepcopy__); settings (precision, use_graph, viz_mode,
+        pixel_input, the keep schedule, ...) are not in here."""
+        self._packed = None              # _pack(): dict(key, W, cfg, keep_alive, gen, tblocks)
+        self._ws = {}                    # _workspace(): {B or (B, slot): dict(buf, nbytes, kept, compl, soft, feat, graphs, ...)}
+        self._last_ws = None             # workspace and per-block token counts of the last forward
+        self._last_tokens = None
+        self._pack_slots = {}            # persistent operand copies {(call index, kind): tensor} (_Packer)
+        self._pack_table = None          # device-side item table of the fused cast launch (_run_fused_pack)
+        self._pack_all_fused = False     # that table covers every bf16 operand (optim.FusedAdamW may then refresh them itself)
+        self._mlp_pack_items = None      # ([(fc1_w, fc2_w, fc2_b, pack buffer)], D, Hd) of _refresh_mlp_pack
+        self._mlp_pk_stale = False       # the fragment-major Mlp copies are older than the bf16 copies
+        self._want_transposed = False    # training asked for the transposed copies (dgrad operands)
+        self._weights_dirty = False      # weights_changed(): values changed behind autograd's version counters
+        self._dirty_by_backward = False  # ... by this model's own backward (training.py), which optim.FusedAdamW may declare clean
+        self._tstate = None              # training.TrainState
+        self._grad_reducer = None        # dp.py: gradient reduction overlapped with the backward
+        self._pipe_streams = {}          # forward_async: {device: [side streams]}
+        self._pipe_next = 0
+        self._pixel_luts = None          # {device: uint8 -> normalized fp32 table}
+        self._noise_bufs = {}            # {workspace slot: static buffer of the per-stage random inputs} (DPC-KNN)
+        self._noise_slot = 0             # the slot of the forward being enqueued
+        self._gumbel_buf = None          # DyViT training: the Gumbel draws
+        self._kmed_draws = None          # K-Medoids equal_weight: the first medoids of the last forward
+
+    @property
+    def _noise_buf(self):
+        """The noise buffer of workspace slot 0 (model(x) and the training forward)."""
+        return self._noise_bufs.get(0)
+
+    @_noise_buf.setter
+    def _noise_buf(self, buf):
+        self._noise_bufs[0] = buf
 
     def __deepcopy__(self, memo):
+        """A copy (copy.deepcopy: ModelEma, torch's swa_utils) gets parameters, buffers and settings and starts with an empty executor:
+        captured torch.cuda.CUDAGraph objects cannot be deep-copied at all, and a copied workspace would not belong to the copy's own
+        packed weights."""
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
+        new._reset_executor_state()
+        owned = set(new.__dict__)
         for k, v in self.__dict__.items():
-            if k in self._EXECUTOR_CACHES:
-                if k in ("_pack_slots", "_pack_table", "_pipe_streams", "_pipe_next"):
-                    continue
-                new.__dict__[k] = {} if k == "_ws" else None
-            else:
+            if k not in owned:
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
@@ -218,7 +344,7 @@ class VisionTransformer(nn.Module):
     def _classes_padded(self):
         """The classifier as the kernels see it: rows padded with zeros to a multiple of 8 (any --num_classes works: NABirds 555,
         NUS-WIDE 81, train.py:334); the padded logits columns are cut off again before anything is returned."""
-        return (self.num_classes + 7) // 8 * 8
+        return _pad8(self.num_classes)
 
     @property
     def _out_width(self):
@@ -245,7 +371,7 @@ class VisionTransformer(nn.Module):
         """Makes the caller's current stream wait for every forward that forward_async has put on its side streams.  Called before the
         operand copies are rewritten (_pack) and when the model goes to train mode; call it yourself before you modify parameters in place
         while handles may be outstanding -- like any tensor used on another stream, the weights of a forward in flight must not change under it."""
-        for dev, streams in (self.__dict__.get("_pipe_streams") or {}).items():
+        for dev, streams in self._pipe_streams.items():
             cur = torch.cuda.current_stream(dev)
             for st in streams:
                 cur.wait_stream(st)
@@ -272,9 +398,9 @@ class VisionTransformer(nn.Module):
         self._pre_pack()
         if need_transposed:
             self._want_transposed = True
-        want_t = bool(getattr(self, "_want_transposed", False)) and self.precision == "bf16"
+        want_t = self._want_transposed and self.precision == "bf16"
         key = (self.precision, want_t) + self._param_key()
-        if self._packed is not None and self._packed["key"] == key and not getattr(self, "_weights_dirty", False):
+        if self._packed is not None and self._packed["key"] == key and not self._weights_dirty:
             return self._packed
         self.sync_pipeline()        # the operand copies are rewritten in place: no forward_async forward may still be reading them
         dev = self.pos_embed.device
@@ -283,103 +409,46 @@ class VisionTransformer(nn.Module):
         headless = not isinstance(self.head, nn.Linear)
         if headless != (self.num_classes <= 0):
             raise RuntimeError(f"num_classes = {self.num_classes} but head is {type(self.head).__name__}: use reset_classifier() to change the head")
-        keep_alive = []
         wdt = torch.bfloat16 if self.precision == "bf16" else torch.float32
-        slots = self.__dict__.setdefault("_pack_slots", {})          # persistent operand buffers: {(call index, kind): tensor}
-        own = {p_.untyped_storage().data_ptr() for p_ in self.parameters()}      # storages that ARE parameters: always current, never copied
-
-        def live(t):
-            return t.dtype == torch.float32 and t.is_contiguous() and t.device == dev and t.untyped_storage().data_ptr() in own
-
-        state = {"i": 0, "moved": False, "copied": False}
-        fused = []                                                     # (fp32 source, bf16 slot, transposed bf16 slot or None)
-
-        def slot(kind, shape, dtype):
-            k = (state["i"], kind)
-            t = slots.get(k)
-            if t is None or t.shape != torch.Size(shape) or t.dtype != dtype or t.device != dev:
-                t = slots[k] = torch.zeros(shape, dtype=dtype, device=dev)
-                state["moved"] = True
-            return t
-
-        def w16(t, transposed=False):      # weight matrix in the executor's operand type; transposed=True: also its [cols, rows] copy
-            state["i"] += 1
-            t = t.detach()
-            if wdt == torch.float32:
-                if live(t):
-                    keep_alive.append(t)
-                    return t.data_ptr()           # the parameter's own storage: always current
-                c = slot("w", t.shape, torch.float32)
-                c.copy_(t)
-                return c.data_ptr()
-            c = slot("w", t.shape, torch.bfloat16)
-            ct = slot("t", (t.shape[1], t.shape[0]), torch.bfloat16) if (transposed and want_t) else None
-            # the fused cast kernel moves 16-byte vectors: rows must be whole vectors and start on one
-            if t.dim() == 2 and live(t) and t.numel() >= 4096 and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0 and (ct is None or t.shape[0] % 4 == 0):
-                fused.append((t, c, ct))
-            else:
-                c.copy_(t)
-                state["copied"] = True        # an operand copy the fused table does not cover (optim.FusedAdamW then leaves the refresh here)
-                if ct is not None:
-                    ct.copy_(t.t())
-            if ct is not None:
-                tslots[state["i"]] = ct
-            return c.data_ptr()
-
-        def f32(t):
-            state["i"] += 1
-            t = t.detach()
-            if live(t):
-                keep_alive.append(t)
-                return t.data_ptr()               # the parameter's own storage: always current
-            c = slot("f", t.shape, torch.float32)
-            c.copy_(t)
-            return c.data_ptr()
-
-        tslots = {}
+        pk = _Packer(self, dev, wdt, want_t)
         W = _lib.TrVitWeights()
         D = self.embed_dim
         Hd = self.blocks[0].mlp.fc1.out_features
         lib = _lib.load()
         mlp_pk_bytes = int(lib.tr_mlp_pack_bytes(D, Hd)) if lib.tr_mlp_fused_supported(D, Hd) else 0
         mlp_items = []
-        W.patch_w = w16(self.patch_embed.proj.weight.reshape(D, -1))
-        W.patch_b = f32(self.patch_embed.proj.bias)
-        W.cls_token = f32(self.cls_token.reshape(-1))
-        W.pos_embed = f32(self.pos_embed.reshape(-1, D))
-        W.norm_g, W.norm_b = f32(self.norm.weight), f32(self.norm.bias)
+        W.patch_w = pk.w16(self.patch_embed.proj.weight.reshape(D, -1))
+        W.patch_b = pk.f32(self.patch_embed.proj.bias)
+        W.cls_token = pk.f32(self.cls_token.reshape(-1))
+        W.pos_embed = pk.f32(self.pos_embed.reshape(-1, D))
+        W.norm_g, W.norm_b = pk.f32(self.norm.weight), pk.f32(self.norm.bias)
         cpad = self._classes_padded
         if not headless:             # headless: no classifier operands (tr_vit_weights.head_* stay NULL)
-            W.head_w = w16(self.head.weight if cpad == self.num_classes else _pad_rows(self.head.weight, cpad))
-            W.head_b = f32(self.head.bias if cpad == self.num_classes else _pad_vec(self.head.bias, cpad))
+            W.head_w = pk.w16(self.head.weight if cpad == self.num_classes else _pad_rows(self.head.weight, cpad))
+            W.head_b = pk.f32(self.head.bias if cpad == self.num_classes else _pad_vec(self.head.bias, cpad))
         tblocks = []
         for i, blk in enumerate(self.blocks):
             b = W.blocks[i]
-            b.ln1_g, b.ln1_b = f32(blk.norm1.weight), f32(blk.norm1.bias)
-            b.qkv_w, b.qkv_b = w16(blk.attn.qkv.weight, True), f32(blk.attn.qkv.bias)
-            tq = tslots.get(state["i"] - 1)
-            b.proj_w, b.proj_b = w16(blk.attn.proj.weight, True), f32(blk.attn.proj.bias)
-            tp_ = tslots.get(state["i"] - 1)
-            b.ln2_g, b.ln2_b = f32(blk.norm2.weight), f32(blk.norm2.bias)
-            b.fc1_w, b.fc1_b = w16(blk.mlp.fc1.weight, True), f32(blk.mlp.fc1.bias)
-            t1 = tslots.get(state["i"] - 1)
-            b.fc2_w, b.fc2_b = w16(blk.mlp.fc2.weight, True), f32(blk.mlp.fc2.bias)
-            t2 = tslots.get(state["i"] - 1)
+            b.ln1_g, b.ln1_b = pk.f32(blk.norm1.weight), pk.f32(blk.norm1.bias)
+            (b.qkv_w, tq), b.qkv_b = pk.w16(blk.attn.qkv.weight, True), pk.f32(blk.attn.qkv.bias)
+            (b.proj_w, tp_), b.proj_b = pk.w16(blk.attn.proj.weight, True), pk.f32(blk.attn.proj.bias)
+            b.ln2_g, b.ln2_b = pk.f32(blk.norm2.weight), pk.f32(blk.norm2.bias)
+            (b.fc1_w, t1), b.fc1_b = pk.w16(blk.mlp.fc1.weight, True), pk.f32(blk.mlp.fc1.bias)
+            (b.fc2_w, t2), b.fc2_b = pk.w16(blk.mlp.fc2.weight, True), pk.f32(blk.mlp.fc2.bias)
             tblocks.append((tq, tp_, t1, t2))
             if wdt == torch.bfloat16 and mlp_pk_bytes:
                 # the fragment-major copy of the two Mlp matrices the fused eval Mlp kernel streams (csrc/tr_mlp_fused.hip), refreshed below /
                 # by _refresh_mlp_pack() whenever the bf16 copies were rewritten
-                state["i"] += 1
-                pkb = slot("p", (mlp_pk_bytes,), torch.uint8)
+                pkb = pk.buffer("p", (mlp_pk_bytes,), torch.uint8)
                 b.mlp_pk = pkb.data_ptr()
                 mlp_items.append((b.fc1_w, b.fc2_w, b.fc2_b, pkb))
-        self._pack_stages(W, w16, f32, keep_alive)
+        self._pack_stages(W, pk)
         # may an optimizer that rewrites the fused table's copies itself declare the operands fresh?  Only if that table is all there is:
         # no copied operand, and no reduction module whose transposed matrices training.TrainState keys on the pack generation
-        self._pack_all_fused = (not state["copied"] and wdt == torch.bfloat16
+        self._pack_all_fused = (not pk.copied and wdt == torch.bfloat16
                                 and type(self)._transposed_stage_weights is VisionTransformer._transposed_stage_weights)
-        if fused:
-            self._run_fused_pack(fused, dev, state["moved"])
+        if pk.fused:
+            self._run_fused_pack(pk.fused, dev)
         self._mlp_pack_items = (mlp_items, D, Hd)
         if self.training:
             # a repack from the training forward (every step of a non-fused optimizer, every accumulation micro-step): the train executor
@@ -403,14 +472,14 @@ class VisionTransformer(nn.Module):
             cfg.keep[i] = int(self._keep[i])
         old = self._packed
         gen = 1 if old is None else old.get("gen", 0) + 1
-        self._packed = dict(key=key, W=W, cfg=cfg, keep_alive=keep_alive, gen=gen, tblocks=tblocks if want_t else None)
+        self._packed = dict(key=key, W=W, cfg=cfg, keep_alive=pk.keep_alive, gen=gen, tblocks=tblocks if want_t else None)
         self._weights_dirty = False
         # workspaces and captured graphs hold the operand addresses: they survive a repack unless a buffer had to be (re)allocated or the
         # configuration changed (first pack, precision switch, new head, new keep schedule)
         # ... or a LIVE pointer moved: biases, LayerNorm parameters, pos_embed / cls_token (and every weight in fp32 mode) are read through
         # the parameter's own storage, so `p.data = ...`, load_state_dict(assign=True) or an optimizer that flattens its parameters puts
         # a new address into W while every slot stays where it was -- a captured graph would keep reading the old (possibly freed) memory
-        if state["moved"] or old is None or bytes(old["cfg"]) != bytes(cfg) or bytes(old["W"]) != bytes(W):
+        if pk.moved or old is None or bytes(old["cfg"]) != bytes(cfg) or bytes(old["W"]) != bytes(W):
             self._ws = {}
         return self._packed
 
@@ -418,7 +487,7 @@ class VisionTransformer(nn.Module):
         """Rewrite the fragment-major Mlp copies from the (current) bf16 operand copies: one small launch per block, in place -- after every
         _pack() refresh and, on the first eval forward after an optim.FusedAdamW step (which rewrites the bf16 copies itself and marks these
         stale), from forward()."""
-        items, D, Hd = self.__dict__.get("_mlp_pack_items") or ([], 0, 0)
+        items, D, Hd = self._mlp_pack_items or ([], 0, 0)
         self._mlp_pk_stale = False
         if not items:
             return
@@ -429,10 +498,10 @@ class VisionTransformer(nn.Module):
             for w1, w2, b2, pkb in items:
                 _lib.check(lib.tr_mlp_pack_bf16(w1, w2, b2, pkb.data_ptr(), D, Hd, st), "tr_mlp_pack_bf16")
 
-    def _run_fused_pack(self, fused, dev, moved):
+    def _run_fused_pack(self, fused, dev):
         """All large matrices through ONE tr_cast_pack_bf16 launch; the item table lives on the device and is rebuilt only when an
         address changed."""
-        tab = self.__dict__.get("_pack_table")
+        tab = self._pack_table
         sig = tuple((t.data_ptr(), c.data_ptr(), 0 if ct is None else ct.data_ptr(), t.shape[0], t.shape[1]) for t, c, ct in fused)
         if tab is None or tab["sig"] != sig:
             items = np.zeros(len(fused), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("rows", "<i4"), ("cols", "<i4")]))
@@ -446,7 +515,7 @@ class VisionTransformer(nn.Module):
             _lib.check(_lib.load().tr_cast_pack_bf16(tab["items"].data_ptr(), tab["first"].data_ptr(), tab["n"], tab["tiles"],
                                                      torch.cuda.current_stream().cuda_stream), "tr_cast_pack_bf16")
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         """Families with learned reduction modules fill W.stage[blk] (tr_stage_weights) here."""
 
     def _noise_ptr(self, B, dev):
@@ -503,7 +572,7 @@ class VisionTransformer(nn.Module):
     @property
     def pixel_input(self):
         """None, or the (mean, std) with which uint8 inputs are normalized on the device (set_pixel_input)."""
-        return self.__dict__.get("_pixel_input")
+        return self._pixel_input
 
     def set_pixel_input(self, mean=pixels.IMAGENET_DEFAULT_MEAN, std=pixels.IMAGENET_DEFAULT_STD):
         """Opt-in: a uint8 input [B, C, S, S] -- contiguous (NCHW) or torch.channels_last (NHWC), read in place -- is taken as raw pixels and
@@ -522,7 +591,7 @@ class VisionTransformer(nn.Module):
         if self.pixel_input is None or x.dtype != torch.uint8:
             return x.detach().to(torch.float32).contiguous(), _lib.TR_INPUT_F32, None
         x, fmt = pixels.as_executor_input(x, self.patch_embed.proj.in_channels)
-        luts = self.__dict__.get("_pixel_luts")
+        luts = self._pixel_luts
         if luts is None:
             luts = self._pixel_luts = {}
         if x.device not in luts:                       # one table per device, built at its first uint8 forward
@@ -531,7 +600,7 @@ class VisionTransformer(nn.Module):
 
     # ---- training state (flat gradient buffer, tape, workspaces): training.py -----------------------
     def _train_state(self):
-        st = getattr(self, "_tstate", None)
+        st = self._tstate
         if st is None or st.flat.device != self.pos_embed.device or len(st.order) != len(list(self.parameters())):
             from . import training
             st = self._tstate = training.TrainState(self)
@@ -558,19 +627,19 @@ class VisionTransformer(nn.Module):
         Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete)."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        if self.training or self.viz_mode or getattr(self, "dynamic_width", False) or not x.is_cuda:
+        if self.training or self.viz_mode or self.dynamic_width or not x.is_cuda:
             return _Pending(self(x), None)
-        depth = max(1, int(getattr(self, "pipeline_depth", 2)))
-        st = self.__dict__.setdefault("_pipe_streams", {})
+        depth = max(1, int(self.pipeline_depth))
+        st = self._pipe_streams
         key = x.device
         if key not in st or len(st[key]) != depth:
             st[key] = [torch.cuda.Stream(device=x.device) for _ in range(depth)]
-        slot = self.__dict__.get("_pipe_next", 0) % depth
+        slot = self._pipe_next % depth
         self._pipe_next = slot + 1
         side = st[key][slot]
         cur = torch.cuda.current_stream(x.device)
         self._pack()                                   # (re)pack on the caller's stream, where the optimizer / loader wrote
-        if getattr(self, "_mlp_pk_stale", False):
+        if self._mlp_pk_stale:
             self._refresh_mlp_pack(x.device)
         side.wait_stream(cur)                          # inputs and weights are ready where the forward runs
         with torch.cuda.stream(side):
@@ -585,7 +654,7 @@ class VisionTransformer(nn.Module):
             raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
         lib = _lib.load()
         pk = self._pack()
-        if getattr(self, "_mlp_pk_stale", False):
+        if self._mlp_pk_stale:
             self._refresh_mlp_pack(x.device)
         cfg = pk["cfg"]
         B, Cc, Hh, Ww = x.shape
@@ -595,7 +664,7 @@ class VisionTransformer(nn.Module):
         ws = self._workspace(B, x.device, slot)
         if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
             ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
-        want_feat = self.viz_mode or getattr(self, "_always_features", False)
+        want_feat = self.viz_mode or self._always_features
         if want_feat and ws.get("feat") is None:
             # viz_data["Features"]: the residual stream after every block (upper bound depth * B * N0 * D fp32)
             n0 = self.patch_embed.num_patches + 1
@@ -619,53 +688,12 @@ class VisionTransformer(nn.Module):
             return list(tokens)
 
         with torch.cuda.device(x.device):
+            res = None
             if (self.use_graph and not ws.get("graph_off") and not torch.cuda.is_current_stream_capturing()
-                    and not getattr(self, "dynamic_width", False)):      # (ATS dynamic width: the executor reads a token count back mid-forward)
-                # The forward is a fixed sequence of ~90-130 dependent launches with no host decision in between: replay it as one
-                # hipGraph (captured once per batch size / input buffer / output set; the workspace and every output are static
-                # buffers).  Re-packing the weights or a new batch size drops the workspace and its graphs with it.
-                # A capture bakes the input ADDRESS in.  Callers whose batches arrive at a new address every time (a dtype / layout
-                # conversion above, a loader without a static buffer, K-Medoids --equal_weight with its per-forward draws) would
-                # re-capture on every call -- slower than not using a graph at all: after GRAPH_MISS_LIMIT misses in a row the
-                # workspace goes back to plain launches (at batch 256 within 0.5 % of the replay; bench.py ms_per_step_plain_launches).
+                    and not self.dynamic_width):      # (ATS dynamic width: the executor reads a token count back mid-forward)
                 key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width)
-                graphs = ws.setdefault("graphs", {})
-                ent = graphs.get(key)
-                if ent is None:
-                    ws["graph_misses"] = ws.get("graph_misses", 0) + 1
-                    if graphs and ws["graph_misses"] >= self.GRAPH_MISS_LIMIT:
-                        ws["graph_off"] = True
-                        graphs.clear()
-                        warnings.warn(f"{type(self).__name__}: {self.GRAPH_MISS_LIMIT} forwards in a row came with a new input address (or new "
-                                      "per-forward draws); hipGraph replay is off for this batch size -- keep the input in one static "
-                                      "buffer to get it back (model.use_graph = False silences this)", RuntimeWarning, stacklevel=3)
-                        logits = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
-                        tokens = launch(logits)
-                        if self._out_width != self._out_cols:
-                            logits = logits[:, :self._out_cols].contiguous()
-                        ent = False
-                    else:
-                        out = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
-                        if not ws.get("warm"):
-                            launch(out)                                   # eager once per workspace: first touch, lazy module load
-                            ws["warm"] = True
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
-                            toks = launch(out)
-                        if len(graphs) >= self.GRAPH_CACHE:
-                            graphs.pop(next(iter(graphs)))
-                        ent = graphs[key] = (g, out, toks)
-                else:
-                    ws["graph_misses"] = 0
-                if ent:
-                    g, out, toks = ent
-                    g.replay()
-                    logits, tokens = out[:, :self._out_cols].clone(), toks
-            else:
-                logits = torch.empty(B, self._out_width, dtype=torch.float32, device=x.device)
-                tokens = launch(logits)
-                if self._out_width != self._out_cols:
-                    logits = logits[:, :self._out_cols].contiguous()
+                res = self._replay(ws, key, launch, B, x.device)
+            logits, tokens = res if res is not None else self._plain_launch(launch, B, x.device)
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
         self._last_tokens = list(tokens)
         self._last_ws = ws
@@ -674,6 +702,50 @@ class VisionTransformer(nn.Module):
             viz["Features"] = self._features(ws, B, list(tokens))
             return logits, viz
         return logits
+
+    def _plain_launch(self, launch, B, dev):
+        """The forward as plain launches into a fresh output buffer: (logits without the padded classifier columns, tokens per block)."""
+        logits = torch.empty(B, self._out_width, dtype=torch.float32, device=dev)
+        tokens = launch(logits)
+        if self._out_width != self._out_cols:
+            logits = logits[:, :self._out_cols].contiguous()
+        return logits, tokens
+
+    def _replay(self, ws, key, launch, B, dev):
+        """The forward as ONE hipGraph replay: (logits, tokens), or None when this workspace has gone back to plain launches.
+        The forward is a fixed sequence of ~90-130 dependent launches with no host decision in between: it is captured once per batch size /
+        input buffer / output set (`key`; the workspace and every output are static buffers) and kept in ws["graphs"], at most GRAPH_CACHE
+        per workspace, oldest out first.  Re-packing the weights or a new batch size drops the workspace and its graphs with it.
+        A capture bakes the input ADDRESS in.  Callers whose batches arrive at a new address every time (a dtype / layout conversion, a
+        loader without a static buffer, K-Medoids --equal_weight with its per-forward draws) would re-capture on every call -- slower
+        than not using a graph at all: after GRAPH_MISS_LIMIT misses in a row the workspace goes back to plain launches (at batch 256
+        within 0.5 % of the replay; bench.py ms_per_step_plain_launches)."""
+        graphs = ws.setdefault("graphs", {})
+        ent = graphs.get(key)
+        if ent is not None:
+            ws["graph_misses"] = 0
+        else:
+            ws["graph_misses"] = ws.get("graph_misses", 0) + 1
+            if graphs and ws["graph_misses"] >= self.GRAPH_MISS_LIMIT:
+                ws["graph_off"] = True
+                graphs.clear()
+                warnings.warn(f"{type(self).__name__}: {self.GRAPH_MISS_LIMIT} forwards in a row came with a new input address (or new "
+                              "per-forward draws); hipGraph replay is off for this batch size -- keep the input in one static "
+                              "buffer to get it back (model.use_graph = False silences this)", RuntimeWarning, stacklevel=4)
+                return None
+            out = torch.empty(B, self._out_width, dtype=torch.float32, device=dev)
+            if not ws.get("warm"):
+                launch(out)                                   # eager once per workspace: first touch, lazy module load
+                ws["warm"] = True
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                toks = launch(out)
+            if len(graphs) >= self.GRAPH_CACHE:
+                graphs.pop(next(iter(graphs)))
+            ent = graphs[key] = (g, out, toks)
+        g, out, toks = ent
+        g.replay()
+        return out[:, :self._out_cols].clone(), toks
 
     def check_status(self):
         """Status check of the eval forwards since the last call (tr_vit_forward_status): waits for the stream and raises RuntimeError if
@@ -726,6 +798,11 @@ class VisionTransformer(nn.Module):
             off += n
         return feats
 
+    def _stage_slab(self, arr, blk, B, n):
+        """[B, n] int64: the first B * n entries of block `blk`'s slab in a per-stage index output (ws["kept"], ws["compl"])."""
+        base = blk * B * (self.patch_embed.num_patches + 1)
+        return arr[base: base + B * n].reshape(B, n).astype(np.int64)
+
     def _stage_indices(self, ws, B, tokens):
         """Per reduction block: (blk, N_in, K) from the static per-stage shapes."""
         P = self.patch_embed.num_patches
@@ -747,12 +824,8 @@ class _TopKBase(VisionTransformer):
 
     def __init__(self, *a, args=None, dyvit_distillation=False, **kw):
         super().__init__(*a, args=args, **kw)
-        token_ratio = list(args.keep_rate)
         pruning_loc = list(args.reduction_loc)
-        if len(token_ratio) == 1:
-            token_ratio = [token_ratio[0] ** (idx + 1) for idx in range(len(pruning_loc))]   # topk.py:141-142
-        assert len(token_ratio) == len(pruning_loc), \
-            f"Mismatch between the pruning location ({pruning_loc}) and token ratios ({token_ratio})"
+        token_ratio = _expand_schedule(args.keep_rate, pruning_loc, lambda r, idx: r ** (idx + 1), ("pruning", "token ratios"))   # topk.py:141-142
         self.num_patches = self.patch_embed.num_patches
         self.deit_distillation = False
         self.pruning_loc = pruning_loc
@@ -787,11 +860,8 @@ class TopKVisionTransformer(_TopKBase):
         return K + 1
 
     def _viz_data(self, ws, B, tokens):
-        P = self.patch_embed.num_patches
         kept = ws["kept"].cpu().numpy()
-        decisions = {}
-        for blk, n_in, K in self._stage_indices(ws, B, tokens):
-            decisions[blk] = kept[blk * B * (P + 1): blk * B * (P + 1) + B * K].reshape(B, K).astype(np.int64)
+        decisions = {blk: self._stage_slab(kept, blk, B, K) for blk, n_in, K in self._stage_indices(ws, B, tokens)}
         return {"Kept_Tokens": decisions, "Features": {}}
 
 
@@ -803,15 +873,12 @@ class EfficientVisionTransformer(_TopKBase):
         return K + 2
 
     def _viz_data(self, ws, B, tokens):
-        P = self.patch_embed.num_patches
         kept = ws["kept"].cpu().numpy()
         compl = ws["compl"].cpu().numpy()
         decisions, fusion = {}, {}
         for blk, n_in, K in self._stage_indices(ws, B, tokens):
-            idx = kept[blk * B * (P + 1): blk * B * (P + 1) + B * K].reshape(B, K).astype(np.int64)
-            decisions[blk] = np.concatenate([idx, -np.ones((B, 1), dtype=np.int64)], axis=1)   # evit.py:123
-            nc = n_in - 1 - K
-            fusion[blk] = compl[blk * B * (P + 1): blk * B * (P + 1) + B * nc].reshape(B, nc).astype(np.int64)
+            decisions[blk] = np.concatenate([self._stage_slab(kept, blk, B, K), -np.ones((B, 1), dtype=np.int64)], axis=1)   # evit.py:123
+            fusion[blk] = self._stage_slab(compl, blk, B, n_in - 1 - K)
         return {"Kept_Tokens": decisions, "Fusion_Assign": fusion, "Features": {}}
 
 
@@ -824,13 +891,9 @@ class ToMeVisionTransformer(VisionTransformer):
 
     def __init__(self, *a, args=None, **kw):
         super().__init__(*a, args=args, **kw)
-        token_ratio = list(args.keep_rate)
         pruning_loc = list(args.reduction_loc)
         P0 = self.patch_embed.num_patches
-        if len(token_ratio) == 1:
-            token_ratio = [int(P0 * token_ratio[0] ** (idx + 1)) for idx in range(len(pruning_loc))]      # tome.py:145-146
-        assert len(token_ratio) == len(pruning_loc), \
-            f"Mismatch between the pruning location ({pruning_loc}) and token ratios ({token_ratio})"
+        token_ratio = _expand_schedule(args.keep_rate, pruning_loc, lambda r, idx: int(P0 * r ** (idx + 1)), ("pruning", "token ratios"))   # tome.py:145-146
         # explicit values are ABSOLUTE patch-token counts; the CLI delivers floats, which crash the reference's slicing
         #  -- cast to int here
         token_ratio = [int(t) for t in token_ratio]
@@ -926,12 +989,8 @@ class DynamicVisionTransformer(VisionTransformer):
         assert (dyvit_distillation & distilled) is False, "Cannot have both DeiT Distillation token and DyViT Distillation scheme"
         if distilled:
             raise NotImplementedError("the distillation token is not built")
-        token_ratio = list(args.keep_rate)
         pruning_loc = list(args.reduction_loc)
-        if len(token_ratio) == 1:
-            token_ratio = [token_ratio[0] ** (idx + 1) for idx in range(len(pruning_loc))]                 # dyvit.py:175-176
-        assert len(token_ratio) == len(pruning_loc), \
-            f"Mismatch between the pruning location ({pruning_loc}) and token ratios ({token_ratio})"
+        token_ratio = _expand_schedule(args.keep_rate, pruning_loc, lambda r, idx: r ** (idx + 1), ("pruning", "token ratios"))   # dyvit.py:175-176
         self.num_patches = self.patch_embed.num_patches
         self.score_predictor = nn.ModuleList([PredictorLG(self.embed_dim) for _ in range(len(pruning_loc))])
         for m in self.score_predictor.modules():
@@ -951,7 +1010,7 @@ class DynamicVisionTransformer(VisionTransformer):
 
     def _gumbel_ptr(self, B, dev):
         P, n_st = self.num_patches, len(self.pruning_loc)
-        buf = getattr(self, "_gumbel_buf", None)
+        buf = self._gumbel_buf
         if buf is None or buf.numel() != n_st * B * P * 2 or buf.device != dev:
             buf = self._gumbel_buf = torch.empty(n_st * B * P * 2, dtype=torch.float32, device=dev)
         if self.gumbel_noise is not None:
@@ -970,7 +1029,7 @@ class DynamicVisionTransformer(VisionTransformer):
             g.w3, g.b3 = ptr(pre + "out_conv.4.weight"), ptr(pre + "out_conv.4.bias")
 
     def _transposed_stage_weights(self, WT, t16):
-        hh, qq = (self.embed_dim // 2 + 63) // 64 * 64, (self.embed_dim // 4 + 63) // 64 * 64      # hidden widths as packed (_pack_stages)
+        hh, qq = self._hidden_pad()
         for j, loc in enumerate(self.pruning_loc):
             sp, st = self.score_predictor[j], WT.stage[loc]
             st.w0 = t16(sp.in_conv[1].weight)                                              # [D, D]^T
@@ -980,27 +1039,75 @@ class DynamicVisionTransformer(VisionTransformer):
     def get_reduction_count(self):
         return self.pruning_loc
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _hidden_pad(self):
+        """The predictor's hidden widths D/2 and D/4 as the kernels see them, padded with zero weights: K % 64 for the bf16 GEMMs
+        (DeiT-T: 96 -> 128); the training path's GEMMs reduce over the D/4 rows too."""
+        return _pad64(self.embed_dim // 2), _pad64(self.embed_dim // 4)
+
+    def _pack_stages(self, W, pk):
+        hh, qq = self._hidden_pad()
         for j, loc in enumerate(self.pruning_loc):
             sp, st = self.score_predictor[j], W.stage[loc]
-            st.ln_g, st.ln_b = f32(sp.in_conv[0].weight), f32(sp.in_conv[0].bias)
-            st.w0, st.b0 = w16(sp.in_conv[1].weight), f32(sp.in_conv[1].bias)
-            hh = (self.embed_dim // 2 + 63) // 64 * 64          # D/2 padded with zero weights: K %% 64 for the bf16 GEMM (DeiT-T: 96 -> 128)
-            st.w1, st.b1 = w16(_pad_rows(sp.out_conv[0].weight, hh)), f32(_pad_vec(sp.out_conv[0].bias, hh))
-            qq = (self.embed_dim // 4 + 63) // 64 * 64          # D/4 rows padded likewise: the training path's GEMMs reduce over them
-            st.w2, st.b2 = w16(_pad_rows(_pad_cols(sp.out_conv[2].weight, hh), qq)), f32(_pad_vec(sp.out_conv[2].bias, qq))
+            st.ln_g, st.ln_b = pk.f32(sp.in_conv[0].weight), pk.f32(sp.in_conv[0].bias)
+            st.w0, st.b0 = pk.w16(sp.in_conv[1].weight), pk.f32(sp.in_conv[1].bias)
+            st.w1, st.b1 = pk.w16(_pad_rows(sp.out_conv[0].weight, hh)), pk.f32(_pad_vec(sp.out_conv[0].bias, hh))
+            st.w2, st.b2 = pk.w16(_pad_rows(_pad_cols(sp.out_conv[2].weight, hh), qq)), pk.f32(_pad_vec(sp.out_conv[2].bias, qq))
             st.h_pad = hh
             st.reserved_ = qq
-            st.w3, st.b3 = f32(sp.out_conv[4].weight), f32(sp.out_conv[4].bias)
+            st.w3, st.b3 = pk.f32(sp.out_conv[4].weight), pk.f32(sp.out_conv[4].bias)
 
     def _viz_data(self, ws, B, tokens):
-        P1 = self.patch_embed.num_patches + 1
         kept = ws["kept"].cpu().numpy()
-        decisions = {}
-        for blk in self.pruning_loc:
-            K = self._keep[blk]
-            decisions[blk] = kept[blk * B * P1: blk * B * P1 + B * K].reshape(B, K).astype(np.int64)
-        return {"Kept_Tokens": decisions, "Features": {}}
+        return {"Kept_Tokens": {blk: self._stage_slab(kept, blk, B, self._keep[blk]) for blk in self.pruning_loc}, "Features": {}}
+
+
+class _ClusterBase(VisionTransformer):
+    """Shared part of the five families that replace the patch tokens by cluster_count[j] tokens BEFORE block cluster_loc[j] through a
+    module cluster_layers[j] -- SiT, DPC-KNN, Sinkhorn, K-Medoids, PatchMerger: one schedule rule (sit.py:80-81, dpcknn.py:214-215,
+    sinkhorn.py:128-129, patchmerger.py:78-79) and one constructor order; a family adds its own settings in _cluster_settings and its
+    module in _make_cluster_layer."""
+
+    def __init__(self, *a, args=None, **kw):
+        super().__init__(*a, args=args, **kw)
+        P0 = self.patch_embed.num_patches
+        self.cluster_loc = list(args.reduction_loc)
+        self.cluster_count = [int(c) for c in _expand_schedule(args.keep_rate, self.cluster_loc, lambda r, idx: int(P0 * r ** (idx + 1)),
+                                                               ("cluster", "cluster centers"))]
+        self._cluster_settings(args)
+        self.cluster_layers = nn.ModuleList([self._make_cluster_layer(c) for c in self.cluster_count])
+        for m in self.cluster_layers.modules():
+            _init_vit_weights(m)
+        for c, loc in zip(self.cluster_count, self.cluster_loc):
+            self._set_keep(loc, c, "the cluster schedule")
+
+    def _cluster_settings(self, args):
+        """The family's own constructor arguments (read before its modules are built)."""
+
+    def _make_cluster_layer(self, count):
+        raise NotImplementedError
+
+    def get_new_module_names(self):
+        return ["cluster_layers"]
+
+    def get_reduction_count(self):
+        return self.cluster_loc
+
+    def _stage_shapes(self):
+        """[(blk, K, P_in)] per clustering stage, in block order."""
+        out, p_in = [], self.patch_embed.num_patches
+        for K, loc in sorted(zip(self.cluster_count, self.cluster_loc), key=lambda t: t[1]):
+            out.append((loc, K, p_in))
+            p_in = K
+        return out
+
+    def _viz_data(self, ws, B, tokens):
+        """Hard clusterings (DPC-KNN, K-Medoids): the centre tokens and every input token's cluster."""
+        kept, assign = ws["kept"].cpu().numpy(), ws["compl"].cpu().numpy()
+        decisions, assignments = {}, {}
+        for blk, K, P in self._stage_shapes():
+            decisions[blk] = self._stage_slab(kept, blk, B, K)
+            assignments[blk] = self._stage_slab(assign, blk, B, P)
+        return {"Kept_Tokens": decisions, "Assignment_Maps": assignments, "Center_Feats": {}, "Features": {}}
 
 
 class TokenSlimmingModule(nn.Module):
@@ -1014,52 +1121,35 @@ class TokenSlimmingModule(nn.Module):
         self.scale = nn.Parameter(torch.ones(1, 1, 1))
 
 
-class SelfSlimmedVisionTransformer(VisionTransformer):
+class SelfSlimmedVisionTransformer(_ClusterBase):
     """models/sit.py:43-150: a TokenSlimmingModule softly assigns the patch tokens to K outputs before each block in
     reduction_loc."""
     _family = _lib.TR_FAMILY_SIT
+    _center_feats = False            # viz_data carries an (empty) "Center_Feats" entry (sinkhorn.py / patchmerger.py)
 
-    def __init__(self, *a, args=None, **kw):
-        super().__init__(*a, args=args, **kw)
-        self.cluster_loc = list(args.reduction_loc)
-        self.cluster_count = list(args.keep_rate)
-        P0 = self.patch_embed.num_patches
-        if len(self.cluster_count) == 1:
-            self.cluster_count = [int(P0 * (args.keep_rate[0] ** (idx + 1))) for idx in range(len(self.cluster_loc))]   # sit.py:80-81
-        assert len(self.cluster_count) == len(self.cluster_loc), \
-            f"Mismatch between the cluster location ({self.cluster_loc}) and cluster centers ({self.cluster_count})"
-        self.cluster_count = [int(c) for c in self.cluster_count]
-        self.cluster_layers = nn.ModuleList([TokenSlimmingModule(self.embed_dim, c) for c in self.cluster_count])
-        for m in self.cluster_layers.modules():
-            _init_vit_weights(m)
-        for c, loc in zip(self.cluster_count, self.cluster_loc):
-            self._set_keep(loc, c, "the cluster schedule")
+    def _make_cluster_layer(self, count):
+        return TokenSlimmingModule(self.embed_dim, count)
 
-    def get_new_module_names(self):
-        return ["cluster_layers"]
-
-    def get_reduction_count(self):
-        return self.cluster_loc
-
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         for j, loc in enumerate(self.cluster_loc):
             m, st = self.cluster_layers[j], W.stage[loc]
             K = self.cluster_count[j]
-            n_pad = (K + 7) // 8 * 8
+            n_pad = self._soft_pad(K)[0]
             w1 = torch.zeros(n_pad, m.weight[3].in_features, dtype=torch.float32, device=m.weight[3].weight.device)
             w1[:K] = m.weight[3].weight.detach()
             b1 = torch.zeros(n_pad, dtype=torch.float32, device=w1.device)
             b1[:K] = m.weight[3].bias.detach()
-            st.ln_g, st.ln_b = f32(m.weight[0].weight), f32(m.weight[0].bias)
-            hh = (m.weight[1].out_features + 63) // 64 * 64     # hidden width padded with zero weights (DeiT-T: 96 -> 128)
-            st.w0, st.b0 = w16(_pad_rows(m.weight[1].weight, hh)), f32(_pad_vec(m.weight[1].bias, hh))
-            st.w1, st.b1 = w16(_pad_cols(w1, hh)), f32(b1)
+            st.ln_g, st.ln_b = pk.f32(m.weight[0].weight), pk.f32(m.weight[0].bias)
+            hh = _pad64(m.weight[1].out_features)     # hidden width padded with zero weights (DeiT-T: 96 -> 128)
+            st.w0, st.b0 = pk.w16(_pad_rows(m.weight[1].weight, hh)), pk.f32(_pad_vec(m.weight[1].bias, hh))
+            st.w1, st.b1 = pk.w16(_pad_cols(w1, hh)), pk.f32(b1)
             st.scale = float(m.scale.detach().reshape(-1)[0])
             st.n_pad = n_pad
             st.h_pad = hh
 
     def _soft_pad(self, K):
-        return (K + 7) // 8 * 8, (K + 63) // 64 * 64
+        """(rows, leading dimension of the transposed copy) of a soft-assignment matrix with K outputs, as the kernels pad them."""
+        return _pad8(K), _pad64(K)
 
     def _grad_slot_numel(self, name, p):
         # the last Linear's rows are padded to a multiple of 8 by the weight-gradient kernel (rows >= K receive zeros)
@@ -1081,21 +1171,9 @@ class SelfSlimmedVisionTransformer(VisionTransformer):
     def _transposed_stage_weights(self, WT, t16):
         for j, loc in enumerate(self.cluster_loc):
             m, st = self.cluster_layers[j], WT.stage[loc]
-            hh = (m.weight[1].out_features + 63) // 64 * 64                           # hidden width as packed (DeiT-T: 96 -> 128)
+            hh = _pad64(m.weight[1].out_features)                                     # hidden width as packed (DeiT-T: 96 -> 128)
             st.w0 = t16(_pad_rows(m.weight[1].weight, hh))                            # [Hh, D]^T
             st.w1 = t16(_pad_rows(_pad_cols(m.weight[3].weight, hh), self._soft_pad(self.cluster_count[j])[1]))   # [K -> ld64, Hh]^T
-
-    def _stage_shapes(self):
-        """[(blk, K, P_in)] per slimming stage."""
-        out, p_in = [], self.patch_embed.num_patches
-        for K, loc in sorted(zip(self.cluster_count, self.cluster_loc), key=lambda t: t[1]):
-            out.append((loc, K, p_in))
-            p_in = K
-        return out
-
-    def _noise_ptr(self, B, dev):
-        """Device pointer of the per-stage random inputs (DPC-KNN density noise), None for deterministic families."""
-        return None
 
     def _soft_elems(self, B):
         return sum(B * K * P for _, K, P in self._stage_shapes())
@@ -1109,7 +1187,10 @@ class SelfSlimmedVisionTransformer(VisionTransformer):
             off += B * K * P
             assignments[blk] = a
             hard[blk] = np.argmax(a, axis=-2).astype(np.int64)                       # sit.py:122
-        return {"Assignment_Maps": hard, "Soft_Assignment_Maps": assignments, "Features": {}}
+        out = {"Assignment_Maps": hard, "Soft_Assignment_Maps": assignments, "Features": {}}
+        if self._center_feats:
+            out["Center_Feats"] = {}
+        return out
 
 
 class CTM(nn.Module):
@@ -1122,7 +1203,7 @@ class CTM(nn.Module):
             self.score = nn.Linear(embed_dim, 1)
 
 
-class DPCKNNVisionTransformer(VisionTransformer):
+class DPCKNNVisionTransformer(_ClusterBase):
     """models/dpcknn.py:175-290: before each block in reduction_loc the patch tokens are clustered by DPC-KNN and every cluster
     is replaced by the exp(score)-weighted mean of its tokens.
 
@@ -1130,38 +1211,20 @@ class DPCKNNVisionTransformer(VisionTransformer):
     device each forward, or from `self.density_noise = {blk: tensor[B,P_in]}` when set (tests feed the reference's draws)."""
     _family = _lib.TR_FAMILY_DPCKNN
 
-    def __init__(self, *a, args=None, **kw):
-        super().__init__(*a, args=args, **kw)
-        self.cluster_loc = list(args.reduction_loc)
-        self.cluster_count = list(args.keep_rate)
+    def _cluster_settings(self, args):
         self.k_neighbors = int(args.k_neighbors)
         self.equal_weight = bool(args.equal_weight)
-        P0 = self.patch_embed.num_patches
-        if len(self.cluster_count) == 1:
-            self.cluster_count = [int(P0 * (args.keep_rate[0] ** (idx + 1))) for idx in range(len(self.cluster_loc))]   # dpcknn.py:214-215
-        assert len(self.cluster_count) == len(self.cluster_loc), \
-            f"Mismatch between the cluster location ({self.cluster_loc}) and cluster centers ({self.cluster_count})"
-        self.cluster_count = [int(c) for c in self.cluster_count]
-        self.cluster_layers = nn.ModuleList([CTM(self.embed_dim, c, self.k_neighbors, self.equal_weight) for c in self.cluster_count])
-        for m in self.cluster_layers.modules():
-            _init_vit_weights(m)
-        for c, loc in zip(self.cluster_count, self.cluster_loc):
-            self._set_keep(loc, c, "the cluster schedule")
         self.density_noise = None
-        self._noise_buf = None
 
-    def get_new_module_names(self):
-        return ["cluster_layers"]
+    def _make_cluster_layer(self, count):
+        return CTM(self.embed_dim, count, self.k_neighbors, self.equal_weight)
 
-    def get_reduction_count(self):
-        return self.cluster_loc
-
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         if self.equal_weight:
             return
         for j, loc in enumerate(self.cluster_loc):
             st = W.stage[loc]
-            st.w3, st.b3 = f32(self.cluster_layers[j].score.weight), f32(self.cluster_layers[j].score.bias)
+            st.w3, st.b3 = pk.f32(self.cluster_layers[j].score.weight), pk.f32(self.cluster_layers[j].score.bias)
 
     def _grad_stage_ptrs(self, G, ptr):
         if self.equal_weight:
@@ -1169,42 +1232,19 @@ class DPCKNNVisionTransformer(VisionTransformer):
         for j, loc in enumerate(self.cluster_loc):
             G.stage[loc].w3, G.stage[loc].b3 = ptr(f"cluster_layers.{j}.score.weight"), ptr(f"cluster_layers.{j}.score.bias")
 
-    def _stage_shapes(self):
-        out, p_in = [], self.patch_embed.num_patches
-        for K, loc in sorted(zip(self.cluster_count, self.cluster_loc), key=lambda t: t[1]):
-            out.append((loc, K, p_in))
-            p_in = K
-        return out
-
     def _noise_ptr(self, B, dev):
         shapes = self._stage_shapes()
         n = sum(B * P for _, _, P in shapes)
-        slot = self.__dict__.get("_noise_slot", 0)                                  # forward_async: one buffer per forward in flight
-        buf = self._noise_buf if slot == 0 else (self.__dict__.get("_noise_bufs") or {}).get(slot)
+        buf = self._noise_bufs.get(self._noise_slot)                                 # forward_async: one buffer per forward in flight
         if buf is None or buf.numel() != n or buf.device != dev:
-            buf = torch.empty(n, dtype=torch.float32, device=dev)                    # static: a captured forward reads this address
-            if slot == 0:
-                self._noise_buf = buf
-            else:
-                self.__dict__.setdefault("_noise_bufs", {})
-                if self._noise_bufs is None:
-                    self._noise_bufs = {}
-                self._noise_bufs[slot] = buf
+            # static: a captured forward reads this address
+            buf = self._noise_bufs[self._noise_slot] = torch.empty(n, dtype=torch.float32, device=dev)
         if self.density_noise is not None:
             parts = [self.density_noise[blk].to(device=dev, dtype=torch.float32).reshape(B, P) for blk, _, P in shapes]
             buf.copy_(torch.cat([t.reshape(-1) for t in parts]))
         else:
             buf.uniform_()                                                           # torch.rand: [0, 1)
         return buf.data_ptr()
-
-    def _viz_data(self, ws, B, tokens):
-        P1 = self.patch_embed.num_patches + 1
-        kept, assign = ws["kept"].cpu().numpy(), ws["compl"].cpu().numpy()
-        decisions, assignments = {}, {}
-        for blk, K, P in self._stage_shapes():
-            decisions[blk] = kept[blk * B * P1: blk * B * P1 + B * K].reshape(B, K).astype(np.int64)
-            assignments[blk] = assign[blk * B * P1: blk * B * P1 + B * P].reshape(B, P).astype(np.int64)
-        return {"Kept_Tokens": decisions, "Assignment_Maps": assignments, "Center_Feats": {}, "Features": {}}
 
 
 class ATSVisionTransformer(VisionTransformer):
@@ -1219,7 +1259,6 @@ class ATSVisionTransformer(VisionTransformer):
     _family = _lib.TR_FAMILY_ATS
 
     _features_every_block = False
-    dynamic_width = False
 
     def _per_forward_config(self, cfg):
         super()._per_forward_config(cfg)
@@ -1228,12 +1267,9 @@ class ATSVisionTransformer(VisionTransformer):
     def __init__(self, *a, args=None, **kw):
         super().__init__(*a, args=args, **kw)
         self.sample_loc = list(args.reduction_loc)
-        sample_count = list(args.keep_rate)
-        if len(sample_count) == 1:
-            sample_count = [int(args.keep_rate[0] ** (idx + 1) * self.patch_embed.num_patches) + 1
-                            for idx in range(len(self.sample_loc))]                                        # ats.py:204-205
-        assert len(sample_count) == len(self.sample_loc), \
-            f"Mismatch between the sample location ({self.sample_loc}) and sample centers ({sample_count})"
+        P0 = self.patch_embed.num_patches
+        sample_count = _expand_schedule(args.keep_rate, self.sample_loc, lambda r, idx: int(r ** (idx + 1) * P0) + 1,
+                                        ("sample", "sample centers"))                                     # ats.py:204-205
         cnt = 0
         self.sample_count = [0] * self.depth
         for idx in range(self.depth):
@@ -1254,20 +1290,19 @@ class ATSVisionTransformer(VisionTransformer):
         """ats.py:48, verbatim."""
         return torch.arange(1 / (2 * sample_count), (2 * sample_count - 1) / (2 * sample_count), 2 / (2 * sample_count))
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         for blk, K in enumerate(self.sample_count):
             if K:
                 steps = self.sample_steps(K).to(self.pos_embed.device)
-                W.stage[blk].w3 = f32(steps)
+                W.stage[blk].w3 = pk.f32(steps)
                 W.stage[blk].n_pad = steps.numel()
 
     def _viz_data(self, ws, B, tokens):
-        P1 = self.patch_embed.num_patches + 1
         kept = ws["kept"].cpu().numpy()
         decisions = {}
         for blk, K in enumerate(self._keep):
             if K:
-                ids = kept[blk * B * P1: blk * B * P1 + B * K].reshape(B, K).astype(np.int64)
+                ids = self._stage_slab(kept, blk, B, K)
                 width = int((ids[:, 1:] != 0).sum(axis=1).max())                      # pad_sequence to the batch maximum, ats.py:78
                 decisions[blk] = ids[:, 1:1 + width] - 1                              # ats.py:253
         return {"Kept_Tokens": decisions, "Features": {}}
@@ -1288,23 +1323,14 @@ class SinkhornVisionTransformer(SelfSlimmedVisionTransformer):
     unit-norm tokens.  (The reference re-normalises `v` in place every forward, sinkhorn.py:73-76; here the normalised copy is
     made when the weights are packed and the parameter is left untouched.)"""
     _family = _lib.TR_FAMILY_SINKHORN
+    _center_feats = True
 
-    def __init__(self, *a, args=None, **kw):
-        VisionTransformer.__init__(self, *a, args=args, **kw)
-        self.cluster_loc = list(args.reduction_loc)
-        self.cluster_count = list(args.keep_rate)
+    def _cluster_settings(self, args):
         self.sinkhorn_eps = float(args.sinkhorn_eps)
         self.sinkhorn_iters = int(args.cluster_iters)
-        P0 = self.patch_embed.num_patches
-        if len(self.cluster_count) == 1:
-            self.cluster_count = [int(P0 * (args.keep_rate[0] ** (idx + 1))) for idx in range(len(self.cluster_loc))]   # sinkhorn.py:128-129
-        assert len(self.cluster_count) == len(self.cluster_loc), \
-            f"Mismatch between the cluster location ({self.cluster_loc}) and cluster centers ({self.cluster_count})"
-        self.cluster_count = [int(c) for c in self.cluster_count]
-        self.cluster_layers = nn.ModuleList([Sinkhorn(self.embed_dim, c, self.sinkhorn_eps, self.sinkhorn_iters)
-                                             for c in self.cluster_count])
-        for c, loc in zip(self.cluster_count, self.cluster_loc):
-            self._set_keep(loc, c, "the cluster schedule")
+
+    def _make_cluster_layer(self, count):
+        return Sinkhorn(self.embed_dim, count, self.sinkhorn_eps, self.sinkhorn_iters)
 
     def _pre_pack(self):
         if self.training:                       # sinkhorn.py:72-76: the centres are re-normalised IN PLACE (no grad) at every forward
@@ -1327,20 +1353,15 @@ class SinkhornVisionTransformer(SelfSlimmedVisionTransformer):
             v = torch.nn.functional.normalize(self.cluster_layers[j].v.detach().float(), p=2, dim=-1)
             WT.stage[loc].w1 = t16(_pad_rows(v, self._soft_pad(self.cluster_count[j])[1]))
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         for j, loc in enumerate(self.cluster_loc):
             v, st = self.cluster_layers[j].v.detach(), W.stage[loc]
             K = self.cluster_count[j]
-            n_pad = (K + 7) // 8 * 8
+            n_pad = self._soft_pad(K)[0]
             w1 = torch.zeros(n_pad, v.shape[1], dtype=torch.float32, device=v.device)
             w1[:K] = torch.nn.functional.normalize(v.float(), p=2, dim=-1)
-            st.w1, st.b1 = w16(w1), f32(torch.zeros(n_pad, dtype=torch.float32, device=v.device))
+            st.w1, st.b1 = pk.w16(w1), pk.f32(torch.zeros(n_pad, dtype=torch.float32, device=v.device))
             st.n_pad = n_pad
-
-    def _viz_data(self, ws, B, tokens):
-        out = super()._viz_data(ws, B, tokens)
-        out["Center_Feats"] = {}
-        return out
 
 
 class KMedoids(nn.Module):
@@ -1351,29 +1372,21 @@ class KMedoids(nn.Module):
         self.cluster_count, self.iters, self.equal_weights = num_clusters, iters, equal_weights
 
 
-class KMedoidsVisionTransformer(VisionTransformer):
+class KMedoidsVisionTransformer(_ClusterBase):
     """models/kmedoids.py:152-272: before each block in reduction_loc the patch tokens are clustered by weighted K-Medoids
     (weights = column sums of the previous block's attention) and replaced by the medoid tokens themselves."""
     _blocks_last = True
     _family = _lib.TR_FAMILY_KMEDOIDS
 
-    def __init__(self, *a, args=None, **kw):
-        super().__init__(*a, args=args, **kw)
+    def _cluster_settings(self, args):
         self.num_patches = self.patch_embed.num_patches
-        self.cluster_loc = list(args.reduction_loc)
-        self.cluster_count = list(args.keep_rate)
         self.sinkhorn_iters = self.cluster_iters = int(args.cluster_iters)      # cfg.cluster_iters carries it to the executor
         self.equal_weight = bool(args.equal_weight)
-        if len(self.cluster_count) == 1:
-            self.cluster_count = [int(self.num_patches * (args.keep_rate[0] ** (idx + 1))) for idx in range(len(self.cluster_loc))]
-        assert len(self.cluster_count) == len(self.cluster_loc), \
-            f"Mismatch between the cluster location ({self.cluster_loc}) and cluster centers ({self.cluster_count})"
-        self.cluster_count = [int(c) for c in self.cluster_count]
         if 0 in self.cluster_loc:
             raise ValueError("kmedoids cannot reduce before block 0: there is no previous attention (kmedoids.py:240)")
-        self.cluster_layers = nn.ModuleList([KMedoids(c, self.cluster_iters, self.equal_weight) for c in self.cluster_count])
-        for c, loc in zip(self.cluster_count, self.cluster_loc):
-            self._set_keep(loc, c, "the cluster schedule")
+
+    def _make_cluster_layer(self, count):
+        return KMedoids(count, self.cluster_iters, self.equal_weight)
 
     def _per_forward_config(self, cfg):
         """args.equal_weight (kmedoids.py:43-47): every k_medoids_fit call draws its first medoid with
@@ -1382,33 +1395,12 @@ class KMedoidsVisionTransformer(VisionTransformer):
         keyed on them through the noise key below)."""
         if not self.equal_weight:
             return
-        p_in, draws = self.num_patches, []
-        for K, loc in sorted(zip(self.cluster_count, self.cluster_loc), key=lambda t: t[1]):
+        draws = []
+        for loc, _, p_in in self._stage_shapes():
             first = int(np.random.choice(np.arange(p_in), 1)[0])
             cfg.kmed_init[loc] = first + 1
             draws.append(first)
-            p_in = K
         self._kmed_draws = tuple(draws)
-
-    def _noise_ptr(self, B, dev):
-        return None
-
-    def get_new_module_names(self):
-        return ["cluster_layers"]
-
-    def get_reduction_count(self):
-        return self.cluster_loc
-
-    _stage_shapes = DPCKNNVisionTransformer._stage_shapes
-
-    def _viz_data(self, ws, B, tokens):
-        P1 = self.patch_embed.num_patches + 1
-        kept, assign = ws["kept"].cpu().numpy(), ws["compl"].cpu().numpy()
-        decisions, assignments = {}, {}
-        for blk, K, P in self._stage_shapes():
-            decisions[blk] = kept[blk * B * P1: blk * B * P1 + B * K].reshape(B, K).astype(np.int64)
-            assignments[blk] = assign[blk * B * P1: blk * B * P1 + B * P].reshape(B, P).astype(np.int64)
-        return {"Kept_Tokens": decisions, "Assignment_Maps": assignments, "Center_Feats": {}, "Features": {}}
 
 
 class PatchMerger(nn.Module):
@@ -1425,22 +1417,10 @@ class PatchMergerVisionTransformer(SelfSlimmedVisionTransformer):
     """models/patchmerger.py:42-150: before each block in reduction_loc, K learned queries attend over the LayerNorm-ed patch
     tokens (softmax over the tokens) and the outputs are the attention-weighted sums of the normalised tokens."""
     _family = _lib.TR_FAMILY_PATCHMERGER
+    _center_feats = True
 
-    def __init__(self, *a, args=None, **kw):
-        VisionTransformer.__init__(self, *a, args=args, **kw)
-        self.cluster_loc = list(args.reduction_loc)
-        self.cluster_count = list(args.keep_rate)
-        P0 = self.patch_embed.num_patches
-        if len(self.cluster_count) == 1:
-            self.cluster_count = [int(P0 * (args.keep_rate[0] ** (idx + 1))) for idx in range(len(self.cluster_loc))]   # patchmerger.py:78-79
-        assert len(self.cluster_count) == len(self.cluster_loc), \
-            f"Mismatch between the cluster location ({self.cluster_loc}) and cluster centers ({self.cluster_count})"
-        self.cluster_count = [int(c) for c in self.cluster_count]
-        self.cluster_layers = nn.ModuleList([PatchMerger(self.embed_dim, c) for c in self.cluster_count])
-        for m in self.cluster_layers.modules():
-            _init_vit_weights(m)
-        for c, loc in zip(self.cluster_count, self.cluster_loc):
-            self._set_keep(loc, c, "the cluster schedule")
+    def _make_cluster_layer(self, count):
+        return PatchMerger(self.embed_dim, count)
 
     def _grad_slot_numel(self, name, p):
         for j, K in enumerate(self.cluster_count):
@@ -1458,22 +1438,17 @@ class PatchMergerVisionTransformer(SelfSlimmedVisionTransformer):
         for j, loc in enumerate(self.cluster_loc):
             WT.stage[loc].w1 = t16(_pad_rows(self.cluster_layers[j].queries, self._soft_pad(self.cluster_count[j])[1]))
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         for j, loc in enumerate(self.cluster_loc):
             m, st = self.cluster_layers[j], W.stage[loc]
             K = self.cluster_count[j]
-            n_pad = (K + 7) // 8 * 8
+            n_pad = self._soft_pad(K)[0]
             w1 = torch.zeros(n_pad, self.embed_dim, dtype=torch.float32, device=m.queries.device)
             w1[:K] = m.queries.detach()
-            st.ln_g, st.ln_b = f32(m.norm.weight), f32(m.norm.bias)
-            st.w1, st.b1 = w16(w1), f32(torch.zeros(n_pad, dtype=torch.float32, device=w1.device))
+            st.ln_g, st.ln_b = pk.f32(m.norm.weight), pk.f32(m.norm.bias)
+            st.w1, st.b1 = pk.w16(w1), pk.f32(torch.zeros(n_pad, dtype=torch.float32, device=w1.device))
             st.scale = float(m.scale)
             st.n_pad = n_pad
-
-    def _viz_data(self, ws, B, tokens):
-        out = super()._viz_data(ws, B, tokens)
-        out["Center_Feats"] = {}
-        return out
 
 
 class HeuristicVisionTransformer(VisionTransformer):
@@ -1551,11 +1526,11 @@ class HeuristicVisionTransformer(VisionTransformer):
     def _block_mask(self, idx):
         return (self.distances <= self.threshold[idx]).reshape(self.P * self.P)
 
-    def _pack_stages(self, W, w16, f32, keep_alive):
+    def _pack_stages(self, W, pk):
         dev = self.pos_embed.device
         for idx in self.reduction_loc:
             m = torch.cat([torch.ones(1), self._block_mask(idx).float()]).to(dev)
-            W.stage[idx].w3 = f32(m)
+            W.stage[idx].w3 = pk.f32(m)
             W.stage[idx].n_pad = m.numel()
 
     def _feature_blocks(self, tokens):

@@ -60,8 +60,8 @@ class FusedAdamW(torch.optim.Optimizer):
         m = self._model
         if m is None or getattr(m, "precision", "bf16") != "bf16":
             return None
-        tab = m.__dict__.get("_pack_table")
-        if tab is None or not getattr(m, "_pack_all_fused", False):
+        tab = m._pack_table
+        if tab is None or not m._pack_all_fused:
             return None
         return {sp: (dp, tp_) for sp, dp, tp_, _r, _c in tab["sig"]}
 
@@ -140,7 +140,7 @@ class FusedAdamW(torch.optim.Optimizer):
             # every operand copy was rewritten by the step (fp32 operands are read in place) -- but only the dirt this optimizer's own backward
             # left may be declared clean: a weights_changed() raised for another reason since (a manual p.data edit, an EMA / teacher copy
             # into a matrix this step did not touch) must survive
-            if tab["refreshes"] and getattr(m, "_dirty_by_backward", False):
+            if tab["refreshes"] and m._dirty_by_backward:
                 m._weights_dirty = False
                 m._dirty_by_backward = False
                 m._mlp_pk_stale = True             # the fused eval Mlp's fragment-major copies derive from the bf16 copies just rewritten

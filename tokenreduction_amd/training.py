@@ -326,7 +326,7 @@ class _VitTrainFn(torch.autograd.Function):
                 st.views[n].zero_()
         G = st.grads_struct(model)
         WT = st.transposed(model, pk)
-        reducer = getattr(model, "_grad_reducer", None)
+        reducer = model._grad_reducer
         reduce_now = reducer is not None and reducer.sync
         # one call for the whole model, or -- under a gradient reducer -- one call per bucket's block range, each followed by
         # that bucket's in-place reduction on the reducer's stream while the next range runs
@@ -352,7 +352,7 @@ class _VitTrainFn(torch.autograd.Function):
                 p.grad = st.views[n]
             elif p.grad.data_ptr() != st.views[n].data_ptr():
                 p.grad.add_(st.views[n])
-        was_dirty = bool(getattr(model, "_weights_dirty", False))
+        was_dirty = model._weights_dirty
         model.weights_changed()          # an optimizer step follows; fused optimizers do not bump the version counters the pack cache reads
         model._dirty_by_backward = not was_dirty      # dirt that was there before this backward is somebody else's: only a full repack clears it
         return None, None, None, None, None, None
