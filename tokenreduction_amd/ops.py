@@ -812,26 +812,43 @@ def attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, B: int, N: int, H: int,
     return dqkv
 
 
-def head_bwd(dlogits: torch.Tensor, w: torch.Tensor, xn: torch.Tensor):
+def _grad_out(t, shape, name: str, accumulate: bool, dev) -> torch.Tensor:
+    """A gradient destination: the caller's preallocated fp32 tensor (required when accumulating: the kernel adds to it), or a fresh one."""
+    if t is None:
+        if accumulate:
+            raise ValueError(f"{name}: accumulate=True adds to a destination the caller must pass")
+        return torch.empty(*shape, dtype=torch.float32, device=dev)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    _dev(t, torch.float32, name)
+    return t
+
+
+def head_bwd(dlogits: torch.Tensor, w: torch.Tensor, xn: torch.Tensor, accumulate: bool = False, dw: torch.Tensor = None,
+             db: torch.Tensor = None):
+    """Classifier backward on the CLS rows: (dxn bf16 [B,D], dW fp32 [C,D], db fp32 [C]); dW / db (+)= with accumulate (into the given dw, db)."""
     B, Cc = dlogits.shape
     D = w.shape[1]
     dxn = torch.empty(B, D, dtype=torch.bfloat16, device=w.device)
-    dw = torch.empty(Cc, D, dtype=torch.float32, device=w.device)
-    db = torch.empty(Cc, dtype=torch.float32, device=w.device)
+    dw = _grad_out(dw, (Cc, D), "dw", accumulate, w.device)
+    db = _grad_out(db, (Cc,), "db", accumulate, w.device)
     lib = _lib.load()
     dl16 = torch.empty(B, Cc, dtype=torch.bfloat16, device=w.device)
     ws = _ws(lib.tr_wgrad_workspace_floats(B, Cc, D), w.device)
     _lib.check(lib.tr_head_bwd(_dev(dlogits, torch.float32, "dlogits"), _dev(w, torch.bfloat16, "w"), _dev(xn, torch.bfloat16, "xn"),
-                               dxn.data_ptr(), dw.data_ptr(), db.data_ptr(), 0, dl16.data_ptr(), ws.data_ptr(), ws.numel(), B, Cc, D, _stream()),
+                               dxn.data_ptr(), dw.data_ptr(), db.data_ptr(), int(accumulate), dl16.data_ptr(), ws.data_ptr(), ws.numel(), B, Cc, D,
+                               _stream()),
                "tr_head_bwd")
     return dxn, dw, db
 
 
-def embed_bwd(g: torch.Tensor):
+def embed_bwd(g: torch.Tensor, accumulate: bool = False, dpos: torch.Tensor = None, dcls: torch.Tensor = None):
+    """(d pos_embed fp32 [N,D], d cls_token fp32 [D]) = sums of g fp32 [B,N,D] over the batch; (+)= with accumulate (into the given dpos, dcls)."""
     B, N, D = g.shape
-    dpos = torch.empty(N, D, dtype=torch.float32, device=g.device)
-    dcls = torch.empty(D, dtype=torch.float32, device=g.device)
-    _lib.check(_lib.load().tr_embed_bwd(_dev(g, torch.float32, "g"), dpos.data_ptr(), dcls.data_ptr(), 0, B, N, D, _stream()), "tr_embed_bwd")
+    dpos = _grad_out(dpos, (N, D), "dpos", accumulate, g.device)
+    dcls = _grad_out(dcls, (D,), "dcls", accumulate, g.device)
+    _lib.check(_lib.load().tr_embed_bwd(_dev(g, torch.float32, "g"), dpos.data_ptr(), dcls.data_ptr(), int(accumulate), B, N, D, _stream()),
+               "tr_embed_bwd")
     return dpos, dcls
 
 
@@ -860,20 +877,24 @@ def tome_merge_bwd(g_merged, size_in, size_out, unm, src, dst, N: int):
     return g, gb
 
 
-def cluster_merge_bwd(g_in, x0, x1, wtok, assign, score_w):
-    """DPC-KNN CTM backward.  Returns (g fp32 [B,N,D], gb bf16, d_sw [D]|None, d_sb [1]|None)."""
+def cluster_merge_bwd(g_in, x0, x1, wtok, assign, score_w, accumulate: bool = False, dsw: torch.Tensor = None, dsb: torch.Tensor = None):
+    """DPC-KNN CTM backward.  Returns (g fp32 [B,N,D], gb bf16, d_sw [D]|None, d_sb [1]|None); d_sw / d_sb (+)= with accumulate (into the
+    given dsw, dsb; weighted merge only)."""
     B, N, D = x0.shape
     K = x1.shape[1] - 1
     lib = _lib.load()
     g = torch.empty(B, N, D, dtype=torch.float32, device=x0.device)
     gb = torch.empty(B, N, D, dtype=torch.bfloat16, device=x0.device)
-    dsw = torch.empty(D, dtype=torch.float32, device=x0.device) if score_w is not None else None
-    dsb = torch.empty(1, dtype=torch.float32, device=x0.device) if score_w is not None else None
+    if score_w is not None:
+        dsw = _grad_out(dsw, (D,), "dsw", accumulate, x0.device)
+        dsb = _grad_out(dsb, (1,), "dsb", accumulate, x0.device)
+    elif accumulate or dsw is not None or dsb is not None:
+        raise ValueError("cluster_merge_bwd: accumulate / dsw / dsb need score_w (the equal-weight merge has no score gradient)")
     ws = _ws((8 * B + 1) * (D + 4), x0.device)
     _lib.check(lib.tr_cluster_merge_bwd(_dev(g_in, torch.float32, "g_in"), _dev(x0, torch.float32, "x0"), _dev(x1, torch.float32, "x1"),
                                         _opt(wtok, torch.float32, "wtok"), _dev(assign, torch.int32, "assign"), _opt(score_w, torch.float32, "score_w"),
                                         g.data_ptr(), gb.data_ptr(), None if dsw is None else dsw.data_ptr(), None if dsb is None else dsb.data_ptr(),
-                                        0, ws.data_ptr(), ws.numel(), B, N, K, D, _stream()), "tr_cluster_merge_bwd")
+                                        int(accumulate), ws.data_ptr(), ws.numel(), B, N, K, D, _stream()), "tr_cluster_merge_bwd")
     return g, gb, dsw, dsb
 
 
