@@ -3,6 +3,9 @@
 PyTorch is plumbing here: it owns device memory and the stream; every byte of arithmetic happens
 in the hand-written gfx950 kernels behind include/tokenreduction_hip.h.  All tensors must live
 on a ROCm device -- there is no CPU path.
+
+The soft-assignment backward wrappers (soft_merge_bwd, token_softmax_bwd, sinkhorn_bwd) ZERO the outputs they allocate; the kernels
+write the patch rows of columns < K only (ds also a zero CLS row for those columns) and leave a caller's own output alone elsewhere.
 """
 from __future__ import annotations
 
@@ -908,38 +911,64 @@ def ats_scatter(g, dao_s, ids, N: int):
 
 
 # ---------------------------------------------------------------------------------------- soft-assignment reducers, backward (csrc/tr_soft_bwd.hip)
-def soft_merge_bwd(g: torch.Tensor, wt: torch.Tensor, src: torch.Tensor):
+def _soft_out(t, shape, dtype, name: str, dev) -> torch.Tensor:
+    """An output of the soft-assignment backward: a fresh ZEROED tensor, or the caller's (contiguous, of this shape; NOT zeroed here -- the
+    kernels write the patch rows of columns < K only, and `ds` a zero CLS row for those columns)."""
+    if t is None:
+        return torch.zeros(*shape, dtype=dtype, device=dev)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    _dev(t, dtype, name)
+    return t
+
+
+def _soft_ldo(ds, ldo, K: int) -> int:
+    if ldo is None:
+        return (K + 63) // 64 * 64 if ds is None else ds.shape[-1]
+    return int(ldo)
+
+
+def soft_merge_bwd(g: torch.Tensor, wt: torch.Tensor, src: torch.Tensor, dwt: torch.Tensor = None, dsrc: torch.Tensor = None):
     """out[b,1+k] = sum_p wt[b,1+p,k] src[b,1+p] backwards: g fp32 [B,K+1,D], wt fp32 [B,N,ldl], src fp32 [B,N,D] ->
-    (dwt fp32 [B,N,ldl] (CLS rows / columns >= K zero), dsrc fp32 [B,N,D] (CLS rows zero))."""
+    (dwt fp32 [B,N,ldl] (CLS rows / columns >= K zero), dsrc fp32 [B,N,D] (CLS rows zero)).  A given dwt / dsrc is written on the patch
+    rows (dwt: columns < K) and keeps what it held everywhere else."""
     B, N, D = src.shape
     K, ldl = g.shape[1] - 1, wt.shape[2]
     lib = _lib.load()
-    dwt = torch.zeros(B, N, ldl, dtype=torch.float32, device=src.device)
-    dsrc = torch.zeros(B, N, D, dtype=torch.float32, device=src.device)
+    dwt = _soft_out(dwt, (B, N, ldl), torch.float32, "dwt", src.device)
+    dsrc = _soft_out(dsrc, (B, N, D), torch.float32, "dsrc", src.device)
     _lib.check(lib.tr_soft_dweights(_dev(g, torch.float32, "g"), _dev(src, torch.float32, "src"), dwt.data_ptr(), ldl, B, N, K, D, _stream()),
                "tr_soft_dweights")
     _lib.check(lib.tr_soft_dsrc(_dev(g, torch.float32, "g"), _dev(wt, torch.float32, "wt"), ldl, dsrc.data_ptr(), B, N, K, D, _stream()), "tr_soft_dsrc")
     return dwt, dsrc
 
 
-def token_softmax_bwd(wt: torch.Tensor, dwt: torch.Tensor, logits: torch.Tensor, scale: float, K: int, want_dscale: bool = False):
-    """-> (ds bf16 [B,N,ld64], dscale fp32[1] | None)."""
+def token_softmax_bwd(wt: torch.Tensor, dwt: torch.Tensor, logits: torch.Tensor, scale: float, K: int, want_dscale: bool = False,
+                      ds: torch.Tensor = None, ldo: int = None, dscale: torch.Tensor = None, accumulate: bool = False):
+    """-> (ds bf16 [B,N,ldo], dscale fp32[1] | None); ldo = the given one, else the given ds's, else K rounded up to 64.  A given ds keeps
+    what it held in columns >= K.  d scale goes to the given `dscale` ((+)= with accumulate) or, with want_dscale, to a fresh one;
+    `logits` may be None when no d scale is asked for."""
     B, N, ldl = wt.shape
-    ldo = (K + 63) // 64 * 64
+    ldo = _soft_ldo(ds, ldo, K)
     lib = _lib.load()
-    ds = torch.zeros(B, N, ldo, dtype=torch.bfloat16, device=wt.device)
-    dscale = torch.zeros(1, dtype=torch.float32, device=wt.device) if want_dscale else None
+    ds = _soft_out(ds, (B, N, ldo), torch.bfloat16, "ds", wt.device)
+    if dscale is not None or accumulate:
+        dscale = _grad_out(dscale, (1,), "dscale", accumulate, wt.device)
+    elif want_dscale:
+        dscale = torch.zeros(1, dtype=torch.float32, device=wt.device)
     ws = _ws(lib.tr_token_softmax_bwd_workspace_floats(B, K), wt.device)
-    _lib.check(lib.tr_token_softmax_bwd(_dev(wt, torch.float32, "wt"), _dev(dwt, torch.float32, "dwt"), _dev(logits, torch.float32, "logits"), ldl,
-                                        float(scale), ds.data_ptr(), ldo, None if dscale is None else dscale.data_ptr(), 0, ws.data_ptr(), ws.numel(),
-                                        B, N, K, _stream()), "tr_token_softmax_bwd")
+    _lib.check(lib.tr_token_softmax_bwd(_dev(wt, torch.float32, "wt"), _dev(dwt, torch.float32, "dwt"), _opt(logits, torch.float32, "logits"), ldl,
+                                        float(scale), ds.data_ptr(), ldo, None if dscale is None else dscale.data_ptr(), int(accumulate),
+                                        ws.data_ptr(), ws.numel(), B, N, K, _stream()), "tr_token_softmax_bwd")
     return ds, dscale
 
 
-def sinkhorn_bwd(scores: torch.Tensor, dplan: torch.Tensor, K: int, eps: float, iters: int) -> torch.Tensor:
+def sinkhorn_bwd(scores: torch.Tensor, dplan: torch.Tensor, K: int, eps: float, iters: int, ds: torch.Tensor = None,
+                 ldo: int = None) -> torch.Tensor:
+    """-> ds bf16 [B,N,ldo] (ldo as token_softmax_bwd's); a given ds keeps what it held in columns >= K."""
     B, N, ldl = scores.shape
-    ldo = (K + 63) // 64 * 64
-    ds = torch.zeros(B, N, ldo, dtype=torch.bfloat16, device=scores.device)
+    ldo = _soft_ldo(ds, ldo, K)
+    ds = _soft_out(ds, (B, N, ldo), torch.bfloat16, "ds", scores.device)
     _lib.check(_lib.load().tr_sinkhorn_bwd(_dev(scores, torch.float32, "scores"), _dev(dplan, torch.float32, "dplan"), ldl, float(eps), iters,
                                            ds.data_ptr(), ldo, B, N, K, _stream()), "tr_sinkhorn_bwd")
     return ds
