@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests._hires_params import HIRES_CASES
+from tests._launches import forward_launches
 from tests._params import GOLDEN_CASES, make_images
 from tests.test_hip_model import build_model
 
@@ -144,22 +145,8 @@ def test_forward_async_and_model_call_both_honour_the_switch(name):
 
 
 def _launch_labels(model, x):
-    """Launch labels (tr_profile_begin / tr_profile_end) of one plain-launch forward."""
-    from tokenreduction_amd import _lib
-    lib = _lib.load()
-    graph, model.use_graph = model.use_graph, False
-    try:
-        model(x)
-        torch.cuda.synchronize()
-        cap = 1024
-        buf = torch.zeros(cap * 48, dtype=torch.uint8).numpy()
-        assert lib.tr_profile_begin(torch.cuda.current_stream().cuda_stream) == 0
-        model(x)
-        n = lib.tr_profile_end(cap, buf.ctypes.data, None, None, None)
-    finally:
-        model.use_graph = graph
-    assert 0 < n <= cap
-    return [bytes(buf[i * 48:(i + 1) * 48]).split(b"\0")[0].decode() for i in range(n)]
+    """Launch labels of one plain-launch forward."""
+    return [label for label, _, _ in forward_launches(model, x)]
 
 
 def test_the_switch_changes_the_launches_and_only_where_the_predicate_holds():

@@ -2,13 +2,12 @@
 that refused these shapes -- ToMe matching above 600 tokens, fp32 attention above 640, split attention above 1024, Sinkhorn with more
 than 640 centres once K x P exceeds the LDS -- against the oracle on the same inputs, and the launch labels that show the kernels of
 the shorter lengths are still the ones selected there."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import oracle
+from tests._launches import labels as _labels          # launch labels of the entry-point calls fn makes on the current stream
 
 pytestmark = pytest.mark.gpu
 
@@ -23,19 +22,6 @@ def ops():
 
 def _randn(seed, *shape, scale=1.0):
     return torch.from_numpy((np.random.default_rng(seed).standard_normal(shape) * scale).astype(np.float32))
-
-
-def _labels(fn):
-    """Launch labels (tr_profile_begin / tr_profile_end) of the entry-point calls fn makes on the current stream."""
-    from tokenreduction_amd import _lib
-    lib = _lib.load()
-    assert lib.tr_profile_begin(torch.cuda.current_stream().cuda_stream) == 0
-    fn()
-    cap = 64
-    buf = C.create_string_buffer(48 * cap)
-    n = lib.tr_profile_end(cap, buf, None, None, None)
-    assert 0 <= n <= cap
-    return [buf.raw[48 * i:48 * (i + 1)].split(b"\0")[0].decode() for i in range(n)]
 
 
 # ---------------------------------------------------------------------------------------- ToMe bipartite matching

@@ -8,117 +8,9 @@
 // Host-side only: shape bookkeeping and kernel launches (no allocation, no synchronisation, no
 // device->host copies), so one call is a fixed launch sequence that a caller may capture in a hipGraph.
 // Token counts are static per (config) -- topk.py:56 int(ratio*196) -- so every buffer size is known up front.
-#include <stdarg.h>
 #include <string.h>
-#include <vector>
 #include "tr_common.h"
-#include <mutex>
 #include "tr_plan.h"
-
-static thread_local char g_err[512] = "";
-
-void tr_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* tr_last_error(void) { return g_err; }
-
-// ---- launch profiler (see tr_common.h) ---------------------------------------------------------------------------------
-namespace {
-struct ProfRec { char label[48]; double flops, bytes; };
-struct Prof {
-  std::atomic<bool> on{false};
-  hipStream_t st = nullptr;
-  std::vector<hipEvent_t> ev;       // ev[0] = begin, ev[i+1] = after mark i
-  std::vector<ProfRec> recs;
-  size_t used = 0;
-};
-// ONE recording per process, whatever thread launches: a training step's forward runs on the caller's thread, its backward on the
-// autograd engine's device thread, and a recording started by the caller must see both (round 3: per-thread state recorded a third of
-// the step).  The launches of a recording are sequential on one stream; the mutex only keeps the vectors consistent.
-Prof g_prof;
-std::mutex g_prof_mu;
-thread_local ProfRec t_note;        // the pending note -> mark pair of this thread's current launch
-thread_local bool t_noted = false;
-}  // namespace
-
-void tr_prof_note(const char* label, double flops, double bytes) {
-  if (!g_prof.on.load(std::memory_order_relaxed)) return;
-  snprintf(t_note.label, sizeof(t_note.label), "%s", label);
-  t_note.flops = flops;
-  t_note.bytes = bytes;
-  t_noted = true;
-}
-
-void tr_prof_mark(const char* label) {
-  Prof& p = g_prof;
-  if (!p.on.load(std::memory_order_relaxed)) return;
-  ProfRec r;
-  if (t_noted) r = t_note;
-  else { snprintf(r.label, sizeof(r.label), "%s", label); r.flops = 0; r.bytes = 0; }
-  t_noted = false;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  if (!p.on.load(std::memory_order_relaxed)) return;
-  if (p.used + 1 >= p.ev.size()) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    p.ev.push_back(e);
-  }
-  (void)hipEventRecord(p.ev[p.used + 1], p.st);
-  ++p.used;
-  p.recs.push_back(r);
-}
-
-// Called at the top of the executors: when a recording is active and nothing has been marked yet, the opening event is taken again
-// HERE, so the first mark does not include the host time between tr_profile_begin and the executor's first launch.
-void tr_prof_restart() {
-  Prof& p = g_prof;
-  if (!p.on.load(std::memory_order_relaxed)) return;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  if (p.on.load(std::memory_order_relaxed) && p.used == 0) (void)hipEventRecord(p.ev[0], p.st);
-}
-
-// Start recording the launches the process enqueues on stream s through this library (must not be capturing).
-extern "C" int tr_profile_begin(tr_stream_t s) {
-  Prof& p = g_prof;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  if (p.ev.empty()) {
-    hipEvent_t e;
-    TR_REQUIRE(hipEventCreate(&e) == hipSuccess, TR_ERR_LAUNCH, "tr_profile_begin: cannot create an event");
-    p.ev.push_back(e);
-  }
-  p.st = static_cast<hipStream_t>(s);
-  p.recs.clear();
-  p.used = 0;
-  t_noted = false;
-  TR_REQUIRE(hipEventRecord(p.ev[0], p.st) == hipSuccess, TR_ERR_LAUNCH, "tr_profile_begin: event record failed");
-  p.on.store(true);
-  return TR_OK;
-}
-
-// Stop, wait for the stream, and return up to `max` marks: label (48 chars each), ms since the previous mark, FLOPs, bytes.
-// Returns the number of marks recorded (may exceed max; only max are written), or < 0 on error.
-extern "C" int tr_profile_end(int max, char* labels, float* ms, double* flops, double* bytes) {
-  Prof& p = g_prof;
-  TR_REQUIRE(p.on.load(), TR_ERR_CONFIG, "tr_profile_end: no recording is active");
-  p.on.store(false);
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  TR_REQUIRE(hipStreamSynchronize(p.st) == hipSuccess, TR_ERR_LAUNCH, "tr_profile_end: stream synchronize failed");
-  const int n = (int)p.recs.size();
-  for (int i = 0; i < n && i < max; ++i) {
-    float t = 0.f;
-    (void)hipEventElapsedTime(&t, p.ev[i], p.ev[i + 1]);
-    if (labels) memcpy(labels + (size_t)i * 48, p.recs[i].label, 48);
-    if (ms) ms[i] = t;
-    if (flops) flops[i] = p.recs[i].flops;
-    if (bytes) bytes[i] = p.recs[i].bytes;
-  }
-  return n;
-}
-extern "C" int tr_version(void) { return 100; }
 
 int tr_mlp_fused_wanted(int M, int D, int Hd, int have_scratch, int concurrent);      // tr_mlp_fused.hip: the schedule policy behind tr_set_mlp_fused
 int tr_mlp_resid_ln_enabled();                                        // tr_mlp_fused.hip: tr_set_mlp_resid_ln's switch
@@ -274,18 +166,755 @@ extern "C" size_t tr_vit_workspace_bytes(const tr_vit_config* cfg, int B) {
     if (rc__ != TR_OK) return rc__; \
   } while (0)
 
+namespace {
+
+inline const uint16_t* u16(const void* p) { return static_cast<const uint16_t*>(p); }
+inline uint16_t* u16(void* p) { return static_cast<uint16_t*>(p); }
+
+// Lab A/B switches of this file, read once per process: the eager norm2 (no lazy residual), the three-launch patch embedding, a memset
+// node in front of every fused-Mlp launch, whole blocks round-robin (no stream-K hand-over).
+struct Lab { bool ln_eager, patch_unfused, mlp_memset_each, mlp_no_streamk; };
+const Lab& lab() {
+  static const Lab l = [] {
+    auto on = [](const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; };
+    return Lab{on("TR_LN_EAGER"), on("TR_PATCH_UNFUSED"), on("TR_MLP_MEMSET_EACH"), on("TR_MLP_NO_STREAMK")};
+  }();
+  return l;
+}
+
+// One forward being enqueued: vit_forward_impl builds it and calls its steps in the reference forward's order.
 // tape != nullptr: TRAINING forward -- every activation the backward pass needs goes to its own slot of the tape (tr_plan.h)
 // instead of the shared scratch, the residual stream is written out of place (the inputs of norm1 / norm2 of every block stay),
 // fc1 keeps its pre-activation (GELU as a separate kernel), and the decisions (kept ids, sizes) are kept per block.
-// img: fp32 [B,C,S,S] (input_format TR_INPUT_F32) or uint8 pixels normalized through pixel_lut by the patch embedding
+struct Fwd {
+  // ---- fixed inputs, each read once ---------------------------------------------------------------------------------------------------
+  const tr_vit_config* cfg;
+  const tr_vit_weights* w;
+  Plan p;
+  int B, D, H, prec;
+  tr_stream_t s;
+  bool f32, train;              // f32: fp32 activations (TR_PREC_FP32 and TR_PREC_BF16X3)
+  char *ws, *tape;
+  const trplan::TapePlan* tp;
+  const void* img;              // fp32 [B,C,S,S] (TR_INPUT_F32) or uint8 pixels normalized through pixel_lut by the patch embedding
+  int input_format;
+  const float *pixel_lut, *aug_noise;
+  const tr_augment_rec* aug;
+  long aug_noise_len;
+  const float* drop_scale;      // DropPath: per block and image, attention branch then MLP branch
+  float drop_mul;               // Dropout: survivors are scaled by 1 / (1 - p) like nn.Dropout
+  float* logits;
+  int32_t *kept_idx, *compl_idx;
+  int* tokens_out;
+  // Lazy norm2 (eval, bf16, families whose blocks all start with a plain norm1): a norm2 that no reduction follows reads x + d_attn but
+  // does not store it; the next norm1 (or the final norm) adds d_attn and d_mlp in the reference's order and writes the stream once.
+  // Bit-identical to the eager sequence (same fp32 additions), 22 instead of 24 bytes per element and block through the norms.
+  bool lazy_base;
+  // Fused block tail (tr_mlp_fused_resid_ln_bf16): where the fused eval Mlp runs and the next block starts with a plain norm1, ONE launch does
+  // fc1 -> GELU -> fc2, adds the result to the stream in place and writes the next block's norm1 -- into the hidden-activation buffer, which the
+  // fused Mlp leaves unused and which nothing touches until that block's own Mlp (its only reader is the next qkv GEMM).  The block's norm2
+  // then writes the stream (eager): the kernel's accumulators start at the stream row.  OFF by default (tr_set_mlp_resid_ln): measured in the
+  // model it loses 4 % against fused Mlp + LayerNorm launch (the epilogue stalls the workgroup; profiles/r05_mlp_lab.md).
+  bool rl_base;
+  int conc;                     // other forwards run beside this one: a launch need not fill the chip on its own
+  // the fused Mlp's stream-K scratch is there and wanted.  Beside other forwards it is not: the other forward's launches fill the second
+  // round's idle compute units, and whole blocks round-robin move no accumulators (125 MB per launch at the first stage): measured with two
+  // forwards in flight +0.5 % (Top-K kr 0.7), +1.5 % (kr 0.5), +2 % (dense DeiT-S); one at a time -1.5 ... -4 % (tools/lab/inflight_ab2.py)
+  bool sk_ok;
+  bool one_memset;              // the stream-K counters of every fused-Mlp launch (block i: set i) are zeroed by ONE memset in front of the blocks
+
+  // ---- buffers: the shared scratch ... ------------------------------------------------------------------------------------------------
+  void *xn_shared, *ao_shared, *dbuf_shared, *dbuf2, *cols, *xcls;
+  float *cls_rows, *scores, *colsum_part, *size_a, *size_b;
+  int32_t *idx_ws, *compl_ws;
+  // ... and what currently stands in for each buffer (training re-points them at the block's tape slots: begin_block)
+  float *x, *x_alt;             // the residual stream and the buffer its next out-of-place form goes to
+  void *xn, *qkv, *ao, *hbuf;
+  void* dbuf;                   // bf16 output of proj / fc2, added to x by the NEXT norm
+
+  // ---- cursors ------------------------------------------------------------------------------------------------------------------------
+  int N;                        // tokens (incl. CLS) of the stream: the stage reducers and the in-block reducers lower it
+  const void* pending = nullptr;        // residual not yet added to x (the previous block's fc2 output): mlp sets it, the next norm takes it
+  const void* pending_attn = nullptr;   // the attention branch's residual of the previous block, not yet in x (lazy norm2 / cls_tail)
+  long pending_ld = 0;          // row stride of the pending residuals at the final norm's CLS rows; 0: N * D (cls_tail sets D)
+  const void* xn1_ready = nullptr;      // norm1 of the block about to start, written by the previous block's fused tail (mlp -> norm1_qkv)
+  float* size_cur = nullptr;    // ToMe token sizes / ATS and Heuristic key masks: none until the first merge (tome.py:185)
+  const float* policy_cur = nullptr;    // DyViT training: the keep policy every block attends under (all ones before the first stage)
+  const float* noise_in;        // DPC-KNN density noise / DyViT Gumbel noise, consumed stage by stage
+  float* soft_out;              // soft assignments of the stages, written back to back
+  const uint8_t* drop_keep;     // Dropout keep masks, consumed in the order tr_vit_dropout_mask_bytes documents
+  float* features_out;          // eval: the stream after every block, back to back; training: DyViT's distillation output
+  // ---- the block being enqueued (pre_block, begin_block) ------------------------------------------------------------------------------
+  bool have_xn = false;         // norm1(x) already in xn (written by a pre-block reducer)
+  bool tail = false;            // this block runs as the CLS tail
+  bool norm2_in_mlp = false;    // this block's norm2 runs inside its fused Mlp launch
+  int K = 0, Ks = 0, r = 0;              // Top-K / EViT tokens kept, ATS sample_count, ToMe tokens merged away (0 = plain block)
+
+  // the arguments of vit_forward_impl, validated; every member is set here
+  Fwd(const tr_vit_config* cfg_, const tr_vit_weights* w_, const Plan& plan, int B_, tr_stream_t s_, void* workspace, char* tape_,
+      const trplan::TapePlan* tp_, const void* img_, int input_format_, const float* pixel_lut_, const tr_augment_rec* aug_,
+      const float* aug_noise_, long aug_noise_len_, float* logits_, int32_t* kept_idx_, int32_t* compl_idx_, float* soft_out_,
+      const float* noise_in_, float* features_out_, int* tokens_out_, const float* drop_scale_, const uint8_t* drop_keep_, float drop_rate)
+      : cfg(cfg_), w(w_), p(plan), B(B_), D(plan.D), H(plan.H), prec(cfg_->precision), s(s_), f32(cfg_->precision != TR_PREC_BF16),
+        train(tape_ != nullptr), ws(static_cast<char*>(workspace)), tape(tape_), tp(tp_), img(img_), input_format(input_format_),
+        pixel_lut(pixel_lut_), aug_noise(aug_noise_), aug(aug_), aug_noise_len(aug_noise_len_), drop_scale(drop_scale_),
+        drop_mul(drop_keep_ != nullptr ? 1.0f / (1.0f - drop_rate) : 1.0f), logits(logits_), kept_idx(kept_idx_), compl_idx(compl_idx_),
+        tokens_out(tokens_out_), N(plan.N0), noise_in(noise_in_), soft_out(soft_out_), drop_keep(drop_keep_), features_out(features_out_) {
+    lazy_base = !train && !f32 && !lab().ln_eager && features_out == nullptr;
+    rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
+    conc = (!train && cfg->concurrent) ? 1 : 0;
+    sk_ok = p.mlp_sk_bytes > 0 && !lab().mlp_no_streamk && !conc;
+    one_memset = !train && prec == TR_PREC_BF16 && sk_ok && w->blocks[0].mlp_pk != nullptr && !lab().mlp_memset_each;
+    x = scratch(p.off_x0);
+    x_alt = scratch(p.off_x1);
+    xn = xn_shared = ws + p.off_xn;
+    qkv = ws + p.off_qkv;
+    ao = ao_shared = ws + p.off_ao;
+    hbuf = ws + p.off_h;
+    dbuf = dbuf_shared = ws + p.off_d;
+    dbuf2 = ws + p.off_d2;      // second residual buffer (norm2 without a stream write)
+    cols = train ? static_cast<void*>(tape + tp->cols) : static_cast<void*>(ws + p.off_cols);
+    cls_rows = scratch(p.off_cls);
+    scores = scratch(p.off_scores);
+    idx_ws = scratch<int32_t>(p.off_idx);
+    compl_ws = scratch<int32_t>(p.off_compl);
+    xcls = ws + p.off_xcls;
+    colsum_part = cfg->family == TR_FAMILY_KMEDOIDS ? scratch(p.off_cluster + align_up(tr_dpcknn_workspace_floats(B, p.N0) * 4)) : nullptr;
+    size_a = scratch(p.off_size0);
+    size_b = scratch(p.off_size1);
+  }
+
+  // ---- small helpers ------------------------------------------------------------------------------------------------------------------
+  template <class T = float> T* scratch(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+  template <class T = float> T* slot(size_t off) const { return reinterpret_cast<T*>(tape + off); }
+  void* sk_scratch() const { return sk_ok ? ws + p.off_mlp_sk : nullptr; }
+  void swap_x() { float* t = x; x = x_alt; x_alt = t; }
+  // where a stage's kept / centre ids and its complement / assignment ids go: the block's tape slot, the caller's per-block slab, or scratch
+  int32_t* kept_dst(int i) const {
+    return train ? slot<int32_t>(tp->blk[i].idx) : kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
+  }
+  int32_t* compl_dst(int i) const {
+    return train ? slot<int32_t>(tp->blk[i].idx2) : compl_idx ? compl_idx + (size_t)i * B * p.N0 : compl_ws;
+  }
+  void soft_advance(int Kc) { if (soft_out) soft_out += (size_t)B * Kc * (N - 1); }
+  // what consumes the pending residuals after block j - 1: a plain norm1 (or the final norm) unless a pre-block reducer fires at block j
+  bool starts_plain(int j) const {
+    if (j >= cfg->depth) return true;
+    switch (cfg->family) {
+      case TR_FAMILY_DPCKNN: case TR_FAMILY_KMEDOIDS: case TR_FAMILY_PATCHMERGER: case TR_FAMILY_SINKHORN: case TR_FAMILY_DYVIT:
+      case TR_FAMILY_SIT: return cfg->keep[j] <= 0;
+      default: return true;                                   // in-block families (Top-K, EViT, ToMe, ATS), DeiT, Heuristic (masks only)
+    }
+  }
+  // x + resid -> dst (out of place: x stays, on the tape), LayerNorm of the sum -> y (bf16); the stream continues in dst
+  int stream_to(float* dst, const void* resid, const float* g, const float* b, void* y, float eps) {
+    TR_TRY(tr_layernorm_bf16_to(x, D, dst, D, u16(resid), D, g, b, u16(y), B * N, D, eps, s));
+    x = dst;
+    return TR_OK;
+  }
+  // training: the stream entering stage i (x + the previous mlp output) goes to the block's tape slot x0
+  int enter_stage(int i, const float* g, const float* b, void* y, float eps) {
+    TR_TRY(stream_to(slot(tp->blk[i].x0), pending, g, b, y, eps));
+    pending = nullptr;
+    return TR_OK;
+  }
+  // the weighted sums of a soft assignment sc [B*N, ld] into x_alt: on MFMA where the bf16 executor can (K <= 192), else the family's own kernel
+  template <class F>
+  int soft_merge(float* sc, int ld, float scale, int softmax, const float* xh, float* soft, int Kc, F fallback) {
+    if (!f32 && Kc <= 192) return tr_softassign_merge_fast(sc, ld, scale, softmax, x, xh, x_alt, soft, B, N, Kc, D, s);
+    return fallback();
+  }
+  // Dropout (timm's drop_rate: pos_drop topk.py:186, proj_drop :53, the Mlp's two nn.Dropout): training only.  The caller draws the keep
+  // masks (1 byte per element, in forward order: tr_vit_dropout_mask_bytes).  stream: buf is the fp32 stream, else a bf16 branch output.
+  int drop(void* buf, size_t n, bool stream = false) {
+    if (drop_keep == nullptr) return TR_OK;
+    TR_TRY(stream ? tr_dropout_f32(static_cast<float*>(buf), static_cast<float*>(buf), drop_keep, drop_mul, n, s)
+                  : tr_dropout_bf16(u16(buf), u16(buf), drop_keep, drop_mul, n, s));
+    drop_keep += n;
+    return TR_OK;
+  }
+  // DropPath on the branch output in dbuf (topk.py:87, :95): block i's per-image scale, branch 0 = attention, 1 = MLP
+  int drop_path(int i, int branch) {
+    if (drop_scale == nullptr) return TR_OK;
+    return tr_rowscale_bf16(u16(dbuf), u16(dbuf), drop_scale + (size_t)(2 * i + branch) * B, B, N, D, s);
+  }
+
+  // ---- steps, in forward order --------------------------------------------------------------------------------------------------------
+  // a1 + a2: patch embedding, CLS token, position embedding; pos_drop
+  // uint8 pixels: the same choice of path, each with its uint8 loader (normalization through the LUT; same columns, same bits)
+  int embed() {
+    const bool pixels = input_format != TR_INPUT_F32;
+    const uint8_t* u8img = static_cast<const uint8_t*>(img);
+    const float* fimg = static_cast<const float*>(img);
+    const int layout = input_format == TR_INPUT_U8_NHWC ? TR_LAYOUT_NHWC : TR_LAYOUT_NCHW;
+    const int C = cfg->in_chans, S = cfg->img_size, patch = cfg->patch;
+    if (!train && !f32 && !lab().patch_unfused && tr_patch_embed_supported(C, S, patch, D)) {
+      // eval: unfold + GEMM + cls/pos in one launch (tr_patch.hip), at every batch size (the two paths differ in the last bit: an image's
+      // tokens must not depend on its batch); training keeps the column matrix (PatchEmbed's weight-gradient operand)
+      if (pixels)
+        TR_TRY(tr_patch_embed_u8_bf16(u8img, pixel_lut, layout, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, S, patch, D, s));
+      else
+        TR_TRY(tr_patch_embed_bf16(fimg, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, S, patch, D, s));
+    } else {
+      if (pixels && aug != nullptr)      // training on uint8 pixels with the device-side erase / mixup / cutmix: the same columns, of the augmented image
+        TR_TRY(tr_im2col_u8_aug_bf16(u8img, pixel_lut, layout, aug, aug_noise, aug_noise_len, u16(cols), B, C, S, S, patch, s));
+      else if (pixels)
+        TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, C, S, S, patch, s));
+      else
+        TR_TRY(op_im2col(f32, fimg, cols, B, C, S, S, patch, s));
+      TR_TRY(op_gemm(prec, cols, w->patch_w, w->patch_b, x, w->pos_embed, p.P, B * p.P, D, p.kcols, TR_EPI_PATCH_F32, s));
+      TR_TRY(tr_cls_pos_rows(w->cls_token, w->pos_embed, x, B, p.N0, D, s));
+    }
+    return drop(x, (size_t)B * p.N0 * D, true);
+  }
+
+  // what the blocks need before the first one: the fused Mlp's zeroed counters, DyViT training's all-ones policy
+  int before_blocks() {
+    if (one_memset) TR_TRY(tr_mlp_fused_zero_counters(ws + p.off_mlp_sk, p.mlp_sk_bytes, D, p.Hd, cfg->depth, s));
+    if (train && cfg->family == TR_FAMILY_DYVIT) {
+      float* ones = slot(tp->ones);
+      TR_TRY(tr_fill_f32(ones, 1.0f, (size_t)B * p.N0, s));
+      policy_cur = ones;
+    }
+    return TR_OK;
+  }
+
+  // the reduction stage in FRONT of block i, for the families that have one there
+  int pre_block(int i) {
+    have_xn = false;
+    const bool stage = cfg->keep[i] > 0;
+    switch (cfg->family) {
+      case TR_FAMILY_DPCKNN: return stage ? stage_dpcknn(i) : TR_OK;
+      case TR_FAMILY_KMEDOIDS: return stage ? stage_kmedoids(i) : TR_OK;
+      case TR_FAMILY_HEURISTIC: return w->stage[i].w3 != nullptr ? stage_heuristic(i) : TR_OK;
+      case TR_FAMILY_PATCHMERGER: return stage ? stage_patchmerger(i) : TR_OK;
+      case TR_FAMILY_SINKHORN: return stage ? stage_sinkhorn(i) : TR_OK;
+      case TR_FAMILY_DYVIT: return !stage ? TR_OK : train ? stage_dyvit_train(i) : stage_dyvit(i);
+      case TR_FAMILY_SIT: return !stage ? TR_OK : train ? stage_sit_train(i) : stage_sit(i);
+      default: return TR_OK;
+    }
+  }
+
+  // DPC-KNN / K-Medoids: x += previous mlp output ahead of the clustering.  Training: the stream entering the reduction stays on the tape
+  // and the block's slots take over (x1: the reduced stream, norm1's input).  The norm output of that pass is not used -- it goes to the
+  // shared scratch, NOT to xn, which still names the previous block's norm2 slot on the tape.
+  int enter_cluster_stage(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    if (train) {
+      TR_TRY(enter_stage(i, bw->ln1_g, bw->ln1_b, xn_shared, cfg->ln_eps));
+      x_alt = slot(tp->blk[i].x1);
+      xn = tape + tp->blk[i].xn1;
+    } else if (pending) TR_TRY(op_ln(f32, x, D, pending, D, bw->ln1_g, bw->ln1_b, xn, B * N, D, cfg->ln_eps, s));
+    pending = nullptr;
+    return TR_OK;
+  }
+
+  // a19 + a20: CTM (dpcknn.py:153-172) on x[:, 1:] BEFORE the block; merge fused with the block's norm1
+  int stage_dpcknn(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const tr_stage_weights* sw = &w->stage[i];
+    const int Kc = cfg->keep[i];
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d clusters of %d patch tokens", i, Kc, N - 1);
+    TR_TRY(enter_cluster_stage(i));
+    float* cws = scratch(p.off_cluster);
+    float* wtok = train ? slot(tp->blk[i].scores) : cws + tr_dpcknn_workspace_floats(B, p.N0);
+    int32_t* assign = compl_dst(i);
+    TR_TRY(tr_dpcknn_cluster(x, noise_in, cws, kept_dst(i), assign, scores, B, N, D, Kc, cfg->knn_k > 0 ? cfg->knn_k : 5, f32 ? 0 : 1, s));
+    if (noise_in) noise_in += (size_t)B * (N - 1);
+    TR_TRY(tr_cluster_merge_layernorm(x, sw->w3, sw->b3, wtok, assign, bw->ln1_g, bw->ln1_b, x_alt, xn, f32 ? 1 : 0, B, N, Kc, D, cfg->ln_eps, s));
+    swap_x();
+    N = Kc + 1;
+    have_xn = true;
+    return TR_OK;
+  }
+
+  // a21: KMedoids (kmedoids.py:135-149) on x[:, 1:] BEFORE the block: the medoid tokens replace the patch tokens
+  int stage_kmedoids(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const int Kc = cfg->keep[i];
+    TR_REQUIRE(i > 0, TR_ERR_CONFIG, "tr_vit_forward: K-Medoids at block 0 has no previous attention to weigh the tokens "
+                                     "(the reference fails there too: `attn` is unbound, kmedoids.py:240)");
+    const int kinit = cfg->kmed_init[i];             // > 0: args.equal_weight, first medoid id + 1
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d medoids of %d patch tokens", i, Kc, N - 1);
+    TR_TRY(enter_cluster_stage(i));
+    int32_t* centers = kept_dst(i);
+    if (kinit > 0)
+      TR_TRY(tr_kmedoids_equal(x, kinit - 1, scratch(p.off_cluster), centers, compl_dst(i), B, N, D, Kc, cfg->cluster_iters, f32 ? 0 : 1, s));
+    else
+      TR_TRY(tr_kmedoids(x, colsum_part, scratch(p.off_cluster), centers, compl_dst(i), B, N, D, H, Kc, cfg->cluster_iters, f32 ? 0 : 1, s));
+    TR_TRY(op_gather(f32, x, nullptr, centers, nullptr, nullptr, bw->ln1_g, bw->ln1_b, x_alt, xn, B, N, Kc, D, cfg->ln_eps, s));
+    swap_x();
+    N = Kc + 1;
+    have_xn = true;
+    return TR_OK;
+  }
+
+  // f4: a new spatial mask takes effect at this block and stays until the next one (heuristic.py:247-258)
+  int stage_heuristic(int i) {
+    TR_REQUIRE(w->stage[i].n_pad == N, TR_ERR_CONFIG, "tr_vit_forward: block %d mask has %d entries for %d tokens", i, w->stage[i].n_pad, N);
+    float* mask_dst = train ? slot(tp->blk[i].size) : size_a;      // training keeps every block's mask
+    TR_TRY(tr_broadcast_rows(w->stage[i].w3, mask_dst, B, N, s));
+    size_cur = mask_dst;
+    return TR_OK;
+  }
+
+  // f4: PatchMerger.forward patchmerger.py:35-39 on x[:, 1:] BEFORE the block
+  int stage_patchmerger(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const int Kc = cfg->keep[i];
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d outputs of %d patch tokens", i, Kc, N - 1);
+    TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w1 && sw->b1 && sw->n_pad >= Kc && sw->n_pad % 8 == 0 &&
+                   sw->n_pad == trplan::soft_ld(Kc),
+               TR_ERR_CONFIG, "tr_vit_forward: block %d PatchMerger weights missing or n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
+    return train ? patchmerger_train(i, sw, Kc) : patchmerger_eval(sw, Kc);
+  }
+  // every operand of the stage's backward stays on the tape; the merged stream is written to norm1's input slot (x1: no swap, no xn)
+  int patchmerger_train(int i, const tr_stage_weights* sw, int Kc) {
+    const trplan::BlockTape& bt = tp->blk[i];
+    const int M = B * N;
+    TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG, "tr_vit_forward_train: block %d PatchMerger n_pad=%d K=%d", i, sw->n_pad, Kc);
+    float *xh = slot(bt.sxh), *slog = slot(bt.slog), *swt = slot(bt.swt);
+    uint16_t* pu = slot<uint16_t>(bt.pu);
+    TR_TRY(enter_stage(i, sw->ln_g, sw->ln_b, pu, 1e-5f));
+    TR_TRY(tr_layernorm_f32(x, D, nullptr, D, sw->ln_g, sw->ln_b, xh, M, D, 1e-5f, s));
+    TR_TRY(tr_gemm_bf16(pu, u16(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
+    TR_REQUIRE(hipMemcpyAsync(swt, slog, (size_t)M * sw->n_pad * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)) == hipSuccess,
+               TR_ERR_LAUNCH, "tr_vit_forward_train: copy failed");
+    TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, sw->scale, 1, x, xh, slot(bt.x1), soft_out, B, N, Kc, D, s));
+    soft_advance(Kc);
+    x = slot(bt.x1);
+    N = Kc + 1;
+    return TR_OK;
+  }
+  int patchmerger_eval(const tr_stage_weights* sw, int Kc) {
+    const int M = B * N;
+    float* xh = static_cast<float*>(qkv);              // LayerNorm-ed tokens, fp32 [M, D]
+    float* sc = scratch(p.off_soft);                   // similarities [M, n_pad]
+    TR_TRY(op_ln(f32, x, D, pending, D, sw->ln_g, sw->ln_b, xn, M, D, 1e-5f, s));        // x += previous mlp output; GEMM operand
+    pending = nullptr;
+    TR_TRY(tr_layernorm_f32(x, D, nullptr, D, sw->ln_g, sw->ln_b, xh, M, D, 1e-5f, s));  // the rows that are summed
+    TR_TRY(op_gemm(prec, xn, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
+    TR_TRY(soft_merge(sc, sw->n_pad, sw->scale, 1, xh, soft_out, Kc,
+                      [&] { return tr_softassign_merge(sc, sw->n_pad, sw->scale, x, xh, x_alt, soft_out, B, N, Kc, D, s); }));
+    soft_advance(Kc);
+    swap_x();
+    N = Kc + 1;
+    return TR_OK;
+  }
+
+  // a22: Sinkhorn.forward sinkhorn.py:66-86 on x[:, 1:] BEFORE the block
+  int stage_sinkhorn(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const int Kc = cfg->keep[i];
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d clusters of %d patch tokens", i, Kc, N - 1);
+    TR_REQUIRE(sw->w1 && sw->b1 && sw->n_pad >= Kc && sw->n_pad % 8 == 0 && sw->n_pad == trplan::soft_ld(Kc),
+               TR_ERR_CONFIG, "tr_vit_forward: block %d Sinkhorn centres missing or n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
+    return train ? sinkhorn_train(i, sw, Kc) : sinkhorn_eval(i, sw, Kc);
+  }
+  int sinkhorn_train(int i, const tr_stage_weights* sw, int Kc) {
+    const trplan::BlockTape& bt = tp->blk[i];
+    const tr_block_weights* bw = &w->blocks[i];
+    const int M = B * N;
+    const float eps = cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f;
+    TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG, "tr_vit_forward_train: block %d Sinkhorn n_pad=%d K=%d", i, sw->n_pad, Kc);
+    float *xh = slot(bt.sxh), *slog = slot(bt.slog), *swt = slot(bt.swt);
+    uint16_t* pu = slot<uint16_t>(bt.pu);
+    // x0 = x + pending (the norm output of this pass is not used: shared scratch)
+    TR_TRY(enter_stage(i, bw->ln1_g, bw->ln1_b, xn_shared, cfg->ln_eps));
+    TR_TRY(tr_rownorm(x, xh, pu, 0, M, D, s));
+    TR_TRY(tr_gemm_bf16(pu, u16(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
+    TR_TRY(tr_sinkhorn(slog, sw->n_pad, eps, cfg->cluster_iters, swt, soft_out, B, N, Kc, s));
+    soft_advance(Kc);
+    TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, 1.0f, 0, x, xh, slot(bt.x1), nullptr, B, N, Kc, D, s));
+    x = slot(bt.x1);                                   // norm1's input slot: no swap, no xn
+    N = Kc + 1;
+    return TR_OK;
+  }
+  int sinkhorn_eval(int i, const tr_stage_weights* sw, int Kc) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const int M = B * N;
+    const float eps = cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f;
+    if (pending) TR_TRY(op_ln(f32, x, D, pending, D, bw->ln1_g, bw->ln1_b, xn, M, D, cfg->ln_eps, s));   // x += previous mlp output
+    pending = nullptr;
+    float* xh = static_cast<float*>(qkv);              // unit-norm tokens, fp32 [M, D] (the qkv slab is free here)
+    float* sc = scratch(p.off_soft);                   // scores, then the transport plan in place [M, n_pad]
+    TR_TRY(tr_rownorm(x, xh, xn, f32 ? 1 : 0, M, D, s));
+    TR_TRY(op_gemm(prec, xn, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
+    TR_TRY(tr_sinkhorn(sc, sw->n_pad, eps, cfg->cluster_iters, sc, soft_out, B, N, Kc, s));
+    soft_advance(Kc);
+    TR_TRY(soft_merge(sc, sw->n_pad, 1.0f, 0, xh, nullptr, Kc,
+                      [&] { return tr_weighted_merge(sc, sw->n_pad, x, xh, x_alt, B, N, Kc, D, s); }));
+    swap_x();
+    N = Kc + 1;
+    return TR_OK;
+  }
+
+  // a11 / f4: DyViT TRAINING (dyvit.py:221-229): PredictorLG on the patch tokens under the previous decision, a straight-through
+  // Gumbel-softmax sample becomes this stage's policy; no token is removed (N stays).  Every activation goes to the stage's tape slots.
+  int stage_dyvit_train(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const trplan::BlockTape& bt = tp->blk[i];
+    const int M = B * N, Hh = sw->h_pad > 0 ? sw->h_pad : D / 2, Q = (D / 4 + 63) / 64 * 64;
+    TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1 && sw->w2 && sw->b2 && sw->w3 && sw->b3, TR_ERR_NULL,
+               "tr_vit_forward_train: block %d predictor weights missing", i);
+    // Hh: the D/2 hidden layer as packed -- zero-padded to a multiple of 64 (DeiT-T: 96 -> 128; zero weight rows / columns and zero
+    // bias: the padded activations are gelu(0) = 0 and carry no gradient), like the D/4 layer is padded to Q rows
+    TR_REQUIRE(Hh >= D / 2 && Hh % 64 == 0 && Hh == (D / 2 + 63) / 64 * 64 && sw->reserved_ == Q, TR_ERR_CONFIG,
+               "tr_vit_forward_train: the DyViT predictor must be packed with its hidden layers padded to %d / %d columns (got h_pad=%d, %d)",
+               (D / 2 + 63) / 64 * 64, Q, sw->h_pad, sw->reserved_);
+    TR_REQUIRE(noise_in != nullptr, TR_ERR_NULL, "tr_vit_forward_train: DyViT needs the Gumbel noise of every stage (noise_in)");
+    uint16_t *pu = slot<uint16_t>(bt.pu), *pcat = slot<uint16_t>(bt.pcat), *ph1 = slot<uint16_t>(bt.ph1), *ph2 = slot<uint16_t>(bt.ph2);
+    float* pol = slot(bt.pol);
+    TR_TRY(enter_stage(i, sw->ln_g, sw->ln_b, pu, 1e-5f));
+    TR_TRY(tr_gemm_gelu_keep_bf16(pu, u16(sw->w0), sw->b0, slot<uint16_t>(bt.ppre0), pcat, M, D, D, s));
+    TR_TRY(tr_pool_policy(pcat, policy_cur, B, N, D, 1e-6f, s));
+    TR_TRY(tr_gemm_gelu_keep_bf16(pcat, u16(sw->w1), sw->b1, slot<uint16_t>(bt.ppre1), ph1, M, Hh, D, s));
+    TR_TRY(tr_gemm_gelu_keep_bf16(ph1, u16(sw->w2), sw->b2, slot<uint16_t>(bt.ppre2), ph2, M, Q, Hh, s));
+    TR_TRY(tr_dyvit_decide(ph2, Q, sw->w3, sw->b3, noise_in, policy_cur, pol, slot(bt.ysoft), slot(bt.sm), slot(bt.hard), B, N, D / 4, s));
+    noise_in += (size_t)B * (N - 1) * 2;
+    policy_cur = pol;
+    return TR_OK;
+  }
+
+  // a23 TRAINING: TokenSlimmingModule (sit.py:36-40) with every activation on the tape
+  int stage_sit_train(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const trplan::BlockTape& bt = tp->blk[i];
+    const int Kc = cfg->keep[i], M = B * N, Hh = (D / 2 + 63) / 64 * 64;     // hidden width as packed (DeiT-T: 96 -> 128, zero padded)
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward_train: block %d asks for %d of %d patch tokens", i, Kc, N - 1);
+    TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1, TR_ERR_NULL, "tr_vit_forward_train: block %d SiT weights missing", i);
+    TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc) && (sw->h_pad == Hh || (sw->h_pad == 0 && Hh == D / 2)), TR_ERR_CONFIG,
+               "tr_vit_forward_train: the SiT module must be packed with its hidden layer padded to %d columns and n_pad == %d (got h_pad=%d n_pad=%d)",
+               Hh, trplan::soft_ld(Kc), sw->h_pad, sw->n_pad);
+    float *slog = slot(bt.slog), *swt = slot(bt.swt);
+    uint16_t *pu = slot<uint16_t>(bt.pu), *ph0 = slot<uint16_t>(bt.pcat);
+    TR_TRY(enter_stage(i, sw->ln_g, sw->ln_b, pu, 1e-5f));
+    TR_TRY(tr_gemm_gelu_keep_bf16(pu, u16(sw->w0), sw->b0, slot<uint16_t>(bt.ppre0), ph0, M, Hh, D, s));
+    TR_TRY(tr_gemm_bf16(ph0, u16(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, Hh, TR_EPI_F32, s));
+    TR_REQUIRE(hipMemcpyAsync(swt, slog, (size_t)M * sw->n_pad * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)) == hipSuccess,
+               TR_ERR_LAUNCH, "tr_vit_forward_train: copy failed");
+    TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, sw->scale, 1, x, x, slot(bt.x1), soft_out, B, N, Kc, D, s));
+    soft_advance(Kc);
+    x = slot(bt.x1);                                   // norm1's input slot: no swap, no xn
+    N = Kc + 1;
+    return TR_OK;
+  }
+
+  // eval DyViT / SiT: x (+= previous mlp output), the module's own LayerNorm (nn.LayerNorm default eps 1e-5: dyvit.py:97, sit.py:30) -> xn
+  int enter_module_stage(int i, const tr_stage_weights* sw, int Kc) {
+    TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d of %d patch tokens", i, Kc, N - 1);
+    TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1, TR_ERR_NULL,
+               "tr_vit_forward: block %d has no reduction-module weights (tr_vit_weights.stage)", i);
+    TR_TRY(op_ln(f32, x, D, pending, D, sw->ln_g, sw->ln_b, xn, B * N, D, 1e-5f, s));
+    pending = nullptr;
+    return TR_OK;
+  }
+
+  // a10: PredictorLG (dyvit.py:113-119, policy == 1 in eval) -> score -> argsort(desc)[:K] -> batch_index_select
+  int stage_dyvit(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const tr_block_weights* bw = &w->blocks[i];
+    const int Kc = cfg->keep[i], M = B * N;
+    TR_TRY(enter_module_stage(i, sw, Kc));
+    TR_REQUIRE(sw->w2 && sw->b2 && sw->w3 && sw->b3, TR_ERR_NULL, "tr_vit_forward: block %d predictor weights missing", i);
+    const int Hh = sw->h_pad > 0 ? sw->h_pad : D / 2;            // hidden width as packed (zero-padded to 64 for DeiT-T)
+    TR_REQUIRE(Hh >= D / 2 && (Hh % 64 == 0 || f32), TR_ERR_CONFIG, "tr_vit_forward: DyViT predictor hidden width %d invalid (D=%d)", Hh, D);
+    TR_TRY(op_gemm(prec, xn, sw->w0, sw->b0, ao, nullptr, 0, M, D, D, TR_EPI_GELU_BF16, s));
+    TR_TRY(tr_pool_broadcast(ao, f32 ? 1 : 0, B, N, D, 1e-6f, s));
+    TR_TRY(op_gemm(prec, ao, sw->w1, sw->b1, qkv, nullptr, 0, M, Hh, D, TR_EPI_GELU_BF16, s));
+    TR_TRY(op_gemm(prec, qkv, sw->w2, sw->b2, hbuf, nullptr, 0, M, D / 4, Hh, TR_EPI_GELU_BF16, s));
+    TR_TRY(tr_dyvit_score(hbuf, f32 ? 1 : 0, sw->w3, sw->b3, cls_rows, M, D / 4, s));
+    int32_t* idx_dst = kept_dst(i);
+    TR_TRY(tr_cls_topk(cls_rows, idx_dst, nullptr, scores, B, 1, N, Kc, s));
+    TR_TRY(op_gather(f32, x, nullptr, idx_dst, nullptr, nullptr, bw->ln1_g, bw->ln1_b, x_alt, xn, B, N, Kc, D, cfg->ln_eps, s));
+    have_xn = true;
+    swap_x();
+    N = Kc + 1;
+    return TR_OK;
+  }
+
+  // a23: TokenSlimmingModule (sit.py:36-40)
+  int stage_sit(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const int Kc = cfg->keep[i], M = B * N;
+    TR_TRY(enter_module_stage(i, sw, Kc));
+    TR_REQUIRE(sw->n_pad >= Kc && sw->n_pad % 8 == 0 && sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG,
+               "tr_vit_forward: block %d SiT n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
+    const int Hh = sw->h_pad > 0 ? sw->h_pad : D / 2;
+    TR_REQUIRE(Hh >= D / 2 && (Hh % 64 == 0 || f32), TR_ERR_CONFIG, "tr_vit_forward: SiT hidden width %d invalid (D=%d)", Hh, D);
+    TR_TRY(op_gemm(prec, xn, sw->w0, sw->b0, ao, nullptr, 0, M, Hh, D, TR_EPI_GELU_BF16, s));
+    float* sc = scratch(p.off_soft);                   // logits [M, n_pad]
+    TR_TRY(op_gemm(prec, ao, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, Hh, TR_EPI_F32, s));
+    TR_TRY(soft_merge(sc, sw->n_pad, sw->scale, 1, x, soft_out, Kc,
+                      [&] { return tr_sit_merge(sc, sw->n_pad, sw->scale, x, x_alt, soft_out, B, N, Kc, D, s); }));
+    soft_advance(Kc);
+    swap_x();
+    N = Kc + 1;
+    return TR_OK;
+  }
+
+  // what block i reduces inside the block, whether it runs as the CLS tail; training: its tape slots replace the shared scratch
+  int begin_block(int i) {
+    const int fam = cfg->family;
+    Ks = fam == TR_FAMILY_ATS ? cfg->keep[i] : 0;
+    K = (fam == TR_FAMILY_TOPK || fam == TR_FAMILY_EVIT) ? cfg->keep[i] : 0;
+    TR_REQUIRE(K >= 0 && K <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d keeps %d of %d patch tokens", i, K, N - 1);
+    if (K == N - 1) K = 0;  // topk.py:57 / evit.py:79: left_tokens == N-1 -> plain block
+    r = 0;                  // ToMe: r = min(r, (N - protected) // 2)  (tome.py:253)
+    if (fam == TR_FAMILY_TOME) {
+      TR_REQUIRE(cfg->keep[i] >= 0, TR_ERR_CONFIG, "tr_vit_forward: block %d has negative ToMe r", i);
+      r = cfg->keep[i] < (N - 1) / 2 ? cfg->keep[i] : (N - 1) / 2;
+    }
+    // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features).
+    // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
+    // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
+    // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
+    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && K == 0 && r == 0 && Ks == 0 &&
+           drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0 &&
+           tr_attention_cls_available() != 0;
+    norm2_in_mlp = false;
+    if (train) {
+      const trplan::BlockTape& bt = tp->blk[i];
+      xn = tape + bt.xn1; qkv = tape + bt.qkv; hbuf = tape + bt.h;
+      ao = Ks > 0 ? ao_shared : static_cast<void*>(tape + bt.ao);      // ATS keeps only the sampled rows of attn @ v
+      dbuf = (fam == TR_FAMILY_EVIT && K > 0) ? static_cast<void*>(tape + bt.dattn) : dbuf_shared;
+      x_alt = slot(bt.x2);
+    }
+    return TR_OK;
+  }
+
+  // x (+= previous mlp output); norm1(x) -> xn unless a stage reducer or the previous block's fused tail has written it; qkv
+  int norm1_qkv(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    if (train && !have_xn) {
+      TR_TRY(stream_to(slot(tp->blk[i].x1), pending, bw->ln1_g, bw->ln1_b, xn, cfg->ln_eps));
+    } else if (!have_xn && xn1_ready == nullptr) {
+      TR_TRY(op_ln_pending(f32, x, D, pending, pending_attn, D, bw->ln1_g, bw->ln1_b, xn, B * N, D, cfg->ln_eps, s));
+      pending_attn = nullptr;
+    }
+    TR_REQUIRE(pending_attn == nullptr, TR_ERR_CONFIG, "tr_vit_forward: internal: block %d did not absorb the lazy residual", i);
+    TR_TRY(op_gemm(prec, xn1_ready ? xn1_ready : xn, bw->qkv_w, bw->qkv_b, qkv, nullptr, 0, B * N, 3 * D, D, TR_EPI_BF16, s));
+    xn1_ready = nullptr;
+    return TR_OK;
+  }
+
+  // ToMe: log(size) bias on the keys; ATS / Heuristic: key mask as a 1/0 "size" (log 0 = -inf -> exactly zero weight, like
+  // masked_fill(-finfo.max) underflowing in the reference's softmax, ats.py:117-120)
+  const float* key_size() const {
+    const int fam = cfg->family;
+    return (fam == TR_FAMILY_TOME || fam == TR_FAMILY_ATS || fam == TR_FAMILY_HEURISTIC) ? size_cur : nullptr;
+  }
+
+  // the whole rest of the last block on the B CLS rows; the final norm takes both residuals at row stride D
+  int cls_tail(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    // every buffer below holds B compact rows [B, D] (or [B, Hd]); the stream keeps its row stride N * D
+    uint16_t *const ao_c = u16(ao), *const xn_c = u16(xn), *const h_c = u16(hbuf), *const d_attn = u16(dbuf_shared), *const d_mlp = u16(dbuf2);
+    TR_TRY(tr_attention_cls_bf16(u16(qkv), ao_c, key_size(), B, N, H, s));
+    TR_TRY(tr_gemm_bf16(ao_c, u16(bw->proj_w), bw->proj_b, d_attn, nullptr, 0, B, D, D, TR_EPI_BF16, s));
+    // norm2 of x + d_attn without a stream write (lazy): the final norm adds both residuals in the reference's order
+    TR_TRY(tr_layernorm2_bf16(x, (long)N * D, nullptr, 0, d_attn, D, nullptr, 0, bw->ln2_g, bw->ln2_b, xn_c, B, D, cfg->ln_eps, s));
+    // the GEMM pair, not the fused Mlp: two workgroups of that kernel would be one long latency chain (same bits: tr_mlp_fused.hip)
+    TR_TRY(tr_gemm_bf16(xn_c, u16(bw->fc1_w), bw->fc1_b, h_c, nullptr, 0, B, p.Hd, D, TR_EPI_GELU_BF16, s));
+    TR_TRY(tr_gemm_bf16(h_c, u16(bw->fc2_w), bw->fc2_b, d_mlp, nullptr, 0, B, D, p.Hd, TR_EPI_BF16, s));
+    pending_attn = d_attn;
+    pending = d_mlp;
+    pending_ld = D;
+    if (tokens_out) tokens_out[i] = N;
+    return TR_OK;
+  }
+
+  // attn(norm1(x)) -> ao   [x + proj(ao) is the reference's post-attention x, topk.py:87]
+  int attention(int i) {
+    if (policy_cur != nullptr)       // DyViT training: softmax_with_policy in every block (dyvit.py:245-246)
+      return tr_attention_policy_bf16(u16(qkv), u16(ao), policy_cur, B, N, H, s);
+    // K-Medoids: the NEXT block's clustering is seeded by the column sums of THIS block's attention (kmedoids.py:240)
+    const bool want_colsum = cfg->family == TR_FAMILY_KMEDOIDS && i + 1 < cfg->depth && cfg->keep[i + 1] > 0;
+    return op_attn(prec, qkv, ao, (K > 0 || Ks > 0) ? cls_rows : nullptr, key_size(), want_colsum ? colsum_part : nullptr, B, N, H, s);
+  }
+
+  // a16-a18: sample token ids on the CLS attention x |v|, keep those rows of x and of attn @ v (-> xn: proj's operand)
+  int reduce_ats(int i) {
+    const tr_stage_weights* sw = &w->stage[i];
+    const bool dyn = cfg->ats_dynamic != 0 && !train;
+    // (dynamic width: N is the batch maximum of the previous stage and may be below the static Ks; the buffers -- ids, the mask in the
+    // score buffer -- are sized for the first stage's N0 rows, which bounds Ks in either mode)
+    TR_REQUIRE(Ks >= 2 && (dyn ? Ks <= p.N0 : Ks <= N), TR_ERR_CONFIG, "tr_vit_forward: block %d ATS sample_count %d out of range for %d tokens", i, Ks,
+               dyn ? p.N0 : N);
+    TR_REQUIRE(sw->w3 && sw->n_pad >= 1, TR_ERR_NULL, "tr_vit_forward: block %d has no ATS sample grid (tr_vit_weights.stage)", i);
+    int32_t* ids = kept_dst(i);
+    float* mask_next = train ? slot(tp->blk[i].size) : (size_cur == size_a) ? size_b : size_a;
+    int Kg = Ks;             // rows the block keeps
+    if (dyn) {
+      // ats.py:77-78: the reference pads the unique ids to the batch maximum -- sample at the static bound (ids [B,Ks] stay the
+      // Kept_Tokens record), read that maximum back (one int: the stream is synchronised HERE), continue on the first Kg columns
+      float* mask_full = scores;                                   // [B,Ks]; the score buffer is not used by this family
+      int32_t* width_dev = scratch<int32_t>(p.off_misc);
+      TR_TRY(tr_ats_sample(cls_rows, qkv, f32 ? 1 : 0, size_cur, sw->w3, sw->n_pad, ids, mask_full, nullptr, B, N, H, Ks, s));
+      TR_TRY(tr_ats_width(mask_full, width_dev, B, Ks, s));
+      int32_t width = 0;
+      hipError_t e = hipMemcpyAsync(&width, width_dev, sizeof(width), hipMemcpyDeviceToHost, static_cast<hipStream_t>(s));
+      if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(s));
+      TR_REQUIRE(e == hipSuccess, TR_ERR_LAUNCH, "tr_vit_forward: ATS dynamic width read-back at block %d: %s (not capturable in a hipGraph)", i,
+                 hipGetErrorString(e));
+      Kg = width < 2 ? 2 : (width > Ks ? Ks : width);              // CLS + at least one column (an all-masked batch cannot occur: >= 1 sample)
+      TR_TRY(tr_ats_narrow(ids, mask_full, compl_ws, mask_next, B, Ks, Kg, s));
+      ids = compl_ws;
+    } else {
+      TR_TRY(tr_ats_sample(cls_rows, qkv, f32 ? 1 : 0, size_cur, sw->w3, sw->n_pad, ids, mask_next, nullptr, B, N, H, Ks, s));
+    }
+    if (train) {          // sampled rows of the stream -> x0 slot, of attn @ v -> ao slot (proj's operand); norm1's input stays in x1
+      float* xg = slot(tp->blk[i].x0);
+      xn = tape + tp->blk[i].ao;
+      TR_TRY(tr_ats_gather(x, ao, 0, ids, xg, xn, B, N, Ks, D, s));
+      x = xg;
+    } else {
+      TR_TRY(tr_ats_gather(x, ao, f32 ? 1 : 0, ids, x_alt, xn, B, N, Kg, D, s));
+      swap_x();
+    }
+    size_cur = mask_next;
+    N = Kg;
+    return TR_OK;
+  }
+
+  // proj -> dbuf (on the rows ATS kept, where it sampled), proj_drop (topk.py:53: inside the attention module, before the branch's DropPath)
+  int proj(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    TR_TRY(op_gemm(prec, Ks > 0 ? xn : ao, bw->proj_w, bw->proj_b, dbuf, nullptr, 0, B * N, D, D, TR_EPI_BF16, s));
+    TR_TRY(drop(dbuf, (size_t)B * N * D));
+    return drop_path(i, 0);
+  }
+
+  // Top-K on the CLS attention, then residual add + gather/compact (+ EViT fused token) + norm2 in one pass
+  int reduce_topk(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const bool fuse = cfg->family == TR_FAMILY_EVIT;
+    int32_t* idx_dst = kept_dst(i);
+    int32_t* cidx_dst = fuse ? compl_dst(i) : nullptr;
+    float* sc_dst = train ? slot(tp->blk[i].scores) : scores;
+    if (train) xn = tape + tp->blk[i].xn2;
+    TR_TRY(tr_cls_topk(cls_rows, idx_dst, cidx_dst, sc_dst, B, H, N, K, s));
+    TR_TRY(op_gather(f32, x, dbuf, idx_dst, cidx_dst, sc_dst, bw->ln2_g, bw->ln2_b, x_alt, xn, B, N, K, D, cfg->ln_eps, s));
+    swap_x();
+    N = K + 1 + (fuse ? 1 : 0);
+    return TR_OK;
+  }
+
+  // ToMe: bipartite matching on mean-over-heads K, then residual add + size-weighted merge + norm2 in one pass
+  int reduce_tome(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const int na = (N + 1) / 2;
+    if (train) xn = tape + tp->blk[i].xn2;
+    int32_t* unm = kept_dst(i);
+    int32_t* src = unm + (size_t)B * (na - r);
+    int32_t* dst = src + (size_t)B * r;
+    float* size_next = train ? slot(tp->blk[i].size) : (size_cur == size_a) ? size_b : size_a;
+    TR_TRY(tr_tome_match(qkv, f32 ? 1 : 0, unm, src, dst, B, N, H, r, s));
+    TR_TRY(tr_tome_merge_layernorm(x, dbuf, f32 ? 1 : 0, size_cur, unm, src, dst, bw->ln2_g, bw->ln2_b, x_alt, size_next, xn, B, N, r, D,
+                                   cfg->ln_eps, s));
+    swap_x();
+    size_cur = size_next;
+    N -= r;
+    return TR_OK;
+  }
+
+  // norm2 of a block that reduces nothing after its attention: on the tape, lazy, inside the fused Mlp, or eager
+  int norm2(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const int M = B * N;
+    if (train) {
+      xn = tape + tp->blk[i].xn2;
+      return stream_to(x_alt, dbuf, bw->ln2_g, bw->ln2_b, xn, cfg->ln_eps);
+    }
+    if (lazy_base && starts_plain(i + 1) &&
+        !(rl_base && i + 1 < cfg->depth && bw->mlp_pk != nullptr && tr_mlp_fused_wanted(M, D, p.Hd, sk_ok, conc))) {
+      // lazy norm2.  Where the fused Mlp follows as ONE round of blocks, the norm moves INTO that launch (tr_mlp_fused_ln_bf16: its fc1 waves
+      // normalise x + dbuf in registers; bit-identical to the launch below followed by the plain fused Mlp) -- no LayerNorm launch, no bf16
+      // rows in between (tr_set_mlp_ln; under the stream-K schedule the separate launch is faster: tr_mlp_fused.hip)
+      norm2_in_mlp = prec == TR_PREC_BF16 && drop_keep == nullptr && bw->mlp_pk != nullptr && tr_mlp_ln_wanted(M, D, p.Hd, sk_ok, conc);
+      if (!norm2_in_mlp)
+        TR_TRY(tr_layernorm2_bf16(x, D, nullptr, 0, u16(dbuf), D, nullptr, 0, bw->ln2_g, bw->ln2_b, u16(xn), M, D, cfg->ln_eps, s));
+      pending_attn = dbuf;
+      return TR_OK;
+    }
+    return op_ln(f32, x, D, dbuf, D, bw->ln2_g, bw->ln2_b, xn, M, D, cfg->ln_eps, s);
+  }
+
+  // mlp(norm2(x)) -> dbuf, added to x by the next block's norm1 (or the final norm)
+  int mlp(int i) {
+    const tr_block_weights* bw = &w->blocks[i];
+    const int M = B * N, Hd = p.Hd, cset = one_memset ? i : -1;
+    bool fused = false;
+    if (train) {
+      TR_TRY(tr_gemm_gelu_keep_bf16(u16(xn), u16(bw->fc1_w), bw->fc1_b, slot<uint16_t>(tp->blk[i].pre), u16(hbuf), M, Hd, D, s));
+    } else if (prec == TR_PREC_BF16 && bw->mlp_pk != nullptr && tr_mlp_fused_wanted(M, D, Hd, sk_ok, conc)) {
+      // eval: fc1 -> GELU -> fc2 in one launch, the hidden activation never leaves the CU (tr_mlp_fused.hip; bit-identical to the pair below,
+      // taken where its block schedule fills the chip)
+      fused = true;
+    } else {
+      TR_REQUIRE(!norm2_in_mlp, TR_ERR_CONFIG, "tr_vit_forward: internal: block %d skipped its norm2 launch but does not run the fused Mlp", i);
+      TR_TRY(op_gemm(prec, xn, bw->fc1_w, bw->fc1_b, hbuf, nullptr, 0, M, Hd, D, TR_EPI_GELU_BF16, s));
+    }
+    TR_TRY(drop(hbuf, (size_t)M * Hd));      // timm Mlp: drop after the activation ...
+    // the attention residual is still pending: fc2 writes beside it.  (Eval: the toggle persists across blocks; training: begin_block re-points dbuf)
+    dbuf = (pending_attn == dbuf_shared) ? dbuf2 : dbuf_shared;
+    const bool fused_tail = fused && rl_base && pending_attn == nullptr && i + 1 < cfg->depth && starts_plain(i + 1);
+    if (fused_tail) {
+      const tr_block_weights* nb = &w->blocks[i + 1];
+      TR_TRY(tr_mlp_fused_resid_ln_bf16_set(u16(xn), bw->mlp_pk, bw->fc1_b, bw->fc2_b, x, nb->ln1_g, nb->ln1_b, cfg->ln_eps, u16(hbuf), sk_scratch(),
+                                            p.mlp_sk_bytes, M, D, Hd, cset, s));
+      xn1_ready = hbuf;
+    } else if (fused && norm2_in_mlp)
+      TR_TRY(tr_mlp_fused_ln_bf16_set(x, u16(pending_attn), bw->ln2_g, bw->ln2_b, cfg->ln_eps, bw->mlp_pk, bw->fc1_b, u16(dbuf), sk_scratch(),
+                                      p.mlp_sk_bytes, M, D, Hd, cset, s));
+    else if (fused)
+      TR_TRY(tr_mlp_fused_bf16_set(u16(xn), bw->mlp_pk, bw->fc1_b, u16(dbuf), sk_scratch(), p.mlp_sk_bytes, M, D, Hd, cset, s));
+    else
+      TR_TRY(op_gemm(prec, hbuf, bw->fc2_w, bw->fc2_b, dbuf, nullptr, 0, M, D, Hd, TR_EPI_BF16, s));
+    TR_TRY(drop(dbuf, (size_t)M * D));       // ... and after fc2
+    TR_TRY(drop_path(i, 1));
+    pending = fused_tail ? nullptr : dbuf;
+    if (features_out && !train) {      // viz_data["Features"][i] (topk.py:197): x + mlp output, which x itself only absorbs in the next norm
+      TR_TRY(tr_residual_snapshot(x, pending, f32 ? 1 : 0, features_out, (size_t)M * D, s));
+      features_out += (size_t)M * D;
+    }
+    if (tokens_out) tokens_out[i] = N;
+    return TR_OK;
+  }
+
+  // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier -- or, headless (C == 0), the
+  // normed CLS rows themselves are the output (deit_viz.py:209-212 with head = nn.Identity()): the norm writes fp32 straight into `logits`
+  int final_norm_head() {
+    const bool headless = p.C == 0;
+    const long ld = (long)N * D, ldd_cls = pending_ld > 0 ? pending_ld : ld;
+    if (train && features_out != nullptr) {
+      // DyViT distillation (dyvit.py:252-258): the final norm of EVERY row is an output; the whole stream stays for its backward
+      TR_TRY(stream_to(slot(tp->xfin_all), pending, w->norm_g, w->norm_b, xn_shared, cfg->ln_eps));
+      TR_TRY(tr_layernorm_f32(x, D, nullptr, D, w->norm_g, w->norm_b, features_out, B * N, D, cfg->ln_eps, s));
+      pending = nullptr;
+    }
+    if (train && headless)          // the CLS rows entering the norm stay on the tape (xfinal) for the backward; the tape's xcls is not needed
+      return tr_layernorm_bf16_f32(x, ld, slot(tp->xfinal), D, u16(pending), ld, nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s);
+    if (train) {
+      xcls = tape + tp->xcls;
+      TR_TRY(tr_layernorm_bf16_to(x, ld, slot(tp->xfinal), D, u16(pending), ld, w->norm_g, w->norm_b, u16(xcls), B, D, cfg->ln_eps, s));
+    } else if (headless) {
+      return op_ln_pending(f32, x, ld, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
+    } else {
+      TR_TRY(op_ln_pending(f32, x, ld, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
+    }
+    return op_gemm(prec, xcls, w->head_w, w->head_b, logits, nullptr, 0, B, p.C, D, TR_EPI_F32, s);
+  }
+};
+
+}  // namespace
+
 static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
-                            float* logits, void* workspace,
-                            size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
+                            float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
                             const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0) {
   Plan p;
-  const bool train = tape != nullptr;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
              "tr_vit_forward: invalid config (need embed_dim == 64*heads, dims %% 64 == 0, classes >= 0 and %% 4 == 0, depth <= %d)",
@@ -295,635 +924,34 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   TR_REQUIRE(input_format == TR_INPUT_F32 || input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
              "tr_vit_forward: input_format %d is not a TR_INPUT_* format", input_format);
   TR_REQUIRE(input_format == TR_INPUT_F32 || pixel_lut != nullptr, TR_ERR_CONFIG, "tr_vit_forward: a uint8 input needs the pixel LUT");
-
   tr_prof_restart();
-  char* ws = static_cast<char*>(workspace);
-  float* x = reinterpret_cast<float*>(ws + p.off_x0);
-  float* x_alt = reinterpret_cast<float*>(ws + p.off_x1);
-  void* xn = static_cast<void*>(ws + p.off_xn);
-  void* const xn_shared = xn;
-  void* qkv = static_cast<void*>(ws + p.off_qkv);
-  void* ao = static_cast<void*>(ws + p.off_ao);
-  void* const ao_shared = ao;
-  void* hbuf = static_cast<void*>(ws + p.off_h);
-  void* dbuf = static_cast<void*>(ws + p.off_d);   // bf16 output of proj / fc2, added to x by the NEXT norm
-  void* const dbuf_shared = dbuf;
-  void* const dbuf2 = static_cast<void*>(ws + p.off_d2);
-  void* cols = train ? static_cast<void*>(tape + tp->cols) : static_cast<void*>(ws + p.off_cols);
-  float* cls_rows = reinterpret_cast<float*>(ws + p.off_cls);
-  float* scores = reinterpret_cast<float*>(ws + p.off_scores);
-  int32_t* idx_ws = reinterpret_cast<int32_t*>(ws + p.off_idx);
-  int32_t* compl_ws = reinterpret_cast<int32_t*>(ws + p.off_compl);
-  void* xcls = static_cast<void*>(ws + p.off_xcls);
-  float* colsum_part = cfg->family == TR_FAMILY_KMEDOIDS
-                           ? reinterpret_cast<float*>(ws + p.off_cluster + align_up(tr_dpcknn_workspace_floats(B, p.N0) * 4))
-                           : nullptr;
-  float* size_cur = nullptr;                                            // ToMe token sizes: none until the first merge (tome.py:185)
-  float* size_a = reinterpret_cast<float*>(ws + p.off_size0);
-  float* size_b = reinterpret_cast<float*>(ws + p.off_size1);
 
-  const int D = p.D, H = p.H;
-  const int prec = cfg->precision;
-  const bool f32 = prec != TR_PREC_BF16;            // fp32 activations (TR_PREC_FP32 and TR_PREC_BF16X3)
-  // Lazy norm2 (eval, bf16, families whose blocks all start with a plain norm1): a norm2 that no reduction follows reads x + d_attn but
-  // does not store it; the next norm1 (or the final norm) adds d_attn and d_mlp in the reference's order and writes the stream once.
-  // Bit-identical to the eager sequence (same fp32 additions), 22 instead of 24 bytes per element and block through the norms.
-  static const bool ln_eager = [] { const char* e = getenv("TR_LN_EAGER"); return e && atoi(e) != 0; }();      // lab: A/B switch
-  const bool lazy_base = !train && !f32 && !ln_eager && features_out == nullptr;
-  // what consumes the pending residuals after block j - 1: a plain norm1 (or the final norm) unless a pre-block reducer fires at block j
-  auto starts_plain = [&](int j) {
-    if (j >= cfg->depth) return true;
-    switch (cfg->family) {
-      case TR_FAMILY_DPCKNN: case TR_FAMILY_KMEDOIDS: case TR_FAMILY_PATCHMERGER: case TR_FAMILY_SINKHORN: case TR_FAMILY_DYVIT:
-      case TR_FAMILY_SIT: return cfg->keep[j] <= 0;
-      default: return true;                                   // in-block families (Top-K, EViT, ToMe, ATS), DeiT, Heuristic (masks only)
-    }
-  };
-  const void* pending_attn = nullptr;      // the attention branch's residual of the previous block, not yet in x (lazy norm2)
-  // Fused block tail (tr_mlp_fused_resid_ln_bf16): where the fused eval Mlp runs and the next block starts with a plain norm1, ONE launch does
-  // fc1 -> GELU -> fc2, adds the result to the stream in place and writes the next block's norm1 -- into the hidden-activation buffer, which the
-  // fused Mlp leaves unused and which nothing touches until that block's own Mlp (its only reader is the next qkv GEMM).  The block's norm2
-  // then writes the stream (eager): the kernel's accumulators start at the stream row.  OFF by default (tr_set_mlp_resid_ln): measured in the
-  // model it loses 4 % against fused Mlp + LayerNorm launch (the epilogue stalls the workgroup; profiles/r05_mlp_lab.md).
-  const bool rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
-  const void* xn1_ready = nullptr;         // norm1 of the block about to start, written by the previous block's fused tail
-  // a1 + a2: patch embedding, CLS token, position embedding
-  // uint8 pixels: the same choice of path, each with its uint8 loader (normalization through the LUT; same columns, same bits)
-  const bool pixels = input_format != TR_INPUT_F32;
-  const uint8_t* u8img = static_cast<const uint8_t*>(img);
-  const int layout = input_format == TR_INPUT_U8_NHWC ? TR_LAYOUT_NHWC : TR_LAYOUT_NCHW;
-  static const bool unfused_patch = [] { const char* e = getenv("TR_PATCH_UNFUSED"); return e && atoi(e) != 0; }();   // lab: the three-launch path
-  if (!train && !f32 && !unfused_patch && tr_patch_embed_supported(cfg->in_chans, cfg->img_size, cfg->patch, D)) {
-    // eval: unfold + GEMM + cls/pos in one launch (tr_patch.hip), at every batch size (the two paths differ in the last bit: an image's
-    // tokens must not depend on its batch); training keeps the column matrix (PatchEmbed's weight-gradient operand)
-    if (pixels)
-      TR_TRY(tr_patch_embed_u8_bf16(u8img, pixel_lut, layout, static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x,
-                                    B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
-    else
-      TR_TRY(tr_patch_embed_bf16(static_cast<const float*>(img), static_cast<const uint16_t*>(w->patch_w), w->patch_b, w->cls_token,
-                                 w->pos_embed, x, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
-  } else {
-    if (pixels && aug != nullptr)      // training on uint8 pixels with the device-side erase / mixup / cutmix: the same columns, of the augmented image
-      TR_TRY(tr_im2col_u8_aug_bf16(u8img, pixel_lut, layout, aug, aug_noise, aug_noise_len, static_cast<uint16_t*>(cols), B, cfg->in_chans,
-                                   cfg->img_size, cfg->img_size, cfg->patch, s));
-    else if (pixels)
-      TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
-    else
-      TR_TRY(op_im2col(f32, static_cast<const float*>(img), cols, B, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch, s));
-    TR_TRY(op_gemm(prec, cols, w->patch_w, w->patch_b, x, w->pos_embed, p.P, B * p.P, D, p.kcols, TR_EPI_PATCH_F32, s));
-    TR_TRY(tr_cls_pos_rows(w->cls_token, w->pos_embed, x, B, p.N0, D, s));
-  }
-  // Dropout (timm's drop_rate: pos_drop topk.py:186, proj_drop :53, the Mlp's two nn.Dropout): training only.  The caller draws the keep
-  // masks (1 byte per element, in forward order: tr_vit_dropout_mask_bytes); survivors are scaled by 1 / (1 - p) like nn.Dropout.
-  const float drop_mul = drop_keep != nullptr ? 1.0f / (1.0f - drop_rate) : 1.0f;
-  if (drop_keep != nullptr) {
-    TR_TRY(tr_dropout_f32(x, x, drop_keep, drop_mul, (size_t)B * p.N0 * D, s));
-    drop_keep += (size_t)B * p.N0 * D;
-  }
+  Fwd f(cfg, w, p, B, s, workspace, tape, tp, img, input_format, pixel_lut, aug, aug_noise, aug_noise_len, logits, kept_idx, compl_idx, soft_out,
+        noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate);
 
-  // the stream-K hand-over counters of every fused-Mlp launch of this forward (block i: set i) start at zero: ONE memset node here instead
-  // of one in front of each launch
-  static const bool memset_each = [] { const char* e = getenv("TR_MLP_MEMSET_EACH"); return e && atoi(e) != 0; }();      // lab: A/B switch (a memset node per launch)
-  static const bool no_streamk = [] { const char* e = getenv("TR_MLP_NO_STREAMK"); return e && atoi(e) != 0; }();          // lab: whole blocks round-robin, no hand-over
-  const int conc = (!train && cfg->concurrent) ? 1 : 0;       // other forwards run beside this one: a launch need not fill the chip on its own
-  // the fused Mlp's stream-K scratch is there and wanted.  Beside other forwards it is not: the other forward's launches fill the second
-  // round's idle compute units, and whole blocks round-robin move no accumulators (125 MB per launch at the first stage): measured with two
-  // forwards in flight +0.5 % (Top-K kr 0.7), +1.5 % (kr 0.5), +2 % (dense DeiT-S); one at a time -1.5 ... -4 % (tools/lab/inflight_ab2.py)
-  const bool sk_ok = p.mlp_sk_bytes > 0 && !no_streamk && !conc;
-  const bool one_memset = !train && prec == TR_PREC_BF16 && sk_ok && w->blocks[0].mlp_pk != nullptr && !memset_each;
-  if (one_memset) TR_TRY(tr_mlp_fused_zero_counters(ws + p.off_mlp_sk, p.mlp_sk_bytes, D, p.Hd, cfg->depth, s));
-  int N = p.N0;
-  const void* pending = nullptr;   // residual not yet added to x (the previous block's fc2 output)
-  long pending_ld = 0;             // row stride of the pending residuals at the final norm's CLS rows; 0: N * D (full-width last block)
-  const float* policy_cur = nullptr;      // DyViT training: the keep policy every block attends under (all ones before the first stage)
-  if (train && cfg->family == TR_FAMILY_DYVIT) {
-    float* ones = reinterpret_cast<float*>(tape + tp->ones);
-    TR_TRY(tr_fill_f32(ones, 1.0f, (size_t)B * p.N0, s));
-    policy_cur = ones;
-  }
+  // patch_embed -> cat(cls) + pos_embed -> depth x Block -> norm -> x[:,0] -> head, with
+  // Block: [stage reducer]; x += attn(norm1(x)); [in-block reducer]; x += mlp(norm2(x))
+  TR_TRY(f.embed());
+  TR_TRY(f.before_blocks());
   for (int i = 0; i < cfg->depth; ++i) {
-    const tr_block_weights* bw = &w->blocks[i];
-    const bool tome = cfg->family == TR_FAMILY_TOME;
-    bool have_xn = false;   // norm1(x) already in xn (written by a pre-block reducer)
-    if (cfg->family == TR_FAMILY_DPCKNN && cfg->keep[i] > 0) {
-      // a19 + a20: CTM (dpcknn.py:153-172) on x[:, 1:] BEFORE the block; merge fused with the block's norm1
-      const tr_stage_weights* sw = &w->stage[i];
-      const int Kc = cfg->keep[i], M = B * N;
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d clusters of %d patch tokens", i, Kc, N - 1);
-      if (train) {          // the stream entering the merge stays on the tape (out of place), norm1's input / output go to their slots
-        float* x0 = reinterpret_cast<float*>(tape + tp->blk[i].x0);
-        // (the norm output of this pass is not used -- it goes to the shared scratch, NOT to xn, which still names the previous
-        // block's norm2 slot on the tape)
-        TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, bw->ln1_g, bw->ln1_b, static_cast<uint16_t*>(xn_shared), M,
-                                    D, cfg->ln_eps, s));
-        x = x0;
-        x_alt = reinterpret_cast<float*>(tape + tp->blk[i].x1);
-        xn = tape + tp->blk[i].xn1;
-      } else if (pending) TR_TRY(op_ln(f32, x, D, pending, D, bw->ln1_g, bw->ln1_b, xn, M, D, cfg->ln_eps, s));   // x += previous mlp output
-      pending = nullptr;
-      float* cws = reinterpret_cast<float*>(ws + p.off_cluster);
-      float* wtok = train ? reinterpret_cast<float*>(tape + tp->blk[i].scores) : cws + tr_dpcknn_workspace_floats(B, p.N0);
-      int32_t* centers = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-      int32_t* assign = compl_idx ? compl_idx + (size_t)i * B * p.N0 : compl_ws;
-      if (train) {
-        centers = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx);
-        assign = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx2);
-      }
-      TR_TRY(tr_dpcknn_cluster(x, noise_in, cws, centers, assign, scores, B, N, D, Kc, cfg->knn_k > 0 ? cfg->knn_k : 5, f32 ? 0 : 1, s));
-      if (noise_in) noise_in += (size_t)B * (N - 1);
-      TR_TRY(tr_cluster_merge_layernorm(x, sw->w3, sw->b3, wtok, assign, bw->ln1_g, bw->ln1_b, x_alt, xn, f32 ? 1 : 0, B, N, Kc, D,
-                                        cfg->ln_eps, s));
-      float* t = x; x = x_alt; x_alt = t;
-      N = Kc + 1;
-      have_xn = true;
-    }
-    if (cfg->family == TR_FAMILY_KMEDOIDS && cfg->keep[i] > 0) {
-      // a21: KMedoids (kmedoids.py:135-149) on x[:, 1:] BEFORE the block: the medoid tokens replace the patch tokens
-      const int Kc = cfg->keep[i], M = B * N;
-      TR_REQUIRE(i > 0, TR_ERR_CONFIG, "tr_vit_forward: K-Medoids at block 0 has no previous attention to weigh the tokens "
-                                       "(the reference fails there too: `attn` is unbound, kmedoids.py:240)");
-      const int kinit = cfg->kmed_init[i];             // > 0: args.equal_weight, first medoid id + 1
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d medoids of %d patch tokens", i, Kc, N - 1);
-      int32_t* centers = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-      int32_t* assign = compl_idx ? compl_idx + (size_t)i * B * p.N0 : compl_ws;
-      if (train) {          // as for DPC-KNN: the stream entering the reduction stays on the tape, the medoid rows become norm1's input slot
-        float* x0 = reinterpret_cast<float*>(tape + tp->blk[i].x0);
-        TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, bw->ln1_g, bw->ln1_b, static_cast<uint16_t*>(xn_shared), M,
-                                    D, cfg->ln_eps, s));
-        x = x0;
-        x_alt = reinterpret_cast<float*>(tape + tp->blk[i].x1);
-        xn = tape + tp->blk[i].xn1;
-        centers = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx);
-        assign = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx2);
-      } else if (pending) TR_TRY(op_ln(f32, x, D, pending, D, bw->ln1_g, bw->ln1_b, xn, M, D, cfg->ln_eps, s));   // x += previous mlp output
-      pending = nullptr;
-      if (kinit > 0)
-        TR_TRY(tr_kmedoids_equal(x, kinit - 1, reinterpret_cast<float*>(ws + p.off_cluster), centers, assign, B, N, D, Kc, cfg->cluster_iters,
-                                 f32 ? 0 : 1, s));
-      else
-        TR_TRY(tr_kmedoids(x, colsum_part, reinterpret_cast<float*>(ws + p.off_cluster), centers, assign, B, N, D, H, Kc,
-                           cfg->cluster_iters, f32 ? 0 : 1, s));
-      TR_TRY(op_gather(f32, x, nullptr, centers, nullptr, nullptr, bw->ln1_g, bw->ln1_b, x_alt, xn, B, N, Kc, D, cfg->ln_eps, s));
-      float* t = x; x = x_alt; x_alt = t;
-      N = Kc + 1;
-      have_xn = true;
-    }
-    if (cfg->family == TR_FAMILY_HEURISTIC && w->stage[i].w3 != nullptr) {
-      // f4: a new spatial mask takes effect at this block and stays until the next one (heuristic.py:247-258)
-      TR_REQUIRE(w->stage[i].n_pad == N, TR_ERR_CONFIG, "tr_vit_forward: block %d mask has %d entries for %d tokens", i, w->stage[i].n_pad, N);
-      float* mask_dst = train ? reinterpret_cast<float*>(tape + tp->blk[i].size) : size_a;      // training keeps every block's mask
-      TR_TRY(tr_broadcast_rows(w->stage[i].w3, mask_dst, B, N, s));
-      size_cur = mask_dst;
-    }
-    if (cfg->family == TR_FAMILY_PATCHMERGER && cfg->keep[i] > 0) {
-      // f4: PatchMerger.forward patchmerger.py:35-39 on x[:, 1:] BEFORE the block
-      const tr_stage_weights* sw = &w->stage[i];
-      const int Kc = cfg->keep[i], M = B * N;
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d outputs of %d patch tokens", i, Kc, N - 1);
-      TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w1 && sw->b1 && sw->n_pad >= Kc && sw->n_pad % 8 == 0 &&
-                     sw->n_pad == trplan::soft_ld(Kc),
-                 TR_ERR_CONFIG, "tr_vit_forward: block %d PatchMerger weights missing or n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
-      if (train) {
-        // every operand of the stage's backward stays on the tape; the merged stream is written to norm1's input slot
-        const trplan::BlockTape& bt = tp->blk[i];
-        TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG, "tr_vit_forward_train: block %d PatchMerger n_pad=%d K=%d", i, sw->n_pad, Kc);
-        float* x0 = reinterpret_cast<float*>(tape + bt.x0);
-        float* xh = reinterpret_cast<float*>(tape + bt.sxh);
-        float* slog = reinterpret_cast<float*>(tape + bt.slog);
-        float* swt = reinterpret_cast<float*>(tape + bt.swt);
-        uint16_t* pu = reinterpret_cast<uint16_t*>(tape + bt.pu);
-        float* x1 = reinterpret_cast<float*>(tape + bt.x1);
-        TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, sw->ln_g, sw->ln_b, pu, M, D, 1e-5f, s));
-        pending = nullptr;
-        TR_TRY(tr_layernorm_f32(x0, D, nullptr, D, sw->ln_g, sw->ln_b, xh, M, D, 1e-5f, s));
-        TR_TRY(tr_gemm_bf16(pu, static_cast<const uint16_t*>(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
-        TR_REQUIRE(hipMemcpyAsync(swt, slog, (size_t)M * sw->n_pad * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)) == hipSuccess,
-                   TR_ERR_LAUNCH, "tr_vit_forward_train: copy failed");
-        TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, sw->scale, 1, x0, xh, x1, soft_out, B, N, Kc, D, s));
-        if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-        x = x1;
-        N = Kc + 1;
-      } else {
-      float* xh = static_cast<float*>(qkv);                       // LayerNorm-ed tokens, fp32 [M, D]
-      float* sc = reinterpret_cast<float*>(ws + p.off_soft);      // similarities [M, n_pad]
-      TR_TRY(op_ln(f32, x, D, pending, D, sw->ln_g, sw->ln_b, xn, M, D, 1e-5f, s));        // x += previous mlp output; GEMM operand
-      pending = nullptr;
-      TR_TRY(tr_layernorm_f32(x, D, nullptr, D, sw->ln_g, sw->ln_b, xh, M, D, 1e-5f, s));  // the rows that are summed
-      TR_TRY(op_gemm(prec, xn, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
-      if (!f32 && Kc <= 192)
-        TR_TRY(tr_softassign_merge_fast(sc, sw->n_pad, sw->scale, 1, x, xh, x_alt, soft_out, B, N, Kc, D, s));
-      else
-        TR_TRY(tr_softassign_merge(sc, sw->n_pad, sw->scale, x, xh, x_alt, soft_out, B, N, Kc, D, s));
-      if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-      float* t = x; x = x_alt; x_alt = t;
-      N = Kc + 1;
-      }
-    }
-    if (cfg->family == TR_FAMILY_SINKHORN && cfg->keep[i] > 0) {
-      // a22: Sinkhorn.forward sinkhorn.py:66-86 on x[:, 1:] BEFORE the block
-      const tr_stage_weights* sw = &w->stage[i];
-      const int Kc = cfg->keep[i], M = B * N;
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d clusters of %d patch tokens", i, Kc, N - 1);
-      TR_REQUIRE(sw->w1 && sw->b1 && sw->n_pad >= Kc && sw->n_pad % 8 == 0 && sw->n_pad == trplan::soft_ld(Kc),
-                 TR_ERR_CONFIG, "tr_vit_forward: block %d Sinkhorn centres missing or n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
-      if (train) {
-        const trplan::BlockTape& bt = tp->blk[i];
-        TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG, "tr_vit_forward_train: block %d Sinkhorn n_pad=%d K=%d", i, sw->n_pad, Kc);
-        float* x0 = reinterpret_cast<float*>(tape + bt.x0);
-        float* xh = reinterpret_cast<float*>(tape + bt.sxh);
-        float* slog = reinterpret_cast<float*>(tape + bt.slog);
-        float* swt = reinterpret_cast<float*>(tape + bt.swt);
-        uint16_t* pu = reinterpret_cast<uint16_t*>(tape + bt.pu);
-        float* x1 = reinterpret_cast<float*>(tape + bt.x1);
-        // x0 = x + pending (the norm output of this pass is not used: shared scratch)
-        TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, bw->ln1_g, bw->ln1_b, static_cast<uint16_t*>(xn_shared), M, D,
-                                    cfg->ln_eps, s));
-        pending = nullptr;
-        TR_TRY(tr_rownorm(x0, xh, pu, 0, M, D, s));
-        TR_TRY(tr_gemm_bf16(pu, static_cast<const uint16_t*>(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
-        TR_TRY(tr_sinkhorn(slog, sw->n_pad, cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f, cfg->cluster_iters, swt, soft_out, B, N, Kc, s));
-        if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-        TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, 1.0f, 0, x0, xh, x1, nullptr, B, N, Kc, D, s));
-        x = x1;
-        N = Kc + 1;
-      } else {
-      if (pending) TR_TRY(op_ln(f32, x, D, pending, D, bw->ln1_g, bw->ln1_b, xn, M, D, cfg->ln_eps, s));   // x += previous mlp output
-      pending = nullptr;
-      float* xh = static_cast<float*>(qkv);                       // unit-norm tokens, fp32 [M, D] (the qkv slab is free here)
-      float* sc = reinterpret_cast<float*>(ws + p.off_soft);      // scores, then the transport plan in place [M, n_pad]
-      TR_TRY(tr_rownorm(x, xh, xn, f32 ? 1 : 0, M, D, s));
-      TR_TRY(op_gemm(prec, xn, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, D, TR_EPI_F32, s));
-      TR_TRY(tr_sinkhorn(sc, sw->n_pad, cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f, cfg->cluster_iters, sc, soft_out, B, N,
-                         Kc, s));
-      if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-      if (!f32 && Kc <= 192)
-        TR_TRY(tr_softassign_merge_fast(sc, sw->n_pad, 1.0f, 0, x, xh, x_alt, nullptr, B, N, Kc, D, s));
-      else
-        TR_TRY(tr_weighted_merge(sc, sw->n_pad, x, xh, x_alt, B, N, Kc, D, s));
-      float* t = x; x = x_alt; x_alt = t;
-      N = Kc + 1;
-      }
-    }
-    if (train && cfg->family == TR_FAMILY_DYVIT && cfg->keep[i] > 0) {
-      // a11 / f4: DyViT TRAINING (dyvit.py:221-229): PredictorLG on the patch tokens under the previous decision, a straight-through
-      // Gumbel-softmax sample becomes this stage's policy; no token is removed.  Every activation goes to the stage's tape slots.
-      const tr_stage_weights* sw = &w->stage[i];
-      const trplan::BlockTape& bt = tp->blk[i];
-      const int M = B * N, Hh = sw->h_pad > 0 ? sw->h_pad : D / 2, Q = (D / 4 + 63) / 64 * 64;
-      TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1 && sw->w2 && sw->b2 && sw->w3 && sw->b3, TR_ERR_NULL,
-                 "tr_vit_forward_train: block %d predictor weights missing", i);
-      // Hh: the D/2 hidden layer as packed -- zero-padded to a multiple of 64 (DeiT-T: 96 -> 128; zero weight rows / columns and zero
-      // bias: the padded activations are gelu(0) = 0 and carry no gradient), like the D/4 layer is padded to Q rows
-      TR_REQUIRE(Hh >= D / 2 && Hh % 64 == 0 && Hh == (D / 2 + 63) / 64 * 64 && sw->reserved_ == Q, TR_ERR_CONFIG,
-                 "tr_vit_forward_train: the DyViT predictor must be packed with its hidden layers padded to %d / %d columns (got h_pad=%d, %d)",
-                 (D / 2 + 63) / 64 * 64, Q, sw->h_pad, sw->reserved_);
-      TR_REQUIRE(noise_in != nullptr, TR_ERR_NULL, "tr_vit_forward_train: DyViT needs the Gumbel noise of every stage (noise_in)");
-      float* x0 = reinterpret_cast<float*>(tape + bt.x0);
-      uint16_t* pu = reinterpret_cast<uint16_t*>(tape + bt.pu);
-      uint16_t* ppre0 = reinterpret_cast<uint16_t*>(tape + bt.ppre0);
-      uint16_t* pcat = reinterpret_cast<uint16_t*>(tape + bt.pcat);
-      uint16_t* ppre1 = reinterpret_cast<uint16_t*>(tape + bt.ppre1);
-      uint16_t* ph1 = reinterpret_cast<uint16_t*>(tape + bt.ph1);
-      uint16_t* ppre2 = reinterpret_cast<uint16_t*>(tape + bt.ppre2);
-      uint16_t* ph2 = reinterpret_cast<uint16_t*>(tape + bt.ph2);
-      float* pol = reinterpret_cast<float*>(tape + bt.pol);
-      TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, sw->ln_g, sw->ln_b, pu, M, D, 1e-5f, s));
-      pending = nullptr;
-      x = x0;
-      TR_TRY(tr_gemm_gelu_keep_bf16(pu, static_cast<const uint16_t*>(sw->w0), sw->b0, ppre0, pcat, M, D, D, s));
-      TR_TRY(tr_pool_policy(pcat, policy_cur, B, N, D, 1e-6f, s));
-      TR_TRY(tr_gemm_gelu_keep_bf16(pcat, static_cast<const uint16_t*>(sw->w1), sw->b1, ppre1, ph1, M, Hh, D, s));
-      TR_TRY(tr_gemm_gelu_keep_bf16(ph1, static_cast<const uint16_t*>(sw->w2), sw->b2, ppre2, ph2, M, Q, Hh, s));
-      TR_TRY(tr_dyvit_decide(ph2, Q, sw->w3, sw->b3, noise_in, policy_cur, pol, reinterpret_cast<float*>(tape + bt.ysoft),
-                             reinterpret_cast<float*>(tape + bt.sm), reinterpret_cast<float*>(tape + bt.hard), B, N, D / 4, s));
-      noise_in += (size_t)B * (N - 1) * 2;
-      policy_cur = pol;
-    } else if (train && cfg->family == TR_FAMILY_SIT && cfg->keep[i] > 0) {
-      // a23 TRAINING: TokenSlimmingModule (sit.py:36-40) with every activation on the tape
-      const tr_stage_weights* sw = &w->stage[i];
-      const trplan::BlockTape& bt = tp->blk[i];
-      const int Kc = cfg->keep[i], M = B * N, Hh = (D / 2 + 63) / 64 * 64;     // hidden width as packed (DeiT-T: 96 -> 128, zero padded)
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward_train: block %d asks for %d of %d patch tokens", i, Kc, N - 1);
-      TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1, TR_ERR_NULL, "tr_vit_forward_train: block %d SiT weights missing", i);
-      TR_REQUIRE(sw->n_pad == trplan::soft_ld(Kc) && (sw->h_pad == Hh || (sw->h_pad == 0 && Hh == D / 2)), TR_ERR_CONFIG,
-                 "tr_vit_forward_train: the SiT module must be packed with its hidden layer padded to %d columns and n_pad == %d (got h_pad=%d n_pad=%d)",
-                 Hh, trplan::soft_ld(Kc), sw->h_pad, sw->n_pad);
-      float* x0 = reinterpret_cast<float*>(tape + bt.x0);
-      float* slog = reinterpret_cast<float*>(tape + bt.slog);
-      float* swt = reinterpret_cast<float*>(tape + bt.swt);
-      uint16_t* pu = reinterpret_cast<uint16_t*>(tape + bt.pu);
-      uint16_t* ppre0 = reinterpret_cast<uint16_t*>(tape + bt.ppre0);
-      uint16_t* ph0 = reinterpret_cast<uint16_t*>(tape + bt.pcat);
-      float* x1 = reinterpret_cast<float*>(tape + bt.x1);
-      TR_TRY(tr_layernorm_bf16_to(x, D, x0, D, static_cast<const uint16_t*>(pending), D, sw->ln_g, sw->ln_b, pu, M, D, 1e-5f, s));
-      pending = nullptr;
-      TR_TRY(tr_gemm_gelu_keep_bf16(pu, static_cast<const uint16_t*>(sw->w0), sw->b0, ppre0, ph0, M, Hh, D, s));
-      TR_TRY(tr_gemm_bf16(ph0, static_cast<const uint16_t*>(sw->w1), sw->b1, slog, nullptr, 0, M, sw->n_pad, Hh, TR_EPI_F32, s));
-      TR_REQUIRE(hipMemcpyAsync(swt, slog, (size_t)M * sw->n_pad * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)) == hipSuccess,
-                 TR_ERR_LAUNCH, "tr_vit_forward_train: copy failed");
-      TR_TRY(tr_softassign_merge_fast(swt, sw->n_pad, sw->scale, 1, x0, x0, x1, soft_out, B, N, Kc, D, s));
-      if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-      x = x1;
-      N = Kc + 1;
-    } else if ((cfg->family == TR_FAMILY_DYVIT || cfg->family == TR_FAMILY_SIT) && cfg->keep[i] > 0) {
-      const tr_stage_weights* sw = &w->stage[i];
-      const int Kc = cfg->keep[i], M = B * N;
-      TR_REQUIRE(Kc <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d asks for %d of %d patch tokens", i, Kc, N - 1);
-      TR_REQUIRE(sw->ln_g && sw->ln_b && sw->w0 && sw->b0 && sw->w1 && sw->b1, TR_ERR_NULL,
-                 "tr_vit_forward: block %d has no reduction-module weights (tr_vit_weights.stage)", i);
-      // x (+= previous mlp output), module's own LayerNorm (nn.LayerNorm default eps 1e-5: dyvit.py:97, sit.py:30)
-      TR_TRY(op_ln(f32, x, D, pending, D, sw->ln_g, sw->ln_b, xn, M, D, 1e-5f, s));
-      pending = nullptr;
-      if (cfg->family == TR_FAMILY_DYVIT) {
-        // a10: PredictorLG (dyvit.py:113-119, policy == 1 in eval) -> score -> argsort(desc)[:K] -> batch_index_select
-        TR_REQUIRE(sw->w2 && sw->b2 && sw->w3 && sw->b3, TR_ERR_NULL, "tr_vit_forward: block %d predictor weights missing", i);
-        const int Hh = sw->h_pad > 0 ? sw->h_pad : D / 2;            // hidden width as packed (zero-padded to 64 for DeiT-T)
-        TR_REQUIRE(Hh >= D / 2 && (Hh % 64 == 0 || f32), TR_ERR_CONFIG, "tr_vit_forward: DyViT predictor hidden width %d invalid (D=%d)", Hh, D);
-        TR_TRY(op_gemm(prec, xn, sw->w0, sw->b0, ao, nullptr, 0, M, D, D, TR_EPI_GELU_BF16, s));
-        TR_TRY(tr_pool_broadcast(ao, f32 ? 1 : 0, B, N, D, 1e-6f, s));
-        TR_TRY(op_gemm(prec, ao, sw->w1, sw->b1, qkv, nullptr, 0, M, Hh, D, TR_EPI_GELU_BF16, s));
-        TR_TRY(op_gemm(prec, qkv, sw->w2, sw->b2, hbuf, nullptr, 0, M, D / 4, Hh, TR_EPI_GELU_BF16, s));
-        TR_TRY(tr_dyvit_score(hbuf, f32 ? 1 : 0, sw->w3, sw->b3, cls_rows, M, D / 4, s));
-        int32_t* idx_dst = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-        TR_TRY(tr_cls_topk(cls_rows, idx_dst, nullptr, scores, B, 1, N, Kc, s));
-        TR_TRY(op_gather(f32, x, nullptr, idx_dst, nullptr, nullptr, bw->ln1_g, bw->ln1_b, x_alt, xn, B, N, Kc, D, cfg->ln_eps, s));
-        have_xn = true;
-      } else {
-        // a23: TokenSlimmingModule (sit.py:36-40)
-        TR_REQUIRE(sw->n_pad >= Kc && sw->n_pad % 8 == 0 && sw->n_pad == trplan::soft_ld(Kc), TR_ERR_CONFIG,
-                   "tr_vit_forward: block %d SiT n_pad=%d invalid for K=%d", i, sw->n_pad, Kc);
-        const int Hh = sw->h_pad > 0 ? sw->h_pad : D / 2;
-        TR_REQUIRE(Hh >= D / 2 && (Hh % 64 == 0 || f32), TR_ERR_CONFIG, "tr_vit_forward: SiT hidden width %d invalid (D=%d)", Hh, D);
-        TR_TRY(op_gemm(prec, xn, sw->w0, sw->b0, ao, nullptr, 0, M, Hh, D, TR_EPI_GELU_BF16, s));
-        float* sc = reinterpret_cast<float*>(ws + p.off_soft);    // logits [M, n_pad]
-        TR_TRY(op_gemm(prec, ao, sw->w1, sw->b1, sc, nullptr, 0, M, sw->n_pad, Hh, TR_EPI_F32, s));
-        if (!f32 && Kc <= 192)
-          TR_TRY(tr_softassign_merge_fast(sc, sw->n_pad, sw->scale, 1, x, x, x_alt, soft_out, B, N, Kc, D, s));
-        else
-          TR_TRY(tr_sit_merge(sc, sw->n_pad, sw->scale, x, x_alt, soft_out, B, N, Kc, D, s));
-        if (soft_out) soft_out += (size_t)B * Kc * (N - 1);
-      }
-      float* t = x; x = x_alt; x_alt = t;
-      N = Kc + 1;
-    }
-    const bool ats = cfg->family == TR_FAMILY_ATS;
-    const int Ks = ats ? cfg->keep[i] : 0;      // ATS sample_count of this block (0 = plain block)
-    const bool in_block = cfg->family == TR_FAMILY_TOPK || cfg->family == TR_FAMILY_EVIT;
-    int K = in_block ? cfg->keep[i] : 0;
-    TR_REQUIRE(K >= 0 && K <= N - 1, TR_ERR_CONFIG, "tr_vit_forward: block %d keeps %d of %d patch tokens", i, K, N - 1);
-    if (K == N - 1) K = 0;  // topk.py:57 / evit.py:79: left_tokens == N-1 -> plain block
-    int r = 0;              // ToMe: tokens merged away by this block, r = min(r, (N - protected) // 2)  (tome.py:253)
-    if (tome) {
-      TR_REQUIRE(cfg->keep[i] >= 0, TR_ERR_CONFIG, "tr_vit_forward: block %d has negative ToMe r", i);
-      r = cfg->keep[i] < (N - 1) / 2 ? cfg->keep[i] : (N - 1) / 2;
-    }
-    const int M = B * N;
-    // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features).
-    // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
-    // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
-    // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
-    const bool cls_tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && K == 0 && r == 0 && Ks == 0 &&
-                          drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr &&
-                          g_cls_tail.load(std::memory_order_relaxed) != 0 && tr_attention_cls_available() != 0;
-    if (train) {          // this block's tape slots replace the shared scratch
-      const trplan::BlockTape& bt = tp->blk[i];
-      xn = tape + bt.xn1; qkv = tape + bt.qkv; hbuf = tape + bt.h;
-      ao = (ats && Ks > 0) ? ao_shared : static_cast<void*>(tape + bt.ao);      // ATS keeps only the sampled rows of attn @ v
-      dbuf = (cfg->family == TR_FAMILY_EVIT && K > 0) ? static_cast<void*>(tape + bt.dattn) : dbuf_shared;
-      x_alt = reinterpret_cast<float*>(tape + bt.x2);
-    }
-    // x (+= previous mlp output); attn(norm1(x)) -> dbuf   [x + dbuf is the reference's post-attention x, topk.py:87]
-    if (train && !have_xn) {
-      float* x1 = reinterpret_cast<float*>(tape + tp->blk[i].x1);
-      TR_TRY(tr_layernorm_bf16_to(x, D, x1, D, static_cast<const uint16_t*>(pending), D, bw->ln1_g, bw->ln1_b, static_cast<uint16_t*>(xn), M, D,
-                                  cfg->ln_eps, s));
-      x = x1;
-    } else if (!have_xn && xn1_ready == nullptr) {
-      TR_TRY(op_ln_pending(f32, x, D, pending, pending_attn, D, bw->ln1_g, bw->ln1_b, xn, M, D, cfg->ln_eps, s));
-      pending_attn = nullptr;
-    }
-    TR_REQUIRE(pending_attn == nullptr, TR_ERR_CONFIG, "tr_vit_forward: internal: block %d did not absorb the lazy residual", i);
-    TR_TRY(op_gemm(prec, xn1_ready ? xn1_ready : xn, bw->qkv_w, bw->qkv_b, qkv, nullptr, 0, M, 3 * D, D, TR_EPI_BF16, s));
-    xn1_ready = nullptr;
-    // ToMe: log(size) bias on the keys; ATS: key mask as a 1/0 "size" (log 0 = -inf -> exactly zero weight, like
-    // masked_fill(-finfo.max) underflowing in the reference's softmax, ats.py:117-120)
-    // K-Medoids: the NEXT block's clustering is seeded by the column sums of THIS block's attention (kmedoids.py:240)
-    const bool want_colsum = cfg->family == TR_FAMILY_KMEDOIDS && i + 1 < cfg->depth && cfg->keep[i + 1] > 0;
-    const bool masked = ats || cfg->family == TR_FAMILY_HEURISTIC;
-    if (cls_tail) {
-      // every buffer below holds B compact rows [B, D] (or [B, Hd]); the stream keeps its row stride N * D
-      uint16_t* const ao_c = static_cast<uint16_t*>(ao);
-      uint16_t* const xn_c = static_cast<uint16_t*>(xn);
-      uint16_t* const h_c = static_cast<uint16_t*>(hbuf);
-      uint16_t* const d_attn = static_cast<uint16_t*>(dbuf_shared);
-      uint16_t* const d_mlp = static_cast<uint16_t*>(dbuf2);
-      TR_TRY(tr_attention_cls_bf16(static_cast<const uint16_t*>(qkv), ao_c, (tome || masked) ? size_cur : nullptr, B, N, H, s));
-      TR_TRY(tr_gemm_bf16(ao_c, static_cast<const uint16_t*>(bw->proj_w), bw->proj_b, d_attn, nullptr, 0, B, D, D, TR_EPI_BF16, s));
-      // norm2 of x + d_attn without a stream write (lazy, as above): the final norm adds both residuals in the reference's order
-      TR_TRY(tr_layernorm2_bf16(x, (long)N * D, nullptr, 0, d_attn, D, nullptr, 0, bw->ln2_g, bw->ln2_b, xn_c, B, D, cfg->ln_eps, s));
-      // the GEMM pair, not the fused Mlp: two workgroups of that kernel would be one long latency chain (same bits: tr_mlp_fused.hip)
-      TR_TRY(tr_gemm_bf16(xn_c, static_cast<const uint16_t*>(bw->fc1_w), bw->fc1_b, h_c, nullptr, 0, B, p.Hd, D, TR_EPI_GELU_BF16, s));
-      TR_TRY(tr_gemm_bf16(h_c, static_cast<const uint16_t*>(bw->fc2_w), bw->fc2_b, d_mlp, nullptr, 0, B, D, p.Hd, TR_EPI_BF16, s));
-      pending_attn = d_attn;
-      pending = d_mlp;
-      pending_ld = D;
-      if (tokens_out) tokens_out[i] = N;
+    TR_TRY(f.pre_block(i));
+    TR_TRY(f.begin_block(i));
+    TR_TRY(f.norm1_qkv(i));
+    if (f.tail) {                 // the last block, on the CLS rows: leaves the loop with both residuals pending for the final norm
+      TR_TRY(f.cls_tail(i));
       break;
     }
-    if (policy_cur != nullptr)       // DyViT training: softmax_with_policy in every block (dyvit.py:245-246)
-      TR_TRY(tr_attention_policy_bf16(static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(ao), policy_cur, B, N, H, s));
-    else
-      TR_TRY(op_attn(prec, qkv, ao, (K > 0 || Ks > 0) ? cls_rows : nullptr, (tome || masked) ? size_cur : nullptr,
-                     want_colsum ? colsum_part : nullptr, B, N, H, s));
-    int Nn = N;
-    bool norm2_in_mlp = false;      // this block's norm2 runs inside its fused Mlp launch
-    if (Ks > 0) {
-      // a16-a18: sample token ids on the CLS attention x |v|, keep those rows of x and of attn @ v
-      const tr_stage_weights* sw = &w->stage[i];
-      const bool dyn = cfg->ats_dynamic != 0 && !train;
-      // (dynamic width: N is the batch maximum of the previous stage and may be below the static Ks; the buffers -- ids, the mask in the
-      // score buffer -- are sized for the first stage's N0 rows, which bounds Ks in either mode)
-      TR_REQUIRE(Ks >= 2 && (dyn ? Ks <= p.N0 : Ks <= N), TR_ERR_CONFIG, "tr_vit_forward: block %d ATS sample_count %d out of range for %d tokens", i, Ks,
-                 dyn ? p.N0 : N);
-      TR_REQUIRE(sw->w3 && sw->n_pad >= 1, TR_ERR_NULL, "tr_vit_forward: block %d has no ATS sample grid (tr_vit_weights.stage)", i);
-      int32_t* ids = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-      float* mask_next = (size_cur == size_a) ? size_b : size_a;
-      if (train) {
-        ids = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx);
-        mask_next = reinterpret_cast<float*>(tape + tp->blk[i].size);
-      }
-      int Kg = Ks;             // rows the block keeps
-      if (dyn) {
-        // ats.py:77-78: the reference pads the unique ids to the batch maximum -- sample at the static bound (ids [B,Ks] stay the
-        // Kept_Tokens record), read that maximum back (one int: the stream is synchronised HERE), continue on the first Kg columns
-        float* mask_full = scores;                                   // [B,Ks]; the score buffer is not used by this family
-        int32_t* width_dev = reinterpret_cast<int32_t*>(ws + p.off_misc);
-        TR_TRY(tr_ats_sample(cls_rows, qkv, f32 ? 1 : 0, size_cur, sw->w3, sw->n_pad, ids, mask_full, nullptr, B, N, H, Ks, s));
-        TR_TRY(tr_ats_width(mask_full, width_dev, B, Ks, s));
-        int32_t width = 0;
-        hipError_t e = hipMemcpyAsync(&width, width_dev, sizeof(width), hipMemcpyDeviceToHost, static_cast<hipStream_t>(s));
-        if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(s));
-        TR_REQUIRE(e == hipSuccess, TR_ERR_LAUNCH, "tr_vit_forward: ATS dynamic width read-back at block %d: %s (not capturable in a hipGraph)", i,
-                   hipGetErrorString(e));
-        Kg = width < 2 ? 2 : (width > Ks ? Ks : width);              // CLS + at least one column (an all-masked batch cannot occur: >= 1 sample)
-        TR_TRY(tr_ats_narrow(ids, mask_full, compl_ws, mask_next, B, Ks, Kg, s));
-        ids = compl_ws;
-      } else {
-        TR_TRY(tr_ats_sample(cls_rows, qkv, f32 ? 1 : 0, size_cur, sw->w3, sw->n_pad, ids, mask_next, nullptr, B, N, H, Ks, s));
-      }
-      if (train) {          // sampled rows of the stream -> x0 slot, of attn @ v -> ao slot (proj's operand); norm1's input stays in x1
-        float* xg = reinterpret_cast<float*>(tape + tp->blk[i].x0);
-        xn = tape + tp->blk[i].ao;
-        TR_TRY(tr_ats_gather(x, ao, 0, ids, xg, xn, B, N, Ks, D, s));
-        x = xg;
-      } else {
-        TR_TRY(tr_ats_gather(x, ao, f32 ? 1 : 0, ids, x_alt, xn, B, N, Kg, D, s));
-        float* t = x; x = x_alt; x_alt = t;
-      }
-      size_cur = mask_next;
-      Nn = Kg;
-      TR_TRY(op_gemm(prec, xn, bw->proj_w, bw->proj_b, dbuf, nullptr, 0, B * Nn, D, D, TR_EPI_BF16, s));
-    } else {
-      TR_TRY(op_gemm(prec, ao, bw->proj_w, bw->proj_b, dbuf, nullptr, 0, M, D, D, TR_EPI_BF16, s));
-    }
-    if (drop_keep != nullptr) {      // proj_drop (topk.py:53), inside the attention module: before the branch's DropPath
-      TR_TRY(tr_dropout_bf16(static_cast<const uint16_t*>(dbuf), static_cast<uint16_t*>(dbuf), drop_keep, drop_mul, (size_t)B * Nn * D, s));
-      drop_keep += (size_t)B * Nn * D;
-    }
-    if (drop_scale != nullptr)      // DropPath on the attention branch (topk.py:87): this block's per-image scale, first of its two draws
-      TR_TRY(tr_rowscale_bf16(static_cast<const uint16_t*>(dbuf), static_cast<uint16_t*>(dbuf), drop_scale + (size_t)(2 * i) * B, B, Nn, D, s));
-    if (K > 0) {
-      // Top-K on the CLS attention, then residual add + gather/compact (+ EViT fused token) + norm2 in one pass
-      const bool fuse = cfg->family == TR_FAMILY_EVIT;
-      int32_t* idx_dst = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-      int32_t* compl_dst = fuse ? (compl_idx ? compl_idx + (size_t)i * B * p.N0 : compl_ws) : nullptr;
-      float* sc_dst = scores;
-      if (train) {
-        idx_dst = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx);
-        if (fuse) compl_dst = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx2);
-        sc_dst = reinterpret_cast<float*>(tape + tp->blk[i].scores);
-        xn = tape + tp->blk[i].xn2;
-      }
-      TR_TRY(tr_cls_topk(cls_rows, idx_dst, compl_dst, sc_dst, B, H, N, K, s));
-      TR_TRY(op_gather(f32, x, dbuf, idx_dst, compl_dst, sc_dst, bw->ln2_g, bw->ln2_b, x_alt, xn, B, N, K, D, cfg->ln_eps, s));
-      float* t = x; x = x_alt; x_alt = t;
-      Nn = K + 1 + (fuse ? 1 : 0);
-    } else if (r > 0) {
-      // ToMe: bipartite matching on mean-over-heads K, then residual add + size-weighted merge + norm2 in one pass
-      const int na = (N + 1) / 2;
-      int32_t* slab = kept_idx ? kept_idx + (size_t)i * B * p.N0 : idx_ws;
-      if (train) {
-        slab = reinterpret_cast<int32_t*>(tape + tp->blk[i].idx);
-        xn = tape + tp->blk[i].xn2;
-      }
-      int32_t* unm = slab;
-      int32_t* src = slab + (size_t)B * (na - r);
-      int32_t* dst = src + (size_t)B * r;
-      float* size_next = train ? reinterpret_cast<float*>(tape + tp->blk[i].size) : ((size_cur == size_a) ? size_b : size_a);
-      TR_TRY(tr_tome_match(qkv, f32 ? 1 : 0, unm, src, dst, B, N, H, r, s));
-      TR_TRY(tr_tome_merge_layernorm(x, dbuf, f32 ? 1 : 0, size_cur, unm, src, dst, bw->ln2_g, bw->ln2_b, x_alt, size_next, xn, B, N, r,
-                                     D, cfg->ln_eps, s));
-      float* t = x; x = x_alt; x_alt = t;
-      size_cur = size_next;
-      Nn = N - r;
-    } else if (train) {
-      xn = tape + tp->blk[i].xn2;
-      TR_TRY(tr_layernorm_bf16_to(x, D, x_alt, D, static_cast<const uint16_t*>(dbuf), D, bw->ln2_g, bw->ln2_b, static_cast<uint16_t*>(xn), B * Nn, D,
-                                  cfg->ln_eps, s));
-      x = x_alt;
-    } else if (lazy_base && starts_plain(i + 1) && !(rl_base && i + 1 < cfg->depth && bw->mlp_pk != nullptr &&
-                                                     tr_mlp_fused_wanted(B * Nn, D, p.Hd, sk_ok, conc))) {
-      // lazy norm2.  Where the fused Mlp follows as ONE round of blocks, the norm moves INTO that launch (tr_mlp_fused_ln_bf16: its fc1 waves
-      // normalise x + dbuf in registers; bit-identical to the launch below followed by the plain fused Mlp) -- no LayerNorm launch, no bf16
-      // rows in between (tr_set_mlp_ln; under the stream-K schedule the separate launch is faster: tr_mlp_fused.hip)
-      norm2_in_mlp = prec == TR_PREC_BF16 && drop_keep == nullptr && bw->mlp_pk != nullptr &&
-                     tr_mlp_ln_wanted(B * Nn, D, p.Hd, sk_ok, conc);
-      if (!norm2_in_mlp)
-        TR_TRY(tr_layernorm2_bf16(x, D, nullptr, 0, static_cast<const uint16_t*>(dbuf), D, nullptr, 0, bw->ln2_g, bw->ln2_b,
-                                  static_cast<uint16_t*>(xn), B * Nn, D, cfg->ln_eps, s));
-      pending_attn = dbuf;
-    } else {
-      TR_TRY(op_ln(f32, x, D, dbuf, D, bw->ln2_g, bw->ln2_b, xn, B * Nn, D, cfg->ln_eps, s));
-    }
-    N = Nn;
-    const int M2 = B * N;
-    // mlp(norm2(x)) -> dbuf, added to x by the next block's norm1 (or the final norm)
-    bool fused_mlp = false;
-    if (train) {
-      void* pre = tape + tp->blk[i].pre;
-      TR_TRY(tr_gemm_gelu_keep_bf16(static_cast<const uint16_t*>(xn), static_cast<const uint16_t*>(bw->fc1_w), bw->fc1_b, static_cast<uint16_t*>(pre),
-                                    static_cast<uint16_t*>(hbuf), M2, p.Hd, D, s));
-    } else if (prec == TR_PREC_BF16 && bw->mlp_pk != nullptr && tr_mlp_fused_wanted(M2, D, p.Hd, sk_ok, conc)) {
-      // eval: fc1 -> GELU -> fc2 in one launch, the hidden activation never leaves the CU (tr_mlp_fused.hip; bit-identical to the pair below,
-      // taken where its block schedule fills the chip)
-      fused_mlp = true;
-    } else {
-      TR_REQUIRE(!norm2_in_mlp, TR_ERR_CONFIG, "tr_vit_forward: internal: block %d skipped its norm2 launch but does not run the fused Mlp", i);
-      TR_TRY(op_gemm(prec, xn, bw->fc1_w, bw->fc1_b, hbuf, nullptr, 0, M2, p.Hd, D, TR_EPI_GELU_BF16, s));
-    }
-    if (drop_keep != nullptr) {      // timm Mlp: drop after the activation ...
-      TR_TRY(tr_dropout_bf16(static_cast<const uint16_t*>(hbuf), static_cast<uint16_t*>(hbuf), drop_keep, drop_mul, (size_t)M2 * p.Hd, s));
-      drop_keep += (size_t)M2 * p.Hd;
-    }
-    dbuf = (pending_attn == dbuf_shared) ? dbuf2 : dbuf_shared;      // the attention residual is still pending: fc2 writes beside it
-    const bool fused_tail = fused_mlp && rl_base && pending_attn == nullptr && i + 1 < cfg->depth && starts_plain(i + 1);
-    if (fused_tail) {
-      const tr_block_weights* nb = &w->blocks[i + 1];
-      TR_TRY(tr_mlp_fused_resid_ln_bf16_set(static_cast<const uint16_t*>(xn), bw->mlp_pk, bw->fc1_b, bw->fc2_b, x, nb->ln1_g, nb->ln1_b, cfg->ln_eps,
-                                            static_cast<uint16_t*>(hbuf), sk_ok ? ws + p.off_mlp_sk : nullptr, p.mlp_sk_bytes, M2, D, p.Hd,
-                                            one_memset ? i : -1, s));
-      xn1_ready = hbuf;
-    } else if (fused_mlp && norm2_in_mlp)
-      TR_TRY(tr_mlp_fused_ln_bf16_set(x, static_cast<const uint16_t*>(pending_attn), bw->ln2_g, bw->ln2_b, cfg->ln_eps, bw->mlp_pk, bw->fc1_b,
-                                      static_cast<uint16_t*>(dbuf), sk_ok ? ws + p.off_mlp_sk : nullptr, p.mlp_sk_bytes, M2, D, p.Hd, one_memset ? i : -1, s));
-    else if (fused_mlp)
-      TR_TRY(tr_mlp_fused_bf16_set(static_cast<const uint16_t*>(xn), bw->mlp_pk, bw->fc1_b, static_cast<uint16_t*>(dbuf),
-                                   sk_ok ? ws + p.off_mlp_sk : nullptr, p.mlp_sk_bytes, M2, D, p.Hd, one_memset ? i : -1, s));
-    else
-      TR_TRY(op_gemm(prec, hbuf, bw->fc2_w, bw->fc2_b, dbuf, nullptr, 0, M2, D, p.Hd, TR_EPI_BF16, s));
-    if (drop_keep != nullptr) {      // ... and after fc2
-      TR_TRY(tr_dropout_bf16(static_cast<const uint16_t*>(dbuf), static_cast<uint16_t*>(dbuf), drop_keep, drop_mul, (size_t)M2 * D, s));
-      drop_keep += (size_t)M2 * D;
-    }
-    if (drop_scale != nullptr)      // DropPath on the MLP branch (topk.py:95)
-      TR_TRY(tr_rowscale_bf16(static_cast<const uint16_t*>(dbuf), static_cast<uint16_t*>(dbuf), drop_scale + (size_t)(2 * i + 1) * B, B, N, D, s));
-    pending = fused_tail ? nullptr : dbuf;
-    if (features_out && !train) {      // viz_data["Features"][i] (topk.py:197): x + mlp output, which x itself only absorbs in the next norm
-      TR_TRY(tr_residual_snapshot(x, pending, f32 ? 1 : 0, features_out, (size_t)M2 * D, s));
-      features_out += (size_t)M2 * D;
-    }
-    if (tokens_out) tokens_out[i] = N;
+    TR_TRY(f.attention(i));
+    if (f.Ks > 0) TR_TRY(f.reduce_ats(i));
+    TR_TRY(f.proj(i));
+    if (f.K > 0) TR_TRY(f.reduce_topk(i));
+    else if (f.r > 0) TR_TRY(f.reduce_tome(i));
+    else TR_TRY(f.norm2(i));
+    TR_TRY(f.mlp(i));
   }
-  // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier -- or, headless (C == 0), the
-  // normed CLS rows themselves are the output (deit_viz.py:209-212 with head = nn.Identity()): the norm writes fp32 straight into `logits`
-  const bool headless = p.C == 0;
-  const long ldd_cls = pending_ld > 0 ? pending_ld : (long)N * D;
-  if (train && features_out != nullptr) {
-    // DyViT distillation (dyvit.py:252-258): the final norm of EVERY row is an output; the whole stream stays for its backward
-    float* xfa = reinterpret_cast<float*>(tape + tp->xfin_all);
-    TR_TRY(tr_layernorm_bf16_to(x, D, xfa, D, static_cast<const uint16_t*>(pending), D, w->norm_g, w->norm_b, static_cast<uint16_t*>(xn_shared),
-                                B * N, D, cfg->ln_eps, s));
-    TR_TRY(tr_layernorm_f32(xfa, D, nullptr, D, w->norm_g, w->norm_b, features_out, B * N, D, cfg->ln_eps, s));
-    x = xfa;
-    pending = nullptr;
-  }
-  if (train && headless) {          // the CLS rows entering the norm stay on the tape (xfinal) for the backward; the tape's xcls is not needed
-    TR_TRY(tr_layernorm_bf16_f32(x, (long)N * D, reinterpret_cast<float*>(tape + tp->xfinal), D, static_cast<const uint16_t*>(pending), (long)N * D,
-                                 nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s));
-    return TR_OK;
-  }
-  if (train) {
-    xcls = tape + tp->xcls;
-    TR_TRY(tr_layernorm_bf16_to(x, (long)N * D, reinterpret_cast<float*>(tape + tp->xfinal), D, static_cast<const uint16_t*>(pending), (long)N * D,
-                                w->norm_g, w->norm_b, static_cast<uint16_t*>(xcls), B, D, cfg->ln_eps, s));
-  } else if (headless) {
-    return op_ln_pending(f32, x, (long)N * D, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
-  } else {
-    TR_TRY(op_ln_pending(f32, x, (long)N * D, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
-  }
-  TR_TRY(op_gemm(prec, xcls, w->head_w, w->head_b, logits, nullptr, 0, B, p.C, D, TR_EPI_F32, s));
-  return TR_OK;
+  return f.final_norm_head();
 }
+
 
 extern "C" int tr_vit_forward_status(const tr_vit_config* cfg, void* workspace, size_t workspace_bytes, int B, tr_stream_t s) {
   Plan p;
