@@ -414,9 +414,14 @@ int tr_tome_merge_layernorm(const float* x, const void* delta, int f32_path, con
  *   [B, n_in] of a Top-K block (n_in = K+1, or K+2 with EViT's fused token); row r of image b is written to row
  *   (r == 0 ? 0 : 1 + idx[b,r-1]) of [B, n_out, D] and the fused row to g_fused fp32 [B, D] (the caller zero-fills g_out/gb_out).
  *   ws: tr_layernorm_bwd_workspace_floats(M, D) floats.
+ *   Frozen norm: d_gamma == d_beta == NULL (both, never one: TR_ERR_NULL) computes the data gradient only -- the same bits in g_out /
+ *   gb_out / g_fused, no parameter partials, ws (may be NULL) untouched, no reduce launch, nothing added to a deferred reduce; every
+ *   form takes it (plain, index scatter with and without g_fused, tr_layernorm_bwd_scatter_add).  Profiler label
+ *   "ln_bwd_kernel<no_params>" instead of "ln_bwd_kernel".
  * tr_attention_bwd_bf16: d qkv from d out (see csrc/tr_attention_bwd.hip), N <= 224.
  * tr_head_bwd: dxn bf16 [B,D] = dlogits W; dW (+)= dlogits^T xn; db (+)= colsum(dlogits)   (topk.py:203; W, xn bf16); the weight and
  *   bias gradients run through tr_wgrad_bf16 / tr_colsum_bf16 on dl16, a bf16 copy of dlogits ([B,C] scratch); ws as tr_wgrad_bf16.
+ *   Frozen classifier: dW == db == NULL (both) runs the data gradient alone; xn, dl16 and ws are then not read.
  * tr_embed_bwd: d pos_embed [N,D] (+)= sum_b g[b,n,:], d cls_token [D] (+)= sum_b g[b,0,:]   (topk.py:183-186).
  * tr_evit_fuse_bwd: evit.py:117-120: g_out[b,1+c,:] = scores[b,c] g_fused[b] (fp32 + bf16 copy) for the complement tokens c,
  *   dscore[b,1+c] = <x[b,1+c] + delta[b,1+c], g_fused[b]>  (dscore fp32 [B,N], zero-filled by the caller).
@@ -458,7 +463,8 @@ int tr_layernorm_bwd(const uint16_t* dy, const float* x, long ldx, const float* 
                      float* dbeta, int accumulate, float* ws, size_t ws_floats, int M, int D, float eps, tr_stream_t s);
 int tr_layernorm_bwd_scatter_add(const uint16_t* dy, const float* x, const float* gamma, const float* g_in, float* g_out,
                                  const int32_t* idx, int K, int n_out, float* dgamma, float* dbeta, int accumulate, float* ws,
-                                 size_t ws_floats, int M, int D, float eps, tr_stream_t s);   /* repeated ids: rows are added (atomics) */
+                                 size_t ws_floats, int M, int D, float eps, tr_stream_t s);   /* repeated ids: rows are added (atomics);
+                                                                                                 dgamma == dbeta == NULL as above */
 int tr_attention_bwd_bf16(const uint16_t* qkv, const uint16_t* dout, const float* size, const float* dcls, uint16_t* dqkv, int B,
                           int N, int H, tr_stream_t s);
 /* The same gradient for ANY sequence length (the training executor uses it beyond 224 tokens: 384 x 384 inputs): keys in blocks of 64,
@@ -678,7 +684,18 @@ int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, con
  *   [blk_hi .. blk_lo]: the blocks this call walks, in reverse; blk_hi == depth-1 runs the classifier + final norm first, blk_lo == 0
  *   the embedding gradients last; a whole pass is (depth-1, 0) or consecutive ranges in descending order (the stream's gradient
  *   stays in the workspace in between) -- the hook for overlapping the data-parallel gradient reduction (train.py:405-407) with
- *   the backward: reduce one range's gradients on a second stream while the next range runs. */
+ *   the backward: reduce one range's gradients on a second stream while the next range runs.
+ *   Frozen parameters: a gradient UNIT of `grads` may be NULL -- both pointers, a half-NULL unit is TR_ERR_NULL -- and its work is left
+ *   out: {head_w, head_b} (only the classifier's data gradient runs), {norm_g, norm_b} and per block {ln1_g, ln1_b}, {ln2_g, ln2_b} (the
+ *   LayerNorm backward without parameter partials), per block {qkv_w, qkv_b}, {proj_w, proj_b}, {fc1_w, fc1_b}, {fc2_w, fc2_b} (left out of
+ *   the block's weight-gradient group; what remains is planned as its own group), {pos_embed, cls_token} (no tr_embed_bwd), {patch_w,
+ *   patch_b} (no patch weight-gradient product).  The walk stops at the lowest block that takes a gradient: when the embedding unit, the
+ *   patch unit and every unit and stage pointer of the blocks below block i are NULL, block i's parameter gradients are the last
+ *   launches (its qkv data gradient and a frozen norm1 do not run), the blocks below and the embedding do not run, and a range call
+ *   that starts below block i returns TR_OK without a launch; with no block unit at all only the classifier step (and a present final
+ *   norm) runs.  A block above the stop block is walked in full whatever is frozen in it.  Stage modules (grads->stage[i]) are not
+ *   skipped one by one: a stage the walk reaches needs every pointer its family writes (TR_ERR_NULL otherwise, before any launch); a
+ *   stage may be all NULL only at or below the stop block.  With nothing NULL the launch sequence is unchanged. */
 size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B);
 int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
                          size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,

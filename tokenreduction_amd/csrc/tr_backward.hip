@@ -504,7 +504,9 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const uint16_t* __restric
 // (r == 0 ? 0 : 1 + idx[b,r-1]) of the [B, n_out] gradient, and EViT's fused row r == K+1 to g_fused[b] (fp32 [B, D]).
 // ADD (K-Medoids: the gathered ids may repeat -- an empty cluster's medoid is token 0, kmedoids.py:74-79): the scattered rows are
 // ADDED to the zero-filled destination with float atomics and no bf16 copy is written (the caller converts afterwards).
-template <int NCH, bool ADD>
+// PARAMS = false (a frozen norm: the caller passed no d_gamma / d_beta): the parameter partials are neither accumulated nor stored and
+// `part` is not read; the row loop, its reductions and the stores of g_out / gb_out are the same code, so those bits do not change.
+template <int NCH, bool ADD, bool PARAMS>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict__ dy, const float* __restrict__ x, long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ g_in, long ldgi,
                                                      float* __restrict__ g_out, long ldgo, uint16_t* __restrict__ gb_out,
@@ -516,8 +518,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     gm[c] = *reinterpret_cast<const float4*>(gamma + 4 * min(lane + 64 * c, nchunks - 1));
-    ag[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    ab[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (PARAMS) {
+      ag[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      ab[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
   }
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
     float4 v[NCH], d[NCH], gi[NCH];
@@ -546,8 +550,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
     for (int c = 0; c < NCH; ++c)
       if (lane + 64 * c < nchunks) {
         v[c].x *= rstd; v[c].y *= rstd; v[c].z *= rstd; v[c].w *= rstd;                       // xhat
-        ag[c].x += d[c].x * v[c].x; ag[c].y += d[c].y * v[c].y; ag[c].z += d[c].z * v[c].z; ag[c].w += d[c].w * v[c].w;
-        ab[c].x += d[c].x; ab[c].y += d[c].y; ab[c].z += d[c].z; ab[c].w += d[c].w;
+        if constexpr (PARAMS) {
+          ag[c].x += d[c].x * v[c].x; ag[c].y += d[c].y * v[c].y; ag[c].z += d[c].z * v[c].z; ag[c].w += d[c].w * v[c].w;
+          ab[c].x += d[c].x; ab[c].y += d[c].y; ab[c].z += d[c].z; ab[c].w += d[c].w;
+        }
         d[c].x *= gm[c].x; d[c].y *= gm[c].y; d[c].z *= gm[c].z; d[c].w *= gm[c].w;           // dy * gamma
         s1 += (d[c].x + d[c].y) + (d[c].z + d[c].w);
         s2 += (d[c].x * v[c].x + d[c].y * v[c].y) + (d[c].z * v[c].z + d[c].w * v[c].w);
@@ -587,30 +593,32 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       }
     }
   }
-  // per-workgroup partial of d_gamma / d_beta: waves combined in wave order
-  __shared__ float4 red[3][2][64 * NCH];
-  if (wave > 0) {
+  if constexpr (PARAMS) {
+    // per-workgroup partial of d_gamma / d_beta: waves combined in wave order
+    __shared__ float4 red[3][2][64 * NCH];
+    if (wave > 0) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      red[wave - 1][0][lane + 64 * c] = ag[c];
-      red[wave - 1][1][lane + 64 * c] = ab[c];
+      for (int c = 0; c < NCH; ++c) {
+        red[wave - 1][0][lane + 64 * c] = ag[c];
+        red[wave - 1][1][lane + 64 * c] = ab[c];
+      }
     }
-  }
-  __syncthreads();
-  if (wave == 0) {
+    __syncthreads();
+    if (wave == 0) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + 64 * c;
-      if (ch < nchunks) {
-        float4 a = ag[c], b = ab[c];
+      for (int c = 0; c < NCH; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nchunks) {
+          float4 a = ag[c], b = ab[c];
 #pragma unroll
-        for (int w = 0; w < 3; ++w) {
-          const float4 a2 = red[w][0][ch], b2 = red[w][1][ch];
-          a.x += a2.x; a.y += a2.y; a.z += a2.z; a.w += a2.w;
-          b.x += b2.x; b.y += b2.y; b.z += b2.z; b.w += b2.w;
+          for (int w = 0; w < 3; ++w) {
+            const float4 a2 = red[w][0][ch], b2 = red[w][1][ch];
+            a.x += a2.x; a.y += a2.y; a.z += a2.z; a.w += a2.w;
+            b.x += b2.x; b.y += b2.y; b.z += b2.z; b.w += b2.w;
+          }
+          *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * D + 4 * ch) = a;                          // part[0][wg][D]
+          *reinterpret_cast<float4*>(part + ((size_t)gridDim.x + blockIdx.x) * D + 4 * ch) = b;            // part[1][wg][D]
         }
-        *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * D + 4 * ch) = a;                          // part[0][wg][D]
-        *reinterpret_cast<float4*>(part + ((size_t)gridDim.x + blockIdx.x) * D + 4 * ch) = b;            // part[1][wg][D]
       }
     }
   }
@@ -1298,18 +1306,32 @@ static int layernorm_bwd_impl(const uint16_t* dy, const float* x, long ldx, cons
                               float* g_out, long ldgo, uint16_t* gb_out, const int32_t* idx, int K, int n_in, int n_out,
                               float* g_fused, float* dgamma, float* dbeta, int accumulate, float* ws, size_t ws_floats, int M, int D,
                               float eps, bool scatter_add, tr_stream_t s) {
-  TR_REQUIRE(dy && x && gamma && g_out && dgamma && dbeta && ws, TR_ERR_NULL, "tr_layernorm_bwd: null pointer");
+  TR_REQUIRE(dy && x && gamma && g_out, TR_ERR_NULL, "tr_layernorm_bwd: null pointer");
+  TR_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), TR_ERR_NULL, "tr_layernorm_bwd: d_gamma and d_beta are both given or both NULL");
+  const bool params = dgamma != nullptr;
+  TR_REQUIRE(!params || ws != nullptr, TR_ERR_NULL, "tr_layernorm_bwd: null workspace");
   TR_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAX_CHUNKS && ldx % 4 == 0 && ldgo % 4 == 0 && (g_in == nullptr || ldgi % 4 == 0),
              TR_ERR_SHAPE, "tr_layernorm_bwd: need D %% 4 == 0, D <= 1024, strides %% 4 == 0 (M=%d D=%d)", M, D);
   if (idx != nullptr)
     TR_REQUIRE(K >= 1 && n_in >= K + 1 && n_in <= K + 2 && n_out >= K + 1 && M % n_in == 0 && (n_in == K + 1 || g_fused != nullptr) && ldgo == D,
                TR_ERR_SHAPE, "tr_layernorm_bwd: scatter needs n_in in {K+1, K+2}, M %% n_in == 0 (K=%d n_in=%d n_out=%d M=%d)", K, n_in, n_out, M);
   const int grid = ln_bwd_grid(M);
-  TR_REQUIRE(ws_floats >= (size_t)grid * 2 * D, TR_ERR_SHAPE, "tr_layernorm_bwd: workspace too small (%zu < %zu floats)", ws_floats, (size_t)grid * 2 * D);
+  TR_REQUIRE(!params || ws_floats >= (size_t)grid * 2 * D, TR_ERR_SHAPE, "tr_layernorm_bwd: workspace too small (%zu < %zu floats)", ws_floats, (size_t)grid * 2 * D);
   TR_REQUIRE(tr_aligned16(dy) && tr_aligned16(x) && tr_aligned16(gamma) && tr_aligned16(g_in) && tr_aligned16(g_out) && tr_aligned16(gb_out) &&
-                 tr_aligned16(ws) && tr_aligned16(g_fused),
+                 (!params || tr_aligned16(ws)) && tr_aligned16(g_fused),
              TR_ERR_ALIGN, "tr_layernorm_bwd: pointers must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(s);
+  if (!params) {      // frozen norm: the data gradient only -- no partials, no slice of the workspace or the deferred region, no reduce
+    tr_prof_note("ln_bwd_kernel<no_params>", 0.0, (double)M * D * (2.0 + 4.0 + (g_in ? 4.0 : 0.0) + 4.0 + (gb_out ? 2.0 : 0.0)));
+    if (scatter_add)
+      TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, true, false>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo,
+                                            static_cast<uint16_t*>(nullptr), idx, K, n_in, n_out, g_fused, static_cast<float*>(nullptr), M, D, eps));
+    else
+      TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, false, false>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo,
+                                            gb_out, idx, K, n_in, n_out, g_fused, static_cast<float*>(nullptr), M, D, eps));
+    TR_CHECK_LAUNCH("tr_layernorm_bwd");
+    return TR_OK;
+  }
   LnDefer* dc = g_ln_defer;
   const size_t need = (size_t)grid * 2 * D;
   const bool defer = dc != nullptr && dc->st == st && grid >= 64 && D <= 4096 && need <= dc->cap;
@@ -1320,10 +1342,10 @@ static int layernorm_bwd_impl(const uint16_t* dy, const float* x, long ldx, cons
   }
   tr_prof_note("ln_bwd_kernel", 0.0, (double)M * D * (2.0 + 4.0 + (g_in ? 4.0 : 0.0) + 4.0 + (gb_out ? 2.0 : 0.0)));
   if (scatter_add)
-    TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, true>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo,
+    TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, true, true>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo,
                                           static_cast<uint16_t*>(nullptr), idx, K, n_in, n_out, g_fused, ws, M, D, eps));
   else
-    TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, false>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo, gb_out,
+    TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, false, true>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo, gb_out,
                                           idx, K, n_in, n_out, g_fused, ws, M, D, eps));
   TR_CHECK_LAUNCH("tr_layernorm_bwd");
   if (defer) {
@@ -1365,11 +1387,14 @@ extern "C" int tr_layernorm_bwd_scatter_add(const uint16_t* dy, const float* x, 
 // dl16: bf16 scratch [B, C]; ws: tr_wgrad_workspace_floats(B, C, D) floats
 extern "C" int tr_head_bwd(const float* dlogits, const uint16_t* W, const uint16_t* xn, uint16_t* dxn, float* dW, float* db,
                            int accumulate, uint16_t* dl16, float* ws, size_t ws_floats, int B, int C, int D, tr_stream_t s) {
-  TR_REQUIRE(dlogits && W && xn && dxn && dW && db && dl16 && ws, TR_ERR_NULL, "tr_head_bwd: null pointer");
+  TR_REQUIRE(dlogits && W && dxn, TR_ERR_NULL, "tr_head_bwd: null pointer");
+  TR_REQUIRE((dW == nullptr) == (db == nullptr), TR_ERR_NULL, "tr_head_bwd: dW and db are both given or both NULL");
+  TR_REQUIRE(dW == nullptr || (xn && dl16 && ws), TR_ERR_NULL, "tr_head_bwd: null pointer");
   TR_REQUIRE(B > 0 && C > 0 && D > 0 && C % 8 == 0 && D % 8 == 0, TR_ERR_SHAPE, "tr_head_bwd: need classes, D multiples of 8 (B=%d C=%d D=%d)", B, C, D);
   hipStream_t st = static_cast<hipStream_t>(s);
   hipLaunchKernelGGL(head_dx_kernel, dim3((B + 3) / 4, (D + 63) / 64), dim3(256), 0, st, dlogits, W, dxn, B, C, D);
   TR_CHECK_LAUNCH("tr_head_bwd");
+  if (dW == nullptr) return TR_OK;      // frozen classifier: the data gradient only
   int rc = tr_f32_to_bf16(dlogits, dl16, (size_t)B * C, s);
   if (rc != TR_OK) return rc;
   rc = tr_wgrad_bf16(dl16, C, 0, xn, D, dW, accumulate, ws, ws_floats, B, C, D, s);

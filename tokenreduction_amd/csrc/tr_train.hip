@@ -111,6 +111,23 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
 inline float* F(const void* p) { return const_cast<float*>(static_cast<const float*>(p)); }
 inline const uint16_t* U(const void* p) { return static_cast<const uint16_t*>(p); }
 
+// A parameter unit of `grads` (the two gradients one launch produces together): 1 = present, 0 = frozen (both NULL), -1 = half-NULL.
+inline int unit(const void* a, const void* b) { return (a != nullptr) == (b != nullptr) ? (a != nullptr ? 1 : 0) : -1; }
+inline bool stage_any(const tr_stage_weights& g) {
+  return g.ln_g || g.ln_b || g.w0 || g.b0 || g.w1 || g.b1 || g.w2 || g.b2 || g.w3 || g.b3;
+}
+// every gradient pointer the backward of block i's reduction stage writes through is there (w: the forward's weights)
+inline bool stage_complete(const tr_vit_config* c, const tr_stage_weights& w, const tr_stage_weights& g) {
+  switch (c->family) {
+    case TR_FAMILY_DYVIT: return g.ln_g && g.ln_b && g.w0 && g.b0 && g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3;
+    case TR_FAMILY_SIT: return g.ln_g && g.ln_b && g.w0 && g.b0 && g.w1 && g.b1 && g.b2;
+    case TR_FAMILY_PATCHMERGER: return g.ln_g && g.ln_b && g.w1;
+    case TR_FAMILY_SINKHORN: return g.w1 != nullptr;
+    case TR_FAMILY_DPCKNN: return w.w3 == nullptr || (g.w3 && g.b3);       // no score Linear with args.equal_weight
+    default: return true;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int B) {
@@ -123,6 +140,15 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 // wt: the weight MATRICES transposed (bf16): blocks[i].qkv_w = qkv.weight^T [D,3D], proj_w = proj.weight^T [D,D], fc1_w = fc1.weight^T
 //     [D,Hd], fc2_w = fc2.weight^T [Hd,D]; other fields unused.  w: the forward's weights (head_w and the LayerNorm gammas are read).
 // grads: same layout as tr_vit_weights, every pointer an fp32 gradient buffer of the parameter's shape (matrices included).
+// Frozen parameters: a UNIT of grads may be NULL (both pointers, never one) and its gradient work is left out -- {head_w, head_b},
+//     {norm_g, norm_b}, per block {ln1_g, ln1_b} {qkv_w, qkv_b} {proj_w, proj_b} {ln2_g, ln2_b} {fc1_w, fc1_b} {fc2_w, fc2_b},
+//     {pos_embed, cls_token}, {patch_w, patch_b}: a NULL Linear unit is left out of the block's weight-gradient group, a NULL norm runs the
+//     LayerNorm backward without its parameter partials, a NULL head unit runs the classifier's data gradient only.  The walk STOPS at
+//     the lowest block that owns a gradient: when the embedding unit, the patch unit and every unit and stage pointer of the blocks
+//     below block i are NULL, block i's own parameter gradients are the last launches (its qkv data gradient and a frozen norm1 do not
+//     run), and a range call below that block launches nothing; with no block unit at all only the classifier (+ a present final norm)
+//     runs.  Stage modules (grads->stage[i]) are not skipped one by one: a stage the walk reaches needs all its pointers (TR_ERR_NULL
+//     otherwise); they may be NULL only below the stop block.
 // accumulate != 0: gradients are added to the buffers (engine.py:41 grad accumulation), else overwritten.
 // [blk_hi .. blk_lo] (blk_hi >= blk_lo): the blocks this call walks, in reverse.  blk_hi == depth-1 also runs the classifier and
 // the final norm first; blk_lo == 0 also runs the embedding gradients last.
@@ -150,6 +176,32 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
              tape_bytes, tp.total, workspace_bytes, bp.total);
   TR_REQUIRE(tr_aligned16(tape_) && tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_backward: tape / workspace must be 16-byte aligned");
   TR_REQUIRE(blk_lo >= 0 && blk_hi >= blk_lo && blk_hi < cfg->depth, TR_ERR_CONFIG, "tr_vit_backward: bad block range [%d .. %d]", blk_hi, blk_lo);
+  // ---- frozen parameters: which units are there, and the block the walk stops at
+  const int u_head = cfg->num_classes > 0 ? unit(grads->head_w, grads->head_b) : 0, u_norm = unit(grads->norm_g, grads->norm_b);
+  const int u_embed = unit(grads->pos_embed, grads->cls_token), u_patch = unit(grads->patch_w, grads->patch_b);
+  TR_REQUIRE(u_head >= 0 && u_norm >= 0 && u_embed >= 0 && u_patch >= 0, TR_ERR_NULL,
+             "tr_vit_backward: a gradient unit (head, norm, pos_embed + cls_token, patch) is half NULL: both pointers or neither");
+  // stop: block i whose own parameter gradients end the walk (nothing below it takes a gradient); depth: no block takes one; -1: the
+  // embedding does, the walk goes all the way
+  int stop = (u_embed || u_patch) ? -1 : cfg->depth;
+  for (int i = 0; i < cfg->depth; ++i) {
+    const tr_block_weights& b = grads->blocks[i];
+    const int u[6] = {unit(b.ln1_g, b.ln1_b), unit(b.qkv_w, b.qkv_b), unit(b.proj_w, b.proj_b),
+                      unit(b.ln2_g, b.ln2_b), unit(b.fc1_w, b.fc1_b), unit(b.fc2_w, b.fc2_b)};
+    bool any = stage_any(grads->stage[i]);
+    for (int k = 0; k < 6; ++k) {
+      TR_REQUIRE(u[k] >= 0, TR_ERR_NULL, "tr_vit_backward: a gradient unit of block %d is half NULL: both pointers or neither", i);
+      any = any || u[k] == 1;
+    }
+    if (any && stop == cfg->depth) stop = i;
+  }
+  for (int i = stop < 0 ? 0 : stop; i < cfg->depth; ++i) {
+    const bool reached = i > stop || stage_any(grads->stage[i]);          // the stop block's stage runs only when it owns a gradient
+    TR_REQUIRE(t.kk[i] <= 0 || !reached || stage_complete(cfg, w->stage[i], grads->stage[i]), TR_ERR_NULL,
+               "tr_vit_backward: the backward reaches the reduction stage of block %d (a parameter at or below it takes a gradient) but its "
+               "gradient pointers are NULL: stage modules are frozen only below the lowest block that takes a gradient", i);
+  }
+  if (blk_hi < stop && blk_hi < cfg->depth - 1) return TR_OK;        // the whole range lies below the stop block
   const char* tape = static_cast<const char*>(tape_);
   char* ws = static_cast<char*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(s);
@@ -191,6 +243,13 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
     }
   }
   if (blk_hi == cfg->depth - 1) {
+    const bool walk = stop < cfg->depth;          // a block (or the embedding) takes a gradient: the stream gradient is needed
+    if (!walk && !u_norm) {       // head-only probe: the classifier's parameter gradients and nothing else
+      if (u_head)
+        TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
+                           reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
+      return TR_OK;
+    }
     size_t zmax = (size_t)(3 * D > Hd ? 3 * D : Hd);
     if ((size_t)kcols > zmax) zmax = kcols;
     TR_REQUIRE(hipMemsetAsync(zeros, 0, zmax * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
@@ -211,6 +270,7 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
       TR_TRY(tr_layernorm_bwd(dxn, reinterpret_cast<const float*>(tape + tp.xfin_all), D, w->norm_g, g, D, g, D, nullptr, nullptr, 0, 0, 0, nullptr,
                               F(grads->norm_g), F(grads->norm_b), 1, wsf, wsn, B * Nl, D, cfg->ln_eps, s));
     }
+    if (!walk) return TR_OK;      // the final norm was the lowest parameter
     TR_TRY(tr_f32_to_bf16(g, gb, (size_t)B * Nl * D, s));
     if (cfg->family == TR_FAMILY_DYVIT)
       TR_REQUIRE(hipMemsetAsync(ws + bp.dpol, 0, (size_t)B * t.N0 * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
@@ -224,7 +284,7 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
     LnDeferScope(float* r, size_t n, hipStream_t st) { tr_ln_defer_begin(r, n, st); }
     ~LnDeferScope() { tr_ln_defer_end(); }
   } ln_scope(reinterpret_cast<float*>(ws + bp.lnpart), bp.lnpart_floats, st);
-  for (int i = blk_hi; i >= blk_lo; --i) {
+  for (int i = blk_hi; i >= blk_lo && i >= stop; --i) {
     const trplan::BlockTape& bt = tp.blk[i];
     const tr_block_weights* bw = &w->blocks[i];
     const tr_block_weights* bwt = &wt->blocks[i];
@@ -248,10 +308,15 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
     if (dropout_keep != nullptr)      // ... and the first one (after the activation): d pre = (dY W) * keep/(1-p) * gelu'(pre), the factors commute
       TR_TRY(tr_dropout_bf16(dh, dh, keep_h, drop_mul, (size_t)M2 * Hd, s));
     // fc2's and fc1's parameter gradients: both dY (gy, dh) exist now; launched here as a pair, or with proj's and qkv's further down
+    // (a frozen layer is left out of the list: what remains is planned as a group of its own; an empty list launches nothing)
     tr_linear_grad LG[4];
-    LG[0] = {gy, (long)D, U(tape + bt.h), (long)Hd, F(bg->fc2_w), F(bg->fc2_b), M2, D, Hd};
-    LG[1] = {dh, (long)Hd, U(tape + bt.xn2), (long)D, F(bg->fc1_w), F(bg->fc1_b), M2, Hd, D};
-    if (!four) TR_TRY(tr_linear_bwd_group(LG, 2, acc, wsf, wsn, s));
+    int nlg = 0;
+    if (bg->fc2_w != nullptr) LG[nlg++] = {gy, (long)D, U(tape + bt.h), (long)Hd, F(bg->fc2_w), F(bg->fc2_b), M2, D, Hd};
+    if (bg->fc1_w != nullptr) LG[nlg++] = {dh, (long)Hd, U(tape + bt.xn2), (long)D, F(bg->fc1_w), F(bg->fc1_b), M2, Hd, D};
+    if (!four && nlg > 0) {
+      TR_TRY(tr_linear_bwd_group(LG, nlg, acc, wsf, wsn, s));
+      nlg = 0;
+    }
     TR_TRY(tr_gemm_bf16(dh, U(bwt->fc1_w), zeros, dxn, nullptr, 0, M2, D, Hd, TR_EPI_BF16, s));
     // ---- norm2 (+ the block's in-block token reduction)
     const float* x2 = reinterpret_cast<const float*>(tape + bt.x2);
@@ -341,10 +406,12 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
       TR_TRY(tr_attention_bwd_bf16(U(tape + bt.qkv), dao, size_att, dcls, dqkv, B, Na, H, s));
     }
     // the block's parameter gradients (dY: the branch gradients kept above, dh and dqkv): one launch for all four, or the second pair
-    LG[2] = {gy_proj, (long)D, U(tape + bt.ao), (long)D, F(bg->proj_w), F(bg->proj_b), Mp, D, D};
-    LG[3] = {dqkv, (long)(3 * D), U(tape + bt.xn1), (long)D, F(bg->qkv_w), F(bg->qkv_b), M1, 3 * D, D};
-    if (four) TR_TRY(tr_linear_bwd_group(LG, 4, acc, wsf, wsn, s));
-    else TR_TRY(tr_linear_bwd_group(LG + 2, 2, acc, wsf, wsn, s));
+    if (bg->proj_w != nullptr) LG[nlg++] = {gy_proj, (long)D, U(tape + bt.ao), (long)D, F(bg->proj_w), F(bg->proj_b), Mp, D, D};
+    if (bg->qkv_w != nullptr) LG[nlg++] = {dqkv, (long)(3 * D), U(tape + bt.xn1), (long)D, F(bg->qkv_w), F(bg->qkv_b), M1, 3 * D, D};
+    if (nlg > 0) TR_TRY(tr_linear_bwd_group(LG, nlg, acc, wsf, wsn, s));
+    // the stop block: what follows only feeds the blocks below, except norm1's own parameters and a stage that owns a gradient
+    const bool stage_here = K > 0 && stage_any(grads->stage[i]);
+    if (i == stop && bg->ln1_g == nullptr && !stage_here) break;
     TR_TRY(tr_gemm_bf16(dqkv, U(bwt->qkv_w), zeros, dxn, nullptr, 0, M1, D, 3 * D, TR_EPI_BF16, s));
     if (cfg->family == TR_FAMILY_KMEDOIDS && K > 0) {
       // norm1 ran on the gathered medoid rows (kmedoids.py:243-248): its backward scatter-ADDS into the pre-reduction stream's gradient
@@ -352,13 +419,14 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
       TR_REQUIRE(hipMemsetAsync(g_alt, 0, nfull * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
       TR_TRY(tr_layernorm_bwd_scatter_add(dxn, x1, bw->ln1_g, g, g_alt, reinterpret_cast<const int32_t*>(tape + bt.idx), K, t.n_pre[i], F(bg->ln1_g),
                                           F(bg->ln1_b), acc, wsf, wsn, M1, D, cfg->ln_eps, s));
-      TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, nfull, s));
+      if (i > stop) TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, nfull, s));          // (the bf16 copy only feeds the blocks below)
       float* tg = g; g = g_alt; g_alt = tg;
       uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
     } else {
       TR_TRY(tr_layernorm_bwd(dxn, x1, D, bw->ln1_g, g, D, g, D, gb, nullptr, 0, 0, 0, nullptr, F(bg->ln1_g), F(bg->ln1_b), acc, wsf, wsn, M1, D,
                               cfg->ln_eps, s));
     }
+    if (i == stop && !stage_here) break;
     if (cfg->family == TR_FAMILY_DYVIT && K > 0) {
       // PredictorLG + Gumbel straight-through of this stage (dyvit.py:221-224), backwards.  d keep = the policy gradient collected
       // from the blocks that attended under this stage's policy (+ the later stage's d prev_decision) + d out_pred_prob
@@ -461,13 +529,13 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
     }
   }
   TR_TRY(tr_ln_defer_flush());
-  if (blk_lo > 0) return TR_OK;
+  if (blk_lo > 0 || stop >= 0) return TR_OK;
   // ---- embedding (topk.py:181-186): g is d x0 [B, N0, D]
   if (dropout_keep != nullptr) {      // pos_drop (topk.py:186): on the stream gradient and on its bf16 copy (the patch projection's dY)
     TR_TRY(tr_dropout_f32(g, g, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
     TR_TRY(tr_dropout_bf16(gb, gb, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
   }
-  TR_TRY(tr_embed_bwd(g, F(grads->pos_embed), F(grads->cls_token), acc, B, t.N0, D, s));
-  TR_TRY(tr_linear_bwd_params(gb, D, t.P, U(tape + tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
+  if (u_embed) TR_TRY(tr_embed_bwd(g, F(grads->pos_embed), F(grads->cls_token), acc, B, t.N0, D, s));
+  if (u_patch) TR_TRY(tr_linear_bwd_params(gb, D, t.P, U(tape + tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
   return TR_OK;
 }

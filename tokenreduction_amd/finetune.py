@@ -11,6 +11,7 @@ Mirrors, for models built by tokenreduction_amd.create_model (same parameter nam
                          restated in CosineSchedule): linear warm-up, cosine to lr_min, counted in optimizer STEPS when
                          `sched_in_steps` (t_in_epochs=False) -- `step_update(num_updates)` -- or in epochs -- `step(epoch)`.
 
+    train.py:372-392     freeze_attn_only()        --attn-only: attention layers, head and pos_embed train, everything else is frozen
     train.py:343-370     load_finetune_checkpoint() ingest of a DeiT-layout checkpoint: mismatching classifier dropped, position
                                                    embedding resized to the model's patch grid
 
@@ -57,6 +58,20 @@ def get_parameter_groups(model, learning_rate, weight_decay=1e-5, bone_lr_scale=
             groups[group] = {"weight_decay": wd, "params": [], "lr": learning_rate * scale, "fix_step": fix}
         groups[group]["params"].append(name if with_names else param)
     return list(groups.values())
+
+
+def freeze_attn_only(model) -> List[str]:
+    """train.py:372-392 (--attn-only): only the attention layers (every name with `.attn.`: qkv and proj, weights and biases), the
+    classifier and `pos_embed` keep requires_grad; everything else is frozen -- `cls_token`, `patch_embed`, every norm, the Mlps and
+    the family's own modules included.  Returns the trainable names.  The HIP backward skips the frozen gradients (training.py)."""
+    for name, p in model.named_parameters():
+        p.requires_grad = ".attn." in name
+    model.head.weight.requires_grad = True
+    model.head.bias.requires_grad = True
+    model.pos_embed.requires_grad = True
+    for p in model.patch_embed.parameters():
+        p.requires_grad = False
+    return [name for name, p in model.named_parameters() if p.requires_grad]
 
 
 def frozen_lr(param_groups: Iterable[dict], epoch: int) -> None:

@@ -7,6 +7,8 @@ that keeps its activations on a tape) and returns logits that carry an autograd 
 into that buffer, laid out in the order the backward finishes them (head, norm, blocks depth-1..0, embedding), so a
 data-parallel reducer can all-reduce contiguous slices in place while the rest of the backward is still running
 (dp.FlatGradReducer) -- no flatten/unflatten copies.
+Frozen parameters (requires_grad False) cost no gradient work: a unit whose parameters are all frozen reaches the executor as NULL
+pointers, and the backward stops at the lowest block that still has a trainable parameter at or below it (TrainState.grads_struct).
 
 PyTorch is plumbing: memory, the stream, the autograd hook and the loss.  No arithmetic of the model happens in torch.
 """
@@ -69,6 +71,7 @@ class TrainState:
         self.tape = self.bws = None
         self.key = None
         self.events = None
+        self._stage_names = None
         self.gen = 0                 # counts training forwards: the tape belongs to the LAST one (see _VitTrainFn.backward)
 
     def _block_slices(self, model):
@@ -91,28 +94,69 @@ class TrainState:
         return out
 
     def grads_struct(self, model):
-        """tr_vit_weights-shaped struct whose pointers are the gradient views."""
+        """tr_vit_weights-shaped struct whose pointers are the gradient views, read off `requires_grad` as it is NOW (built per
+        backward, nothing cached).  A unit of tr_vit_backward (the two gradients one launch produces) whose parameters are all frozen
+        is NULL: the executor leaves its work out.  A mixed unit (pos_embed trainable, cls_token frozen) keeps both pointers; the frozen
+        half lands in its slot of the flat buffer and is discarded.  The pointers of a family's reduction stage are NULL only where
+        the backward never arrives: below the lowest block that has a trainable parameter at or below it.
+        Returns (struct, names of the frozen parameters the executor still writes)."""
         G = _lib.TrVitWeights()
         v = self.views
+        named = dict(self.order)
 
         def ptr(name):
             return v[name].data_ptr()
 
-        G.patch_w, G.patch_b = ptr("patch_embed.proj.weight"), ptr("patch_embed.proj.bias")
-        G.cls_token, G.pos_embed = ptr("cls_token"), ptr("pos_embed")
-        G.norm_g, G.norm_b = ptr("norm.weight"), ptr("norm.bias")
+        discarded = []
+
+        def unit(a, b):
+            if not (named[a].requires_grad or named[b].requires_grad):
+                return None, None
+            discarded.extend(n for n in (a, b) if not named[n].requires_grad)
+            return ptr(a), ptr(b)
+
+        G.patch_w, G.patch_b = unit("patch_embed.proj.weight", "patch_embed.proj.bias")
+        G.cls_token, G.pos_embed = unit("cls_token", "pos_embed")
+        G.norm_g, G.norm_b = unit("norm.weight", "norm.bias")
         if "head.weight" in v:       # headless models (num_classes == 0) have no classifier slices: the head pointers stay NULL
-            G.head_w, G.head_b = ptr("head.weight"), ptr("head.bias")
+            G.head_w, G.head_b = unit("head.weight", "head.bias")
         for i in range(model.depth):
             b, pre = G.blocks[i], f"blocks.{i}."
-            b.ln1_g, b.ln1_b = ptr(pre + "norm1.weight"), ptr(pre + "norm1.bias")
-            b.qkv_w, b.qkv_b = ptr(pre + "attn.qkv.weight"), ptr(pre + "attn.qkv.bias")
-            b.proj_w, b.proj_b = ptr(pre + "attn.proj.weight"), ptr(pre + "attn.proj.bias")
-            b.ln2_g, b.ln2_b = ptr(pre + "norm2.weight"), ptr(pre + "norm2.bias")
-            b.fc1_w, b.fc1_b = ptr(pre + "mlp.fc1.weight"), ptr(pre + "mlp.fc1.bias")
-            b.fc2_w, b.fc2_b = ptr(pre + "mlp.fc2.weight"), ptr(pre + "mlp.fc2.bias")
+            b.ln1_g, b.ln1_b = unit(pre + "norm1.weight", pre + "norm1.bias")
+            b.qkv_w, b.qkv_b = unit(pre + "attn.qkv.weight", pre + "attn.qkv.bias")
+            b.proj_w, b.proj_b = unit(pre + "attn.proj.weight", pre + "attn.proj.bias")
+            b.ln2_g, b.ln2_b = unit(pre + "norm2.weight", pre + "norm2.bias")
+            b.fc1_w, b.fc1_b = unit(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
+            b.fc2_w, b.fc2_b = unit(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
         model._grad_stage_ptrs(G, ptr)
-        return G
+        stage_names = self._stage_names      # {block: names of the family's parameters behind G.stage[block]}: structure, not mask
+        if stage_names is None:
+            by_ptr = {ptr(n): n for n, _ in self.order}
+            stage_names = self._stage_names = {}
+            for loc in range(model.depth):
+                names = [by_ptr[a] for a in (getattr(G.stage[loc], f) for f in _STAGE_PTRS) if a]
+                if names:
+                    stage_names[loc] = names
+        # the floor: the lowest block with a trainable parameter at or below it (-1: the embedding trains, the backward goes all the way).
+        # Conservative for family modules: a stage's parameter counts at the stage's block, any other family parameter at block 0.
+        at = {n: loc for loc, names in stage_names.items() for n in names}
+        floor = model.depth
+        for n, p in self.order:
+            if not p.requires_grad or n.startswith(("head.", "norm.")):
+                continue
+            if n.startswith("blocks."):
+                floor = min(floor, int(n.split(".")[1]))
+            elif n.startswith(("pos_embed", "cls_token", "patch_embed")):
+                floor = -1
+            else:
+                floor = min(floor, at.get(n, 0))
+        for loc, names in stage_names.items():
+            if loc < floor or (loc == floor and not any(named[n].requires_grad for n in names)):
+                for f in _STAGE_PTRS:
+                    setattr(G.stage[loc], f, None)
+            else:
+                discarded.extend(n for n in names if not named[n].requires_grad)
+        return G, discarded
 
     def transposed(self, model, pk):
         """bf16 transposed copies of the block matrices (the dgrad GEMM operands): made by the model's own repack (models._pack with
@@ -149,6 +193,8 @@ class TrainState:
             self.B = B
         return self.tape, self.bws
 
+
+_STAGE_PTRS = ("ln_g", "ln_b", "w0", "b0", "w1", "b1", "w2", "b2", "w3", "b3")
 
 TAPE_FIELDS = ("x0", "x1", "xn1", "qkv", "ao", "dattn", "x2", "xn2", "pre", "h", "idx", "idx2", "scores", "size",
                "n_pre", "n_att", "n_mlp", "kk")
@@ -317,14 +363,17 @@ class _VitTrainFn(torch.autograd.Function):
                 dfeat[:, 1:] = dextra[ctx.n_pred].detach()
         # gradient views: when NO parameter holds a gradient yet (zero_grad(set_to_none=True), torch's default) the backward OVERWRITES
         # the flat buffer -- nothing to clear, nothing to read back; otherwise the slices of the parameters without a gradient are zeroed
-        # and the backward accumulates (engine.py:41-84: gradient accumulation over micro-steps).  Every parameter of the executor is
-        # written exactly once per backward (csrc/tr_train.hip); parameters the executor does not touch keep the zeros they were born with.
-        fresh = [n for n, p in st.order if p.grad is None or p.grad.data_ptr() != st.views[n].data_ptr()]
-        accumulate = 0 if len(fresh) == len(st.order) else 1
+        # and the backward accumulates (engine.py:41-84: gradient accumulation over micro-steps).  Every trainable parameter of the
+        # executor is written exactly once per backward (csrc/tr_train.hip); parameters the executor does not touch keep the zeros they
+        # were born with.  Frozen parameters (requires_grad False) take no part: their slices are neither cleared nor -- when their whole
+        # unit is frozen (grads_struct) -- written.
+        train = [(n, p) for n, p in st.order if p.requires_grad]
+        fresh = [n for n, p in train if p.grad is None or p.grad.data_ptr() != st.views[n].data_ptr()]
+        accumulate = 0 if len(fresh) == len(train) else 1
+        G, discarded = st.grads_struct(model)
         if accumulate:
-            for n in fresh:
+            for n in fresh + discarded:          # (a discarded slice is cleared so that it cannot grow without bound over the steps)
                 st.views[n].zero_()
-        G = st.grads_struct(model)
         WT = st.transposed(model, pk)
         reducer = model._grad_reducer
         reduce_now = reducer is not None and reducer.sync
