@@ -247,3 +247,19 @@ def test_attention_cls_equals_row_0_of_the_full_attention(N, H, masked):
     full, _ = ops.attention(qkv, B, N, H, size=size)
     got = ops.attention_cls(qkv, B, N, H, size=size)
     assert torch.equal(got.view(torch.int16), full.view(B, N, H * 64)[:, 0].contiguous().view(torch.int16))
+
+
+@pytest.mark.parametrize("N", [1, 16, 17, 32, 33, 224, 225, 256, 257, 1025])
+def test_attention_cls_equals_row_0_at_the_block_edges(N):
+    """The first query block alone at the 16- and 32-query block edges and both sides of the 224-token dispatch, with and without a key
+    bias, on the shifted and masked inputs of tests/_attn_fwd_ref.py as well (a masked key 25 above every real one)."""
+    from tokenreduction_amd import ops
+    from tests import _attn_fwd_ref as R
+    B, H = R.shape_of(N)
+    cases = [(kind, bias) for kind in ("gaussian", "shift_neg") for bias in (False, True)] + ([("masked_dominant", True)] if N >= 2 else [])
+    for kind, bias in cases:
+        qkv, size = R.build(kind, B, N, H, bias)
+        qkv, size = qkv.cuda(), None if size is None else size.cuda()
+        full, _ = ops.attention(qkv, B, N, H, size=size)
+        got = ops.attention_cls(qkv, B, N, H, size=size)
+        assert torch.equal(got.view(torch.int16), full.view(B, N, H * 64)[:, 0].contiguous().view(torch.int16)), (kind, bias)

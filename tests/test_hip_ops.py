@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import oracle
+from tests import _attn_fwd_ref as AF
 from tests._params import make_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -714,6 +715,7 @@ def test_attention_proportional(ops, B, N, H):
     got, _ = ops.attention(qkv.bfloat16().cuda(), B, N, H, size=size.cuda())
     # P is rounded to bf16 before P.V (as in the size-free kernel): 2^-8 relative on O(1) values
     torch.testing.assert_close(got.float().cpu(), want, atol=3e-2, rtol=2e-2)
+    AF.assert_blocks(got, want, B, N, H, AF.MEASURED["proportional"], "attention proportional")   # per 16 queries, image and head
     got32, _ = ops.attention_f32(qkv.cuda(), B, N, H, size=size.cuda())
     torch.testing.assert_close(got32.cpu(), want, atol=2e-5, rtol=2e-5)
 
@@ -929,6 +931,7 @@ def test_attention_key_mask(ops, B, N, H):
     want = (attn @ v).transpose(1, 2).reshape(B * N, H * 64).float()
     got, cls = ops.attention(qkv.bfloat16().cuda(), B, N, H, want_cls=True, size=mask.cuda())
     torch.testing.assert_close(got.float().cpu(), want, atol=3e-2, rtol=2e-2)
+    AF.assert_blocks(got, want, B, N, H, AF.MEASURED["key_mask"], "attention key mask")
     assert (cls.cpu()[mask[:, None, :].expand(B, H, N) == 0] == 0).all()           # exactly zero, like the underflowing softmax
     got32, cls32 = ops.attention_f32(qkv.cuda(), B, N, H, want_cls=True, size=mask.cuda())
     torch.testing.assert_close(got32.cpu(), want, atol=2e-5, rtol=2e-5)
@@ -1069,11 +1072,13 @@ def test_attention_long(ops, B, N, H):
         part = torch.full((B, H, 4, N), float("nan"), device="cuda")
         got, cls = ops.attention(qkv.bfloat16().cuda(), B, N, H, want_cls=True, size=None if sz is None else sz.cuda(), colsum_part=part)
         torch.testing.assert_close(got.float().cpu(), want, atol=3e-2, rtol=2e-2)
+        AF.assert_blocks(got, want, B, N, H, AF.MEASURED["long"], "attention long, column sums")
         torch.testing.assert_close(cls.cpu(), attn[:, :, 0, :].float(), atol=2e-6, rtol=2e-3)
         torch.testing.assert_close(part.sum(dim=(1, 2)).cpu(), attn.sum(dim=1).sum(dim=1).float(), atol=5e-4, rtol=2e-3)
         # without column sums the online-softmax kernel runs (key chunks of 128): same contract, its own rounding points
         got2, cls2 = ops.attention(qkv.bfloat16().cuda(), B, N, H, want_cls=True, size=None if sz is None else sz.cuda())
         torch.testing.assert_close(got2.float().cpu(), want, atol=3e-2, rtol=2e-2)
+        AF.assert_blocks(got2, want, B, N, H, AF.MEASURED["long"], "attention long")
         torch.testing.assert_close(cls2.cpu(), attn[:, :, 0, :].float(), atol=2e-6, rtol=2e-3)
         got3, _ = ops.attention(qkv.bfloat16().cuda(), B, N, H, size=None if sz is None else sz.cuda())
         assert torch.equal(got3, got2)                                           # the CLS side output does not change the main one
@@ -1122,6 +1127,7 @@ def test_attention_with_policy(ops, B, N, H):
     want = (attn @ v).transpose(1, 2).reshape(B * N, H * 64)
     got = ops.attention_policy(qkv.bfloat16().cuda(), policy.cuda(), B, N, H)
     torch.testing.assert_close(got.float().cpu(), want, atol=3e-2, rtol=2e-2)
+    AF.assert_blocks(got, want, B, N, H, AF.MEASURED["policy"], "attention with policy")
     if N > 256:
         return
     got32 = ops.attention_policy(qkv.cuda(), policy.cuda(), B, N, H)
@@ -1149,6 +1155,7 @@ def test_attention_every_sequence_length(ops):
         err = (got.float().cpu() - want).abs().max().item()
         worst = max(worst, err)
         assert err < 3e-2, (N, err)
+        AF.assert_blocks(got, want, B, N, H, AF.MEASURED["sweep"], "attention N sweep")
         torch.testing.assert_close(cls.cpu(), attn[:, :, 0, :].float(), atol=2e-6, rtol=2e-3)
     print(f"attention N sweep ({len(ns)} lengths): worst abs error {worst:.2e}")
 
@@ -1192,6 +1199,7 @@ def test_attention_beyond_the_lds_limit(ops, B, N, H):
     want = (attn @ v).transpose(1, 2).reshape(B * N, H * 64).float()
     got, cls = ops.attention(qkv.bfloat16().cuda(), B, N, H, want_cls=True)
     torch.testing.assert_close(got.float().cpu(), want, atol=3e-2, rtol=2e-2)
+    AF.assert_blocks(got, want, B, N, H, AF.MEASURED["beyond"], "attention beyond the LDS limit")
     torch.testing.assert_close(cls.cpu(), attn[:, :, 0, :].float(), atol=2e-6, rtol=2e-3)
     part = torch.full((B, H, 4, N), float("nan"), device="cuda")                 # column sums: second pass over the keys
     got2, _ = ops.attention(qkv.bfloat16().cuda(), B, N, H, colsum_part=part)
