@@ -571,16 +571,21 @@ def test_linear_bwd_params2_pairs_two_layers_in_one_launch(ops, shapes):
 def test_linear_bwd_group_up_to_four_layers_in_one_launch(ops, shapes):
     """The block's four parameter-gradient products from one weight-gradient launch: exact on small integers (unit -> layer -> tile -> token
     range), layers with different token counts, three layers, a group with a layer the 192-tile kernel does not take (separate calls),
-    accumulate, run-to-run bitwise.  The short groups (3200 and 200 rows: one token range per layer) store their results in place
-    without a reduce launch when they overwrite, and go through partials + reduce when they accumulate: both asserted here."""
+    accumulate, run-to-run bitwise.  The 3200-row group (one token range per layer) stores its results in place without a reduce launch
+    when it overwrites -- no partial is written: the workspace keeps its sentinel -- and goes through partials + reduce when it
+    accumulates; every other group here (the 200-row one included: its layers get 4, 2 and 1 ranges) writes partials either way.  Both
+    asserted here by the workspace."""
     g = torch.Generator().manual_seed(shapes[0][0] + len(shapes))
     mk = lambda m, n: torch.randint(-2, 3, (m, n), generator=g).to(torch.bfloat16).cuda()
     layers = [(mk(M, N), mk(M, K)) for M, N, K in shapes]
-    outs = ops.linear_bwd_group(layers)
+    ws = torch.full((ops.linear_bwd_group_workspace_floats(shapes),), -12345.5, device="cuda")
+    outs = ops.linear_bwd_group(layers, ws=ws)
+    assert bool((ws == -12345.5).all()) == (shapes[0][0] == 3200), "only the 3200-row group stores in place"
     for (dy, x), (dw, db) in zip(layers, outs):
         assert torch.equal(dw, dy.float().t() @ x.float()) and torch.equal(db, dy.float().sum(0))
     acc = [(dw.clone(), db.clone()) for dw, db in outs]
-    ops.linear_bwd_group(layers, accumulate=True, outs=acc)
+    ops.linear_bwd_group(layers, accumulate=True, outs=acc, ws=ws)
+    assert not bool((ws == -12345.5).all()), "an accumulating group writes partials"
     for (dw, db), (aw, ab) in zip(outs, acc):
         assert torch.equal(aw, 2 * dw) and torch.equal(ab, 2 * db)
     layers = [(_randn(70 + 2 * i, *dy.shape, dtype=torch.bfloat16), _randn(71 + 2 * i, *x.shape, dtype=torch.bfloat16)) for i, (dy, x) in enumerate(layers)]

@@ -1052,7 +1052,10 @@ extern "C" int tr_wgrad_bf16(const uint16_t* dY, long ldy, int yskip, const uint
     hipLaunchKernelGGL(wgrad_kernel<false>, dim3(tiles, S), dim3(256), 0, st, dY, ldy, yskip, X, ldx, ws, static_cast<float*>(nullptr), M, N, K, nNt, sps);
   }
   TR_CHECK_LAUNCH("tr_wgrad_bf16");
-  reduce_partials(ws, S, (size_t)N * K, dW, accumulate, st);
+  // many partials of a small matrix: the tall order tr_linear_bwd_params' reduce takes there (second result empty), so that dW stays
+  // bit-equal to the fused call's at every shape; the 64 x 4 order otherwise (the same in both reduces)
+  if (S >= 64 && (size_t)N * K <= 4096) reduce_partials2(ws, (size_t)N * K, dW, ws, (size_t)0, dW, S, accumulate, st);
+  else reduce_partials(ws, S, (size_t)N * K, dW, accumulate, st);
   TR_CHECK_LAUNCH("tr_wgrad_bf16 (reduce)");
   return TR_OK;
 }

@@ -712,52 +712,69 @@ def _ws(n_floats: int, dev) -> torch.Tensor:
     return torch.empty(max(int(n_floats), 4), dtype=torch.float32, device=dev)
 
 
+def _ws_arg(ws, ws_floats, need: int, dev):
+    """(workspace pointer, floats told to the C ABI).  Default: a fresh workspace of the size the library recommends.  ws: the caller's own
+    fp32 buffer (a slice of a larger one: what lies around it can be watched); ws_floats: what the kernels may use of it -- fewer floats
+    than recommended make the launch re-plan its token ranges, as the executor's shared workspace does."""
+    if ws is None:
+        ws = _ws(need if ws_floats is None else ws_floats, dev)
+        return ws, ws.data_ptr(), ws.numel() if ws_floats is None else int(ws_floats)
+    n = ws.numel() if ws_floats is None else int(ws_floats)
+    if n > ws.numel():
+        raise ValueError(f"ws: {n} floats asked of a workspace of {ws.numel()}")
+    return ws, _dev(ws, torch.float32, "ws"), n
+
+
+def _rows(t: torch.Tensor, dtype, name: str):
+    """(pointer, row stride): 2-D operands may be column slices of a wider tensor (unit column stride, any row stride) -- the C ABI takes
+    a leading dimension; everything else must be contiguous."""
+    if t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == dtype:
+        return t.data_ptr(), t.stride(0)
+    return _dev(t, dtype, name), t.shape[-1]
+
+
 def wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor = None, accumulate: bool = False, yskip: int = 0,
-          rows: int = None) -> torch.Tensor:
+          rows: int = None, ws: torch.Tensor = None, ws_floats: int = None) -> torch.Tensor:
     """nn.Linear weight gradient dW[N,K] (+)= dy[M,N]^T x[M,K] (bf16 operands, fp32 result)."""
     M = rows if rows is not None else x.shape[0]
     N, K = dy.shape[-1], x.shape[-1]
     lib = _lib.load()
     if out is None:
         out = torch.empty(N, K, dtype=torch.float32, device=x.device)
-    nws = lib.tr_wgrad_workspace_floats(M, N, K)
-    ws = _ws(nws, x.device)
-    _lib.check(lib.tr_wgrad_bf16(_dev(dy, torch.bfloat16, "dy"), N, yskip, _dev(x, torch.bfloat16, "x"), K, _dev(out, torch.float32, "out"),
-                                 int(accumulate), ws.data_ptr(), ws.numel(), M, N, K, _stream()), "tr_wgrad_bf16")
+    ws, pws, nws = _ws_arg(ws, ws_floats, lib.tr_wgrad_workspace_floats(M, N, K), x.device)
+    (py, ldy), (px, ldx) = _rows(dy, torch.bfloat16, "dy"), _rows(x, torch.bfloat16, "x")
+    _lib.check(lib.tr_wgrad_bf16(py, ldy, yskip, px, ldx, _dev(out, torch.float32, "out"), int(accumulate), pws, nws, M, N, K, _stream()),
+               "tr_wgrad_bf16")
     return out
 
 
 def linear_bwd_params(dy: torch.Tensor, x: torch.Tensor, accumulate: bool = False, dw: torch.Tensor = None, db: torch.Tensor = None,
-                      yskip: int = 0):
+                      yskip: int = 0, ws: torch.Tensor = None, ws_floats: int = None):
     """Weight and bias gradient of an nn.Linear in one pass (tr_linear_bwd_params): (dW fp32 [N,K], db fp32 [N]).  yskip > 0: dy holds one
     extra leading row per `yskip` rows (the CLS row of [B, P + 1, D]) that the layer never saw (PatchEmbed)."""
     M, N, K = x.shape[0], dy.shape[-1], x.shape[-1]
     lib = _lib.load()
     dw = torch.empty(N, K, dtype=torch.float32, device=x.device) if dw is None else dw
     db = torch.empty(N, dtype=torch.float32, device=x.device) if db is None else db
-    ws = _ws(lib.tr_wgrad_workspace_floats(M, N, K), x.device)
-
-    def rows(t, name):      # 2-D operands may be column slices of a wider tensor (unit column stride, any row stride): the C ABI takes ldy / ldx
-        if t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == torch.bfloat16:
-            return t.data_ptr(), t.stride(0)
-        return _dev(t, torch.bfloat16, name), t.shape[-1]
-    (py, ldy), (px, ldx) = rows(dy, "dy"), rows(x, "x")
+    ws, pws, nws = _ws_arg(ws, ws_floats, lib.tr_wgrad_workspace_floats(M, N, K), x.device)
+    (py, ldy), (px, ldx) = _rows(dy, torch.bfloat16, "dy"), _rows(x, torch.bfloat16, "x")
     _lib.check(lib.tr_linear_bwd_params(py, ldy, yskip, px, ldx, _dev(dw, torch.float32, "dw"),
-                                        _dev(db, torch.float32, "db"), int(accumulate), ws.data_ptr(), ws.numel(), M, N, K, _stream()),
+                                        _dev(db, torch.float32, "db"), int(accumulate), pws, nws, M, N, K, _stream()),
                "tr_linear_bwd_params")
     return dw, db
 
 
-def colsum(dy: torch.Tensor, out: torch.Tensor = None, accumulate: bool = False, yskip: int = 0, rows: int = None) -> torch.Tensor:
+def colsum(dy: torch.Tensor, out: torch.Tensor = None, accumulate: bool = False, yskip: int = 0, rows: int = None, ws: torch.Tensor = None,
+           ws_floats: int = None) -> torch.Tensor:
     """nn.Linear bias gradient db[N] (+)= sum_m dy[m,n]."""
     N = dy.shape[-1]
-    M = rows if rows is not None else dy.numel() // N
+    M = rows if rows is not None else (dy.shape[0] if dy.dim() == 2 else dy.numel() // N)
     lib = _lib.load()
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=dy.device)
-    ws = _ws(lib.tr_colsum_workspace_floats(M, N), dy.device)
-    _lib.check(lib.tr_colsum_bf16(_dev(dy, torch.bfloat16, "dy"), N, yskip, _dev(out, torch.float32, "out"), int(accumulate),
-                                  ws.data_ptr(), ws.numel(), M, N, _stream()), "tr_colsum_bf16")
+    ws, pws, nws = _ws_arg(ws, ws_floats, lib.tr_colsum_workspace_floats(M, N), dy.device)
+    py, ldy = _rows(dy, torch.bfloat16, "dy")
+    _lib.check(lib.tr_colsum_bf16(py, ldy, yskip, _dev(out, torch.float32, "out"), int(accumulate), pws, nws, M, N, _stream()), "tr_colsum_bf16")
     return out
 
 
@@ -775,35 +792,62 @@ def gelu_bwd(pre: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
 
 
 def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, eps: float, g_in: torch.Tensor = None, idx: torch.Tensor = None,
-                  n_out: int = None, fused: bool = False):
+                  n_out: int = None, fused: bool = False, g_out: torch.Tensor = None, ldx: int = None, ldgi: int = None, gb: bool = True,
+                  accumulate: bool = False, dgamma: torch.Tensor = None, dbeta: torch.Tensor = None, params: bool = True, add: bool = False,
+                  ws: torch.Tensor = None, ws_floats: int = None):
     """LayerNorm backward fused with the residual gradient.  dy bf16 [M,D], x fp32 [M,D] (LayerNorm input), g_in fp32 [M,D]|None.
     Plain: returns (g fp32 [M,D], gb bf16 [M,D], dgamma, dbeta).  With idx int32 [B,K] (Top-K gather backward): rows are
-    [B, K+1(+1 fused)], results scattered into zero-filled [B, n_out, D]; also returns g_fused [B,D] when fused."""
+    [B, K+1(+1 fused)], results scattered into zero-filled [B, n_out, D]; also returns g_fused [B,D] when fused.
+    The forms the backward executor uses: x, g_in and g_out may be row-strided 2-D views (ldx / ldgi override the stride taken from the
+    view); g_out: the caller's destination (g_in itself: in place; with idx: zero-filled by the caller); gb=False: no bf16 copy (None
+    returned); accumulate: ADD to the given dgamma / dbeta; params=False: a frozen norm, no parameter gradients (None returned);
+    add=True (needs idx): tr_layernorm_bwd_scatter_add -- repeated ids are summed with float atomics, no bf16 copy."""
     M, D = dy.shape
     lib = _lib.load()
-    dgamma = torch.empty(D, dtype=torch.float32, device=dy.device)
-    dbeta = torch.empty(D, dtype=torch.float32, device=dy.device)
-    ws = _ws(lib.tr_layernorm_bwd_workspace_floats(M, D), dy.device)
-    g_fused = None
+    dev = dy.device
+    if params:
+        dgamma = _grad_out(dgamma, (D,), "dgamma", accumulate, dev)
+        dbeta = _grad_out(dbeta, (D,), "dbeta", accumulate, dev)
+        ws, pws, nws = _ws_arg(ws, ws_floats, lib.tr_layernorm_bwd_workspace_floats(M, D), dev)
+        pdg, pdb = dgamma.data_ptr(), dbeta.data_ptr()
+    else:
+        dgamma = dbeta = pws = pdg = pdb = None
+        nws = 0
+    g_fused = gbuf = None
     if idx is None:
-        g = torch.empty(M, D, dtype=torch.float32, device=dy.device)
-        gb = torch.empty(M, D, dtype=torch.bfloat16, device=dy.device)
+        if add:
+            raise ValueError("layernorm_bwd: add=True is the scatter of repeated ids and needs idx")
+        g = torch.empty(M, D, dtype=torch.float32, device=dev) if g_out is None else g_out
+        if gb:
+            gbuf = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
         K = n_in = no = 0
     else:
         B, K = idx.shape
         n_in = K + 1 + (1 if fused else 0)
         no = n_out
-        g = torch.zeros(B * n_out, D, dtype=torch.float32, device=dy.device)
-        gb = torch.zeros(B * n_out, D, dtype=torch.bfloat16, device=dy.device)
+        g = torch.zeros(B * n_out, D, dtype=torch.float32, device=dev) if g_out is None else g_out
+        if gb and not add:
+            gbuf = torch.zeros(B * n_out, D, dtype=torch.bfloat16, device=dev)
         if fused:
-            g_fused = torch.empty(B, D, dtype=torch.float32, device=dy.device)
-    _lib.check(lib.tr_layernorm_bwd(_dev(dy, torch.bfloat16, "dy"), _dev(x, torch.float32, "x"), D, _dev(gamma, torch.float32, "gamma"),
-                                    _opt(g_in, torch.float32, "g_in"), D, g.data_ptr(), D, gb.data_ptr(), _opt(idx, torch.int32, "idx"), K, n_in,
-                                    no, None if g_fused is None else g_fused.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0,
-                                    ws.data_ptr(), ws.numel(), M, D, eps, _stream()), "tr_layernorm_bwd")
+            g_fused = torch.empty(B, D, dtype=torch.float32, device=dev)
+    px, sx = _rows(x, torch.float32, "x")
+    pgi, sgi = (None, D) if g_in is None else _rows(g_in, torch.float32, "g_in")
+    pgo, sgo = _rows(g, torch.float32, "g_out")
+    ldx, ldgi = sx if ldx is None else ldx, sgi if ldgi is None else ldgi
+    if add:
+        if fused or ldx != D or ldgi != D or sgo != D:
+            raise ValueError("layernorm_bwd: add=True takes contiguous rows and no fused row")
+        _lib.check(lib.tr_layernorm_bwd_scatter_add(_dev(dy, torch.bfloat16, "dy"), px, _dev(gamma, torch.float32, "gamma"), pgi, pgo,
+                                                    _dev(idx, torch.int32, "idx"), K, no, pdg, pdb, int(accumulate), pws, nws, M, D, eps,
+                                                    _stream()), "tr_layernorm_bwd_scatter_add")
+        return g, None, dgamma, dbeta
+    _lib.check(lib.tr_layernorm_bwd(_dev(dy, torch.bfloat16, "dy"), px, ldx, _dev(gamma, torch.float32, "gamma"), pgi, ldgi, pgo, sgo,
+                                    None if gbuf is None else gbuf.data_ptr(), _opt(idx, torch.int32, "idx"), K, n_in,
+                                    no, None if g_fused is None else g_fused.data_ptr(), pdg, pdb, int(accumulate),
+                                    pws, nws, M, D, eps, _stream()), "tr_layernorm_bwd")
     if idx is not None and fused:
-        return g, gb, dgamma, dbeta, g_fused
-    return g, gb, dgamma, dbeta
+        return g, gbuf, dgamma, dbeta, g_fused
+    return g, gbuf, dgamma, dbeta
 
 
 def attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, B: int, N: int, H: int, size: torch.Tensor = None, dcls: torch.Tensor = None):
@@ -1057,10 +1101,16 @@ def linear_bwd_params2(dy0: torch.Tensor, x0: torch.Tensor, dy1: torch.Tensor, x
     return (outs[0], outs[1]), (outs[2], outs[3])
 
 
-def linear_bwd_group(layers, accumulate: bool = False, outs=None):
+def linear_bwd_group_workspace_floats(shapes) -> int:
+    """Workspace floats tr_linear_bwd_group wants for layers of the given (M, N, K)."""
+    arr = (_lib.TrLinearGrad * len(shapes))(*[_lib.TrLinearGrad(None, N, None, K, None, None, M, N, K) for M, N, K in shapes])
+    return int(_lib.load().tr_linear_bwd_group_workspace_floats(ctypes.cast(arr, ctypes.c_void_p), len(shapes)))
+
+
+def linear_bwd_group(layers, accumulate: bool = False, outs=None, ws: torch.Tensor = None, ws_floats: int = None):
     """Weight and bias gradients of up to four Linear layers in ONE weight-gradient launch + one reduce (tr_linear_bwd_group).
-    layers: [(dy bf16 [M_i, N_i], x bf16 [M_i, K_i]), ...]; returns [(dW_i fp32 [N_i, K_i], db_i fp32 [N_i]), ...]; outs: the same list
-    of destination tensors when accumulating."""
+    layers: [(dy bf16 [M_i, N_i], x bf16 [M_i, K_i]), ...] (row-strided column slices allowed); returns [(dW_i fp32 [N_i, K_i],
+    db_i fp32 [N_i]), ...]; outs: the same list of destination tensors when accumulating."""
     lib = _lib.load()
     n = len(layers)
     if not 1 <= n <= 4:
@@ -1072,10 +1122,10 @@ def linear_bwd_group(layers, accumulate: bool = False, outs=None):
     for i, ((dy, x), (dw, db)) in enumerate(zip(layers, outs)):
         if dy.shape[0] != x.shape[0] or tuple(dw.shape) != (dy.shape[1], x.shape[1]) or db.numel() != dy.shape[1]:
             raise ValueError(f"linear_bwd_group: layer {i}: dy {tuple(dy.shape)}, x {tuple(x.shape)}, dw {tuple(dw.shape)}, db {tuple(db.shape)} do not fit")
-        arr[i] = _lib.TrLinearGrad(_dev(dy, torch.bfloat16, "dy"), dy.shape[1], _dev(x, torch.bfloat16, "x"), x.shape[1], _dev(dw, torch.float32, "dw"),
-                                   _dev(db, torch.float32, "db"), dy.shape[0], dy.shape[1], x.shape[1])
-    ws = _ws(lib.tr_linear_bwd_group_workspace_floats(ctypes.cast(arr, ctypes.c_void_p), n), dev)
-    _lib.check(lib.tr_linear_bwd_group(ctypes.cast(arr, ctypes.c_void_p), n, int(accumulate), ws.data_ptr(), ws.numel(), _stream()), "tr_linear_bwd_group")
+        (py, ldy), (px, ldx) = _rows(dy, torch.bfloat16, "dy"), _rows(x, torch.bfloat16, "x")
+        arr[i] = _lib.TrLinearGrad(py, ldy, px, ldx, _dev(dw, torch.float32, "dw"), _dev(db, torch.float32, "db"), dy.shape[0], dy.shape[1], x.shape[1])
+    ws, pws, nws = _ws_arg(ws, ws_floats, lib.tr_linear_bwd_group_workspace_floats(ctypes.cast(arr, ctypes.c_void_p), n), dev)
+    _lib.check(lib.tr_linear_bwd_group(ctypes.cast(arr, ctypes.c_void_p), n, int(accumulate), pws, nws, _stream()), "tr_linear_bwd_group")
     return outs
 
 
