@@ -70,6 +70,16 @@ int tr_patch_embed_supported(int C, int HW, int patch, int D);
 int tr_patch_embed_bf16(const float* img, const uint16_t* W, const float* bias, const float* cls_token, const float* pos_embed, float* x,
                         int B, int C, int HW, int patch, int D, tr_stream_t s);
 
+/* PatchEmbed's data gradient (the gradient of the stride-16 Conv2d with respect to the image): for patch p = (py, px) of image b
+ *   dx[b, c, 16 py + iy, 16 px + ix] = sum_k dY[(b, p), k] * W[k, (c, iy, ix)]
+ * dY bf16 token rows at row stride ldy (elements): row (b, p) is dY + (b (P+1) + 1 + p) ldy -- the yskip = P convention of tr_wgrad_bf16,
+ * the CLS row of every image is never read; Wt bf16 [C*16*16, D] = the patch weight TRANSPOSED; dx fp32 [B, C, HW, HW].  fp32
+ * accumulation on the bf16 MFMA path in one fixed order; every element of dx is written exactly once (patches do not overlap): no memset,
+ * no atomics, no accumulate flag.  tr_patch_embed_dgrad_supported: patch 16, HW % 16 == 0 (up to 4096), C = 1 or 3, D = 128, 192, 384 or 768;
+ * anything else is TR_ERR_SHAPE. */
+int tr_patch_embed_dgrad_supported(int C, int HW, int patch, int D);
+int tr_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int HW, int patch, int D, tr_stream_t s);
+
 /* Raw uint8 pixels: img uint8 [B,C,H,W] (layout TR_LAYOUT_NCHW) or [B,H,W,C] (TR_LAYOUT_NHWC), 16-byte aligned; lut fp32 [C][256] is the
  * normalized value of every pixel value, lut[c][v] = (v / 255 - mean[c]) / std[c] computed by the host (torchvision's ToTensor + Normalize
  * order).  The kernels only gather from it: their output is bitwise what the fp32 entry points give for the normalized image.
@@ -695,7 +705,16 @@ int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, con
  *   that starts below block i returns TR_OK without a launch; with no block unit at all only the classifier step (and a present final
  *   norm) runs.  A block above the stop block is walked in full whatever is frozen in it.  Stage modules (grads->stage[i]) are not
  *   skipped one by one: a stage the walk reaches needs every pointer its family writes (TR_ERR_NULL otherwise, before any launch); a
- *   stage may be all NULL only at or below the stop block.  With nothing NULL the launch sequence is unchanged. */
+ *   stage may be all NULL only at or below the stop block.  With nothing NULL the launch sequence is unchanged.
+ * tr_vit_backward_dx: tr_vit_backward plus the gradient with respect to the INPUT image, dx fp32 [B, in_chans, img, img] (nullable: with
+ *   dx == NULL the call IS tr_vit_backward).  For the fp32 image of tr_vit_forward_train only (uint8 pixels and augmented batches have no
+ *   gradient).  With dx the walk never stops early: it goes down to the embedding whatever is frozen -- every unit may be NULL (a fully
+ *   frozen model: an adversarial step on fixed weights), but the stage pointers of EVERY reduction stage are then required (TR_ERR_NULL
+ *   otherwise).  wt->patch_w = the patch weight transposed, bf16 [in_chans*patch*patch, D] (TR_ERR_NULL when missing); shapes are those of
+ *   tr_patch_embed_dgrad (TR_ERR_SHAPE before any launch otherwise).  The one extra launch, tr_patch_embed_dgrad on the bf16 gradient of
+ *   the embedded stream (after pos_drop's mask), runs in the call whose blk_lo == 0, beside the embedding gradients; the other range
+ *   calls of a pass take the same dx (so that they walk the same blocks) and do not touch it.  dx is overwritten, never accumulated
+ *   into; no workspace beyond tr_vit_backward_workspace_bytes. */
 size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B);
 int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
                          size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, float* features_out,
@@ -744,6 +763,10 @@ int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_
                     const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape,
                     size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
                     tr_stream_t s, const uint8_t* dropout_keep, float drop_rate);
+int tr_vit_backward_dx(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                       const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape,
+                       size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                       tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx);
 
 #ifdef __cplusplus
 }

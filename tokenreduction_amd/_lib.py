@@ -89,6 +89,8 @@ SIGNATURES = {
     "tr_cls_pos_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tr_patch_embed_supported": (_i, [_i, _i, _i, _i]),
     "tr_patch_embed_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tr_patch_embed_dgrad_supported": (_i, [_i, _i, _i, _i]),
+    "tr_patch_embed_dgrad": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_aug_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -180,6 +182,8 @@ SIGNATURES = {
     "tr_vit_backward_workspace_bytes": (_sz, [C.POINTER(TrVitConfig), _i]),
     "tr_vit_backward": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), _vp, _vp, _vp,
                              _vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _f]),
+    "tr_vit_backward_dx": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), _vp, _vp, _vp,
+                                _vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _f, _vp]),
     "tr_rowscale_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tr_reduce_partials_f32": (_i, [_vp, _i, _sz, _vp, _i, _vp]),
     "tr_pool_policy": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),

@@ -138,7 +138,8 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 }
 
 // wt: the weight MATRICES transposed (bf16): blocks[i].qkv_w = qkv.weight^T [D,3D], proj_w = proj.weight^T [D,D], fc1_w = fc1.weight^T
-//     [D,Hd], fc2_w = fc2.weight^T [Hd,D]; other fields unused.  w: the forward's weights (head_w and the LayerNorm gammas are read).
+//     [D,Hd], fc2_w = fc2.weight^T [Hd,D]; patch_w = the patch weight^T [in_chans*patch*patch, D], read by tr_vit_backward_dx only; other fields
+//     unused.  w: the forward's weights (head_w and the LayerNorm gammas are read).
 // grads: same layout as tr_vit_weights, every pointer an fp32 gradient buffer of the parameter's shape (matrices included).
 // Frozen parameters: a UNIT of grads may be NULL (both pointers, never one) and its gradient work is left out -- {head_w, head_b},
 //     {norm_g, norm_b}, per block {ln1_g, ln1_b} {qkv_w, qkv_b} {proj_w, proj_b} {ln2_g, ln2_b} {fc1_w, fc1_b} {fc2_w, fc2_b},
@@ -157,10 +158,14 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 // DyViT only: dpred (nullable) fp32 [stages, B, P]: gradient wrt each stage's out_pred_prob (the ratio loss, losses.py:113-118), stages in
 // block order; dfeat (nullable) fp32 [B, N0, D]: gradient wrt the final-norm token features (distillation, losses.py:134-156; row 0 = 0).  The gradient of the residual stream stays in the
 // workspace between calls, so a backward pass is the calls (depth-1 .. a), (a-1 .. b), ..., (c .. 0) in this order.
-extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
-                               const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
-                               size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
-                               tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+// dx (nullable): the gradient with respect to the input image, fp32 [B, in_chans, img, img] (tr_vit_backward_dx).  With dx the walk goes all the
+// way down whatever is frozen (stop = -1: a fully frozen model is valid, the stage pointers are required everywhere), and the call with
+// blk_lo == 0 ends with one more launch: tr_patch_embed_dgrad on gb (after pos_drop's mask) and wt->patch_w = the patch weight transposed.
+namespace {
+int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                 const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                 size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                 tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
   TR_REQUIRE(cfg && w && wt && grads && dlogits && tape_ && workspace, TR_ERR_NULL, "tr_vit_backward: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_backward: dropout needs the forward's keep mask AND its drop_rate (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
@@ -183,7 +188,14 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
              "tr_vit_backward: a gradient unit (head, norm, pos_embed + cls_token, patch) is half NULL: both pointers or neither");
   // stop: block i whose own parameter gradients end the walk (nothing below it takes a gradient); depth: no block takes one; -1: the
   // embedding does, the walk goes all the way
-  int stop = (u_embed || u_patch) ? -1 : cfg->depth;
+  int stop = (u_embed || u_patch || dx != nullptr) ? -1 : cfg->depth;
+  if (dx != nullptr) {
+    TR_REQUIRE(wt->patch_w != nullptr, TR_ERR_NULL, "tr_vit_backward_dx: wt->patch_w (the patch weight transposed) is NULL");
+    TR_REQUIRE(tr_patch_embed_dgrad_supported(cfg->in_chans, cfg->img_size, cfg->patch, cfg->embed_dim), TR_ERR_SHAPE,
+               "tr_vit_backward_dx: no input gradient for in_chans %d, img_size %d, patch %d, embed_dim %d (tr_patch_embed_dgrad)", cfg->in_chans,
+               cfg->img_size, cfg->patch, cfg->embed_dim);
+    TR_REQUIRE(tr_aligned16(dx), TR_ERR_ALIGN, "tr_vit_backward_dx: dx must be 16-byte aligned");
+  }
   for (int i = 0; i < cfg->depth; ++i) {
     const tr_block_weights& b = grads->blocks[i];
     const int u[6] = {unit(b.ln1_g, b.ln1_b), unit(b.qkv_w, b.qkv_b), unit(b.proj_w, b.proj_b),
@@ -537,5 +549,24 @@ extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w
   }
   if (u_embed) TR_TRY(tr_embed_bwd(g, F(grads->pos_embed), F(grads->cls_token), acc, B, t.N0, D, s));
   if (u_patch) TR_TRY(tr_linear_bwd_params(gb, D, t.P, U(tape + tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
+  // the input gradient: the patch projection's data gradient, folded back into the image (every element of dx written once)
+  if (dx != nullptr) TR_TRY(tr_patch_embed_dgrad(gb, D, U(wt->patch_w), dx, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
   return TR_OK;
+}
+}  // namespace
+
+extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                               const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                               size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                               tr_stream_t s, const uint8_t* dropout_keep, float drop_rate) {
+  return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
+                      s, dropout_keep, drop_rate, nullptr);
+}
+
+extern "C" int tr_vit_backward_dx(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                                  const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                                  size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                                  tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
+  return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
+                      s, dropout_keep, drop_rate, dx);
 }

@@ -269,7 +269,7 @@ class VisionTransformer(nn.Module):
         gradient buffer, noise buffers, side streams), at its empty value: state of THIS object's executor, rebuilt on demand.  This is
         their one declaration -- __init__ starts from it and a copy does (__deepcopy__); settings (precision, use_graph, viz_mode,
         pixel_input, the keep schedule, ...) are not in here."""
-        self._packed = None              # _pack(): dict(key, W, cfg, keep_alive, gen, tblocks)
+        self._packed = None              # _pack(): dict(key, W, cfg, keep_alive, gen, tblocks, tpatch)
         self._ws = {}                    # _workspace(): {B or (B, slot): dict(buf, nbytes, kept, compl, soft, feat, graphs, ...)}
         self._last_ws = None             # workspace and per-block token counts of the last forward
         self._last_tokens = None
@@ -417,7 +417,7 @@ class VisionTransformer(nn.Module):
         lib = _lib.load()
         mlp_pk_bytes = int(lib.tr_mlp_pack_bytes(D, Hd)) if lib.tr_mlp_fused_supported(D, Hd) else 0
         mlp_items = []
-        W.patch_w = pk.w16(self.patch_embed.proj.weight.reshape(D, -1))
+        W.patch_w, tpatch = pk.w16(self.patch_embed.proj.weight.reshape(D, -1), True)      # (tpatch: the input gradient's operand, training.py)
         W.patch_b = pk.f32(self.patch_embed.proj.bias)
         W.cls_token = pk.f32(self.cls_token.reshape(-1))
         W.pos_embed = pk.f32(self.pos_embed.reshape(-1, D))
@@ -472,7 +472,8 @@ class VisionTransformer(nn.Module):
             cfg.keep[i] = int(self._keep[i])
         old = self._packed
         gen = 1 if old is None else old.get("gen", 0) + 1
-        self._packed = dict(key=key, W=W, cfg=cfg, keep_alive=pk.keep_alive, gen=gen, tblocks=tblocks if want_t else None)
+        self._packed = dict(key=key, W=W, cfg=cfg, keep_alive=pk.keep_alive, gen=gen, tblocks=tblocks if want_t else None,
+                            tpatch=tpatch)
         self._weights_dirty = False
         # workspaces and captured graphs hold the operand addresses: they survive a repack unless a buffer had to be (re)allocated or the
         # configuration changed (first pack, precision switch, new head, new keep schedule)

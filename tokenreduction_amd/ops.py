@@ -748,6 +748,26 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor = None, accumulat
     return out
 
 
+def patch_embed_dgrad(dy: torch.Tensor, wt: torch.Tensor, B: int, C: int, HW: int, patch: int = 16, out: torch.Tensor = None) -> torch.Tensor:
+    """PatchEmbed's data gradient folded back into the image (tr_patch_embed_dgrad): dy bf16 token rows [B * (P + 1), D] (or a column slice
+    of a wider tensor; the CLS row of every image is never read), wt bf16 [C*patch*patch, D] = the patch weight transposed -> dx fp32
+    [B, C, HW, HW], every element written exactly once.  An unsupported shape raises."""
+    D = wt.shape[-1]
+    if out is None:
+        out = torch.empty(B, C, HW, HW, dtype=torch.float32, device=dy.device)
+    _same_device(dy, wt, out)
+    pdy, ldy = _rows(dy, torch.bfloat16, "dy")
+    if wt.dim() != 2 or wt.shape[0] != C * patch * patch:
+        raise ValueError(f"wt: expected [{C * patch * patch}, D] (the patch weight transposed), got {tuple(wt.shape)}")
+    if dy.dim() != 2 or dy.shape[1] != D or patch <= 0 or HW % patch or dy.shape[0] != B * ((HW // patch) ** 2 + 1):
+        raise ValueError(f"dy: expected token rows [B * (P + 1), {D}] for B = {B}, HW = {HW}, patch = {patch}, got {tuple(dy.shape)}")
+    if out.shape != (B, C, HW, HW):
+        raise ValueError(f"out: expected {(B, C, HW, HW)}, got {tuple(out.shape)}")
+    _lib.check(_lib.load().tr_patch_embed_dgrad(pdy, ldy, _dev(wt, torch.bfloat16, "wt"), _dev(out, torch.float32, "out"), B, C, HW, patch, D,
+                                                _stream(dy)), "tr_patch_embed_dgrad")
+    return out
+
+
 def linear_bwd_params(dy: torch.Tensor, x: torch.Tensor, accumulate: bool = False, dw: torch.Tensor = None, db: torch.Tensor = None,
                       yskip: int = 0, ws: torch.Tensor = None, ws_floats: int = None):
     """Weight and bias gradient of an nn.Linear in one pass (tr_linear_bwd_params): (dW fp32 [N,K], db fp32 [N]).  yskip > 0: dy holds one

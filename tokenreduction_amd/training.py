@@ -9,6 +9,9 @@ data-parallel reducer can all-reduce contiguous slices in place while the rest o
 (dp.FlatGradReducer) -- no flatten/unflatten copies.
 Frozen parameters (requires_grad False) cost no gradient work: a unit whose parameters are all frozen reaches the executor as NULL
 pointers, and the backward stops at the lowest block that still has a trainable parameter at or below it (TrainState.grads_struct).
+The input takes a gradient like any autograd leaf: when `x.requires_grad` is set (or a module in front of the model trains) the
+backward runs `tr_vit_backward_dx`, which walks down to the embedding whatever is frozen and folds the patch projection's data gradient
+back into the image; the node returns it in x's slot and autograd accumulates `x.grad`.  Eval mode is not differentiable.
 
 PyTorch is plumbing: memory, the stream, the autograd hook and the loss.  No arithmetic of the model happens in torch.
 """
@@ -93,12 +96,14 @@ class TrainState:
         del names
         return out
 
-    def grads_struct(self, model):
+    def grads_struct(self, model, want_dx=False):
         """tr_vit_weights-shaped struct whose pointers are the gradient views, read off `requires_grad` as it is NOW (built per
         backward, nothing cached).  A unit of tr_vit_backward (the two gradients one launch produces) whose parameters are all frozen
         is NULL: the executor leaves its work out.  A mixed unit (pos_embed trainable, cls_token frozen) keeps both pointers; the frozen
         half lands in its slot of the flat buffer and is discarded.  The pointers of a family's reduction stage are NULL only where
         the backward never arrives: below the lowest block that has a trainable parameter at or below it.
+        want_dx: the input takes a gradient, so the backward goes all the way whatever is frozen (the floor is -1): every reduction stage is
+        reached and keeps its pointers, a frozen stage parameter's slice is computed and discarded.
         Returns (struct, names of the frozen parameters the executor still writes)."""
         G = _lib.TrVitWeights()
         v = self.views
@@ -150,6 +155,8 @@ class TrainState:
                 floor = -1
             else:
                 floor = min(floor, at.get(n, 0))
+        if want_dx:
+            floor = -1
         for loc, names in stage_names.items():
             if loc < floor or (loc == floor and not any(named[n].requires_grad for n in names)):
                 for f in _STAGE_PTRS:
@@ -175,6 +182,8 @@ class TrainState:
         for i, (tq, tp_, t1, t2) in enumerate(pk["tblocks"]):
             b = WT.blocks[i]
             b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w = tq.data_ptr(), tp_.data_ptr(), t1.data_ptr(), t2.data_ptr()
+        if pk.get("tpatch") is not None:      # the patch weight transposed [C*p*p, D]: the operand of the input gradient (tr_vit_backward_dx)
+            WT.patch_w = pk["tpatch"].data_ptr()
         model._transposed_stage_weights(WT, t16)
         self.wt, self.wt_keep, self.key = WT, keep, pk["gen"]
         return WT
@@ -281,11 +290,22 @@ class _VitTrainFn(torch.autograd.Function):
     [B,P] (straight-through differentiable, dyvit.py:223-225), features = the final norm of the patch tokens [B,P,D]."""
 
     @staticmethod
-    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None):
+    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None, xe=None):
         lib = _lib.load()
         pk = model._pack(need_transposed=True)
         cfg = pk["cfg"]
         B = x.shape[0]
+        # the input gradient is computed only when autograd wants it, and only for the fp32 image (uint8 pixels and augmented batches cannot
+        # require one); the executor reads xe, train_forward's detached fp32 contiguous copy of the caller's tensor (made once)
+        ctx.want_dx = bool(ctx.needs_input_grad[1]) and fmt == _lib.TR_INPUT_F32 and aug is None
+        ctx.x_dtype = x.dtype
+        if ctx.want_dx and not lib.tr_patch_embed_dgrad_supported(cfg.in_chans, cfg.img_size, cfg.patch, cfg.embed_dim):
+            raise NotImplementedError(
+                f"{type(model).__name__}: the input requires a gradient, but the input gradient is built for patch 16, 1 or 3 channels and "
+                f"embed_dim 128 / 192 / 384 / 768 (got patch {cfg.patch}, in_chans {cfg.in_chans}, embed_dim {cfg.embed_dim}); "
+                "detach the input to train the parameters alone")
+        if xe is not None:          # the executor's tensor of train_forward: x is the caller's own, here only for autograd
+            x = xe
         st = model._train_state()
         tape, bws = st.buffers(model, pk, B, x.device)
         st.gen += 1
@@ -370,7 +390,7 @@ class _VitTrainFn(torch.autograd.Function):
         train = [(n, p) for n, p in st.order if p.requires_grad]
         fresh = [n for n, p in train if p.grad is None or p.grad.data_ptr() != st.views[n].data_ptr()]
         accumulate = 0 if len(fresh) == len(train) else 1
-        G, discarded = st.grads_struct(model)
+        G, discarded = st.grads_struct(model, want_dx=ctx.want_dx)
         if accumulate:
             for n in fresh + discarded:          # (a discarded slice is cleared so that it cannot grow without bound over the steps)
                 st.views[n].zero_()
@@ -383,12 +403,16 @@ class _VitTrainFn(torch.autograd.Function):
         if reduce_now:
             reducer.begin(st.flat) if hasattr(reducer, "begin") else setattr(reducer, "launched", [])
         stream = torch.cuda.current_stream().cuda_stream
+        # the input gradient (x.requires_grad, or something learnable in front of the model): every range call takes dx so that all of them
+        # walk down to the embedding whatever is frozen; only the call with lo == 0 writes it -- once, in full: autograd accumulates x.grad
+        dx = torch.empty(ctx.keep[0].shape, dtype=torch.float32, device=dev) if ctx.want_dx else None
         with torch.cuda.device(dl.device):
             for hi, lo, start, stop in ranges:
-                rc = lib.tr_vit_backward(C.byref(pk["cfg"]), C.byref(pk["W"]), C.byref(WT), C.byref(G), dl.data_ptr(),
-                                         None if dpred is None else dpred.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
-                                         None if ctx.drop is None else ctx.drop.data_ptr(), st.tape.data_ptr(), st.tape.numel(), st.bws.data_ptr(), st.bws.numel(), accumulate, hi, lo, B, stream,
-                                         None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(), float(model.drop_rate or 0.0))
+                args = (C.byref(pk["cfg"]), C.byref(pk["W"]), C.byref(WT), C.byref(G), dl.data_ptr(),
+                        None if dpred is None else dpred.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
+                        None if ctx.drop is None else ctx.drop.data_ptr(), st.tape.data_ptr(), st.tape.numel(), st.bws.data_ptr(), st.bws.numel(), accumulate, hi, lo, B, stream,
+                        None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(), float(model.drop_rate or 0.0))
+                rc = lib.tr_vit_backward(*args) if dx is None else lib.tr_vit_backward_dx(*args, dx.data_ptr())
                 _lib.check(rc, "tr_vit_backward")
                 if reduce_now:
                     reducer.reduce_slice(st.flat, start, stop)
@@ -404,7 +428,9 @@ class _VitTrainFn(torch.autograd.Function):
         was_dirty = model._weights_dirty
         model.weights_changed()          # an optimizer step follows; fused optimizers do not bump the version counters the pack cache reads
         model._dirty_by_backward = not was_dirty      # dirt that was there before this backward is somebody else's: only a full repack clears it
-        return None, None, None, None, None, None
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return None, dx, None, None, None, None, None
 
 
 def train_forward(model, x: torch.Tensor) -> torch.Tensor:
@@ -422,9 +448,15 @@ def train_forward(model, x: torch.Tensor) -> torch.Tensor:
             raise ValueError(f"the batch normalizes with (mean, std) = {x.mean_std}, the model with {model.pixel_input}: "
                              "give DeviceAugment the mean and std of model.set_pixel_input")
         aug, x = (x.table, x.noise), x.pixels
-    x, fmt, lut = model._executor_input(x)
-    anchor = torch.empty(0, dtype=torch.float32, device=x.device, requires_grad=True)
-    out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug)
+    xe, fmt, lut = model._executor_input(x)
+    # an fp32-format input that takes a gradient goes through autograd as the caller's own tensor (x.grad, a module in front of the model);
+    # anything else -- uint8 pixels, an augmented batch, an input without requires_grad, torch.no_grad() -- as the executor's detached
+    # tensor, as before
+    anchor = torch.empty(0, dtype=torch.float32, device=xe.device, requires_grad=True)
+    if fmt == _lib.TR_INPUT_F32 and aug is None and x.requires_grad and torch.is_grad_enabled():
+        out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug, xe)
+    else:
+        out = _VitTrainFn.apply(anchor, xe, model, fmt, lut, aug)
     if model._family != _lib.TR_FAMILY_DYVIT:
         return out
     # dyvit.py:257-261: (x, features, prev_decision.detach(), out_pred_prob) with the DyViT distillation scheme, else (x, out_pred_prob)
