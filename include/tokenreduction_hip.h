@@ -221,6 +221,17 @@ int tr_layernorm_bf16_f32(const float* x, long ldx, float* x_out, long ldxo, con
 /* out[i] = x[i] + delta[i] for n elements (delta nullable; bf16, fp32 when delta_is_f32): the residual stream after a block as
  * the reference's viz_data["Features"] records it (topk.py:197) -- x itself absorbs the pending mlp output only in the next norm. */
 int tr_residual_snapshot(const float* x, const void* delta, int delta_is_f32, float* out, size_t n, tr_stream_t s);
+/* Output taps (tr_vit_forward_taps; csrc/tr_taps.hip).  The pending operands are bf16 rows, fp32 when delta_is_f32; d1 and d2 nullable (d2
+ * needs d1); D % 4 == 0, D <= 1024; every stride in elements, % 4 == 0 and >= D.  The sums are fp32 additions in this order: the value
+ * tr_residual_snapshot stores behind a norm that wrote x + d1 back, bit for bit.
+ * tr_cls_tap: out[b] = (x[b] + d1[b]) + d2[b] for B rows of D.  x rows at stride ldx (the CLS rows of a [B,N,D] stream: N * D), d1 / d2 at ld1 /
+ * ld2 (N * D, or D for the compact buffers of the CLS tail), out rows at ldo (n_blocks * D: the taps of one image are contiguous).
+ * tr_final_tokens_f32: y[row] = LayerNorm((x[row] + d1[row]) + d2[row]) over contiguous fp32 rows [M,D] with tr_layernorm_f32's arithmetic:
+ * tr_residual_snapshot followed by tr_layernorm_f32 in one launch and one pass; x is not written. */
+int tr_cls_tap(const float* x, long ldx, const void* d1, long ld1, const void* d2, long ld2, int delta_is_f32, float* out, long ldo, int B,
+               int D, tr_stream_t s);
+int tr_final_tokens_f32(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* gamma, const float* beta, float* y,
+                        int M, int D, float eps, tr_stream_t s);
 /* dst fp32 [B,N] = src fp32 [N] in every row (the Heuristic family's per-block key mask, heuristic.py:247-258). */
 int tr_broadcast_rows(const float* src, float* dst, int B, int N, tr_stream_t s);
 
@@ -676,6 +687,30 @@ int tr_vit_forward(const tr_vit_config* cfg, const tr_vit_weights* w, const floa
 int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
                           float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                           const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s);
+
+/* Output taps: a caller-chosen subset of the residual stream, written by the eval forward while it runs (fp32, device memory).
+ *   cls_blocks        bit i set: the CLS row of the stream after block i -- x plus the residuals still pending there, the value
+ *                     features_out holds in row 0 of that block, bit for bit
+ *   cls_out           fp32 [B, n, D], n = number of set bits, ascending block order (required when cls_blocks != 0)
+ *   final_tokens_out  (nullable) fp32 [B, N_last, D]: the final norm of EVERY row after the last block, in fp32 arithmetic
+ *                     (tr_final_tokens_f32) -- norm(x) of the DyViT teacher, dyvit.py:325-334
+ * tr_vit_forward_taps / tr_vit_forward_pixels_taps are tr_vit_forward / tr_vit_forward_pixels with that struct.  A CLS tap changes nothing
+ * else about the launch sequence: lazy norms and the CLS tail stay (the last block's tap reads the tail's compact buffers).  final_tokens_out
+ * needs every row of the last block, so the last block runs full width, as under features_out; nothing else changes.  With no tap asked for
+ * (cls_blocks == 0, final_tokens_out == NULL) the launches are those of tr_vit_forward.  A bit at or above depth, cls_blocks without
+ * cls_out, or taps together with features_out: TR_ERR_CONFIG.  Eval only. */
+typedef struct {
+  uint32_t cls_blocks;
+  float* cls_out;
+  float* final_tokens_out;
+} tr_vit_taps;
+int tr_vit_forward_taps(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
+                        size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out, const float* noise_in,
+                        float* features_out, int* tokens_out, int B, tr_stream_t s, const tr_vit_taps* taps);
+int tr_vit_forward_pixels_taps(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                               float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx,
+                               float* soft_out, const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s,
+                               const tr_vit_taps* taps);
 
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and

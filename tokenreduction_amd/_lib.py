@@ -47,6 +47,10 @@ class TrVitConfig(C.Structure):
                 ("kmed_init", _i * TR_MAX_DEPTH), ("ats_dynamic", _i), ("concurrent", _i)]
 
 
+class TrVitTaps(C.Structure):        # tr_vit_taps: the output taps of tr_vit_forward_taps
+    _fields_ = [("cls_blocks", C.c_uint32), ("cls_out", _vp), ("final_tokens_out", _vp)]
+
+
 class TrAugmentRec(C.Structure):     # tr_augment_rec: one image of the device-side erase / mixup / cutmix table (64 bytes)
     _fields_ = [("kind", C.c_int32), ("lam", _f), ("oml", _f), ("yl", C.c_int32), ("yh", C.c_int32), ("xl", C.c_int32), ("xh", C.c_int32),
                 ("erased", C.c_int32), ("ey", C.c_int32), ("eh", C.c_int32), ("ex", C.c_int32), ("ew", C.c_int32), ("noise_off", C.c_int64),
@@ -200,6 +204,12 @@ SIGNATURES = {
                             C.POINTER(_i), _i, _vp]),
     "tr_vit_forward_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                    C.POINTER(_i), _i, _vp]),
+    "tr_vit_forward_taps": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                 C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
+    "tr_vit_forward_pixels_taps": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                        C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
+    "tr_cls_tap": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _i, _vp]),
+    "tr_final_tokens_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "tr_vit_forward_train_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
                                          C.POINTER(_i), _i, _vp, _vp, _f]),
     "tr_vit_forward_train_aug": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,

@@ -244,6 +244,12 @@ struct Fwd {
   float* soft_out;              // soft assignments of the stages, written back to back
   const uint8_t* drop_keep;     // Dropout keep masks, consumed in the order tr_vit_dropout_mask_bytes documents
   float* features_out;          // eval: the stream after every block, back to back; training: DyViT's distillation output
+  // output taps (eval, tr_vit_forward_taps): the CLS rows after the blocks of tap_mask go to cls_out [B, n_taps, D] (tap_i: the next column),
+  // the final norm of every row to final_tokens_out.  A CLS tap reads what is there -- it switches nothing off; final_tokens_out needs every
+  // row of the last block and so keeps it full width (begin_block)
+  uint32_t tap_mask = 0;
+  int n_taps = 0, tap_i = 0;
+  float *cls_out = nullptr, *final_tokens_out = nullptr;
   // ---- the block being enqueued (pre_block, begin_block) ------------------------------------------------------------------------------
   bool have_xn = false;         // norm1(x) already in xn (written by a pre-block reducer)
   bool tail = false;            // this block runs as the CLS tail
@@ -254,12 +260,19 @@ struct Fwd {
   Fwd(const tr_vit_config* cfg_, const tr_vit_weights* w_, const Plan& plan, int B_, tr_stream_t s_, void* workspace, char* tape_,
       const trplan::TapePlan* tp_, const void* img_, int input_format_, const float* pixel_lut_, const tr_augment_rec* aug_,
       const float* aug_noise_, long aug_noise_len_, float* logits_, int32_t* kept_idx_, int32_t* compl_idx_, float* soft_out_,
-      const float* noise_in_, float* features_out_, int* tokens_out_, const float* drop_scale_, const uint8_t* drop_keep_, float drop_rate)
+      const float* noise_in_, float* features_out_, int* tokens_out_, const float* drop_scale_, const uint8_t* drop_keep_, float drop_rate,
+      const tr_vit_taps* taps)
       : cfg(cfg_), w(w_), p(plan), B(B_), D(plan.D), H(plan.H), prec(cfg_->precision), s(s_), f32(cfg_->precision != TR_PREC_BF16),
         train(tape_ != nullptr), ws(static_cast<char*>(workspace)), tape(tape_), tp(tp_), img(img_), input_format(input_format_),
         pixel_lut(pixel_lut_), aug_noise(aug_noise_), aug(aug_), aug_noise_len(aug_noise_len_), drop_scale(drop_scale_),
         drop_mul(drop_keep_ != nullptr ? 1.0f / (1.0f - drop_rate) : 1.0f), logits(logits_), kept_idx(kept_idx_), compl_idx(compl_idx_),
         tokens_out(tokens_out_), N(plan.N0), noise_in(noise_in_), soft_out(soft_out_), drop_keep(drop_keep_), features_out(features_out_) {
+    if (taps != nullptr) {
+      tap_mask = taps->cls_blocks;
+      n_taps = __builtin_popcount(tap_mask);
+      cls_out = tap_mask != 0 ? taps->cls_out : nullptr;
+      final_tokens_out = taps->final_tokens_out;
+    }
     lazy_base = !train && !f32 && !lab().ln_eager && features_out == nullptr;
     rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
     conc = (!train && cfg->concurrent) ? 1 : 0;
@@ -669,7 +682,8 @@ struct Fwd {
     // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
     // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
     // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
-    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && K == 0 && r == 0 && Ks == 0 &&
+    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr && K == 0 && r == 0 &&
+           Ks == 0 &&
            drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0 &&
            tr_attention_cls_available() != 0;
     norm2_in_mlp = false;
@@ -721,6 +735,18 @@ struct Fwd {
     pending = d_mlp;
     pending_ld = D;
     if (tokens_out) tokens_out[i] = N;
+    return tap_cls(i);
+  }
+
+  // CLS tap after block i: the CLS rows of x plus what is still pending, in the order the next norm adds it -- (x + attention branch) + mlp
+  // branch, the fp32 additions behind viz_data["Features"][i][:, 0].  Under the CLS tail the pending rows are the compact [B, D] buffers.
+  int tap_cls(int i) {
+    if (cls_out == nullptr || ((tap_mask >> i) & 1u) == 0) return TR_OK;
+    const long ld = (long)N * D, ldp = pending_ld > 0 ? pending_ld : ld;
+    const void* first = pending_attn != nullptr ? pending_attn : pending;
+    const void* second = pending_attn != nullptr ? pending : nullptr;
+    TR_TRY(tr_cls_tap(x, ld, first, ldp, second, ldp, f32 ? 1 : 0, cls_out + (size_t)tap_i * D, (long)n_taps * D, B, D, s));
+    ++tap_i;
     return TR_OK;
   }
 
@@ -879,7 +905,7 @@ struct Fwd {
       features_out += (size_t)M * D;
     }
     if (tokens_out) tokens_out[i] = N;
-    return TR_OK;
+    return tap_cls(i);
   }
 
   // a5: (x += last mlp output and) norm on the CLS rows only (LayerNorm is per-row), then the classifier -- or, headless (C == 0), the
@@ -887,6 +913,13 @@ struct Fwd {
   int final_norm_head() {
     const bool headless = p.C == 0;
     const long ld = (long)N * D, ldd_cls = pending_ld > 0 ? pending_ld : ld;
+    if (final_tokens_out != nullptr) {
+      // norm(x) of every row, in fp32 arithmetic, before the CLS norm below writes the stream's CLS rows: the pending residuals are full width
+      TR_REQUIRE(pending_ld == 0, TR_ERR_CONFIG, "tr_vit_forward: internal: final_tokens_out behind a CLS tail");
+      const void* first = pending_attn != nullptr ? pending_attn : pending;
+      const void* second = pending_attn != nullptr ? pending : nullptr;
+      TR_TRY(tr_final_tokens_f32(x, first, second, f32 ? 1 : 0, w->norm_g, w->norm_b, final_tokens_out, B * N, D, cfg->ln_eps, s));
+    }
     if (train && features_out != nullptr) {
       // DyViT distillation (dyvit.py:252-258): the final norm of EVERY row is an output; the whole stream stays for its backward
       TR_TRY(stream_to(slot(tp->xfin_all), pending, w->norm_g, w->norm_b, xn_shared, cfg->ln_eps));
@@ -913,7 +946,8 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
                             float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
-                            const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0) {
+                            const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
+                            const tr_vit_taps* taps = nullptr) {
   Plan p;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
@@ -924,10 +958,20 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   TR_REQUIRE(input_format == TR_INPUT_F32 || input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
              "tr_vit_forward: input_format %d is not a TR_INPUT_* format", input_format);
   TR_REQUIRE(input_format == TR_INPUT_F32 || pixel_lut != nullptr, TR_ERR_CONFIG, "tr_vit_forward: a uint8 input needs the pixel LUT");
+  if (taps != nullptr && (taps->cls_blocks != 0 || taps->final_tokens_out != nullptr)) {
+    TR_REQUIRE(tape == nullptr, TR_ERR_CONFIG, "tr_vit_forward_taps: output taps are an eval feature");
+    TR_REQUIRE(features_out == nullptr, TR_ERR_CONFIG, "tr_vit_forward_taps: output taps and features_out in one call");
+    TR_REQUIRE(taps->cls_blocks == 0 || taps->cls_out != nullptr, TR_ERR_CONFIG, "tr_vit_forward_taps: cls_blocks 0x%x without cls_out",
+               taps->cls_blocks);
+    TR_REQUIRE(cfg->depth >= 32 || (taps->cls_blocks >> cfg->depth) == 0, TR_ERR_CONFIG,
+               "tr_vit_forward_taps: cls_blocks 0x%x names a block outside 0 ... %d", taps->cls_blocks, cfg->depth - 1);
+    TR_REQUIRE(tr_aligned16(taps->cls_out) && tr_aligned16(taps->final_tokens_out), TR_ERR_ALIGN,
+               "tr_vit_forward_taps: tap buffers must be 16-byte aligned");
+  }
   tr_prof_restart();
 
   Fwd f(cfg, w, p, B, s, workspace, tape, tp, img, input_format, pixel_lut, aug, aug_noise, aug_noise_len, logits, kept_idx, compl_idx, soft_out,
-        noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate);
+        noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate, taps);
 
   // patch_embed -> cat(cls) + pos_embed -> depth x Block -> norm -> x[:,0] -> head, with
   // Block: [stage reducer]; x += attn(norm1(x)); [in-block reducer]; x += mlp(norm2(x))
@@ -979,6 +1023,23 @@ extern "C" int tr_vit_forward_pixels(const tr_vit_config* cfg, const tr_vit_weig
                                      float* soft_out, const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s) {
   return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
                           features_out, tokens_out, B, s, nullptr, nullptr);
+}
+
+extern "C" int tr_vit_forward_taps(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,
+                                   size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out, const float* noise_in,
+                                   float* features_out, int* tokens_out, int B, tr_stream_t s, const tr_vit_taps* taps) {
+  TR_REQUIRE(taps != nullptr, TR_ERR_NULL, "tr_vit_forward_taps: null tr_vit_taps");
+  return vit_forward_impl(cfg, w, img, TR_INPUT_F32, nullptr, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
+                          features_out, tokens_out, B, s, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, 0, taps);
+}
+
+extern "C" int tr_vit_forward_pixels_taps(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format,
+                                          const float* pixel_lut, float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx,
+                                          int32_t* compl_idx, float* soft_out, const float* noise_in, float* features_out, int* tokens_out,
+                                          int B, tr_stream_t s, const tr_vit_taps* taps) {
+  TR_REQUIRE(taps != nullptr, TR_ERR_NULL, "tr_vit_forward_pixels_taps: null tr_vit_taps");
+  return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
+                          features_out, tokens_out, B, s, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, 0, taps);
 }
 
 extern "C" size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B) {

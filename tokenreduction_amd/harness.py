@@ -7,6 +7,7 @@ Mirrors, for the forward (inference) path only:
     timm.utils.accuracy   top-k accuracy in percent   -> accuracy()
     validate.py:163-229   per-image `Stage-{loc}` records, relative -> absolute kept-token composition -> image_records()
     validate.py:26-30, 278-287   NumpyArrayEncoder / write_viz -> write_viz()
+    extract_cls_features.py:113-141   CLS rows after chosen blocks, stacked over the loader -> extract_cls_features()
 
     engine.py:14-114      train_one_epoch()          -> train_one_epoch()  (grad accumulation, clipping, EMA, frozen groups, step-wise LR)
     timm ModelEmaV2       (train.py:399, engine.py:88) -> ModelEma
@@ -102,6 +103,37 @@ def evaluate_multiclass(data_loader: Iterable, model, device) -> Dict[str, float
     for m in meters.values():
         m.synchronize_between_processes(device)
     return {k: m.global_avg for k, m in meters.items()}
+
+
+@torch.no_grad()
+def extract_cls_features(data_loader: Iterable, model, device, blocks: Sequence[int] = (3, 6, 9, 11)) -> Dict[int, np.ndarray]:
+    """extract_cls_features.py:113-141: {block: fp32 [n_images, D]}, the CLS row of the residual stream after each block of `blocks`, the
+    batches stacked in the loader's order (the last one may be short).  The reference reads viz_data["Features"][block][:, 0] of a viz_mode
+    forward; here the rows come from the executor's CLS taps (VisionTransformer.forward_async with cls_blocks: the same bits, a few
+    B x D rows instead of every row of every block, and the forward keeps its graph) with one batch of lookahead as in
+    evaluate_multiclass."""
+    blocks = tuple(int(b) for b in blocks)
+    if hasattr(model, "eval"):
+        model.eval()
+    launch = getattr(model, "module", model).forward_async
+    rows: Dict[int, list] = {b: [] for b in blocks}
+
+    def consume(pending):
+        _, taps = pending.result()
+        cls = _np(taps["cls"])                          # [B, n, D], the columns in taps["blocks"] order (ascending)
+        for col, blk in enumerate(taps["blocks"]):
+            rows[blk].append(cls[:, col])
+
+    prev = None
+    for images, _ in data_loader:
+        cur = launch(images.to(device, non_blocking=True), cls_blocks=blocks)
+        if prev is not None:
+            consume(prev)
+        prev = cur
+    if prev is not None:
+        consume(prev)
+    _check_status(model)
+    return {b: np.vstack(r) if r else None for b, r in rows.items()}
 
 
 class ModelEma:

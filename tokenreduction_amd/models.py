@@ -17,6 +17,8 @@ more than 640 tokens) raises there.  In eval mode every family runs at up to 102
 inputs) in all three precisions; more tokens raise.
 A headless model (num_classes=0 or reset_classifier(0): head = nn.Identity(), deit_viz.py:142,182) returns the fp32 final-normed CLS row
 [B, embed_dim] wherever a classifier returns logits -- eval in all three precisions, viz_mode, forward_async, training and its backward.
+Intermediate outputs of an eval forward: viz_mode (every row of every recorded block, on the host) or the output taps of forward_taps /
+forward_async -- the CLS rows after chosen blocks and the final-normed tokens, fp32 device tensors written while the fast path runs.
 """
 from __future__ import annotations
 
@@ -60,8 +62,9 @@ class _Pending:
             cur = torch.cuda.current_stream()
             cur.wait_event(self._event)
             for t in (self._out if isinstance(self._out, (tuple, list)) else (self._out,)):
-                if torch.is_tensor(t):
-                    t.record_stream(cur)
+                for u in (t.values() if isinstance(t, dict) else (t,)):       # (forward_taps: the taps come as a dict beside the logits)
+                    if torch.is_tensor(u):
+                        u.record_stream(cur)
             self._event = None
         return self._out
 
@@ -208,7 +211,7 @@ class VisionTransformer(nn.Module):
     GRAPH_MISS_LIMIT = GRAPH_CACHE + 1
     pipeline_depth = 2           # side streams (and workspaces) of forward_async
     dynamic_width = False        # ATS only (ATSVisionTransformer)
-    _always_features = False     # the residual stream after every block is recorded outside viz_mode too (VisionTransformerTeacher)
+    _always_features = False     # the residual stream after every block is recorded outside viz_mode too (the teacher's former path: tools/taps_bench.py)
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
@@ -617,7 +620,31 @@ class VisionTransformer(nn.Module):
             return training.train_forward(self, x)
         return self._forward_eval(x, 0)
 
-    def forward_async(self, x: torch.Tensor):
+    def _tap_request(self, cls_blocks, final_tokens):
+        """(ascending block tuple, bool) of a forward_taps / forward_async call, or the refusal."""
+        if self.training:
+            raise RuntimeError("output taps are an eval feature: call model.eval() first (the training executor has no taps)")
+        if self.viz_mode:
+            raise RuntimeError("output taps and viz_mode are two ways to the same rows: switch viz_mode off (viz_data['Features'] "
+                               "already holds every row of every recorded block)")
+        blocks = tuple(sorted({int(b) for b in (cls_blocks or ())}))
+        if blocks and not (0 <= blocks[0] and blocks[-1] < self.depth):
+            raise ValueError(f"cls_blocks {blocks} names a block outside 0 ... {self.depth - 1}")
+        return blocks, bool(final_tokens)
+
+    def forward_taps(self, x: torch.Tensor, cls_blocks=(3, 6, 9, 11), final_tokens=False):
+        """Eval forward with output taps: (logits, {"cls", "blocks", "final_tokens"}).  taps["cls"] is fp32 [B, n, D]: the CLS row of the
+        residual stream after each block of `cls_blocks` (ascending, listed in taps["blocks"]) -- bit for bit what viz_mode's
+        viz_data["Features"][blk][:, 0] holds (extract_cls_features.py:113-132), None for an empty set.  final_tokens=True adds
+        taps["final_tokens"], fp32 [B, N_last, D]: the final norm of every row after the last block in fp32 arithmetic (norm(x) of the DyViT
+        teacher, dyvit.py:325-334).  The taps stay on the device and the forward stays on the fast path: hipGraph replay, lazy norms and --
+        unless final_tokens asks for every row of the last block -- the CLS tail; the logits are those of model(x).  Refuses train mode,
+        viz_mode and a block index outside 0 ... depth-1."""
+        if isinstance(x, AugmentedBatch):
+            x = x.float()
+        return self._forward_eval(x, 0, self._tap_request(cls_blocks, final_tokens))
+
+    def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False):
         """Eval forward that may run BESIDE the previous one: the call enqueues the forward on one of `pipeline_depth` (default 2) side streams
         -- each with its own workspace and captured hipGraph -- behind everything already enqueued on the caller's current stream, and
         returns a handle at once; `handle.result()` makes the caller's current stream wait for that forward and returns what `model(x)`
@@ -625,10 +652,20 @@ class VisionTransformer(nn.Module):
         (partial last rounds of the persistent GEMM-class kernels, the short launches of the last stage) with the other's: the headline
         forward runs 2.65 -> 2.44 ms per batch of 256 with two in flight (tools/lab/two_stream_full.py).  A data loop uses it with one batch
         of lookahead (harness.evaluate_multiclass does): launch batch k + 1, then consume batch k.  Same kernels, same bits as `model(x)`.
-        Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete)."""
+        Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete).
+        cls_blocks / final_tokens: the output taps of forward_taps -- the result is then what forward_taps returns.  With taps, train mode,
+        viz_mode and dynamic_width are refused instead of run synchronously."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        if self.training or self.viz_mode or self.dynamic_width or not x.is_cuda:
+        taps = None
+        if cls_blocks is not None or final_tokens:
+            taps = self._tap_request(cls_blocks, final_tokens)
+            if not x.is_cuda:
+                raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
+            if self.dynamic_width:
+                raise RuntimeError("forward_async with output taps cannot run under dynamic_width (the executor synchronises mid-forward): "
+                                   "use forward_taps")
+        elif self.training or self.viz_mode or self.dynamic_width or not x.is_cuda:
             return _Pending(self(x), None)
         depth = max(1, int(self.pipeline_depth))
         st = self._pipe_streams
@@ -644,13 +681,13 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(x.device)
         side.wait_stream(cur)                          # inputs and weights are ready where the forward runs
         with torch.cuda.stream(side):
-            out = self._forward_eval(x, slot + 1)
+            out = self._forward_eval(x, slot + 1, taps)
             done = torch.cuda.Event()
             done.record(side)
         x.record_stream(side)
         return _Pending(out, done)
 
-    def _forward_eval(self, x: torch.Tensor, slot: int):
+    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None):
         if not x.is_cuda:
             raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
         lib = _lib.load()
@@ -665,11 +702,22 @@ class VisionTransformer(nn.Module):
         ws = self._workspace(B, x.device, slot)
         if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
             ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
-        want_feat = self.viz_mode or self._always_features
+        want_feat = (self.viz_mode or self._always_features) and taps is None
         if want_feat and ws.get("feat") is None:
             # viz_data["Features"]: the residual stream after every block (upper bound depth * B * N0 * D fp32)
             n0 = self.patch_embed.num_patches + 1
             ws["feat"] = torch.empty(self.depth * B * n0 * self.embed_dim, dtype=torch.float32, device=x.device)
+        tap_arg = None
+        if taps is not None:
+            # static per workspace slot like every other output: the CLS taps [B, n, D] (room for every block), the final tokens [B, N0, D]
+            blocks, want_final = taps
+            D, n0 = self.embed_dim, self.patch_embed.num_patches + 1
+            if blocks and ws.get("tap_cls") is None:
+                ws["tap_cls"] = torch.empty(B * self.depth * D, dtype=torch.float32, device=x.device)
+            if want_final and ws.get("tap_final") is None:
+                ws["tap_final"] = torch.empty(B * n0 * D, dtype=torch.float32, device=x.device)
+            tap_arg = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
+                                     ws["tap_final"].data_ptr() if want_final else None)
         self._noise_slot = slot                      # (a static buffer per workspace slot: two forwards in flight must not share one)
         noise_ptr = self._noise_ptr(B, x.device)
         self._kmed_draws = None
@@ -681,7 +729,11 @@ class VisionTransformer(nn.Module):
             rest = (out.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
                     None if ws.get("soft") is None else ws["soft"].data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
                     torch.cuda.current_stream().cuda_stream)
-            if fmt == _lib.TR_INPUT_F32:
+            if tap_arg is not None and fmt == _lib.TR_INPUT_F32:
+                rc = lib.tr_vit_forward_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest, C.byref(tap_arg))
+            elif tap_arg is not None:
+                rc = lib.tr_vit_forward_pixels_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest, C.byref(tap_arg))
+            elif fmt == _lib.TR_INPUT_F32:
                 rc = lib.tr_vit_forward(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest)
             else:
                 rc = lib.tr_vit_forward_pixels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest)
@@ -692,12 +744,20 @@ class VisionTransformer(nn.Module):
             res = None
             if (self.use_graph and not ws.get("graph_off") and not torch.cuda.is_current_stream_capturing()
                     and not self.dynamic_width):      # (ATS dynamic width: the executor reads a token count back mid-forward)
-                key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width)
+                key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width,
+                       taps)
                 res = self._replay(ws, key, launch, B, x.device)
             logits, tokens = res if res is not None else self._plain_launch(launch, B, x.device)
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
         self._last_tokens = list(tokens)
         self._last_ws = ws
+        if taps is not None:
+            # cloned out of the static buffers in stream order, the way a replay's logits are: the next forward on this slot overwrites them
+            blocks, want_final = taps
+            D, n_last = self.embed_dim, tokens[-1]
+            out = {"cls": ws["tap_cls"][:B * len(blocks) * D].view(B, len(blocks), D).clone() if blocks else None, "blocks": blocks,
+                   "final_tokens": ws["tap_final"][:B * n_last * D].view(B, n_last, D).clone() if want_final else None}
+            return logits, out
         if self.viz_mode:
             viz = self._viz_data(ws, B, list(tokens))
             viz["Features"] = self._features(ws, B, list(tokens))
@@ -1550,20 +1610,15 @@ class VisionTransformerTeacher(VisionTransformer):
     (head(norm(x)[:, 0]), norm(x)[:, 1:]): the logits and the final-norm patch-token features, always as a tuple.  The teacher is
     only ever run under `torch.no_grad()` (losses.py:122-123), so its forward is the inference executor whatever `self.training` says;
     its outputs carry no gradient."""
-    _always_features = True
 
     def forward(self, x):
+        # norm(x) of every row is the executor's final_tokens tap (forward_taps): one launch beside the forward, which keeps its graph
+        # and its lazy norms -- the same bits as the residual stream after the last block pushed through a separate fp32 LayerNorm
         viz, self.viz_mode = self.viz_mode, False
         was_training, self.training = self.training, False          # the module flag only: the teacher has no train-mode behaviour
         try:
-            logits = super().forward(x)
+            logits, taps = self.forward_taps(x, cls_blocks=(), final_tokens=True)
         finally:
             self.viz_mode = viz
             self.training = was_training
-        from . import ops
-        B, N, D = x.shape[0], self._last_tokens[-1], self.embed_dim
-        off = sum(B * n * D for n in self._last_tokens[:-1])
-        x_final = self._last_ws["feat"][off: off + B * N * D]                    # residual stream after the last block
-        feature = ops.layernorm_f32(x_final.view(B * N, D), self.norm.weight.detach().float().contiguous(),
-                                    self.norm.bias.detach().float().contiguous(), float(self.norm.eps)).view(B, N, D)
-        return logits, feature[:, 1:]
+        return logits, taps["final_tokens"][:, 1:]

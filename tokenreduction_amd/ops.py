@@ -466,6 +466,46 @@ def layernorm_f32(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor 
     return y
 
 
+def _pending(d, name):
+    """Pointer of a pending residual operand (bf16 or fp32 rows) or None."""
+    if d is None:
+        return None
+    if d.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"{name}: expected bf16 or fp32, got {d.dtype}")
+    return _dev(d, d.dtype, name)
+
+
+def _pending_f32(d1, d2):
+    if d1 is not None and d2 is not None and d1.dtype != d2.dtype:
+        raise TypeError("the two pending operands must have one dtype")
+    return int(d1 is not None and d1.dtype == torch.float32)
+
+
+def cls_tap(x: torch.Tensor, ldx: int, B: int, D: int, d1: torch.Tensor = None, ld1: int = 0, d2: torch.Tensor = None, ld2: int = 0,
+            out: torch.Tensor = None, ldo: int = None, offset: int = 0) -> torch.Tensor:
+    """out[b] = (x[b] + d1[b]) + d2[b] for B rows of D at their own strides (tr_cls_tap): x fp32 rows at ldx, the pending operands (bf16 or
+    fp32, both nullable) at ld1 / ld2, the destination rows at ldo starting `offset` elements into `out` (fp32; allocated [B, D] if None)."""
+    _same_device(x, d1, d2, out)
+    if out is None:
+        out, ldo, offset = torch.empty(B, D, dtype=torch.float32, device=x.device), D, 0
+    _lib.check(_lib.load().tr_cls_tap(_dev(x, torch.float32, "x"), ldx, _pending(d1, "d1"), ld1, _pending(d2, "d2"), ld2, _pending_f32(d1, d2),
+                                      _dev(out, torch.float32, "out") + 4 * offset, D if ldo is None else ldo, B, D, _stream(x)), "tr_cls_tap")
+    return out
+
+
+def final_tokens_f32(x: torch.Tensor, gamma, beta, eps: float, d1: torch.Tensor = None, d2: torch.Tensor = None) -> torch.Tensor:
+    """y = LayerNorm((x + d1) + d2) over fp32 rows [M, D] in fp32 arithmetic, one pass (tr_final_tokens_f32): d1 / d2 bf16 or fp32 rows
+    [M, D], both nullable; x is not written.  Bit for bit layernorm_f32 of the fp32 sums."""
+    _same_device(x, d1, d2, gamma, beta)
+    D = x.shape[-1]
+    M = x.numel() // D
+    y = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().tr_final_tokens_f32(_dev(x, torch.float32, "x"), _pending(d1, "d1"), _pending(d2, "d2"), _pending_f32(d1, d2),
+                                               _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps,
+                                               _stream(x)), "tr_final_tokens_f32")
+    return y
+
+
 def attention_f32(qkv: torch.Tensor, B: int, N: int, H: int, want_cls: bool = False, size: torch.Tensor = None,
                   colsum_part: torch.Tensor = None, split: bool = False):
     out = torch.empty(B * N, H * 64, dtype=torch.float32, device=qkv.device)
