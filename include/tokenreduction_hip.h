@@ -712,6 +712,50 @@ int tr_vit_forward_pixels_taps(const tr_vit_config* cfg, const tr_vit_weights* w
                                float* soft_out, const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s,
                                const tr_vit_taps* taps);
 
+/* Decision taps (csrc/tr_decisions.hip): the raw stage slabs of an eval forward -> the per-image decisions of validate.py's `Stage-{loc}`
+ * records (validate.py:199-229 on the viz_data of topk.py:196, evit.py:123, tome.py:91-99, sit.py:122, ats.py:78,253, dpcknn.py / kmedoids.py),
+ * on the device: ONE launch behind tr_vit_forward* on the same stream, one workgroup per image, the stages walked in block order; no launch
+ * for n_stages == 0.  kept_idx / compl_idx / soft are the buffers that forward wrote (idx_elems / soft_elems: their lengths in elements;
+ * the slab of block blk starts at blk * B * N0, N0 = patch tokens + 1 <= 1025).  `stages`: HOST table, ascending blocks, at most
+ * TR_MAX_DECISION_STAGES entries; n_in = tokens entering the stage (CLS included), 2 <= n_in <= N0, 1 <= k < n_in; P = n_in - 1.
+ *   kind     slab                              kept_out [B, W] at kept_off                        assign_out [B, P] at assign_off
+ *   PRUNE    kept_idx [B, k] (Top-K, DyViT)    W = k: prev[rel] (first stage: rel)                -
+ *   EVIT     kept_idx [B, k]                   W = k + 1: as PRUNE, then one -1; rel == -1 -> -1  -
+ *   ATS      kept_idx [B, k] ids: column 0     W = k - 1, rel = id - 1 of columns 1..: first      -
+ *            the CLS id, 1-based, 0 = padding  stage as is (padding -1); later stages drop the
+ *                                              padding, order kept, then prev[rel], -1 fill
+ *   CENTRES  kept_idx [B, k], compl_idx [B, P] W = k: as PRUNE (DPC-KNN, K-Medoids)               the compl_idx rows, copied
+ *   TOME     kept_idx (unm [B, na-r], src      -                                                  with pos_a[unm[j]] = j, pos_a[src[j]] = (na-r) + dst[j],
+ *            [B, r], dst [B, r]); k = the r                                                       out[0::2] = pos_a, out[1::2] = (na-r) + arange(nb):
+ *            asked for, r = min(k, (n_in-1)/2),                                                   (out - 1)[1:]
+ *            na = (n_in+1)/2, nb = n_in/2
+ *   SOFT     soft [B, k, P] fp32 at soft_off   -                                                  argmax over k, the first maximum wins
+ * prev = the kept list of the stage before (its valid entries for a later ATS stage); a stage without a kept list leaves it alone.
+ * count_out int32 [n_stages, B]: valid entries of each kept row (W; ATS: the non-zero ids; 0 where the stage has no kept list).  All
+ * outputs are stage-relative or composed exactly as the record stores them.  An index is compared with the length of the list it indexes
+ * before the read: one that is neither valid nor a padding named above comes out as -2 (a ToMe position nobody claims likewise).
+ * n_stages > 32, an unknown kind or blocks not ascending: TR_ERR_CONFIG; n_in / k / an offset outside its buffer: TR_ERR_SHAPE; a pointer
+ * not 16-byte aligned: TR_ERR_ALIGN -- each before any launch. */
+#define TR_MAX_DECISION_STAGES 32
+#define TR_DECISION_PRUNE 0
+#define TR_DECISION_EVIT 1
+#define TR_DECISION_ATS 2
+#define TR_DECISION_CENTRES 3
+#define TR_DECISION_TOME 4
+#define TR_DECISION_SOFT 5
+typedef struct {
+  int32_t block;
+  int32_t kind;
+  int32_t n_in;
+  int32_t k;
+  int64_t kept_off;     /* elements into kept_out (ignored for TOME / SOFT) */
+  int64_t assign_off;   /* elements into assign_out (CENTRES / TOME / SOFT) */
+  int64_t soft_off;     /* elements into soft (SOFT) */
+} tr_decision_stage;
+int tr_stage_decisions(const int32_t* kept_idx, const int32_t* compl_idx, size_t idx_elems, const float* soft, size_t soft_elems,
+                       const tr_decision_stage* stages, int n_stages, int B, int N0, int32_t* kept_out, size_t kept_elems,
+                       int32_t* count_out, int32_t* assign_out, size_t assign_elems, tr_stream_t s);
+
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
  * gradients), up to 640 tokens (224 x 224 and 384 x 384 inputs).  DyViT (dyvit.py:221-229): noise_in = the Gumbel noise of every stage, fp32 [B,P,2] back to back (torch's

@@ -20,6 +20,8 @@ TR_FAMILY_DEIT, TR_FAMILY_TOPK, TR_FAMILY_EVIT, TR_FAMILY_TOME, TR_FAMILY_DYVIT,
 TR_PREC_BF16, TR_PREC_FP32, TR_PREC_BF16X3 = 0, 1, 2
 TR_LAYOUT_NCHW, TR_LAYOUT_NHWC = 0, 1
 TR_INPUT_F32, TR_INPUT_U8_NCHW, TR_INPUT_U8_NHWC = 0, 1, 2
+TR_MAX_DECISION_STAGES = 32
+TR_DECISION_PRUNE, TR_DECISION_EVIT, TR_DECISION_ATS, TR_DECISION_CENTRES, TR_DECISION_TOME, TR_DECISION_SOFT = 0, 1, 2, 3, 4, 5
 
 _vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -49,6 +51,11 @@ class TrVitConfig(C.Structure):
 
 class TrVitTaps(C.Structure):        # tr_vit_taps: the output taps of tr_vit_forward_taps
     _fields_ = [("cls_blocks", C.c_uint32), ("cls_out", _vp), ("final_tokens_out", _vp)]
+
+
+class TrDecisionStage(C.Structure):  # tr_decision_stage: one row of tr_stage_decisions' stage table (40 bytes)
+    _fields_ = [("block", C.c_int32), ("kind", C.c_int32), ("n_in", C.c_int32), ("k", C.c_int32), ("kept_off", C.c_int64),
+                ("assign_off", C.c_int64), ("soft_off", C.c_int64)]
 
 
 class TrAugmentRec(C.Structure):     # tr_augment_rec: one image of the device-side erase / mixup / cutmix table (64 bytes)
@@ -208,6 +215,7 @@ SIGNATURES = {
                                  C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
     "tr_vit_forward_pixels_taps": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                         C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
+    "tr_stage_decisions": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "tr_cls_tap": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _i, _vp]),
     "tr_final_tokens_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "tr_vit_forward_train_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,

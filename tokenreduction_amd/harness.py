@@ -8,6 +8,7 @@ Mirrors, for the forward (inference) path only:
     validate.py:163-229   per-image `Stage-{loc}` records, relative -> absolute kept-token composition -> image_records()
     validate.py:26-30, 278-287   NumpyArrayEncoder / write_viz -> write_viz()
     extract_cls_features.py:113-141   CLS rows after chosen blocks, stacked over the loader -> extract_cls_features()
+    validate.py:199-229   the same records from the device-side decision taps (model.forward_decisions) -> decision_records()
 
     engine.py:14-114      train_one_epoch()          -> train_one_epoch()  (grad accumulation, clipping, EMA, frozen groups, step-wise LR)
     timm ModelEmaV2       (train.py:399, engine.py:88) -> ModelEma
@@ -259,14 +260,61 @@ def image_records(model_name: str, reduction_count: Sequence[int], viz_data: dic
     return out
 
 
+def decisions_to_host(dec: dict) -> dict:
+    """The dec dictionary of model.forward_decisions with every tensor as a host int64 array: ONE copy per tensor and batch (the views of
+    one stage share their buffer with the other stages, so a buffer crosses once however many stages it holds)."""
+    bases: Dict[int, np.ndarray] = {}
+
+    def host(t):
+        if not isinstance(t, torch.Tensor):
+            return np.asarray(t).astype(np.int64)
+        base = t._base if t._base is not None else t
+        if not t.is_contiguous():
+            return t.cpu().numpy().astype(np.int64)                # (an expanded static table: copy the view, not the stride-0 base)
+        flat = bases.get(id(base))
+        if flat is None:
+            flat = bases[id(base)] = base.detach().reshape(-1).cpu().numpy().astype(np.int64)
+        off = t.storage_offset() - base.storage_offset()
+        return flat[off: off + t.numel()].reshape(tuple(t.shape))
+    return {"stages": tuple(dec["stages"]), "host": True, **{key: {blk: host(t) for blk, t in dec[key].items()}
+                                                             for key in ("kept", "kept_count", "assign")}}
+
+
+def decision_records(model_name: str, reduction_count: Sequence[int], dec: dict, i: int) -> Dict[str, dict]:
+    """image_records() from the decision taps: the `Stage-{loc}` part of image i's record out of `dec` (model.forward_decisions, or its
+    decisions_to_host() copy -- pass that when a whole batch is turned into records, so every tensor crosses to the host once per batch).
+    The composition into absolute indices already happened on the device; what is left is the slicing: a kept row is cut to the width
+    the reference's record has -- all of it, except under ATS's static padding, where the first stage keeps the batch maximum of the
+    valid counts (pad_sequence, ats.py:78) and a later stage the image's own count (validate.py:213-214 drops the padding before it
+    composes)."""
+    if not dec.get("host"):
+        dec = decisions_to_host(dec)
+    out: Dict[str, dict] = {}
+    for stage_idx, stage in enumerate(reduction_count):
+        rec: dict = {}
+        if stage in dec["kept"]:
+            row, counts = dec["kept"][stage][i], dec["kept_count"][stage]
+            width = row.shape[0]
+            if "ats" in model_name:
+                width = int(counts.max()) if stage_idx == 0 else int(counts[i])
+            rec["Kept_Token"] = row[:width]
+        if stage in dec["assign"]:
+            rec["Assignment_Maps"] = dec["assign"][stage][i]
+        out[f"Stage-{stage}"] = rec
+    return out
+
+
 @torch.no_grad()
 def validate(data_loader: Iterable, model, device, model_name: str, image_names: Sequence[str], keep_rate=None,
-             reduction_loc=None) -> dict:
+             reduction_loc=None, stage_records: bool = False) -> dict:
     """validate.py:59-276 without dataset/checkpoint plumbing: runs the loader, returns the `*_viz_results.json` dictionary
-    (per image: top-5 `Predictions`, `Target`, the batch `Loss`, and -- with `model.viz_mode` -- the stage records)."""
+    (per image: top-5 `Predictions`, `Target`, the batch `Loss`, and -- with `model.viz_mode` -- the stage records).
+    stage_records=True with viz_mode off: the same stage records, taken from the decision taps of the fast-path forward
+    (forward_async(decisions=True), one batch of lookahead) instead of a viz_mode forward."""
     data = {"Model": model_name, "Ratio": keep_rate, "Location": reduction_loc}
     top1, top5 = _Meter(), _Meter()
     viz_mode = bool(getattr(model, "viz_mode", False))
+    taps = bool(stage_records) and not viz_mode
     count = 0
     # one batch of lookahead, as in evaluate_multiclass (with viz_mode the forward runs synchronously: forward_async says so itself)
     launch = getattr(getattr(model, "module", model), "forward_async", None)
@@ -274,9 +322,12 @@ def validate(data_loader: Iterable, model, device, model_name: str, image_names:
     def consume(pending, target, n):
         nonlocal count
         output = pending.result() if launch is not None else pending
-        viz_data = None
+        viz_data = dec = None
         if viz_mode:
             output, viz_data = output
+        elif taps:
+            output, dec = output
+            dec = decisions_to_host(dec)
         loss = F.cross_entropy(output.float(), target)
         acc1, acc5 = accuracy(output, target, topk=(1, 5))
         _, pred = output.topk(min(5, output.shape[1]), 1, True, True)
@@ -286,6 +337,8 @@ def validate(data_loader: Iterable, model, device, model_name: str, image_names:
             rec = {"Predictions": _np(pred[i]), "Target": _np(target[i]), "Loss": loss.item()}
             if viz_mode:
                 rec.update(image_records(model_name, model.get_reduction_count(), viz_data, i))
+            elif taps:
+                rec.update(decision_records(model_name, model.get_reduction_count(), dec, i))
             data[image_names[count + i]] = rec
         count += n
 
@@ -293,7 +346,10 @@ def validate(data_loader: Iterable, model, device, model_name: str, image_names:
     for images, target in data_loader:
         images = images.to(device, non_blocking=True)
         target = target.to(device, non_blocking=True)
-        cur = (launch(images) if launch is not None else model(images), target, images.shape[0])
+        if taps:
+            cur = (getattr(model, "module", model).forward_async(images, decisions=True), target, images.shape[0])
+        else:
+            cur = (launch(images) if launch is not None else model(images), target, images.shape[0])
         if prev is not None:
             consume(*prev)
         prev = cur

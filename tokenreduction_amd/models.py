@@ -19,6 +19,9 @@ A headless model (num_classes=0 or reset_classifier(0): head = nn.Identity(), de
 [B, embed_dim] wherever a classifier returns logits -- eval in all three precisions, viz_mode, forward_async, training and its backward.
 Intermediate outputs of an eval forward: viz_mode (every row of every recorded block, on the host) or the output taps of forward_taps /
 forward_async -- the CLS rows after chosen blocks and the final-normed tokens, fp32 device tensors written while the fast path runs.
+The stages' decisions (which tokens each stage kept, which output every token went to) come the same two ways: viz_mode's viz_data, or
+forward_decisions / forward_async(decisions=True) -- int32 device tensors in the form of validate.py's per-image records, one launch
+(tr_stage_decisions) behind the fast-path forward.
 """
 from __future__ import annotations
 
@@ -61,10 +64,16 @@ class _Pending:
         if self._event is not None:
             cur = torch.cuda.current_stream()
             cur.wait_event(self._event)
-            for t in (self._out if isinstance(self._out, (tuple, list)) else (self._out,)):
-                for u in (t.values() if isinstance(t, dict) else (t,)):       # (forward_taps: the taps come as a dict beside the logits)
-                    if torch.is_tensor(u):
-                        u.record_stream(cur)
+            def keep(t):                                # (forward_taps / forward_decisions: dicts of tensors beside the logits)
+                if torch.is_tensor(t):
+                    t.record_stream(cur)
+                elif isinstance(t, dict):
+                    for u in t.values():
+                        keep(u)
+                elif isinstance(t, (tuple, list)):
+                    for u in t:
+                        keep(u)
+            keep(self._out)
             self._event = None
         return self._out
 
@@ -293,6 +302,7 @@ class VisionTransformer(nn.Module):
         self._noise_slot = 0             # the slot of the forward being enqueued
         self._gumbel_buf = None          # DyViT training: the Gumbel draws
         self._kmed_draws = None          # K-Medoids equal_weight: the first medoids of the last forward
+        self._decision_tables = {}       # Heuristic: {device: {block: int32 kept-token table}} of forward_decisions
 
     @property
     def _noise_buf(self):
@@ -644,7 +654,33 @@ class VisionTransformer(nn.Module):
             x = x.float()
         return self._forward_eval(x, 0, self._tap_request(cls_blocks, final_tokens))
 
-    def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False):
+    def _decision_request(self, x, what):
+        """The refusals of a forward that asks for the stages' decisions."""
+        if self.training:
+            raise RuntimeError("decision taps are an eval feature: call model.eval() first (the training executor records no decisions)")
+        if self.viz_mode:
+            raise RuntimeError("decision taps and viz_mode are two ways to the same records: switch viz_mode off (viz_data already holds "
+                               "Kept_Tokens / Assignment_Maps on the host)")
+        if self.dynamic_width:
+            raise RuntimeError(f"{what} cannot run under dynamic_width (the token counts of a stage are then data dependent and the executor "
+                               "synchronises mid-forward): switch dynamic_width off or use viz_mode")
+        if not x.is_cuda:
+            raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
+
+    def forward_decisions(self, x: torch.Tensor, cls_blocks=None, final_tokens=False):
+        """Eval forward with decision taps: (logits, dec), dec = {"stages": (blk, ...), "kept": {blk: int32 [B, W]}, "kept_count": {blk: int32
+        [B]}, "assign": {blk: int32 [B, P_in]}} -- per reduction stage what validate.py stores in an image's `Stage-{loc}` record: the kept
+        tokens as ABSOLUTE patch indices of the input grid (-1 behind a row's kept_count valid entries) and the stage-relative assignment map;
+        a family has one, the other or both (harness.decision_records turns a row into the record).  Device tensors, written by one launch
+        (tr_stage_decisions) behind the forward, which stays on the fast path; the logits are those of model(x).  With cls_blocks /
+        final_tokens the output taps of forward_taps ride along: (logits, taps, dec).  Refuses train mode, viz_mode, dynamic_width."""
+        if isinstance(x, AugmentedBatch):
+            x = x.float()
+        self._decision_request(x, "forward_decisions")
+        taps = self._tap_request(cls_blocks, final_tokens) if (cls_blocks is not None or final_tokens) else None
+        return self._forward_eval(x, 0, taps, True)
+
+    def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False, decisions=False):
         """Eval forward that may run BESIDE the previous one: the call enqueues the forward on one of `pipeline_depth` (default 2) side streams
         -- each with its own workspace and captured hipGraph -- behind everything already enqueued on the caller's current stream, and
         returns a handle at once; `handle.result()` makes the caller's current stream wait for that forward and returns what `model(x)`
@@ -654,11 +690,16 @@ class VisionTransformer(nn.Module):
         of lookahead (harness.evaluate_multiclass does): launch batch k + 1, then consume batch k.  Same kernels, same bits as `model(x)`.
         Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete).
         cls_blocks / final_tokens: the output taps of forward_taps -- the result is then what forward_taps returns.  With taps, train mode,
-        viz_mode and dynamic_width are refused instead of run synchronously."""
+        viz_mode and dynamic_width are refused instead of run synchronously.  decisions=True: the decision taps of forward_decisions, with
+        the same refusals -- the result is what forward_decisions returns."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
         taps = None
-        if cls_blocks is not None or final_tokens:
+        if decisions:
+            self._decision_request(x, "forward_async(decisions=True)")
+            if cls_blocks is not None or final_tokens:
+                taps = self._tap_request(cls_blocks, final_tokens)
+        elif cls_blocks is not None or final_tokens:
             taps = self._tap_request(cls_blocks, final_tokens)
             if not x.is_cuda:
                 raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
@@ -681,13 +722,13 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(x.device)
         side.wait_stream(cur)                          # inputs and weights are ready where the forward runs
         with torch.cuda.stream(side):
-            out = self._forward_eval(x, slot + 1, taps)
+            out = self._forward_eval(x, slot + 1, taps, bool(decisions))
             done = torch.cuda.Event()
             done.record(side)
         x.record_stream(side)
         return _Pending(out, done)
 
-    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None):
+    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None, decisions=False):
         if not x.is_cuda:
             raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
         lib = _lib.load()
@@ -718,6 +759,8 @@ class VisionTransformer(nn.Module):
                 ws["tap_final"] = torch.empty(B * n0 * D, dtype=torch.float32, device=x.device)
             tap_arg = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
                                      ws["tap_final"].data_ptr() if want_final else None)
+        dec = self._decision_plan(ws, B, x.device) if decisions else None
+        soft = ws.get("soft") if dec is None or dec["soft"] is None else dec["soft"]      # (a buffer of its own: ws["soft"] stays viz_mode's)
         self._noise_slot = slot                      # (a static buffer per workspace slot: two forwards in flight must not share one)
         noise_ptr = self._noise_ptr(B, x.device)
         self._kmed_draws = None
@@ -727,7 +770,7 @@ class VisionTransformer(nn.Module):
         def launch(out):
             tokens = (C.c_int * self.depth)()
             rest = (out.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
-                    None if ws.get("soft") is None else ws["soft"].data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
+                    None if soft is None else soft.data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
                     torch.cuda.current_stream().cuda_stream)
             if tap_arg is not None and fmt == _lib.TR_INPUT_F32:
                 rc = lib.tr_vit_forward_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest, C.byref(tap_arg))
@@ -738,6 +781,11 @@ class VisionTransformer(nn.Module):
             else:
                 rc = lib.tr_vit_forward_pixels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest)
             _lib.check(rc, "tr_vit_forward")
+            if dec is not None and dec["n"]:
+                # the raw slabs -> record form, in the forward's stream (and its graph): one launch
+                rc = lib.tr_stage_decisions(ws["kept"].data_ptr(), ws["compl"].data_ptr(), ws["kept"].numel(), *dec["args"][0], dec["table"],
+                                            dec["n"], B, self.patch_embed.num_patches + 1, *dec["args"][1], torch.cuda.current_stream().cuda_stream)
+                _lib.check(rc, "tr_stage_decisions")
             return list(tokens)
 
         with torch.cuda.device(x.device):
@@ -745,7 +793,7 @@ class VisionTransformer(nn.Module):
             if (self.use_graph and not ws.get("graph_off") and not torch.cuda.is_current_stream_capturing()
                     and not self.dynamic_width):      # (ATS dynamic width: the executor reads a token count back mid-forward)
                 key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width,
-                       taps)
+                       taps) + ((True,) if dec is not None else ())
                 res = self._replay(ws, key, launch, B, x.device)
             logits, tokens = res if res is not None else self._plain_launch(launch, B, x.device)
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
@@ -757,7 +805,11 @@ class VisionTransformer(nn.Module):
             D, n_last = self.embed_dim, tokens[-1]
             out = {"cls": ws["tap_cls"][:B * len(blocks) * D].view(B, len(blocks), D).clone() if blocks else None, "blocks": blocks,
                    "final_tokens": ws["tap_final"][:B * n_last * D].view(B, n_last, D).clone() if want_final else None}
+            if dec is not None:
+                return logits, out, self._decision_result(dec, B, list(tokens))
             return logits, out
+        if dec is not None:
+            return logits, self._decision_result(dec, B, list(tokens))
         if self.viz_mode:
             viz = self._viz_data(ws, B, list(tokens))
             viz["Features"] = self._features(ws, B, list(tokens))
@@ -826,6 +878,62 @@ class VisionTransformer(nn.Module):
 
     def _viz_data(self, ws, B, tokens):
         return {}
+
+    # ---- decision taps (forward_decisions): the stage table of tr_stage_decisions and its static output buffers ---------------------
+    def _decision_stages(self):
+        """[(blk, TR_DECISION_* kind, n_in, k)] of the stages that decide on the device, in block order (n_in: tokens entering the stage, CLS
+        included; k as tr_stage_decisions reads it).  The shapes are static: the executor's token counts are checked against them."""
+        return []
+
+    def _static_decisions(self, B, dev):
+        """Decisions that do not depend on the image (Heuristic): the dec dictionary, or None."""
+        return None
+
+    def _decision_plan(self, ws, B, dev):
+        """ws["dec"]: the stage table, where every stage's rows lie in the outputs, and the static buffers -- kept / assign (int32, the
+        stages' [B, W] / [B, P_in] blocks back to back), count [S, B], and for the soft families a soft-assignment buffer of its own."""
+        dec = ws.get("dec")
+        if dec is not None:
+            return dec
+        stages = self._decision_stages()
+        if len(stages) > _lib.TR_MAX_DECISION_STAGES:
+            raise ValueError(f"{len(stages)} reduction stages: the decision taps take at most {_lib.TR_MAX_DECISION_STAGES}")
+        from . import ops
+        table, layout, kept_n, assign_n, soft_n = ops.decision_table(stages, B)
+        if soft_n != self._soft_elems(B):
+            raise RuntimeError(f"the soft stages hold {soft_n} elements, the executor writes {self._soft_elems(B)}")
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev) if n else None
+        dec = ws["dec"] = dict(table=table, n=len(stages), layout=layout, kept=i32(kept_n), assign=i32(assign_n), count=i32(max(1, len(stages) * B)),
+                               soft=torch.empty(soft_n, dtype=torch.float32, device=dev) if soft_n else None,
+                               static=self._static_decisions(B, dev), checked=False)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        size = lambda t: 0 if t is None else t.numel()
+        # tr_stage_decisions' arguments around the table: (soft, soft_elems), (kept_out, kept_elems, count_out, assign_out, assign_elems)
+        dec["args"] = ((ptr(dec["soft"]), size(dec["soft"])),
+                       (ptr(dec["kept"]), size(dec["kept"]), dec["count"].data_ptr(), ptr(dec["assign"]), size(dec["assign"])))
+        return dec
+
+    def _decision_result(self, dec, B, tokens):
+        """The dec dictionary of forward_decisions: views of ONE clone per static buffer (the next forward on this slot overwrites them)."""
+        if dec["static"] is not None:
+            return dec["static"]
+        if not dec["checked"]:
+            n0 = self.patch_embed.num_patches + 1
+            for blk, n_in, *_ in dec["layout"]:
+                if n_in != (tokens[blk - 1] if blk else n0):
+                    raise RuntimeError(f"block {blk}: the stage table expects {n_in} tokens, the executor had {tokens[blk - 1] if blk else n0}")
+            dec["checked"] = True
+        kept = None if dec["kept"] is None else dec["kept"].clone()
+        assign = None if dec["assign"] is None else dec["assign"].clone()
+        count = dec["count"].clone() if dec["n"] else None
+        out = {"stages": tuple(lay[0] for lay in dec["layout"]), "kept": {}, "kept_count": {}, "assign": {}}
+        for i, (blk, n_in, W, koff, A, aoff) in enumerate(dec["layout"]):
+            if W:
+                out["kept"][blk] = kept[koff: koff + B * W].view(B, W)
+                out["kept_count"][blk] = count[i * B: (i + 1) * B]
+            if A:
+                out["assign"][blk] = assign[aoff: aoff + B * A].view(B, A)
+        return out
 
     _features_every_block = True
 
@@ -912,6 +1020,16 @@ class _TopKBase(VisionTransformer):
     def get_reduction_count(self):
         return self.pruning_loc
 
+    def _decision_stages(self):
+        kind = _lib.TR_DECISION_EVIT if self._family == _lib.TR_FAMILY_EVIT else _lib.TR_DECISION_PRUNE
+        out, n = [], self.num_patches + 1
+        for blk in range(self.depth):
+            K = self._keep[blk]
+            if K and K != n - 1:                                        # (topk.py:57: left_tokens == N-1 reduces nothing)
+                out.append((blk, kind, n, K))
+                n = self._tokens_after(K)
+        return out
+
 
 class TopKVisionTransformer(_TopKBase):
     """models/topk.py:102-212."""
@@ -973,6 +1091,15 @@ class ToMeVisionTransformer(VisionTransformer):
 
     def get_reduction_count(self):
         return self.pruning_loc
+
+    def _decision_stages(self):
+        out, n = [], self.patch_embed.num_patches + 1
+        for blk in range(self.depth):
+            r = min(self._keep[blk], (n - 1) // 2)
+            if r > 0 and blk in self.pruning_loc:
+                out.append((blk, _lib.TR_DECISION_TOME, n, r))
+            n -= max(r, 0)
+        return out
 
     def _viz_data(self, ws, B, tokens):
         """Assignment_Maps[blk] (tome.py:91-99): for every input patch token, the index of its output token minus 1 -- derived
@@ -1121,6 +1248,13 @@ class DynamicVisionTransformer(VisionTransformer):
         kept = ws["kept"].cpu().numpy()
         return {"Kept_Tokens": {blk: self._stage_slab(kept, blk, B, self._keep[blk]) for blk in self.pruning_loc}, "Features": {}}
 
+    def _decision_stages(self):
+        out, n = [], self.patch_embed.num_patches + 1
+        for blk in sorted(self.pruning_loc):
+            out.append((blk, _lib.TR_DECISION_PRUNE, n, self._keep[blk]))
+            n = self._keep[blk] + 1
+        return out
+
 
 class _ClusterBase(VisionTransformer):
     """Shared part of the five families that replace the patch tokens by cluster_count[j] tokens BEFORE block cluster_loc[j] through a
@@ -1161,6 +1295,11 @@ class _ClusterBase(VisionTransformer):
             p_in = K
         return out
 
+    _decision_kind = _lib.TR_DECISION_CENTRES
+
+    def _decision_stages(self):
+        return [(blk, self._decision_kind, P + 1, K) for blk, K, P in self._stage_shapes()]
+
     def _viz_data(self, ws, B, tokens):
         """Hard clusterings (DPC-KNN, K-Medoids): the centre tokens and every input token's cluster."""
         kept, assign = ws["kept"].cpu().numpy(), ws["compl"].cpu().numpy()
@@ -1187,6 +1326,7 @@ class SelfSlimmedVisionTransformer(_ClusterBase):
     reduction_loc."""
     _family = _lib.TR_FAMILY_SIT
     _center_feats = False            # viz_data carries an (empty) "Center_Feats" entry (sinkhorn.py / patchmerger.py)
+    _decision_kind = _lib.TR_DECISION_SOFT
 
     def _make_cluster_layer(self, count):
         return TokenSlimmingModule(self.embed_dim, count)
@@ -1357,6 +1497,14 @@ class ATSVisionTransformer(VisionTransformer):
                 steps = self.sample_steps(K).to(self.pos_embed.device)
                 W.stage[blk].w3 = pk.f32(steps)
                 W.stage[blk].n_pad = steps.numel()
+
+    def _decision_stages(self):
+        out, n = [], self.patch_embed.num_patches + 1
+        for blk, K in enumerate(self._keep):
+            if K:
+                out.append((blk, _lib.TR_DECISION_ATS, n, K))
+                n = K
+        return out
 
     def _viz_data(self, ws, B, tokens):
         kept = ws["kept"].cpu().numpy()
@@ -1603,6 +1751,15 @@ class HeuristicVisionTransformer(VisionTransformer):
             ind = self._block_mask(idx).nonzero(as_tuple=True)[0]
             decisions[idx] = ind.unsqueeze(0).expand(B, -1).numpy().astype(np.int64)
         return {"Kept_Tokens_Abs": decisions}
+
+    def _static_decisions(self, B, dev):
+        """Kept_Tokens_Abs is constructor-time geometry: uploaded once per device, every image of a batch sees the same rows."""
+        tabs = self._decision_tables.get(dev)
+        if tabs is None:
+            tabs = self._decision_tables[dev] = {idx: self._block_mask(idx).nonzero(as_tuple=True)[0].to(torch.int32).to(dev)
+                                                 for idx in self.reduction_loc}
+        return {"stages": tuple(sorted(tabs)), "kept": {idx: t.unsqueeze(0).expand(B, -1) for idx, t in tabs.items()},
+                "kept_count": {idx: torch.full((B,), t.numel(), dtype=torch.int32, device=dev) for idx, t in tabs.items()}, "assign": {}}
 
 
 class VisionTransformerTeacher(VisionTransformer):

@@ -506,6 +506,51 @@ def final_tokens_f32(x: torch.Tensor, gamma, beta, eps: float, d1: torch.Tensor 
     return y
 
 
+def decision_table(stages, B: int):
+    """tr_stage_decisions' host table for `stages` [(blk, _lib.TR_DECISION_* kind, n_in, k)] at batch size B, its outputs laid out back to
+    back: (ctypes table, [(blk, n_in, W, kept_off, A, assign_off)], kept elements, assign elements, soft elements) -- W / A: width of the
+    stage's kept rows / assignment rows, 0 where it has none."""
+    table = (_lib.TrDecisionStage * max(1, len(stages)))()
+    layout, kept_n, assign_n, soft_n = [], 0, 0, 0
+    for i, (blk, kind, n_in, k) in enumerate(stages):
+        W = max(0, {_lib.TR_DECISION_PRUNE: k, _lib.TR_DECISION_CENTRES: k, _lib.TR_DECISION_EVIT: k + 1, _lib.TR_DECISION_ATS: k - 1}.get(kind, 0))
+        A = max(0, n_in - 1) if kind in (_lib.TR_DECISION_CENTRES, _lib.TR_DECISION_TOME, _lib.TR_DECISION_SOFT) else 0
+        table[i] = _lib.TrDecisionStage(blk, kind, n_in, k, kept_n, assign_n, soft_n)
+        layout.append((blk, n_in, W, kept_n, A, assign_n))
+        kept_n += B * W
+        assign_n += B * A
+        if kind == _lib.TR_DECISION_SOFT:
+            soft_n += B * max(0, k) * max(0, n_in - 1)
+    return table, layout, kept_n, assign_n, soft_n
+
+
+def stage_decisions(kept_idx: torch.Tensor, compl_idx: torch.Tensor, soft: torch.Tensor, stages, B: int, N0: int) -> dict:
+    """The raw stage slabs of an eval forward -> record-form decisions (tr_stage_decisions, one launch): kept_idx / compl_idx int32 slabs
+    (block blk at blk * B * N0; compl_idx nullable), soft fp32 (the SOFT stages' [B, k, P] blocks back to back; nullable), stages
+    [(blk, _lib.TR_DECISION_* kind, n_in, k)] in block order.  Returns {"stages", "kept": {blk: int32 [B, W]}, "kept_count": {blk: int32 [B]},
+    "assign": {blk: int32 [B, P]}} -- what VisionTransformer.forward_decisions returns."""
+    _same_device(kept_idx, compl_idx, soft)
+    if compl_idx is not None and compl_idx.numel() != kept_idx.numel():
+        raise ValueError("kept_idx and compl_idx are slabs of one shape")
+    dev = kept_idx.device
+    table, layout, kept_n, assign_n, _ = decision_table(stages, B)
+    kept = torch.empty(max(1, kept_n), dtype=torch.int32, device=dev)
+    assign = torch.empty(max(1, assign_n), dtype=torch.int32, device=dev)
+    count = torch.empty(max(1, len(stages) * B), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tr_stage_decisions(_dev(kept_idx, torch.int32, "kept_idx"), _opt(compl_idx, torch.int32, "compl_idx"), kept_idx.numel(),
+                                              _opt(soft, torch.float32, "soft"), 0 if soft is None else soft.numel(), table, len(stages), B, N0,
+                                              kept.data_ptr(), kept_n, count.data_ptr(), assign.data_ptr(), assign_n, _stream(kept_idx)),
+               "tr_stage_decisions")
+    out = {"stages": tuple(lay[0] for lay in layout), "kept": {}, "kept_count": {}, "assign": {}}
+    for i, (blk, _, W, koff, A, aoff) in enumerate(layout):
+        if W:
+            out["kept"][blk] = kept[koff: koff + B * W].view(B, W)
+            out["kept_count"][blk] = count[i * B: (i + 1) * B]
+        if A:
+            out["assign"][blk] = assign[aoff: aoff + B * A].view(B, A)
+    return out
+
+
 def attention_f32(qkv: torch.Tensor, B: int, N: int, H: int, want_cls: bool = False, size: torch.Tensor = None,
                   colsum_part: torch.Tensor = None, split: bool = False):
     out = torch.empty(B * N, H * 64, dtype=torch.float32, device=qkv.device)
