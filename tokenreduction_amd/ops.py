@@ -1451,3 +1451,53 @@ def cast_pack(items) -> None:
     d_first = torch.tensor(first, dtype=torch.int32, device=dev)
     _lib.check(_lib.load().tr_cast_pack_bf16(d_items.data_ptr(), d_first.data_ptr(), n, first[-1], _stream(items[0][0])), "tr_cast_pack_bf16")
     torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch
+
+
+class _AdamwItem(ctypes.Structure):          # tr_adamw_item
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+                ("dst_t", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("group", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
+def adamw_step(items, lrs, wds, betas, eps: float, step: int, zero_grads: bool = False) -> None:
+    """One AdamW step of every item in ONE launch (tr_adamw_step, csrc/tr_optim.hip).  items: [(p, g, exp_avg, exp_avg_sq fp32 of one
+    shape, dst bf16 [rows, cols] | None, dst_t bf16 [cols, rows] | None, group), ...] with rows, cols as optim.FusedAdamW derives them
+    (shape[0] x the rest from two dimensions on, one row below); the tensors may be views that start anywhere in a buffer.  lrs / wds: up
+    to 8 learning rates / weight decays, indexed by an item's group.  step: the 1-based count of this step; the bias corrections are
+    formed in double and rounded to float as optim.FusedAdamW forms them.
+    For tests: the item table is built and uploaded per call and the stream is synchronised before it is freed (optim.FusedAdamW keeps a
+    persistent table)."""
+    import math
+    n = len(items)
+    if n == 0:
+        raise ValueError("adamw_step: no items")
+    if not 0 < len(lrs) <= 8 or len(wds) != len(lrs):
+        raise ValueError(f"adamw_step: 1 to 8 learning rates and as many weight decays, got {len(lrs)} and {len(wds)}")
+    if step < 1:
+        raise ValueError(f"adamw_step: step counts from 1, got {step}")
+    arr = (_AdamwItem * n)()
+    first = [0]
+    for i, (p, g, m, v, dst, dst_t, group) in enumerate(items):
+        rows, cols = (p.shape[0], p.numel() // p.shape[0]) if p.dim() >= 2 else (1, p.numel())
+        _same_device(p, g, m, v, dst, dst_t, items[0][0])
+        if not (g.shape == p.shape and m.shape == p.shape and v.shape == p.shape) or rows * cols == 0:
+            raise ValueError(f"adamw_step: item {i}: p, g, exp_avg, exp_avg_sq must share one non-empty shape")
+        if dst is not None and tuple(dst.shape) != (rows, cols) or dst_t is not None and tuple(dst_t.shape) != (cols, rows):
+            raise ValueError(f"adamw_step: item {i}: destinations do not fit a [{rows}, {cols}] parameter")
+        if not 0 <= group < len(lrs):
+            raise ValueError(f"adamw_step: item {i}: group {group} of {len(lrs)}")
+        arr[i] = _AdamwItem(_view_ptr(p, torch.float32, "p"), _view_ptr(g, torch.float32, "g"), _view_ptr(m, torch.float32, "exp_avg"),
+                            _view_ptr(v, torch.float32, "exp_avg_sq"), None if dst is None else _view_ptr(dst, torch.bfloat16, "dst"),
+                            None if dst_t is None else _view_ptr(dst_t, torch.bfloat16, "dst_t"), rows, cols, group, 0)
+        first.append(first[-1] + ((rows + 63) // 64) * ((cols + 63) // 64))
+    beta1, beta2 = betas
+    bc1 = 1.0 - math.pow(beta1, step)
+    bc2_sqrt = math.sqrt(1.0 - math.pow(beta2, step))
+    lr8 = (ctypes.c_double * 8)(*([float(x) for x in lrs] + [0.0] * (8 - len(lrs))))
+    wd8 = (ctypes.c_double * 8)(*([float(x) for x in wds] + [0.0] * (8 - len(wds))))
+    dev = items[0][0].device
+    d_items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    d_first = torch.tensor(first, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tr_adamw_step(d_items.data_ptr(), d_first.data_ptr(), n, first[-1], float(beta1), float(beta2), float(eps), bc1,
+                                             bc2_sqrt, lr8, wd8, 1 if zero_grads else 0, _stream(items[0][0])), "tr_adamw_step")
+    torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch
