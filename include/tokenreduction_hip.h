@@ -232,6 +232,19 @@ int tr_cls_tap(const float* x, long ldx, const void* d1, long ld1, const void* d
                int D, tr_stream_t s);
 int tr_final_tokens_f32(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* gamma, const float* beta, float* y,
                         int M, int D, float eps, tr_stream_t s);
+/* Average-pooled head (tr_vit_config.global_pool == 1; csrc/tr_pool.hip): timm's global_pool='avg' with fc_norm -- the pool runs BEFORE the
+ * final norm.  Pending operands as above (bf16, fp32 when delta_is_f32; d1 / d2 nullable, d2 needs d1), contiguous [B,N,D] like x.
+ * tr_token_pool: out[b] = sum_n w[b,n] * v[b,n] / sum_n w[b,n] over the patch rows n = 1 .. N-1 (row 0, the CLS token, is left out), v = (x +
+ *   d1) + d2 in fp32, out fp32 [B,D].  weight fp32 [B,N] (entry 0 not read): ToMe token sizes / the ATS padding mask; NULL = all ones (the
+ *   same bits as a buffer of ones).  A row of weight 0 adds nothing whatever it holds; an image whose weights sum to 0 pools to exact zeros.
+ *   One pass, every input byte read once (16-byte loads); fp32 accumulation in an order that depends on N alone -- not on B, not on the
+ *   launch geometry: no atomics, two launches give the same bits, an image pools to the same bits in any batch.
+ *   N >= 2, D %% 64 == 0, B <= 65535: anything else is TR_ERR_SHAPE before any launch.
+ * tr_token_pool_bwd: g[b,0,:] = 0, g[b,n,:] = gpool[b,:] * (w[b,n] * (1 / sum_n w[b,n])) (0 where the sum is 0); g fp32 [B,N,D], EVERY element
+ *   written exactly once (no memset in front of it).  No gradient with respect to the weights.  Same shape rules. */
+int tr_token_pool(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* weight, float* out, int B, int N, int D,
+                  tr_stream_t s);
+int tr_token_pool_bwd(const float* gpool, const float* weight, float* g, int B, int N, int D, tr_stream_t s);
 /* dst fp32 [B,N] = src fp32 [N] in every row (the Heuristic family's per-block key mask, heuristic.py:247-258). */
 int tr_broadcast_rows(const float* src, float* dst, int B, int N, tr_stream_t s);
 
@@ -639,12 +652,22 @@ typedef struct {
                                  (ats.py:77-78) instead of running the static bound keep[blk] with masked rows.  Same valid tokens and logits (to
                                  the attention kernels' summation order); fewer rows downstream.  tr_vit_forward then reads one int back per
                                  sampling block: it SYNCHRONISES the stream there and cannot be captured in a hipGraph.  0 = static (default). */
-  int concurrent;             /* eval forward only, a scheduling hint: 1 = the caller runs other forwards BESIDE this one (other streams, other
+  short concurrent;           /* eval forward only, a scheduling hint: 1 = the caller runs other forwards BESIDE this one (other streams, other
                                  workspaces: models.py forward_async), so a launch need not fill the chip on its own -- the other forward's
                                  launches take the compute units it leaves idle.  The executor then runs the fused Mlp wherever it is
                                  supported (also where its blocks fill less than 3/4 of a round) and as whole blocks round-robin (no stream-K
                                  hand-over traffic): measured +2 ... +3 % with two forwards in flight, -2 ... -4 % one at a time.  Same bits
-                                 either way.  0 = one forward at a time (default). */
+                                 either way.  0 = one forward at a time (default).  (A 16-bit flag since global_pool took the upper half of
+                                 what was `int concurrent`: the struct keeps its 80 x 4 bytes and every offset, and a caller that wrote the
+                                 int 0 / 1 wrote concurrent = 0 / 1, global_pool = 0.) */
+  short global_pool;          /* what the final norm and the classifier see.  0 (default): the CLS row, the reference's head (topk.py:201-203).
+                                 1: the average of the patch tokens after the last block, pooled BEFORE the norm (timm's global_pool='avg' with
+                                 fc_norm, the MAE fine-tuning head): feat = LayerNorm(sum_n w_n v_n / sum_n w_n), n = 1 .. N_last-1, v = the stream with
+                                 its pending residuals; w = ToMe's token sizes after the last merge, the ATS padding mask, 1 for every other
+                                 family and before the first merge / sampling stage (tr_token_pool).  The CLS row still runs through every block;
+                                 the last block runs at full width (no CLS tail).  Eval in all three precisions, training and backward
+                                 (tr_token_pool_bwd; no gradient with respect to w) -- except DyViT in TRAINING mode, which keeps masked tokens
+                                 in the stream: TR_ERR_CONFIG.  Any other value: TR_ERR_CONFIG. */
 } tr_vit_config;
 
 /* Diagnostics (lab, tools/lab/clock_probe.py): the in-kernel clock probes of a library built with -DTR_DIAG_CLOCK -- {shader cycles, 100-MHz
@@ -663,6 +686,8 @@ int tr_vit_forward_status(const tr_vit_config* cfg, void* workspace, size_t work
 /* img fp32 [B,C,S,S] -> logits fp32 [B,classes].  Headless (num_classes == 0, deit_viz.py:142,182: head = nn.Identity()): `logits` is
  * fp32 [B,D] and receives pre_logits(norm(x)[:, 0]), the final-normed CLS row; no classifier GEMM runs and w->head_w / head_b may be NULL.
  * In bf16 the row is the final norm's output before its bf16 rounding (tr_layernorm_bf16_f32): bf16(features) is the classifier's operand.
+ * cfg->global_pool == 1: the norm and the classifier (or, headless, `logits`) read the weighted average of the patch rows after the last block
+ * instead of its CLS row (tr_vit_config.global_pool, tr_token_pool); the last block then runs at full width, everything else is unchanged.
  * kept_idx (nullable): device int32 slab of depth*B*(P+1) entries;
  * reduction block blk writes its contiguous [B,K_blk] idx array at offset blk*B*(P+1) (Kept_Tokens, topk.py:196); ToMe
  * writes [unm_idx | src_idx | dst_idx] there ([B,na-r], [B,r], [B,r] back to back).  The slab holds depth*B*(P+1) entries.
@@ -767,7 +792,9 @@ int tr_stage_decisions(const int32_t* kept_idx, const int32_t* compl_idx, size_t
  *   (timm 0.4.12 drop_path, topk.py:78,87,95) as fp32 [2*depth, B]: entry [2i][b] / [2i+1][b] = the scale (0 or 1/keep_prob) of
  *   image b's attention / MLP branch in block i -- the random draw is the caller's.  Dropout: see below.
  * tr_vit_backward: dlogits fp32 [B,classes] -> parameter gradients.  Headless (num_classes == 0): the forward's `logits` are the CLS features
- *   fp32 [B,D], `dlogits` is their gradient fp32 [B,D], no classifier gradient is computed and grads->head_w / head_b may be NULL.  `w` = the forward's weights; `wt` = same struct with the block
+ *   fp32 [B,D], `dlogits` is their gradient fp32 [B,D], no classifier gradient is computed and grads->head_w / head_b may be NULL.
+ *   global_pool == 1: the final norm's row gradient is spread over the patch rows by tr_token_pool_bwd (the forward's weights, read from
+ *   the tape; no gradient with respect to them); the same units, ranges and frozen-parameter rules.  `w` = the forward's weights; `wt` = same struct with the block
  *   matrices TRANSPOSED (bf16: qkv_w [D,3D], proj_w [D,D], fc1_w [D,Hd], fc2_w [Hd,D]); `grads` = same struct, every pointer an
  *   fp32 buffer of the parameter's shape (written; added to when accumulate != 0).  workspace: tr_vit_backward_workspace_bytes.
  *   [blk_hi .. blk_lo]: the blocks this call walks, in reverse; blk_hi == depth-1 runs the classifier + final norm first, blk_lo == 0

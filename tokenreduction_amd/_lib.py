@@ -20,6 +20,7 @@ TR_FAMILY_DEIT, TR_FAMILY_TOPK, TR_FAMILY_EVIT, TR_FAMILY_TOME, TR_FAMILY_DYVIT,
 TR_PREC_BF16, TR_PREC_FP32, TR_PREC_BF16X3 = 0, 1, 2
 TR_LAYOUT_NCHW, TR_LAYOUT_NHWC = 0, 1
 TR_INPUT_F32, TR_INPUT_U8_NCHW, TR_INPUT_U8_NHWC = 0, 1, 2
+TR_POOL_CLS, TR_POOL_AVG = 0, 1          # tr_vit_config.global_pool
 TR_MAX_DECISION_STAGES = 32
 TR_DECISION_PRUNE, TR_DECISION_EVIT, TR_DECISION_ATS, TR_DECISION_CENTRES, TR_DECISION_TOME, TR_DECISION_SOFT = 0, 1, 2, 3, 4, 5
 
@@ -46,7 +47,7 @@ class TrVitConfig(C.Structure):
     _fields_ = [("family", _i), ("img_size", _i), ("patch", _i), ("in_chans", _i), ("embed_dim", _i),
                 ("depth", _i), ("num_heads", _i), ("mlp_hidden", _i), ("num_classes", _i), ("ln_eps", _f),
                 ("keep", _i * TR_MAX_DEPTH), ("precision", _i), ("knn_k", _i), ("cluster_iters", _i), ("sinkhorn_eps", _f),
-                ("kmed_init", _i * TR_MAX_DEPTH), ("ats_dynamic", _i), ("concurrent", _i)]
+                ("kmed_init", _i * TR_MAX_DEPTH), ("ats_dynamic", _i), ("concurrent", C.c_short), ("global_pool", C.c_short)]       # the two 16-bit halves of the last word
 
 
 class TrVitTaps(C.Structure):        # tr_vit_taps: the output taps of tr_vit_forward_taps
@@ -218,6 +219,8 @@ SIGNATURES = {
     "tr_stage_decisions": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "tr_cls_tap": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _i, _vp]),
     "tr_final_tokens_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "tr_token_pool": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "tr_token_pool_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tr_vit_forward_train_pixels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
                                          C.POINTER(_i), _i, _vp, _vp, _f]),
     "tr_vit_forward_train_aug": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,

@@ -14,6 +14,8 @@ inline bool trainable_family(int family) {
          family == TR_FAMILY_DPCKNN || family == TR_FAMILY_ATS || family == TR_FAMILY_DYVIT || family == TR_FAMILY_KMEDOIDS ||
          family == TR_FAMILY_HEURISTIC || family == TR_FAMILY_SIT || family == TR_FAMILY_PATCHMERGER || family == TR_FAMILY_SINKHORN;
 }
+// global_pool == 1: the per-token weights of the pool -- ToMe's token sizes, the ATS padding mask; every other family pools with ones
+inline bool pool_weighted(int family) { return family == TR_FAMILY_TOME || family == TR_FAMILY_ATS; }
 inline bool soft_family(int family) { return family == TR_FAMILY_SIT || family == TR_FAMILY_PATCHMERGER || family == TR_FAMILY_SINKHORN; }
 inline int soft_ld(int K) { return (K + 7) / 8 * 8; }          // row stride of the token-major weight matrices (= tr_stage_weights.n_pad)
 inline int soft_ld64(int K) { return (K + 63) / 64 * 64; }     // row stride of their bf16 gradient (a GEMM contraction dimension)
@@ -31,6 +33,7 @@ inline size_t proj_rows(const tr_vit_config* c, const TokenPlan& t, int i) {
 }
 
 inline bool make_token_plan(const tr_vit_config* c, TokenPlan* t) {
+  if (c->global_pool != 0 && c->global_pool != 1) return false;      // 0 = the CLS row, 1 = the average of the patch tokens
   const int g = c->img_size / c->patch;
   t->P = g * g;
   t->N0 = t->P + 1;
@@ -116,7 +119,7 @@ struct BlockTape {
 struct TapePlan {
   BlockTape blk[TR_MAX_DEPTH];
   size_t cols;     // bf16 [B*P, C*p*p]  im2col of the images (PatchEmbed's weight-gradient operand)
-  size_t xfinal;   // fp32 [B, D]        CLS rows entering the final norm
+  size_t xfinal;   // fp32 [B, D]        the rows entering the final norm: the CLS rows, or (global_pool == 1) the pooled patch tokens
   size_t xcls;     // bf16 [B, D]        final norm output (the classifier's operand)
   size_t ones;     // fp32 [B, N0]       DyViT: the all-ones policy of the blocks before the first predictor stage
   size_t xfin_all; // fp32 [B, N0, D]    DyViT: the whole stream entering the final norm (the distillation features need every row)

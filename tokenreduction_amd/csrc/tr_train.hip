@@ -22,7 +22,7 @@ void tr_ln_defer_end();
 namespace {
 
 struct BwdPlan {
-  size_t g0, g1, gb0, gb1, gb2, dxn, dqkv, dao, dh, zeros, wsf, dscore, gfused, invmap, dxcls, dl16, dpol, dprev, dpolpart, soft_dp, soft_ds, soft_s, attn_stats, lnpart, total;
+  size_t g0, g1, gb0, gb1, gb2, dxn, dqkv, dao, dh, zeros, wsf, dscore, gfused, invmap, dxcls, dl16, dpol, dprev, dpolpart, soft_dp, soft_ds, soft_s, attn_stats, lnpart, gpool, total;
   size_t wsf_floats, lnpart_floats;
 };
 
@@ -98,6 +98,7 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
   for (int i = 0; i < c->depth; ++i) ln_norms += c->keep[i] > 0 ? 1 : 0;
   p->lnpart_floats = (size_t)(ln_norms < 16 ? ln_norms : 16) * tr_layernorm_bwd_workspace_floats((int)T, (int)D);
   p->lnpart = take(p->lnpart_floats * 4);
+  p->gpool = c->global_pool == 1 ? take((size_t)B * D * 4) : 0;      // gradient of the pooled rows fp32 [B, D] (tr_token_pool_bwd's input)
   p->total = o;
   return true;
 }
@@ -155,6 +156,9 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 // the final norm first; blk_lo == 0 also runs the embedding gradients last.
 // Headless (num_classes == 0): dlogits is the gradient of the CLS features fp32 [B,D]; it enters the final norm's backward rounded to bf16
 // (what the classifier's data gradient hands it), and w->head_* / grads->head_* are not read.
+// Average-pooled head (global_pool == 1): the tape's xfinal holds the pooled patch tokens, the final norm's backward writes its row gradient
+// to a [B,D] buffer and tr_token_pool_bwd spreads it over the patch rows of g (zeros in the CLS rows; weights: the sizes / the mask the
+// last merging / sampling block left on the tape) instead of the memset + CLS-row write; everything below is the same walk.
 // DyViT only: dpred (nullable) fp32 [stages, B, P]: gradient wrt each stage's out_pred_prob (the ratio loss, losses.py:113-118), stages in
 // block order; dfeat (nullable) fp32 [B, N0, D]: gradient wrt the final-norm token features (distillation, losses.py:134-156; row 0 = 0).  The gradient of the residual stream stays in the
 // workspace between calls, so a backward pass is the calls (depth-1 .. a), (a-1 .. b), ..., (c .. 0) in this order.
@@ -272,9 +276,25 @@ int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit
     else
       TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
                          reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
-    TR_REQUIRE(hipMemsetAsync(g, 0, (size_t)B * Nl * D * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-    TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, g, (long)Nl * D, nullptr, nullptr, 0, 0,
-                            0, nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));
+    if (cfg->global_pool == 1) {
+      // average-pooled head: xfinal holds the pooled patch tokens; the norm's row gradient goes to a [B, D] buffer and tr_token_pool_bwd
+      // spreads it over the patch rows with the forward's weights (the sizes / the mask the last merging / sampling block left on the tape;
+      // no gradient with respect to them) -- it writes every element of g, the CLS rows' zeros included: no memset
+      TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: global_pool = avg is not built for DyViT in training mode");
+      float* gpool = reinterpret_cast<float*>(ws + bp.gpool);
+      TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, gpool, D, nullptr, nullptr, 0, 0, 0,
+                              nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));
+      if (!walk) return TR_OK;      // the final norm was the lowest parameter
+      const float* pool_w = nullptr;
+      if (trplan::pool_weighted(cfg->family))
+        for (int j = cfg->depth - 1; j >= 0 && pool_w == nullptr; --j)
+          if (t.kk[j] > 0) pool_w = reinterpret_cast<const float*>(tape + tp.blk[j].size);
+      TR_TRY(tr_token_pool_bwd(gpool, pool_w, g, B, Nl, D, s));
+    } else {
+      TR_REQUIRE(hipMemsetAsync(g, 0, (size_t)B * Nl * D * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
+      TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, g, (long)Nl * D, nullptr, nullptr, 0,
+                              0, 0, nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));
+    }
     if (dfeat != nullptr) {
       // distillation: gradient wrt the final norm of every row (dyvit.py:252): a second pass of the norm's backward over all rows
       TR_REQUIRE(cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: dfeat is DyViT's distillation gradient");

@@ -4,6 +4,8 @@
 // (evit.py:209-244) and deit_viz.VisionTransformer.forward (:186-212), eval mode:
 //   patch_embed -> cat(cls) + pos_embed -> 12 x Block -> norm -> x[:,0] -> head
 // with Block_TopK.forward (topk.py:83-99):  x += attn(norm1(x)); [Top-K gather]; x += mlp(norm2(x)).
+// tr_vit_config.global_pool == 1 replaces `norm -> x[:,0]` by `weighted mean of x[:,1:] -> norm` (timm's global_pool='avg' with fc_norm;
+// tr_pool.hip, pooled_norm_head below): not a head the reference has.
 //
 // Host-side only: shape bookkeeping and kernel launches (no allocation, no synchronisation, no
 // device->host copies), so one call is a fixed launch sequence that a caller may capture in a hipGraph.
@@ -38,7 +40,7 @@ using trplan::align_up;
 
 struct Plan {
   int P, N0, D, H, Hd, C, kcols;
-  size_t off_x0, off_x1, off_xn, off_qkv, off_ao, off_h, off_d, off_d2, off_cols, off_cls, off_scores, off_idx, off_compl, off_xcls, off_size0, off_size1, off_cluster, off_soft, off_mlp_sk, mlp_sk_bytes, off_misc, total;
+  size_t off_x0, off_x1, off_xn, off_qkv, off_ao, off_h, off_d, off_d2, off_cols, off_cls, off_scores, off_idx, off_compl, off_xcls, off_size0, off_size1, off_cluster, off_soft, off_mlp_sk, mlp_sk_bytes, off_misc, off_pool, total;
 };
 
 bool make_plan(const tr_vit_config* c, int B, Plan* p) {
@@ -49,6 +51,7 @@ bool make_plan(const tr_vit_config* c, int B, Plan* p) {
   if (c->depth <= 0 || c->depth > TR_MAX_DEPTH) return false;
   if (c->num_heads <= 0 || c->embed_dim != c->num_heads * 64) return false;
   if (c->family < TR_FAMILY_DEIT || c->family > TR_FAMILY_HEURISTIC) return false;
+  if (c->global_pool != 0 && c->global_pool != 1) return false;
   const int g = c->img_size / c->patch;
   p->P = g * g;
   p->N0 = p->P + 1;
@@ -94,6 +97,8 @@ bool make_plan(const tr_vit_config* c, int B, Plan* p) {
   o += align_up(p->mlp_sk_bytes);
   p->off_misc = o;          // device words read back by the host (ATS dynamic width)
   o += align_up(256);
+  p->off_pool = o;          // global_pool == 1: the pooled patch tokens fp32 [B, D], the final norm's input (no slot otherwise)
+  if (c->global_pool == 1) o += align_up((size_t)B * p->D * 4);
   p->total = o;
   return true;
 }
@@ -221,6 +226,7 @@ struct Fwd {
   // round's idle compute units, and whole blocks round-robin move no accumulators (125 MB per launch at the first stage): measured with two
   // forwards in flight +0.5 % (Top-K kr 0.7), +1.5 % (kr 0.5), +2 % (dense DeiT-S); one at a time -1.5 ... -4 % (tools/lab/inflight_ab2.py)
   bool sk_ok;
+  bool pool;                    // global_pool == 1: the head reads the average of the patch tokens (pooled_norm_head), the last block stays full width
   bool one_memset;              // the stream-K counters of every fused-Mlp launch (block i: set i) are zeroed by ONE memset in front of the blocks
 
   // ---- buffers: the shared scratch ... ------------------------------------------------------------------------------------------------
@@ -276,6 +282,7 @@ struct Fwd {
     lazy_base = !train && !f32 && !lab().ln_eager && features_out == nullptr;
     rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
     conc = (!train && cfg->concurrent) ? 1 : 0;
+    pool = cfg->global_pool == 1;
     sk_ok = p.mlp_sk_bytes > 0 && !lab().mlp_no_streamk && !conc;
     one_memset = !train && prec == TR_PREC_BF16 && sk_ok && w->blocks[0].mlp_pk != nullptr && !lab().mlp_memset_each;
     x = scratch(p.off_x0);
@@ -678,12 +685,13 @@ struct Fwd {
       TR_REQUIRE(cfg->keep[i] >= 0, TR_ERR_CONFIG, "tr_vit_forward: block %d has negative ToMe r", i);
       r = cfg->keep[i] < (N - 1) / 2 ? cfg->keep[i] : (N - 1) / 2;
     }
-    // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features).
+    // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features,
+    // no final tokens, no average pool).
     // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
     // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
     // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
-    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr && K == 0 && r == 0 &&
-           Ks == 0 &&
+    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr && !pool && K == 0 &&
+           r == 0 && Ks == 0 &&
            drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0 &&
            tr_attention_cls_available() != 0;
     norm2_in_mlp = false;
@@ -926,6 +934,7 @@ struct Fwd {
       TR_TRY(tr_layernorm_f32(x, D, nullptr, D, w->norm_g, w->norm_b, features_out, B * N, D, cfg->ln_eps, s));
       pending = nullptr;
     }
+    if (pool) return pooled_norm_head();
     if (train && headless)          // the CLS rows entering the norm stay on the tape (xfinal) for the backward; the tape's xcls is not needed
       return tr_layernorm_bf16_f32(x, ld, slot(tp->xfinal), D, u16(pending), ld, nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s);
     if (train) {
@@ -936,6 +945,25 @@ struct Fwd {
     } else {
       TR_TRY(op_ln_pending(f32, x, ld, pending, pending_attn, ldd_cls, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
     }
+    return op_gemm(prec, xcls, w->head_w, w->head_b, logits, nullptr, 0, B, p.C, D, TR_EPI_F32, s);
+  }
+
+  // global_pool == 1 (timm's global_pool='avg' with fc_norm): the weighted mean of the patch rows of x + the pending residuals -> B rows of D
+  // fp32 (training: the tape's xfinal, the final norm's input), then the same final norm and classifier on those rows -- row stride D, nothing
+  // pending.  Weights: ToMe's sizes after the last merge / the ATS padding mask, none (ones) before the first such stage and in every other
+  // family -- Heuristic's size_cur is a KEY mask: its tokens all stay and all count
+  int pooled_norm_head() {
+    const bool headless = p.C == 0;
+    TR_REQUIRE(pending_ld == 0, TR_ERR_CONFIG, "tr_vit_forward: internal: average pool behind a CLS tail");
+    const void* first = pending_attn != nullptr ? pending_attn : pending;
+    const void* second = pending_attn != nullptr ? pending : nullptr;
+    float* pooled = train ? slot(tp->xfinal) : scratch(p.off_pool);
+    TR_TRY(tr_token_pool(x, first, second, f32 ? 1 : 0, trplan::pool_weighted(cfg->family) ? size_cur : nullptr, pooled, B, N, D, s));
+    if (train && headless)
+      return tr_layernorm_bf16_f32(pooled, D, nullptr, 0, nullptr, 0, nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s);
+    if (headless) return op_ln_pending(f32, pooled, D, nullptr, nullptr, D, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s, true);
+    if (train) xcls = tape + tp->xcls;
+    TR_TRY(op_ln(f32, pooled, D, nullptr, D, w->norm_g, w->norm_b, xcls, B, D, cfg->ln_eps, s));
     return op_gemm(prec, xcls, w->head_w, w->head_b, logits, nullptr, 0, B, p.C, D, TR_EPI_F32, s);
   }
 };
@@ -951,13 +979,17 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   Plan p;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
-             "tr_vit_forward: invalid config (need embed_dim == 64*heads, dims %% 64 == 0, classes >= 0 and %% 4 == 0, depth <= %d)",
+             "tr_vit_forward: invalid config (need embed_dim == 64*heads, dims %% 64 == 0, classes >= 0 and %% 4 == 0, depth <= %d, "
+             "global_pool 0 or 1)",
              TR_MAX_DEPTH);
   TR_REQUIRE(workspace_bytes >= p.total, TR_ERR_SHAPE, "tr_vit_forward: workspace too small (%zu < %zu)", workspace_bytes, p.total);
   TR_REQUIRE(tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_forward: workspace must be 16-byte aligned");
   TR_REQUIRE(input_format == TR_INPUT_F32 || input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
              "tr_vit_forward: input_format %d is not a TR_INPUT_* format", input_format);
   TR_REQUIRE(input_format == TR_INPUT_F32 || pixel_lut != nullptr, TR_ERR_CONFIG, "tr_vit_forward: a uint8 input needs the pixel LUT");
+  TR_REQUIRE(!(cfg->global_pool == 1 && tape != nullptr && cfg->family == TR_FAMILY_DYVIT), TR_ERR_CONFIG,
+             "tr_vit_forward_train: global_pool = avg is not built for DyViT in training mode (masked tokens stay in the stream under a "
+             "differentiable policy, there is no token set to average over); DyViT eval pools like Top-K");
   if (taps != nullptr && (taps->cls_blocks != 0 || taps->final_tokens_out != nullptr)) {
     TR_REQUIRE(tape == nullptr, TR_ERR_CONFIG, "tr_vit_forward_taps: output taps are an eval feature");
     TR_REQUIRE(features_out == nullptr, TR_ERR_CONFIG, "tr_vit_forward_taps: output taps and features_out in one call");

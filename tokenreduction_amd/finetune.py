@@ -142,7 +142,8 @@ def load_finetune_checkpoint(model, checkpoint):
     """Ingest of a pre-trained checkpoint for fine-tuning (train.py:343-370): `checkpoint` is what torch.load returns for a
     DeiT-layout .pth ({"model": state_dict}) or the state dict itself.  A classifier whose shape does not fit the model is dropped,
     the position embedding is resized to the model's patch grid (class / distillation rows kept, the grid bicubically
-    interpolated -- 14 x 14 -> 24 x 24 for a 224 -> 384 fine-tune), everything else is loaded non-strictly.  Returns load_state_dict's
+    interpolated -- 14 x 14 -> 24 x 24 for a 224 -> 384 fine-tune), a model with global_pool='avg' takes a checkpoint's fc_norm.* as its
+    norm.* when the checkpoint has no norm.* of its own (timm's layout of MAE fine-tuned weights), everything else is loaded non-strictly.  Returns load_state_dict's
     (missing_keys, unexpected_keys).  Host-side only: the executor re-packs its operand copies at the next forward (new addresses
     and values are detected by the packing key)."""
     import torch.nn.functional as F
@@ -151,6 +152,11 @@ def load_finetune_checkpoint(model, checkpoint):
     for k in ("head.weight", "head.bias", "head_dist.weight", "head_dist.bias"):
         if k in sd and k in own and sd[k].shape != own[k].shape:
             del sd[k]
+    if getattr(model, "global_pool", "") == "avg":
+        # an average-pooled timm checkpoint (MAE fine-tuning) keeps its final norm as fc_norm -- applied after the pool, like this model's norm
+        for k in ("weight", "bias"):
+            if f"fc_norm.{k}" in sd and f"norm.{k}" not in sd:
+                sd[f"norm.{k}"] = sd.pop(f"fc_norm.{k}")
     pos = sd.get("pos_embed")
     if pos is not None and pos.shape != model.pos_embed.shape:
         n_patches = model.patch_embed.num_patches

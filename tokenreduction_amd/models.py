@@ -17,6 +17,10 @@ more than 640 tokens) raises there.  In eval mode every family runs at up to 102
 inputs) in all three precisions; more tokens raise.
 A headless model (num_classes=0 or reset_classifier(0): head = nn.Identity(), deit_viz.py:142,182) returns the fp32 final-normed CLS row
 [B, embed_dim] wherever a classifier returns logits -- eval in all three precisions, viz_mode, forward_async, training and its backward.
+global_pool='avg' (constructor, create_model, reset_classifier; timm's average-pooled head with fc_norm, the MAE fine-tuning layout): the
+head -- or a headless model's output -- reads LayerNorm(weighted mean of the patch tokens after the last block) instead of the final-normed CLS
+row; the weights are ToMe's token sizes and the ATS padding mask, ones elsewhere.  Eval in all three precisions, training and backward; DyViT
+refuses it in train mode (its masked tokens stay in the stream).  '' and 'token' are the CLS row, the default.
 Intermediate outputs of an eval forward: viz_mode (every row of every recorded block, on the host) or the output taps of forward_taps /
 forward_async -- the CLS rows after chosen blocks and the final-normed tokens, fp32 device tensors written while the fast path runs.
 The stages' decisions (which tokens each stage kept, which output every token went to) come the same two ways: viz_mode's viz_data, or
@@ -209,6 +213,15 @@ class _Packer:
         return c.data_ptr()
 
 
+def _pool_code(global_pool):
+    """tr_vit_config.global_pool for timm's `global_pool` argument: '' and 'token' read the CLS row, 'avg' the average of the patch tokens."""
+    if global_pool in ("", "token"):
+        return _lib.TR_POOL_CLS
+    if global_pool == "avg":
+        return _lib.TR_POOL_AVG
+    raise ValueError(f"global_pool must be '', 'token' (the CLS row) or 'avg' (the average of the patch tokens), got {global_pool!r}")
+
+
 class VisionTransformer(nn.Module):
     """DeiT trunk, no reduction (deit_viz.py:75-212); also the base class of the reduction models."""
 
@@ -225,8 +238,9 @@ class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., embed_layer=None, norm_layer=None,
-                 act_layer=None, weight_init='', args=None):
+                 act_layer=None, weight_init='', args=None, global_pool=''):
         super().__init__()
+        _pool_code(global_pool)
         if distilled:
             # the reference's forwards only ever concatenate cls_token -- deit_viz.py:186-189 adds the [1, P + 2, D] position
             # embedding of a distilled model to P + 1 tokens (a broadcast error at the first forward), and head_dist is only created by
@@ -242,6 +256,7 @@ class VisionTransformer(nn.Module):
         if embed_dim != 64 * num_heads:
             raise ValueError("head_dim must be 64 (192/3, 384/6, 768/12 in models_act.py)")
         self.num_classes = num_classes
+        self.global_pool = global_pool   # '' / 'token': the head reads the CLS row; 'avg': LayerNorm(average of the patch tokens) (timm's fc_norm)
         self.num_features = self.embed_dim = embed_dim
         self.num_tokens = 1
         self.depth = depth
@@ -346,12 +361,21 @@ class VisionTransformer(nn.Module):
     def get_classifier(self):
         return self.head
 
-    def reset_classifier(self, num_classes, global_pool=''):
+    def reset_classifier(self, num_classes, global_pool=None):
+        """timm's reset_classifier: a new head of `num_classes` outputs (0: headless); global_pool '' / 'token' (the CLS row) or 'avg' (the
+        average of the patch tokens, normed after the pool) changes what the head reads, None keeps the current pooling."""
+        if global_pool is not None:
+            _pool_code(global_pool)
+            self.global_pool = global_pool
         self.num_classes = num_classes
         dev = self.pos_embed.device
         self.head = (nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()).to(dev)
         self._packed = None
         self._tstate = None          # the flat gradient buffer is laid out for the old head
+
+    def _pool_mode(self):
+        """tr_vit_config.global_pool of this model (ValueError for a value written into the attribute that is none of '', 'token', 'avg')."""
+        return _pool_code(self.global_pool)
 
     @property
     def _classes_padded(self):
@@ -412,7 +436,7 @@ class VisionTransformer(nn.Module):
         if need_transposed:
             self._want_transposed = True
         want_t = self._want_transposed and self.precision == "bf16"
-        key = (self.precision, want_t) + self._param_key()
+        key = (self.precision, want_t, self._pool_mode()) + self._param_key()
         if self._packed is not None and self._packed["key"] == key and not self._weights_dirty:
             return self._packed
         self.sync_pipeline()        # the operand copies are rewritten in place: no forward_async forward may still be reading them
@@ -481,6 +505,7 @@ class VisionTransformer(nn.Module):
         cfg.knn_k = int(getattr(self, "k_neighbors", 0))
         cfg.cluster_iters = int(getattr(self, "sinkhorn_iters", 0))
         cfg.sinkhorn_eps = float(getattr(self, "sinkhorn_eps", 0.0))
+        cfg.global_pool = self._pool_mode()
         for i in range(self.depth):
             cfg.keep[i] = int(self._keep[i])
         old = self._packed

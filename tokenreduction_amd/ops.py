@@ -506,6 +506,40 @@ def final_tokens_f32(x: torch.Tensor, gamma, beta, eps: float, d1: torch.Tensor 
     return y
 
 
+def _pool_weight(weight, B, N):
+    if weight is not None and tuple(weight.shape) != (B, N):
+        raise ValueError(f"weight must be [B, N] = [{B}, {N}] (entry 0, the CLS token's, is not read), got {tuple(weight.shape)}")
+    return _opt(weight, torch.float32, "weight")
+
+
+def token_pool(x: torch.Tensor, d1: torch.Tensor = None, d2: torch.Tensor = None, weight: torch.Tensor = None) -> torch.Tensor:
+    """out fp32 [B, D] = sum_n w[b,n] v[b,n] / sum_n w[b,n] over the patch rows n = 1 .. N-1 of v = (x + d1) + d2 (tr_token_pool): x fp32
+    [B, N, D], the pending operands bf16 or fp32 [B, N, D] (both nullable), weight fp32 [B, N] or None (all ones).  Row 0 (CLS) is left out;
+    an image whose weights sum to 0 pools to zeros.  Deterministic: the same bits on every launch and in any batch."""
+    _same_device(x, d1, d2, weight)
+    B, N, D = x.shape
+    for d, name in ((d1, "d1"), (d2, "d2")):
+        if d is not None and d.shape != x.shape:
+            raise ValueError(f"{name} must have x's shape {tuple(x.shape)}, got {tuple(d.shape)}")
+    out = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().tr_token_pool(_dev(x, torch.float32, "x"), _pending(d1, "d1"), _pending(d2, "d2"), _pending_f32(d1, d2),
+                                         _pool_weight(weight, B, N), out.data_ptr(), B, N, D, _stream(x)), "tr_token_pool")
+    return out
+
+
+def token_pool_bwd(gpool: torch.Tensor, N: int, weight: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+    """g fp32 [B, N, D]: g[b,0] = 0, g[b,n] = gpool[b] * (w[b,n] / sum_n w[b,n]) (tr_token_pool_bwd), the gradient of token_pool with
+    respect to x (and to each pending operand) for gpool fp32 [B, D]; every element of g is written (out: a buffer to write into)."""
+    _same_device(gpool, weight, out)
+    B, D = gpool.shape
+    g = torch.empty(B, N, D, dtype=torch.float32, device=gpool.device) if out is None else out
+    if tuple(g.shape) != (B, N, D):
+        raise ValueError(f"out must be [B, N, D] = [{B}, {N}, {D}], got {tuple(g.shape)}")
+    _lib.check(_lib.load().tr_token_pool_bwd(_dev(gpool, torch.float32, "gpool"), _pool_weight(weight, B, N), _dev(g, torch.float32, "out"),
+                                             B, N, D, _stream(gpool)), "tr_token_pool_bwd")
+    return g
+
+
 def decision_table(stages, B: int):
     """tr_stage_decisions' host table for `stages` [(blk, _lib.TR_DECISION_* kind, n_in, k)] at batch size B, its outputs laid out back to
     back: (ctypes table, [(blk, n_in, W, kept_off, A, assign_off)], kept elements, assign elements, soft elements) -- W / A: width of the

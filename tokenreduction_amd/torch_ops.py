@@ -7,7 +7,7 @@
 Each op has (a) a CUDA (= HIP on ROCm) implementation that calls the library through `ops.py` -- no CPU implementation is
 registered, so a CPU tensor fails loudly with the dispatcher's "no kernel for backend CPU" error instead of falling back;
 (b) a fake (meta) implementation giving output shapes / dtypes, so `torch.compile`, FakeTensorMode and `torch.export` trace
-through the ops without running them; (c) for `linear`, `layernorm`, `attention` and `gelu` an autograd formula whose
+through the ops without running them; (c) for `linear`, `layernorm`, `attention`, `gelu` and `token_pool` an autograd formula whose
 backward is again a HIP entry point -- the hook-up point for a user who composes their own blocks from the ops instead of
 using the whole-model executor (`models.py`, whose single autograd node lives in `training.py`).
 
@@ -135,7 +135,22 @@ _define("softassign_merge(Tensor logits, float scale, Tensor x, int K, bool appl
         lambda logits, scale, x, K, apply_softmax, src: x.new_empty((x.shape[0], K + 1, x.shape[2])))
 
 
+def _token_pool(x: Tensor, weight: Optional[Tensor]) -> Tensor:
+    return _ops.token_pool(x.contiguous(), weight=weight)
+
+
+_define("token_pool(Tensor x, Tensor? weight) -> Tensor", _token_pool, lambda x, weight: x.new_empty((x.shape[0], x.shape[2])))
+
+
 # ------------------------------------------------------------------------------------------------------------ backward ops
+def _token_pool_bwd(gpool: Tensor, N: int, weight: Optional[Tensor]) -> Tensor:
+    return _ops.token_pool_bwd(gpool, N, weight=weight)
+
+
+_define("token_pool_bwd(Tensor gpool, int N, Tensor? weight) -> Tensor", _token_pool_bwd,
+        lambda gpool, N, weight: gpool.new_empty((gpool.shape[0], N, gpool.shape[1])))
+
+
 def _linear_bwd(dy: Tensor, a: Tensor, w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """(d a bf16 [M,K], dW fp32 [N,K], d bias fp32 [N]) of y = a w^T + bias for dy bf16 [M,N]."""
     dw, db = _ops.linear_bwd_params(dy, a)
@@ -236,5 +251,17 @@ def _gelu_backward(ctx, dh):
 
 torch.library.register_autograd(f"{NS}::gelu", _gelu_backward, setup_context=_gelu_setup)
 
+def _token_pool_setup(ctx, inputs, output):
+    x, weight = inputs
+    ctx.save_for_backward(weight)
+    ctx.N = x.shape[1]
+
+
+def _token_pool_backward(ctx, gpool):          # no gradient with respect to the weights (token sizes / masks are decisions)
+    return torch.ops.tokenreduction_amd.token_pool_bwd(gpool.contiguous(), ctx.N, ctx.saved_tensors[0]), None
+
+
+torch.library.register_autograd(f"{NS}::token_pool", _token_pool_backward, setup_context=_token_pool_setup)
+
 OPS = ("linear", "layernorm", "gelu", "attention", "cls_topk", "gather_layernorm", "tome_match", "dpcknn_cluster", "softassign_merge",
-       "linear_bwd", "layernorm_bwd", "attention_bwd", "gelu_bwd")
+       "token_pool", "linear_bwd", "layernorm_bwd", "attention_bwd", "gelu_bwd", "token_pool_bwd")

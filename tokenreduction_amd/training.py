@@ -434,6 +434,10 @@ class _VitTrainFn(torch.autograd.Function):
 
 
 def train_forward(model, x: torch.Tensor) -> torch.Tensor:
+    if model._family == _lib.TR_FAMILY_DYVIT and model._pool_mode() == _lib.TR_POOL_AVG:
+        raise NotImplementedError("global_pool='avg' is not built for DyViT in train mode: training keeps the masked tokens in the stream under a "
+                                  "differentiable policy (dyvit.py:221-229), so there is no token set to average over; DyViT eval, where the tokens "
+                                  "are removed, pools like Top-K -- train with global_pool='' or call model.eval()")
     if not x.is_cuda:
         raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
     if model.precision != "bf16":
