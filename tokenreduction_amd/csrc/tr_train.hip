@@ -9,6 +9,9 @@
 // merge tome.py:309-323).  A call may cover a RANGE of blocks [blk_hi .. blk_lo]: the caller walks the model in a few ranges and,
 // after each, starts that range's gradient bucket on RCCL from a second stream while the next range runs (the DDP overlap).
 // Host-side only: no allocation, no synchronisation -- capturable in a hipGraph.
+//
+// vit_backward validates, works out the frozen-unit plan, builds one Bwd and calls its steps ("The backward executor, step
+// by step"); tests/test_backward_trace_gpu.py pins the launch sequence and the gradient bits.
 #include "tr_common.h"
 #include "tr_plan.h"
 
@@ -23,7 +26,7 @@ namespace {
 
 struct BwdPlan {
   size_t g0, g1, gb0, gb1, gb2, dxn, dqkv, dao, dh, zeros, wsf, dscore, gfused, invmap, dxcls, dl16, dpol, dprev, dpolpart, soft_dp, soft_ds, soft_s, attn_stats, lnpart, gpool, total;
-  size_t wsf_floats, lnpart_floats;
+  size_t wsf_floats, lnpart_floats, zeros_floats, attn_stats_floats;
 };
 
 bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, BwdPlan* p) {
@@ -40,8 +43,9 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
   p->dqkv = take(T * 3 * D * 2);
   p->dao = take(T * D * 2);
   p->dh = take(T * Hd * 2);
-  size_t zmax = 3 * D > Hd ? 3 * D : Hd;
+  size_t zmax = 3 * D > Hd ? 3 * D : Hd;          // the zero bias of every data-gradient GEMM: the widest output
   if (kcols > zmax) zmax = kcols;
+  p->zeros_floats = zmax;
   p->zeros = take(zmax * 4);
   // scratch of the two-stage reductions: the largest request of any call below
   size_t f = tr_wgrad_workspace_floats((int)T, (int)(3 * D), (int)D);
@@ -85,7 +89,9 @@ bool make_bwd_plan(const tr_vit_config* c, int B, const trplan::TokenPlan& t, Bw
   p->dpol = take(T * 4);
   p->dprev = take(T * 4);
   p->dpolpart = take(T * c->num_heads * 4);
-  p->attn_stats = t.N0 > 224 ? take(tr_attention_bwd_long_workspace_floats(B, t.N0, c->num_heads) * 4) : 0;
+  // scratch of the key-blocked attention backward (384 x 384 inputs), sized once at the widest block
+  p->attn_stats_floats = t.N0 > 224 ? tr_attention_bwd_long_workspace_floats(B, t.N0, c->num_heads) : 0;
+  p->attn_stats = t.N0 > 224 ? take(p->attn_stats_floats * 4) : 0;
   p->soft_dp = p->soft_ds = p->soft_s = 0;
   if (soft_k > 0) {
     p->soft_dp = take(T * trplan::soft_ld(soft_k) * 4);
@@ -129,6 +135,498 @@ inline bool stage_complete(const tr_vit_config* c, const tr_stage_weights& w, co
   }
 }
 
+// Frozen parameters: which units of `grads` are there (1 / 0), and the block the walk stops at -- block i whose own parameter gradients
+// end the walk (nothing below it takes a gradient); depth: no block takes one; -1: the embedding (or dx) does, the walk goes all the way
+struct Frozen { int u_head, u_norm, u_embed, u_patch, stop; };
+
+int frozen_plan(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                const trplan::TokenPlan& t, const float* dx, Frozen* f) {
+  f->u_head = cfg->num_classes > 0 ? unit(grads->head_w, grads->head_b) : 0;
+  f->u_norm = unit(grads->norm_g, grads->norm_b);
+  f->u_embed = unit(grads->pos_embed, grads->cls_token);
+  f->u_patch = unit(grads->patch_w, grads->patch_b);
+  TR_REQUIRE(f->u_head >= 0 && f->u_norm >= 0 && f->u_embed >= 0 && f->u_patch >= 0, TR_ERR_NULL,
+             "tr_vit_backward: a gradient unit (head, norm, pos_embed + cls_token, patch) is half NULL: both pointers or neither");
+  int stop = (f->u_embed || f->u_patch || dx != nullptr) ? -1 : cfg->depth;
+  if (dx != nullptr) {
+    TR_REQUIRE(wt->patch_w != nullptr, TR_ERR_NULL, "tr_vit_backward_dx: wt->patch_w (the patch weight transposed) is NULL");
+    TR_REQUIRE(tr_patch_embed_dgrad_supported(cfg->in_chans, cfg->img_size, cfg->patch, cfg->embed_dim), TR_ERR_SHAPE,
+               "tr_vit_backward_dx: no input gradient for in_chans %d, img_size %d, patch %d, embed_dim %d (tr_patch_embed_dgrad)", cfg->in_chans,
+               cfg->img_size, cfg->patch, cfg->embed_dim);
+    TR_REQUIRE(tr_aligned16(dx), TR_ERR_ALIGN, "tr_vit_backward_dx: dx must be 16-byte aligned");
+  }
+  for (int i = 0; i < cfg->depth; ++i) {
+    const tr_block_weights& b = grads->blocks[i];
+    const int u[6] = {unit(b.ln1_g, b.ln1_b), unit(b.qkv_w, b.qkv_b), unit(b.proj_w, b.proj_b),
+                      unit(b.ln2_g, b.ln2_b), unit(b.fc1_w, b.fc1_b), unit(b.fc2_w, b.fc2_b)};
+    bool any = stage_any(grads->stage[i]);
+    for (int k = 0; k < 6; ++k) {
+      TR_REQUIRE(u[k] >= 0, TR_ERR_NULL, "tr_vit_backward: a gradient unit of block %d is half NULL: both pointers or neither", i);
+      any = any || u[k] == 1;
+    }
+    if (any && stop == cfg->depth) stop = i;
+  }
+  for (int i = stop < 0 ? 0 : stop; i < cfg->depth; ++i) {
+    const bool reached = i > stop || stage_any(grads->stage[i]);          // the stop block's stage runs only when it owns a gradient
+    TR_REQUIRE(t.kk[i] <= 0 || !reached || stage_complete(cfg, w->stage[i], grads->stage[i]), TR_ERR_NULL,
+               "tr_vit_backward: the backward reaches the reduction stage of block %d (a parameter at or below it takes a gradient) but its "
+               "gradient pointers are NULL: stage modules are frozen only below the lowest block that takes a gradient", i);
+  }
+  f->stop = stop;
+  return TR_OK;
+}
+
+// One backward call being enqueued: vit_backward builds it and calls its steps, the reference forward's order reversed.
+struct Bwd {
+  // ---- fixed inputs, each read once ---------------------------------------------------------------------------------------------------
+  const tr_vit_config* cfg;
+  const tr_vit_weights *w, *wt, *grads;
+  const trplan::TokenPlan& t;
+  const trplan::TapePlan& tp;
+  const BwdPlan& bp;
+  int B, D, H, Hd, C, kcols;
+  tr_stream_t s;
+  hipStream_t st;
+  const char* tape_;
+  char* ws_;
+  int acc;                      // 1: the gradients are added to the buffers, 0: overwritten
+  const float* drop_scale;      // DropPath: per block and image, attention branch then MLP branch
+  const uint8_t* dropout_keep;  // Dropout keep masks in the order the forward consumed them (tr_vit_dropout_mask_bytes): [pos | block 0: proj, hidden, fc2 | block 1: ...]
+  float drop_mul;
+  size_t drop_off[TR_MAX_DEPTH + 1];      // where block i's masks start
+  const float *dlogits, *dpred, *dfeat;
+  float* dx;
+  // The four parameter-gradient products of a block (fc2, fc1, proj, qkv) run as ONE launch after the attention backward, when all four dY
+  // exist -- provided nothing has rewritten fc2's dY (the bf16 stream gradient gb) by then: norm2's backward writes its bf16 output into the
+  // spare buffer instead and the two trade places.  With DropPath / dropout the scaled dY copies live in scratch that is reused: pairs then.
+  bool four;                    // the branches' dY are the stream gradient itself (no scaled / masked copies)
+  int stop;                     // Frozen::stop
+  bool u_head, u_norm, u_embed, u_patch;
+
+  // ---- buffers: the stream gradient (fp32 g, its bf16 copy gb; the _alt pair is what a token-reducing block writes, gb_spare see `four`) ...
+  float *g, *g_alt;
+  uint16_t *gb, *gb_alt, *gb_spare;
+  // ... and the scratch
+  uint16_t *dxn, *dqkv, *dao, *dh, *dxcls;
+  float *zeros, *wsf, *dscore, *gfused, *dpol, *dprev;
+  int32_t* invmap;
+  size_t wsn;
+
+  // ---- the block being walked (begin_block) -------------------------------------------------------------------------------------------
+  const trplan::BlockTape* bt = nullptr;
+  const tr_block_weights *bw = nullptr, *bwt = nullptr, *bg = nullptr;
+  int Na = 0, Nm = 0, M1 = 0, M2 = 0, Mp = 0, K = 0;      // tokens in the attention / the Mlp, rows of both, rows through proj, kk[i]
+  const uint8_t *keep_proj = nullptr, *keep_h = nullptr, *keep_fc2 = nullptr;      // [Mp, D], [M2, Hd], [M2, D]
+  tr_linear_grad LG[4];         // the weight gradients not launched yet: mlp_bwd and block_wgrads add, mlp_bwd (pairs) / block_wgrads launch
+  int nlg = 0;
+  const uint16_t* gy_proj = nullptr;      // proj's dY: stays valid until norm1's backward rewrites gb (ATS: the swapped-out buffer)
+  const float* dcls = nullptr;  // EViT: the gradient of the CLS attention row norm2_gather leaves for attention_bwd
+  bool stage_here = false;      // the block has a reduction stage that owns a gradient (block_wgrads)
+
+  // the arguments of vit_backward, validated; every member is set here
+  Bwd(const tr_vit_config* cfg_, const tr_vit_weights* w_, const tr_vit_weights* wt_, const tr_vit_weights* grads_, const trplan::TokenPlan& t_,
+      const trplan::TapePlan& tp_, const BwdPlan& bp_, const Frozen& fr, int B_, tr_stream_t s_, const void* tape, void* workspace, int accumulate,
+      const float* drop_scale_, const uint8_t* dropout_keep_, float drop_rate, const float* dlogits_, const float* dpred_, const float* dfeat_,
+      float* dx_)
+      : cfg(cfg_), w(w_), wt(wt_), grads(grads_), t(t_), tp(tp_), bp(bp_), B(B_), D(cfg_->embed_dim), H(cfg_->num_heads), Hd(cfg_->mlp_hidden),
+        C(cfg_->num_classes), kcols(cfg_->in_chans * cfg_->patch * cfg_->patch), s(s_), st(static_cast<hipStream_t>(s_)),
+        tape_(static_cast<const char*>(tape)), ws_(static_cast<char*>(workspace)), acc(accumulate ? 1 : 0), drop_scale(drop_scale_),
+        dropout_keep(dropout_keep_), drop_mul(dropout_keep_ != nullptr ? 1.0f / (1.0f - drop_rate) : 1.0f), dlogits(dlogits_), dpred(dpred_),
+        dfeat(dfeat_), dx(dx_), four(drop_scale_ == nullptr && dropout_keep_ == nullptr), stop(fr.stop), u_head(fr.u_head != 0),
+        u_norm(fr.u_norm != 0), u_embed(fr.u_embed != 0), u_patch(fr.u_patch != 0), wsn(bp_.wsf_floats) {
+    drop_off[0] = (size_t)B * t.N0 * D;
+    for (int i = 0; i < cfg->depth; ++i) drop_off[i + 1] = drop_off[i] + (size_t)B * (trplan::proj_rows(cfg, t, i) * D + (size_t)t.n_mlp[i] * (Hd + D));
+    g = ws<float>(bp.g0);
+    g_alt = ws<float>(bp.g1);
+    gb = ws<uint16_t>(bp.gb0);
+    gb_alt = ws<uint16_t>(bp.gb1);
+    gb_spare = ws<uint16_t>(bp.gb2);
+    dxn = ws<uint16_t>(bp.dxn);
+    dqkv = ws<uint16_t>(bp.dqkv);
+    dao = ws<uint16_t>(bp.dao);
+    dh = ws<uint16_t>(bp.dh);
+    dxcls = ws<uint16_t>(bp.dxcls);
+    zeros = ws<float>(bp.zeros);
+    wsf = ws<float>(bp.wsf);
+    dscore = ws<float>(bp.dscore);
+    gfused = ws<float>(bp.gfused);
+    dpol = ws<float>(bp.dpol);
+    dprev = ws<float>(bp.dprev);
+    invmap = ws<int32_t>(bp.invmap);
+  }
+
+  // ---- small helpers ------------------------------------------------------------------------------------------------------------------
+  template <class T> T* ws(size_t off) const { return reinterpret_cast<T*>(ws_ + off); }
+  template <class T> const T* tape(size_t off) const { return reinterpret_cast<const T*>(tape_ + off); }
+  int zero(void* p, size_t bytes) {
+    TR_REQUIRE(hipMemsetAsync(p, 0, bytes, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
+    return TR_OK;
+  }
+  // The stream-gradient buffers move in two ways, each under ONE predicate that the step which moves them and rewind_to both read:
+  // a block whose norm2 backward writes gb in place (no gather / merge between norm2 and the stream) rotates the spare in, when the
+  // block's four weight gradients are one launch; every token-reducing block of the built families swaps g / gb with their _alt pair
+  // once (DyViT's stages keep every token: no swap).
+  bool gathers(int j) const {
+    return (cfg->family == TR_FAMILY_TOPK || cfg->family == TR_FAMILY_EVIT || cfg->family == TR_FAMILY_TOME) && t.kk[j] > 0;
+  }
+  bool rotates_spare(int j) const { return four && !gathers(j); }
+  bool swaps_stream(int j) const { return t.kk[j] > 0 && cfg->family != TR_FAMILY_DYVIT; }
+  void rotate_spare() { uint16_t* tb = gb; gb = gb_spare; gb_spare = tb; }
+  void swap_stream() {
+    float* tg = g; g = g_alt; g_alt = tg;
+    uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
+  }
+  // which stream-gradient buffers are current at block blk_hi: the moves of the blocks above, in a block's own order (norm2's rotation first)
+  void rewind_to(int blk_hi) {
+    for (int j = cfg->depth - 1; j > blk_hi; --j) {
+      if (rotates_spare(j)) rotate_spare();
+      if (swaps_stream(j)) swap_stream();
+    }
+  }
+  // the last block below i (inclusive: at or below i) whose reduction is in force, or -1: kk > 0; Heuristic (kk is 0 everywhere): a
+  // block that sets a key mask
+  int last_reducer(int i, bool inclusive) const {
+    for (int j = inclusive ? i : i - 1; j >= 0; --j)
+      if (cfg->family == TR_FAMILY_HEURISTIC ? w->stage[j].w3 != nullptr : t.kk[j] > 0) return j;
+    return -1;
+  }
+  // what that block left on the tape: ToMe token sizes / ATS and Heuristic key masks (none before the first), DyViT's policy (all ones)
+  const float* size_at(int i, bool inclusive) const {
+    const int j = last_reducer(i, inclusive);
+    return j < 0 ? nullptr : tape<float>(tp.blk[j].size);
+  }
+  const float* pol_at(int i, bool inclusive) const {
+    const int j = last_reducer(i, inclusive);
+    return tape<float>(j < 0 ? tp.ones : tp.blk[j].pol);
+  }
+  // data gradient of a Linear: out [M, N] bf16 = dy [M, K] @ wT [K, N]
+  int dgrad(const uint16_t* dy, const void* wT, uint16_t* out, int M, int N, int Kd) {
+    return tr_gemm_bf16(dy, U(wT), zeros, out, nullptr, 0, M, N, Kd, TR_EPI_BF16, s);
+  }
+  // LayerNorm backward of M rows: g_out = g_in + d x (dy through the norm of x), gb_out its bf16 copy; dgamma / dbeta: the norm's unit of
+  // grads (NULL: frozen).  ldgo: row stride of g_out (0: D); add: accumulate (-1: acc); idx ...: norm2_gather's scatter
+  int ln_bwd(const uint16_t* dy, const float* x, const float* gamma, const void* dgamma, const void* dbeta, const float* g_in, float* g_out,
+             uint16_t* gb_out, int M, float eps, long ldgo = 0, int add = -1, const int32_t* idx = nullptr, int Kk = 0, int n_in = 0, int n_out = 0,
+             float* g_fused = nullptr) {
+    return tr_layernorm_bwd(dy, x, D, gamma, g_in, g_in != nullptr ? D : 0, g_out, ldgo ? ldgo : D, gb_out, idx, Kk, n_in, n_out, g_fused, F(dgamma),
+                            F(dbeta), add < 0 ? acc : add, wsf, wsn, M, D, eps, s);
+  }
+  int head_bwd() {
+    return tr_head_bwd(dlogits, U(w->head_w), tape<uint16_t>(tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc, ws<uint16_t>(bp.dl16), wsf,
+                       wsn, B, C, D, s);
+  }
+
+  // ---- steps, in call order -----------------------------------------------------------------------------------------------------------
+  // classifier + final norm (topk.py:201-203): the gradient enters the CLS rows of the last block's output stream (pooled head: the patch
+  // rows).  *go: the walk continues into the blocks
+  int head_and_final_norm(bool* go) {
+    *go = false;
+    const bool walk = stop < cfg->depth;          // a block (or the embedding) takes a gradient: the stream gradient is needed
+    if (!walk && !u_norm) return u_head ? head_bwd() : TR_OK;       // head-only probe: the classifier's parameter gradients and nothing else
+    TR_TRY(zero(zeros, bp.zeros_floats * 4));
+    const int Nl = t.n_mlp[cfg->depth - 1];
+    TR_TRY(C == 0 ? tr_f32_to_bf16(dlogits, dxcls, (size_t)B * D, s) : head_bwd());
+    // average-pooled head: xfinal holds the pooled patch tokens; the norm's row gradient goes to a [B, D] buffer and tr_token_pool_bwd
+    // spreads it over the patch rows with the forward's weights (the sizes / the mask the last merging / sampling block left on the tape;
+    // no gradient with respect to them) -- it writes every element of g, the CLS rows' zeros included: no memset
+    const bool pool = cfg->global_pool == 1;
+    float* gpool = pool ? ws<float>(bp.gpool) : nullptr;
+    if (pool)
+      TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: global_pool = avg is not built for DyViT in training mode");
+    else
+      TR_TRY(zero(g, (size_t)B * Nl * D * 4));
+    TR_TRY(ln_bwd(dxcls, tape<float>(tp.xfinal), w->norm_g, grads->norm_g, grads->norm_b, nullptr, pool ? gpool : g, nullptr, B, cfg->ln_eps,
+                  pool ? D : (long)Nl * D));
+    if (pool) {
+      if (!walk) return TR_OK;      // the final norm was the lowest parameter
+      TR_TRY(tr_token_pool_bwd(gpool, trplan::pool_weighted(cfg->family) ? size_at(cfg->depth - 1, true) : nullptr, g, B, Nl, D, s));
+    }
+    if (dfeat != nullptr) {
+      // distillation: gradient wrt the final norm of every row (dyvit.py:252): a second pass of the norm's backward over all rows
+      TR_REQUIRE(cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: dfeat is DyViT's distillation gradient");
+      TR_TRY(tr_f32_to_bf16(dfeat, dxn, (size_t)B * Nl * D, s));
+      TR_TRY(ln_bwd(dxn, tape<float>(tp.xfin_all), w->norm_g, grads->norm_g, grads->norm_b, g, g, nullptr, B * Nl, cfg->ln_eps, 0, 1));
+    }
+    if (!walk) return TR_OK;      // the final norm was the lowest parameter
+    TR_TRY(tr_f32_to_bf16(g, gb, (size_t)B * Nl * D, s));
+    if (cfg->family == TR_FAMILY_DYVIT) TR_TRY(zero(dpol, (size_t)B * t.N0 * 4));
+    *go = true;
+    return TR_OK;
+  }
+
+  void begin_block(int i) {
+    bt = &tp.blk[i];
+    bw = &w->blocks[i];
+    bwt = &wt->blocks[i];
+    bg = &grads->blocks[i];
+    Na = t.n_att[i];
+    Nm = t.n_mlp[i];
+    M1 = B * Na;
+    M2 = B * Nm;
+    K = t.kk[i];
+    Mp = (int)trplan::proj_rows(cfg, t, i) * B;      // ATS: only the sampled rows went through proj (ats.py:86,129)
+    keep_proj = dropout_keep ? dropout_keep + drop_off[i] : nullptr;
+    keep_h = dropout_keep ? keep_proj + (size_t)Mp * D : nullptr;
+    keep_fc2 = dropout_keep ? keep_h + (size_t)M2 * Hd : nullptr;
+    nlg = 0;
+    gy_proj = nullptr;
+    dcls = nullptr;
+    stage_here = false;
+  }
+
+  // mlp: x2 -> norm2 -> fc1 -> gelu -> fc2 -> (+ residual), down to norm2's dY in dxn
+  int mlp_bwd(int i) {
+    const uint16_t* gy = gb;          // the branch's dY: the stream gradient, times the branch's DropPath scale when there is one
+    if (drop_scale != nullptr) {
+      TR_TRY(tr_rowscale_bf16(gb, dao, drop_scale + (size_t)(2 * i + 1) * B, B, Nm, D, s));
+      gy = dao;
+    }
+    if (dropout_keep != nullptr) {    // the Mlp's second dropout (after fc2): the same mask on fc2's dY
+      TR_TRY(tr_dropout_bf16(gy, dao, keep_fc2, drop_mul, (size_t)M2 * D, s));
+      gy = dao;
+    }
+    TR_TRY(tr_gemm_dgelu_bf16(gy, U(bwt->fc2_w), tape<uint16_t>(bt->pre), dh, M2, Hd, D, s));          // d fc2 input, times gelu'(pre): d pre
+    if (dropout_keep != nullptr)      // ... and the first one (after the activation): d pre = (dY W) * keep/(1-p) * gelu'(pre), the factors commute
+      TR_TRY(tr_dropout_bf16(dh, dh, keep_h, drop_mul, (size_t)M2 * Hd, s));
+    // fc2's and fc1's parameter gradients: both dY (gy, dh) exist now; launched here as a pair, or with proj's and qkv's by block_wgrads
+    // (a frozen layer is left out of the list: what remains is planned as a group of its own; an empty list launches nothing)
+    if (bg->fc2_w != nullptr) LG[nlg++] = {gy, (long)D, tape<uint16_t>(bt->h), (long)Hd, F(bg->fc2_w), F(bg->fc2_b), M2, D, Hd};
+    if (bg->fc1_w != nullptr) LG[nlg++] = {dh, (long)Hd, tape<uint16_t>(bt->xn2), (long)D, F(bg->fc1_w), F(bg->fc1_b), M2, Hd, D};
+    if (!four) TR_TRY(launch_wgrads());
+    return dgrad(dh, bwt->fc1_w, dxn, M2, D, Hd);
+  }
+  int launch_wgrads() {
+    if (nlg > 0) TR_TRY(tr_linear_bwd_group(LG, nlg, acc, wsf, wsn, s));
+    nlg = 0;
+    return TR_OK;
+  }
+
+  // norm2 (+ the block's in-block token reduction)
+  int norm2_bwd(int i) {
+    const int f = cfg->family;
+    if (swaps_stream(i) && (f == TR_FAMILY_TOPK || f == TR_FAMILY_EVIT)) return norm2_gather(i);
+    if (swaps_stream(i) && f == TR_FAMILY_TOME) return norm2_tome(i);
+    return norm2_plain(i);
+  }
+  // Top-K / EViT: the kept rows' gradients scatter back to the rows they were gathered from (EViT: + the fused token's backward)
+  int norm2_gather(int i) {
+    const bool fuse = cfg->family == TR_FAMILY_EVIT;
+    TR_TRY(zero(g_alt, (size_t)M1 * D * 4));
+    TR_TRY(zero(gb_alt, (size_t)M1 * D * 2));
+    TR_TRY(ln_bwd(dxn, tape<float>(bt->x2), bw->ln2_g, bg->ln2_g, bg->ln2_b, g, g_alt, gb_alt, M2, cfg->ln_eps, 0, -1, tape<int32_t>(bt->idx), K, Nm,
+                  Na, fuse ? gfused : nullptr));
+    if (fuse) {
+      TR_TRY(zero(dscore, (size_t)M1 * 4));
+      TR_TRY(tr_evit_fuse_bwd(tape<float>(bt->x1), tape<uint16_t>(bt->dattn), tape<int32_t>(bt->idx2), tape<float>(bt->scores), gfused, g_alt,
+                              gb_alt, dscore, B, Na, K, D, s));
+      dcls = dscore;
+    }
+    swap_stream();
+    return TR_OK;
+  }
+  int norm2_tome(int i) {
+    TR_TRY(ln_bwd(dxn, tape<float>(bt->x2), bw->ln2_g, bg->ln2_g, bg->ln2_b, g, g, nullptr, M2, cfg->ln_eps));
+    const int na = (Na + 1) / 2;
+    const int32_t* unm = tape<int32_t>(bt->idx);
+    const int32_t* src = unm + (size_t)B * (na - K);
+    const int32_t* dst = src + (size_t)B * K;
+    // sizes entering this block's merge: after the previous merging block
+    TR_TRY(tr_tome_merge_bwd(g, size_at(i, false), tape<float>(bt->size), unm, src, dst, invmap, g_alt, gb_alt, B, Na, K, D, s));
+    swap_stream();
+    return TR_OK;
+  }
+  int norm2_plain(int i) {
+    TR_TRY(ln_bwd(dxn, tape<float>(bt->x2), bw->ln2_g, bg->ln2_g, bg->ln2_b, g, g, rotates_spare(i) ? gb_spare : gb, M2, cfg->ln_eps));
+    if (rotates_spare(i)) rotate_spare();       // gb_spare: fc2's dY, until this block's weight-gradient launch
+    return TR_OK;
+  }
+
+  // proj: DropPath / proj_drop on its dY, the data gradient into dao (ATS: scattered back to the rows the block sampled from)
+  int proj_bwd(int i) {
+    const uint16_t* gy = gb;
+    if (drop_scale != nullptr) {
+      TR_TRY(tr_rowscale_bf16(gb, dh, drop_scale + (size_t)(2 * i) * B, B, Mp / B, D, s));
+      gy = dh;
+    }
+    if (dropout_keep != nullptr) {    // proj_drop (topk.py:53): the same mask on proj's dY
+      TR_TRY(tr_dropout_bf16(gy, dh, keep_proj, drop_mul, (size_t)Mp * D, s));
+      gy = dh;
+    }
+    gy_proj = gy;
+    if (!(swaps_stream(i) && cfg->family == TR_FAMILY_ATS)) return dgrad(gy, bwt->proj_w, dao, M1, D, D);
+    // d(attn @ v) of the sampled rows and the stream's gradient go back to the rows they were sampled from (ats.py:86,157)
+    TR_TRY(dgrad(gy, bwt->proj_w, dxn, Mp, D, D));
+    TR_TRY(zero(g_alt, (size_t)M1 * D * 4));
+    TR_TRY(zero(dao, (size_t)M1 * D * 2));
+    TR_TRY(tr_ats_scatter(g, dxn, tape<int32_t>(bt->idx), g_alt, dao, B, Na, Nm, D, s));
+    swap_stream();          // gb is rewritten by norm1's backward (qkv_norm1_bwd)
+    return TR_OK;
+  }
+
+  // softmax(q k^T) v: dao -> dqkv; the policy (DyViT), key-blocked (more than 224 tokens: 384 x 384 inputs) and short forms
+  int attention_bwd(int i) {
+    const int f = cfg->family;
+    const uint16_t* qkv = tape<uint16_t>(bt->qkv);
+    float* stats = ws<float>(bp.attn_stats);
+    if (f == TR_FAMILY_DYVIT) {
+      const float* pol = pol_at(i, true);      // the policy this block attended under: the last predictor stage at or before it
+      float* dpart = ws<float>(bp.dpolpart);
+      if (Na > 224)
+        TR_TRY(tr_attention_policy_bwd_long_bf16(qkv, dao, pol, dqkv, dpart, stats, bp.attn_stats_floats, B, Na, H, s));
+      else
+        TR_TRY(tr_attention_policy_bwd_bf16(qkv, dao, pol, dqkv, dpart, B, Na, H, s));
+      return tr_head_sum(dpart, dpol, B, H, Na, s);
+    }
+    // ToMe: log(size) bias of this block's keys (tome.py:48-49), ATS: the key mask (ats.py:117-120) -- what the last block BELOW left;
+    // Heuristic: the spatial key mask in force at this block, the last one set at or before it
+    const float* size_att = (f == TR_FAMILY_TOME || f == TR_FAMILY_ATS) ? size_at(i, false) : f == TR_FAMILY_HEURISTIC ? size_at(i, true) : nullptr;
+    if (Na > 224) return tr_attention_bwd_long_bf16(qkv, dao, size_att, dcls, dqkv, stats, bp.attn_stats_floats, B, Na, H, s);
+    return tr_attention_bwd_bf16(qkv, dao, size_att, dcls, dqkv, B, Na, H, s);
+  }
+
+  // the block's parameter gradients (dY: the branch gradients kept above, dh and dqkv): one launch for all four, or the second pair.
+  // *done: this is the stop block and what follows only feeds the blocks below (no norm1 parameters, no stage that owns a gradient)
+  int block_wgrads(int i, bool* done) {
+    if (bg->proj_w != nullptr) LG[nlg++] = {gy_proj, (long)D, tape<uint16_t>(bt->ao), (long)D, F(bg->proj_w), F(bg->proj_b), Mp, D, D};
+    if (bg->qkv_w != nullptr) LG[nlg++] = {dqkv, (long)(3 * D), tape<uint16_t>(bt->xn1), (long)D, F(bg->qkv_w), F(bg->qkv_b), M1, 3 * D, D};
+    TR_TRY(launch_wgrads());
+    stage_here = K > 0 && stage_any(grads->stage[i]);
+    *done = i == stop && bg->ln1_g == nullptr && !stage_here;
+    return TR_OK;
+  }
+
+  // qkv's data gradient and norm1.  *done: this is the stop block and its stage owns no gradient
+  int qkv_norm1_bwd(int i, bool* done) {
+    TR_TRY(dgrad(dqkv, bwt->qkv_w, dxn, M1, D, 3 * D));
+    const float* x1 = tape<float>(bt->x1);
+    if (swaps_stream(i) && cfg->family == TR_FAMILY_KMEDOIDS) {
+      // norm1 ran on the gathered medoid rows (kmedoids.py:243-248): its backward scatter-ADDS into the pre-reduction stream's gradient
+      const size_t nfull = (size_t)B * t.n_pre[i] * D;
+      TR_TRY(zero(g_alt, nfull * 4));
+      TR_TRY(tr_layernorm_bwd_scatter_add(dxn, x1, bw->ln1_g, g, g_alt, tape<int32_t>(bt->idx), K, t.n_pre[i], F(bg->ln1_g), F(bg->ln1_b), acc, wsf,
+                                          wsn, M1, D, cfg->ln_eps, s));
+      if (i > stop) TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, nfull, s));          // (the bf16 copy only feeds the blocks below)
+      swap_stream();
+    } else {
+      TR_TRY(ln_bwd(dxn, x1, bw->ln1_g, bg->ln1_g, bg->ln1_b, g, g, gb, M1, cfg->ln_eps));
+    }
+    *done = i == stop && !stage_here;
+    return TR_OK;
+  }
+
+  // the reduction stage in front of the block
+  int stage_bwd(int i) {
+    const int f = cfg->family;
+    if (f == TR_FAMILY_DYVIT) return K > 0 ? stage_dyvit_bwd(i) : TR_OK;       // (a predictor stage moves no buffer: not under swaps_stream)
+    if (!swaps_stream(i)) return TR_OK;
+    if (trplan::soft_family(f)) return stage_soft_bwd(i);
+    return f == TR_FAMILY_DPCKNN ? stage_dpcknn_bwd(i) : TR_OK;
+  }
+  // PredictorLG + Gumbel straight-through of this stage (dyvit.py:221-224), backwards.  d keep = the policy gradient collected
+  // from the blocks that attended under this stage's policy (+ the later stage's d prev_decision) + d out_pred_prob
+  int stage_dyvit_bwd(int i) {
+    const tr_stage_weights *sw = &w->stage[i], *swt = &wt->stage[i], *sg = &grads->stage[i];
+    // Hr: the predictor's real hidden width (the shapes of the parameter gradients); Hh: as packed and as laid out on the tape
+    // (DeiT-T: 96 -> 128 with zero weights: the padded columns of every activation and gradient are zero)
+    const int Hr = D / 2, Hh = (D / 2 + 63) / 64 * 64, Q = (D / 4 + 63) / 64 * 64, Cq = D / 4;
+    int stage = 0;
+    for (int j = 0; j < i; ++j) stage += t.kk[j] > 0 ? 1 : 0;
+    if (dpred != nullptr) TR_TRY(tr_add_patch_rows(dpol, dpred + (size_t)stage * B * t.P, B, Na, s));
+    const float* prev = pol_at(i, false);       // prev_decision entering this stage, [B,N] layout
+    TR_TRY(zero(dprev, (size_t)M1 * 4));
+    uint16_t *d2 = dqkv, *d1 = dao, *d0 = dh;   // scratch: [M1, Q], [M1, Hh], [M1, D]
+    TR_TRY(tr_dyvit_decide_bwd(dpol, prev, tape<float>(bt->hard), tape<float>(bt->ysoft), tape<float>(bt->sm), tape<uint16_t>(bt->ph2), Q, sw->w3, d2,
+                               dprev, F(sg->w3), F(sg->b3), acc, wsf, wsn, B, Na, Cq, s));
+    TR_TRY(tr_gelu_bwd_bf16(tape<uint16_t>(bt->ppre2), d2, (size_t)M1 * Q, s));
+    TR_TRY(tr_linear_bwd_params(d2, Q, 0, tape<uint16_t>(bt->ph1), Hh, F(sg->w2), F(sg->b2), acc, wsf, wsn, M1, Cq, Hr, s));
+    TR_TRY(tr_gemm_dgelu_bf16(d2, U(swt->w2), tape<uint16_t>(bt->ppre1), d1, M1, Hh, Q, s));
+    TR_TRY(tr_linear_bwd_params(d1, Hh, 0, tape<uint16_t>(bt->pcat), D, F(sg->w1), F(sg->b1), acc, wsf, wsn, M1, Hr, D, s));
+    TR_TRY(dgrad(d1, swt->w1, dxn, M1, D, Hh));          // d [local | global]
+    TR_TRY(tr_pool_policy_bwd(dxn, tape<uint16_t>(bt->ppre0), tape<uint16_t>(bt->pcat), prev, d0, dprev, B, Na, D, s));
+    TR_TRY(tr_gelu_bwd_bf16(tape<uint16_t>(bt->ppre0), d0, (size_t)M1 * D, s));
+    TR_TRY(tr_linear_bwd_params(d0, D, 0, tape<uint16_t>(bt->pu), D, F(sg->w0), F(sg->b0), acc, wsf, wsn, M1, D, D, s));
+    TR_TRY(dgrad(d0, swt->w0, dxn, M1, D, D));
+    TR_TRY(ln_bwd(dxn, tape<float>(bt->x0), sw->ln_g, sg->ln_g, sg->ln_b, g, g, gb, M1, 1e-5f));
+    // what is left of the policy gradient belongs to the previous stage's decision
+    TR_REQUIRE(hipMemcpyAsync(dpol, dprev, (size_t)M1 * 4, hipMemcpyDeviceToDevice, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: copy failed");
+    return TR_OK;
+  }
+  // soft-assignment stage before the block (sit.py:36-40, patchmerger.py:35-39, sinkhorn.py:66-86): g = d of the merged stream
+  // [B, K+1, D] -> the stream entering the stage [B, n_pre, D] + the stage's parameters (tr_soft_bwd.hip)
+  int stage_soft_bwd(int i) {
+    const tr_stage_weights *sw = &w->stage[i], *swt = &wt->stage[i], *sg = &grads->stage[i];
+    const int Np = t.n_pre[i], Ms = B * Np, ld = trplan::soft_ld(K), ld64 = trplan::soft_ld64(K);
+    const bool sit = cfg->family == TR_FAMILY_SIT, sink = cfg->family == TR_FAMILY_SINKHORN;
+    const float *x0 = tape<float>(bt->x0), *wts = tape<float>(bt->swt), *slog = tape<float>(bt->slog);
+    float* dwt = ws<float>(bp.soft_dp);
+    uint16_t* ds = ws<uint16_t>(bp.soft_ds);
+    float* dsrc = sit ? g_alt : ws<float>(bp.soft_s);       // SiT sums the stream's own rows: d src IS a stream gradient
+    TR_TRY(zero(ds, (size_t)Ms * ld64 * 2));
+    TR_TRY(zero(dsrc, (size_t)Ms * D * 4));
+    TR_TRY(tr_soft_dweights(g, sit ? x0 : tape<float>(bt->sxh), dwt, ld, B, Np, K, D, s));
+    TR_TRY(tr_soft_dsrc(g, wts, ld, dsrc, B, Np, K, D, s));
+    if (sink)
+      TR_TRY(tr_sinkhorn_bwd(slog, dwt, ld, cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f, cfg->cluster_iters, ds, ld64, B, Np, K, s));
+    else
+      TR_TRY(tr_token_softmax_bwd(wts, dwt, slog, ld, sw->scale, ds, ld64, sit ? F(sg->b2) : nullptr, acc, wsf, wsn, B, Np, K, s));
+    if (sit) {
+      TR_TRY(soft_sit_scores_bwd(ds, swt, sg, Ms, ld, ld64));
+    } else {      // the similarity / score product: d queries (d centres) and d of its token operand
+      TR_TRY(tr_wgrad_bf16(ds, ld64, 0, tape<uint16_t>(bt->pu), D, F(sg->w1), acc, wsf, wsn, Ms, ld, D, s));
+      TR_TRY(dgrad(ds, swt->w1, dxn, Ms, D, ld64));
+      TR_TRY(zero(g_alt, (size_t)Ms * D * 4));
+    }
+    if (sink) TR_TRY(tr_rownorm_bwd(x0, dsrc, dxn, g_alt, Ms, D, s));            // d unit-norm rows = merge part + score-product part
+    // the CLS row passes the stage untouched
+    TR_REQUIRE(hipMemcpy2DAsync(g_alt, (size_t)Np * D * 4, g, (size_t)(K + 1) * D * 4, (size_t)D * 4, B, hipMemcpyDeviceToDevice, st) == hipSuccess,
+               TR_ERR_LAUNCH, "tr_vit_backward: copy failed");
+    if (sink) {
+      TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, (size_t)Ms * D, s));
+    } else {
+      if (!sit) TR_TRY(tr_add_into_bf16(dsrc, dxn, (size_t)Ms * D, s));          // PatchMerger sums the LayerNorm output: both uses meet here
+      TR_TRY(ln_bwd(dxn, x0, sw->ln_g, sg->ln_g, sg->ln_b, g_alt, g_alt, gb_alt, Ms, 1e-5f));
+    }
+    swap_stream();
+    return TR_OK;
+  }
+  // SiT's score Mlp (Linear -> GELU -> Linear), backwards: ds [Ms, ld64] -> dxn
+  int soft_sit_scores_bwd(const uint16_t* ds, const tr_stage_weights* swt, const tr_stage_weights* sg, int Ms, int ld, int ld64) {
+    const int Hr = D / 2, Hh = (D / 2 + 63) / 64 * 64;     // real / packed hidden width (DeiT-T: 96 / 128)
+    uint16_t* d1 = dh;                    // [Ms, Hh]
+    TR_TRY(tr_linear_bwd_params(ds, ld64, 0, tape<uint16_t>(bt->pcat), Hh, F(sg->w1), F(sg->b1), acc, wsf, wsn, Ms, ld, Hr, s));
+    TR_TRY(tr_gemm_dgelu_bf16(ds, U(swt->w1), tape<uint16_t>(bt->ppre0), d1, Ms, Hh, ld64, s));
+    TR_TRY(tr_linear_bwd_params(d1, Hh, 0, tape<uint16_t>(bt->pu), D, F(sg->w0), F(sg->b0), acc, wsf, wsn, Ms, Hr, D, s));
+    return dgrad(d1, swt->w0, dxn, Ms, D, Hh);
+  }
+  // CTM before the block (dpcknn.py:257-260): gradient of the merged tokens -> the tokens they were merged from + the score Linear
+  int stage_dpcknn_bwd(int i) {
+    TR_TRY(tr_cluster_merge_bwd(g, tape<float>(bt->x0), tape<float>(bt->x1), tape<float>(bt->scores), tape<int32_t>(bt->idx2), w->stage[i].w3, g_alt,
+                                gb_alt, F(grads->stage[i].w3), F(grads->stage[i].b3), acc, wsf, wsn, B, t.n_pre[i], K, D, s));
+    swap_stream();
+    return TR_OK;
+  }
+
+  // embedding (topk.py:181-186): g is d x0 [B, N0, D]
+  int embed_bwd() {
+    if (dropout_keep != nullptr) {      // pos_drop (topk.py:186): on the stream gradient and on its bf16 copy (the patch projection's dY)
+      TR_TRY(tr_dropout_f32(g, g, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
+      TR_TRY(tr_dropout_bf16(gb, gb, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
+    }
+    if (u_embed) TR_TRY(tr_embed_bwd(g, F(grads->pos_embed), F(grads->cls_token), acc, B, t.N0, D, s));
+    if (u_patch)
+      TR_TRY(tr_linear_bwd_params(gb, D, t.P, tape<uint16_t>(tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
+    // the input gradient: the patch projection's data gradient, folded back into the image (every element of dx written once)
+    if (dx != nullptr) TR_TRY(tr_patch_embed_dgrad(gb, D, U(wt->patch_w), dx, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
+    return TR_OK;
+  }
+};
+
+// every norm of the block loop leaves its d gamma / d beta partials in bp.lnpart; one reduce launch after the loop (tr_ln_defer_flush)
+struct LnDeferScope {
+  LnDeferScope(float* r, size_t n, hipStream_t st) { tr_ln_defer_begin(r, n, st); }
+  ~LnDeferScope() { tr_ln_defer_end(); }
+};
+
 }  // namespace
 
 extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int B) {
@@ -165,15 +663,13 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 // dx (nullable): the gradient with respect to the input image, fp32 [B, in_chans, img, img] (tr_vit_backward_dx).  With dx the walk goes all the
 // way down whatever is frozen (stop = -1: a fully frozen model is valid, the stage pointers are required everywhere), and the call with
 // blk_lo == 0 ends with one more launch: tr_patch_embed_dgrad on gb (after pos_drop's mask) and wt->patch_w = the patch weight transposed.
-namespace {
-int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
-                 const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
-                 size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
-                 tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
+static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                        const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                        size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                        tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
   TR_REQUIRE(cfg && w && wt && grads && dlogits && tape_ && workspace, TR_ERR_NULL, "tr_vit_backward: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_backward: dropout needs the forward's keep mask AND its drop_rate (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
-  const float drop_mul = dropout_keep != nullptr ? 1.0f / (1.0f - drop_rate) : 1.0f;
   TR_REQUIRE(cfg->precision == TR_PREC_BF16 && trplan::trainable_family(cfg->family), TR_ERR_CONFIG,
              "tr_vit_backward: family %d / precision %d has no training path", cfg->family, cfg->precision);
   trplan::TokenPlan t;
@@ -185,395 +681,37 @@ int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit
              tape_bytes, tp.total, workspace_bytes, bp.total);
   TR_REQUIRE(tr_aligned16(tape_) && tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_backward: tape / workspace must be 16-byte aligned");
   TR_REQUIRE(blk_lo >= 0 && blk_hi >= blk_lo && blk_hi < cfg->depth, TR_ERR_CONFIG, "tr_vit_backward: bad block range [%d .. %d]", blk_hi, blk_lo);
-  // ---- frozen parameters: which units are there, and the block the walk stops at
-  const int u_head = cfg->num_classes > 0 ? unit(grads->head_w, grads->head_b) : 0, u_norm = unit(grads->norm_g, grads->norm_b);
-  const int u_embed = unit(grads->pos_embed, grads->cls_token), u_patch = unit(grads->patch_w, grads->patch_b);
-  TR_REQUIRE(u_head >= 0 && u_norm >= 0 && u_embed >= 0 && u_patch >= 0, TR_ERR_NULL,
-             "tr_vit_backward: a gradient unit (head, norm, pos_embed + cls_token, patch) is half NULL: both pointers or neither");
-  // stop: block i whose own parameter gradients end the walk (nothing below it takes a gradient); depth: no block takes one; -1: the
-  // embedding does, the walk goes all the way
-  int stop = (u_embed || u_patch || dx != nullptr) ? -1 : cfg->depth;
-  if (dx != nullptr) {
-    TR_REQUIRE(wt->patch_w != nullptr, TR_ERR_NULL, "tr_vit_backward_dx: wt->patch_w (the patch weight transposed) is NULL");
-    TR_REQUIRE(tr_patch_embed_dgrad_supported(cfg->in_chans, cfg->img_size, cfg->patch, cfg->embed_dim), TR_ERR_SHAPE,
-               "tr_vit_backward_dx: no input gradient for in_chans %d, img_size %d, patch %d, embed_dim %d (tr_patch_embed_dgrad)", cfg->in_chans,
-               cfg->img_size, cfg->patch, cfg->embed_dim);
-    TR_REQUIRE(tr_aligned16(dx), TR_ERR_ALIGN, "tr_vit_backward_dx: dx must be 16-byte aligned");
-  }
-  for (int i = 0; i < cfg->depth; ++i) {
-    const tr_block_weights& b = grads->blocks[i];
-    const int u[6] = {unit(b.ln1_g, b.ln1_b), unit(b.qkv_w, b.qkv_b), unit(b.proj_w, b.proj_b),
-                      unit(b.ln2_g, b.ln2_b), unit(b.fc1_w, b.fc1_b), unit(b.fc2_w, b.fc2_b)};
-    bool any = stage_any(grads->stage[i]);
-    for (int k = 0; k < 6; ++k) {
-      TR_REQUIRE(u[k] >= 0, TR_ERR_NULL, "tr_vit_backward: a gradient unit of block %d is half NULL: both pointers or neither", i);
-      any = any || u[k] == 1;
-    }
-    if (any && stop == cfg->depth) stop = i;
-  }
-  for (int i = stop < 0 ? 0 : stop; i < cfg->depth; ++i) {
-    const bool reached = i > stop || stage_any(grads->stage[i]);          // the stop block's stage runs only when it owns a gradient
-    TR_REQUIRE(t.kk[i] <= 0 || !reached || stage_complete(cfg, w->stage[i], grads->stage[i]), TR_ERR_NULL,
-               "tr_vit_backward: the backward reaches the reduction stage of block %d (a parameter at or below it takes a gradient) but its "
-               "gradient pointers are NULL: stage modules are frozen only below the lowest block that takes a gradient", i);
-  }
+  Frozen fr;
+  TR_TRY(frozen_plan(cfg, w, wt, grads, t, dx, &fr));
+  const int stop = fr.stop;
   if (blk_hi < stop && blk_hi < cfg->depth - 1) return TR_OK;        // the whole range lies below the stop block
-  const char* tape = static_cast<const char*>(tape_);
-  char* ws = static_cast<char*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(s);
-  const int D = cfg->embed_dim, H = cfg->num_heads, Hd = cfg->mlp_hidden, C = cfg->num_classes;
-  const int kcols = cfg->in_chans * cfg->patch * cfg->patch;
-  float* g = reinterpret_cast<float*>(ws + bp.g0);
-  float* g_alt = reinterpret_cast<float*>(ws + bp.g1);
-  uint16_t* gb = reinterpret_cast<uint16_t*>(ws + bp.gb0);
-  uint16_t* gb_alt = reinterpret_cast<uint16_t*>(ws + bp.gb1);
-  uint16_t* dxn = reinterpret_cast<uint16_t*>(ws + bp.dxn);
-  uint16_t* dqkv = reinterpret_cast<uint16_t*>(ws + bp.dqkv);
-  uint16_t* dao = reinterpret_cast<uint16_t*>(ws + bp.dao);
-  uint16_t* dh = reinterpret_cast<uint16_t*>(ws + bp.dh);
-  float* zeros = reinterpret_cast<float*>(ws + bp.zeros);
-  float* wsf = reinterpret_cast<float*>(ws + bp.wsf);
-  float* dscore = reinterpret_cast<float*>(ws + bp.dscore);
-  float* gfused = reinterpret_cast<float*>(ws + bp.gfused);
-  int32_t* invmap = reinterpret_cast<int32_t*>(ws + bp.invmap);
-  uint16_t* dxcls = reinterpret_cast<uint16_t*>(ws + bp.dxcls);
-  const size_t wsn = bp.wsf_floats;
-  const int acc = accumulate ? 1 : 0;
 
-  uint16_t* gb_spare = reinterpret_cast<uint16_t*>(ws + bp.gb2);
-  // The four parameter-gradient products of a block (fc2, fc1, proj, qkv) run as ONE launch after the attention backward, when all four dY
-  // exist -- provided nothing has rewritten fc2's dY (the bf16 stream gradient gb) by then: norm2's backward writes its bf16 output into the
-  // spare buffer instead and the two trade places.  With DropPath the scaled dY copies live in scratch that is reused: pairs then.
-  const bool four = drop_scale == nullptr && dropout_keep == nullptr;    // the branches' dY are the stream gradient itself (no scaled / masked copies)
-  auto plain_ln2 = [&](int j) {      // blocks whose norm2 backward writes gb in place (no gather / merge between norm2 and the stream)
-    const bool gathers = (cfg->family == TR_FAMILY_TOPK || cfg->family == TR_FAMILY_EVIT || cfg->family == TR_FAMILY_TOME) && t.kk[j] > 0;
-    return !gathers;
-  };
-  // which stream-gradient buffers are current at block blk_hi: replay the pointer moves of the blocks above (per block: the spare rotation
-  // of norm2's backward first, then the swap of a token-reducing block)
-  for (int j = cfg->depth - 1; j > blk_hi; --j) {
-    if (four && plain_ln2(j)) { uint16_t* tb = gb; gb = gb_spare; gb_spare = tb; }
-    if (t.kk[j] > 0 && cfg->family != TR_FAMILY_DYVIT) {          // every token-reducing block of the built families swaps once
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    }
-  }
+  Bwd b(cfg, w, wt, grads, t, tp, bp, fr, B, s, tape_, workspace, accumulate, drop_scale, dropout_keep, drop_rate, dlogits, dpred, dfeat, dx);
+  b.rewind_to(blk_hi);
   if (blk_hi == cfg->depth - 1) {
-    const bool walk = stop < cfg->depth;          // a block (or the embedding) takes a gradient: the stream gradient is needed
-    if (!walk && !u_norm) {       // head-only probe: the classifier's parameter gradients and nothing else
-      if (u_head)
-        TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
-                           reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
-      return TR_OK;
-    }
-    size_t zmax = (size_t)(3 * D > Hd ? 3 * D : Hd);
-    if ((size_t)kcols > zmax) zmax = kcols;
-    TR_REQUIRE(hipMemsetAsync(zeros, 0, zmax * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-    // ---- classifier + final norm (topk.py:201-203): gradient enters the CLS rows of the last block's output stream
-    const int Nl = t.n_mlp[cfg->depth - 1];
-    if (C == 0)
-      TR_TRY(tr_f32_to_bf16(dlogits, dxcls, (size_t)B * D, s));
-    else
-      TR_TRY(tr_head_bwd(dlogits, U(w->head_w), U(tape + tp.xcls), dxcls, F(grads->head_w), F(grads->head_b), acc,
-                         reinterpret_cast<uint16_t*>(ws + bp.dl16), wsf, wsn, B, C, D, s));
-    if (cfg->global_pool == 1) {
-      // average-pooled head: xfinal holds the pooled patch tokens; the norm's row gradient goes to a [B, D] buffer and tr_token_pool_bwd
-      // spreads it over the patch rows with the forward's weights (the sizes / the mask the last merging / sampling block left on the tape;
-      // no gradient with respect to them) -- it writes every element of g, the CLS rows' zeros included: no memset
-      TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: global_pool = avg is not built for DyViT in training mode");
-      float* gpool = reinterpret_cast<float*>(ws + bp.gpool);
-      TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, gpool, D, nullptr, nullptr, 0, 0, 0,
-                              nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));
-      if (!walk) return TR_OK;      // the final norm was the lowest parameter
-      const float* pool_w = nullptr;
-      if (trplan::pool_weighted(cfg->family))
-        for (int j = cfg->depth - 1; j >= 0 && pool_w == nullptr; --j)
-          if (t.kk[j] > 0) pool_w = reinterpret_cast<const float*>(tape + tp.blk[j].size);
-      TR_TRY(tr_token_pool_bwd(gpool, pool_w, g, B, Nl, D, s));
-    } else {
-      TR_REQUIRE(hipMemsetAsync(g, 0, (size_t)B * Nl * D * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      TR_TRY(tr_layernorm_bwd(dxcls, reinterpret_cast<const float*>(tape + tp.xfinal), D, w->norm_g, nullptr, 0, g, (long)Nl * D, nullptr, nullptr, 0,
-                              0, 0, nullptr, F(grads->norm_g), F(grads->norm_b), acc, wsf, wsn, B, D, cfg->ln_eps, s));
-    }
-    if (dfeat != nullptr) {
-      // distillation: gradient wrt the final norm of every row (dyvit.py:252): a second pass of the norm's backward over all rows
-      TR_REQUIRE(cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: dfeat is DyViT's distillation gradient");
-      TR_TRY(tr_f32_to_bf16(dfeat, dxn, (size_t)B * Nl * D, s));
-      TR_TRY(tr_layernorm_bwd(dxn, reinterpret_cast<const float*>(tape + tp.xfin_all), D, w->norm_g, g, D, g, D, nullptr, nullptr, 0, 0, 0, nullptr,
-                              F(grads->norm_g), F(grads->norm_b), 1, wsf, wsn, B * Nl, D, cfg->ln_eps, s));
-    }
-    if (!walk) return TR_OK;      // the final norm was the lowest parameter
-    TR_TRY(tr_f32_to_bf16(g, gb, (size_t)B * Nl * D, s));
-    if (cfg->family == TR_FAMILY_DYVIT)
-      TR_REQUIRE(hipMemsetAsync(ws + bp.dpol, 0, (size_t)B * t.N0 * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
+    bool go = false;
+    TR_TRY(b.head_and_final_norm(&go));
+    if (!go) return TR_OK;
   }
-
-  // dropout keep masks: the forward consumed them in order (tr_vit_dropout_mask_bytes): [pos | block 0: proj, hidden, fc2 | block 1: ...]
-  size_t drop_off[TR_MAX_DEPTH + 1];
-  drop_off[0] = (size_t)B * t.N0 * D;
-  for (int i = 0; i < cfg->depth; ++i) drop_off[i + 1] = drop_off[i] + (size_t)B * (trplan::proj_rows(cfg, t, i) * D + (size_t)t.n_mlp[i] * (Hd + D));
-  struct LnDeferScope {       // every norm of the block loop leaves its d gamma / d beta partials in bp.lnpart; one reduce launch after the loop
-    LnDeferScope(float* r, size_t n, hipStream_t st) { tr_ln_defer_begin(r, n, st); }
-    ~LnDeferScope() { tr_ln_defer_end(); }
-  } ln_scope(reinterpret_cast<float*>(ws + bp.lnpart), bp.lnpart_floats, st);
+  LnDeferScope ln_scope(b.ws<float>(bp.lnpart), bp.lnpart_floats, b.st);
   for (int i = blk_hi; i >= blk_lo && i >= stop; --i) {
-    const trplan::BlockTape& bt = tp.blk[i];
-    const tr_block_weights* bw = &w->blocks[i];
-    const tr_block_weights* bwt = &wt->blocks[i];
-    const tr_block_weights* bg = &grads->blocks[i];
-    const int Na = t.n_att[i], Nm = t.n_mlp[i];
-    const int M2 = B * Nm, M1 = B * Na;
-    // ---- mlp: x2 -> norm2 -> fc1 -> gelu -> fc2 -> (+ residual)
-    const uint16_t* gy = gb;          // the branch's dY: the stream gradient, times the branch's DropPath scale when there is one
-    if (drop_scale != nullptr) {
-      TR_TRY(tr_rowscale_bf16(gb, dao, drop_scale + (size_t)(2 * i + 1) * B, B, Nm, D, s));
-      gy = dao;
-    }
-    const uint8_t* keep_proj = dropout_keep ? dropout_keep + drop_off[i] : nullptr;                                  // [B*n_proj, D]
-    const uint8_t* keep_h = dropout_keep ? keep_proj + (size_t)B * trplan::proj_rows(cfg, t, i) * D : nullptr;        // [M2, Hd]
-    const uint8_t* keep_fc2 = dropout_keep ? keep_h + (size_t)M2 * Hd : nullptr;                                      // [M2, D]
-    if (dropout_keep != nullptr) {    // the Mlp's second dropout (after fc2): the same mask on fc2's dY
-      TR_TRY(tr_dropout_bf16(gy, dao, keep_fc2, drop_mul, (size_t)M2 * D, s));
-      gy = dao;
-    }
-    TR_TRY(tr_gemm_dgelu_bf16(gy, U(bwt->fc2_w), U(tape + bt.pre), dh, M2, Hd, D, s));          // d fc2 input, times gelu'(pre): d pre
-    if (dropout_keep != nullptr)      // ... and the first one (after the activation): d pre = (dY W) * keep/(1-p) * gelu'(pre), the factors commute
-      TR_TRY(tr_dropout_bf16(dh, dh, keep_h, drop_mul, (size_t)M2 * Hd, s));
-    // fc2's and fc1's parameter gradients: both dY (gy, dh) exist now; launched here as a pair, or with proj's and qkv's further down
-    // (a frozen layer is left out of the list: what remains is planned as a group of its own; an empty list launches nothing)
-    tr_linear_grad LG[4];
-    int nlg = 0;
-    if (bg->fc2_w != nullptr) LG[nlg++] = {gy, (long)D, U(tape + bt.h), (long)Hd, F(bg->fc2_w), F(bg->fc2_b), M2, D, Hd};
-    if (bg->fc1_w != nullptr) LG[nlg++] = {dh, (long)Hd, U(tape + bt.xn2), (long)D, F(bg->fc1_w), F(bg->fc1_b), M2, Hd, D};
-    if (!four && nlg > 0) {
-      TR_TRY(tr_linear_bwd_group(LG, nlg, acc, wsf, wsn, s));
-      nlg = 0;
-    }
-    TR_TRY(tr_gemm_bf16(dh, U(bwt->fc1_w), zeros, dxn, nullptr, 0, M2, D, Hd, TR_EPI_BF16, s));
-    // ---- norm2 (+ the block's in-block token reduction)
-    const float* x2 = reinterpret_cast<const float*>(tape + bt.x2);
-    const float* x1 = reinterpret_cast<const float*>(tape + bt.x1);
-    const float* dcls = nullptr;
-    const int K = t.kk[i];
-    if ((cfg->family == TR_FAMILY_TOPK || cfg->family == TR_FAMILY_EVIT) && K > 0) {
-      const bool fuse = cfg->family == TR_FAMILY_EVIT;
-      const int32_t* idx = reinterpret_cast<const int32_t*>(tape + bt.idx);
-      TR_REQUIRE(hipMemsetAsync(g_alt, 0, (size_t)M1 * D * 4, st) == hipSuccess && hipMemsetAsync(gb_alt, 0, (size_t)M1 * D * 2, st) == hipSuccess,
-                 TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      TR_TRY(tr_layernorm_bwd(dxn, x2, D, bw->ln2_g, g, D, g_alt, D, gb_alt, idx, K, Nm, Na, fuse ? gfused : nullptr, F(bg->ln2_g), F(bg->ln2_b),
-                              acc, wsf, wsn, M2, D, cfg->ln_eps, s));
-      if (fuse) {
-        TR_REQUIRE(hipMemsetAsync(dscore, 0, (size_t)M1 * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-        TR_TRY(tr_evit_fuse_bwd(x1, U(tape + bt.dattn), reinterpret_cast<const int32_t*>(tape + bt.idx2),
-                                reinterpret_cast<const float*>(tape + bt.scores), gfused, g_alt, gb_alt, dscore, B, Na, K, D, s));
-        dcls = dscore;
-      }
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    } else if (cfg->family == TR_FAMILY_TOME && K > 0) {
-      TR_TRY(tr_layernorm_bwd(dxn, x2, D, bw->ln2_g, g, D, g, D, nullptr, nullptr, 0, 0, 0, nullptr, F(bg->ln2_g), F(bg->ln2_b), acc, wsf, wsn, M2, D,
-                              cfg->ln_eps, s));
-      const int na = (Na + 1) / 2;
-      const int32_t* unm = reinterpret_cast<const int32_t*>(tape + bt.idx);
-      const int32_t* src = unm + (size_t)B * (na - K);
-      const int32_t* dst = src + (size_t)B * K;
-      const float* size_in = nullptr;                       // sizes entering this block's merge: after the previous merging block
-      for (int j = i - 1; j >= 0; --j)
-        if (t.kk[j] > 0) { size_in = reinterpret_cast<const float*>(tape + tp.blk[j].size); break; }
-      TR_TRY(tr_tome_merge_bwd(g, size_in, reinterpret_cast<const float*>(tape + bt.size), unm, src, dst, invmap, g_alt, gb_alt, B, Na, K, D, s));
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    } else {
-      TR_TRY(tr_layernorm_bwd(dxn, x2, D, bw->ln2_g, g, D, g, D, four ? gb_spare : gb, nullptr, 0, 0, 0, nullptr, F(bg->ln2_g), F(bg->ln2_b), acc, wsf,
-                              wsn, M2, D, cfg->ln_eps, s));
-      if (four) { uint16_t* tb = gb; gb = gb_spare; gb_spare = tb; }       // gb_spare: fc2's dY, until this block's weight-gradient launch
-    }
-    // ---- attention: x1 -> norm1 -> qkv -> softmax(q k^T) v -> proj -> (+ residual)
-    const bool ats_sampled = cfg->family == TR_FAMILY_ATS && K > 0;
-    const int Mp = ats_sampled ? M2 : M1;                   // rows that went through proj (ATS: only the sampled ones, ats.py:86,129)
-    gy = gb;
-    if (drop_scale != nullptr) {
-      TR_TRY(tr_rowscale_bf16(gb, dh, drop_scale + (size_t)(2 * i) * B, B, Mp / B, D, s));
-      gy = dh;
-    }
-    if (dropout_keep != nullptr) {    // proj_drop (topk.py:53): the same mask on proj's dY
-      TR_TRY(tr_dropout_bf16(gy, dh, keep_proj, drop_mul, (size_t)Mp * D, s));
-      gy = dh;
-    }
-    const uint16_t* gy_proj = gy;           // proj's dY: stays valid until norm1's backward rewrites gb (ATS: the swapped-out buffer)
-    if (ats_sampled) {
-      // d(attn @ v) of the sampled rows and the stream's gradient go back to the rows they were sampled from (ats.py:86,157)
-      TR_TRY(tr_gemm_bf16(gy, U(bwt->proj_w), zeros, dxn, nullptr, 0, Mp, D, D, TR_EPI_BF16, s));
-      TR_REQUIRE(hipMemsetAsync(g_alt, 0, (size_t)M1 * D * 4, st) == hipSuccess && hipMemsetAsync(dao, 0, (size_t)M1 * D * 2, st) == hipSuccess,
-                 TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      TR_TRY(tr_ats_scatter(g, dxn, reinterpret_cast<const int32_t*>(tape + bt.idx), g_alt, dao, B, Na, Nm, D, s));
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;           // gb is rewritten by norm1's backward below
-    } else {
-      TR_TRY(tr_gemm_bf16(gy, U(bwt->proj_w), zeros, dao, nullptr, 0, M1, D, D, TR_EPI_BF16, s));
-    }
-    const float* size_att = nullptr;       // ToMe: log(size) bias of this block's keys (tome.py:48-49); ATS: the key mask (ats.py:117-120)
-    if (cfg->family == TR_FAMILY_TOME || cfg->family == TR_FAMILY_ATS)
-      for (int j = i - 1; j >= 0; --j)
-        if (t.kk[j] > 0) { size_att = reinterpret_cast<const float*>(tape + tp.blk[j].size); break; }
-    if (cfg->family == TR_FAMILY_HEURISTIC)          // the spatial key mask in force at this block: the last one set at or before it
-      for (int j = i; j >= 0; --j)
-        if (w->stage[j].w3 != nullptr) { size_att = reinterpret_cast<const float*>(tape + tp.blk[j].size); break; }
-    if (cfg->family == TR_FAMILY_DYVIT) {
-      // the policy this block attended under: the last predictor stage at or before it, all ones before the first
-      const float* pol = reinterpret_cast<const float*>(tape + tp.ones);
-      for (int j = i; j >= 0; --j)
-        if (t.kk[j] > 0) { pol = reinterpret_cast<const float*>(tape + tp.blk[j].pol); break; }
-      float* dpart = reinterpret_cast<float*>(ws + bp.dpolpart);
-      if (Na > 224)      // 384 x 384 inputs: the key-blocked kernels' policy variant
-        TR_TRY(tr_attention_policy_bwd_long_bf16(U(tape + bt.qkv), dao, pol, dqkv, dpart, reinterpret_cast<float*>(ws + bp.attn_stats),
-                                                 tr_attention_bwd_long_workspace_floats(B, t.N0, H), B, Na, H, s));
-      else
-        TR_TRY(tr_attention_policy_bwd_bf16(U(tape + bt.qkv), dao, pol, dqkv, dpart, B, Na, H, s));
-      TR_TRY(tr_head_sum(dpart, reinterpret_cast<float*>(ws + bp.dpol), B, H, Na, s));
-    } else if (Na > 224) {       // 384 x 384 inputs: key-blocked kernels (tr_attention_bwd_long.hip)
-      TR_TRY(tr_attention_bwd_long_bf16(U(tape + bt.qkv), dao, size_att, dcls, dqkv, reinterpret_cast<float*>(ws + bp.attn_stats),
-                                        tr_attention_bwd_long_workspace_floats(B, t.N0, H), B, Na, H, s));
-    } else {
-      TR_TRY(tr_attention_bwd_bf16(U(tape + bt.qkv), dao, size_att, dcls, dqkv, B, Na, H, s));
-    }
-    // the block's parameter gradients (dY: the branch gradients kept above, dh and dqkv): one launch for all four, or the second pair
-    if (bg->proj_w != nullptr) LG[nlg++] = {gy_proj, (long)D, U(tape + bt.ao), (long)D, F(bg->proj_w), F(bg->proj_b), Mp, D, D};
-    if (bg->qkv_w != nullptr) LG[nlg++] = {dqkv, (long)(3 * D), U(tape + bt.xn1), (long)D, F(bg->qkv_w), F(bg->qkv_b), M1, 3 * D, D};
-    if (nlg > 0) TR_TRY(tr_linear_bwd_group(LG, nlg, acc, wsf, wsn, s));
-    // the stop block: what follows only feeds the blocks below, except norm1's own parameters and a stage that owns a gradient
-    const bool stage_here = K > 0 && stage_any(grads->stage[i]);
-    if (i == stop && bg->ln1_g == nullptr && !stage_here) break;
-    TR_TRY(tr_gemm_bf16(dqkv, U(bwt->qkv_w), zeros, dxn, nullptr, 0, M1, D, 3 * D, TR_EPI_BF16, s));
-    if (cfg->family == TR_FAMILY_KMEDOIDS && K > 0) {
-      // norm1 ran on the gathered medoid rows (kmedoids.py:243-248): its backward scatter-ADDS into the pre-reduction stream's gradient
-      const size_t nfull = (size_t)B * t.n_pre[i] * D;
-      TR_REQUIRE(hipMemsetAsync(g_alt, 0, nfull * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      TR_TRY(tr_layernorm_bwd_scatter_add(dxn, x1, bw->ln1_g, g, g_alt, reinterpret_cast<const int32_t*>(tape + bt.idx), K, t.n_pre[i], F(bg->ln1_g),
-                                          F(bg->ln1_b), acc, wsf, wsn, M1, D, cfg->ln_eps, s));
-      if (i > stop) TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, nfull, s));          // (the bf16 copy only feeds the blocks below)
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    } else {
-      TR_TRY(tr_layernorm_bwd(dxn, x1, D, bw->ln1_g, g, D, g, D, gb, nullptr, 0, 0, 0, nullptr, F(bg->ln1_g), F(bg->ln1_b), acc, wsf, wsn, M1, D,
-                              cfg->ln_eps, s));
-    }
-    if (i == stop && !stage_here) break;
-    if (cfg->family == TR_FAMILY_DYVIT && K > 0) {
-      // PredictorLG + Gumbel straight-through of this stage (dyvit.py:221-224), backwards.  d keep = the policy gradient collected
-      // from the blocks that attended under this stage's policy (+ the later stage's d prev_decision) + d out_pred_prob
-      const tr_stage_weights* sw = &w->stage[i];
-      const tr_stage_weights* swt = &wt->stage[i];
-      const tr_stage_weights* sg = &grads->stage[i];
-      // Hr: the predictor's real hidden width (the shapes of the parameter gradients); Hh: as packed and as laid out on the tape
-      // (DeiT-T: 96 -> 128 with zero weights: the padded columns of every activation and gradient are zero)
-      const int Hr = D / 2, Hh = (D / 2 + 63) / 64 * 64, Q = (D / 4 + 63) / 64 * 64, Cq = D / 4;
-      float* dpol = reinterpret_cast<float*>(ws + bp.dpol);
-      float* dprev = reinterpret_cast<float*>(ws + bp.dprev);
-      int stage = 0;
-      for (int j = 0; j < i; ++j) stage += t.kk[j] > 0 ? 1 : 0;
-      if (dpred != nullptr) TR_TRY(tr_add_patch_rows(dpol, dpred + (size_t)stage * B * t.P, B, Na, s));
-      const float* prev = reinterpret_cast<const float*>(tape + tp.ones);       // prev_decision entering this stage, [B,N] layout
-      for (int j = i - 1; j >= 0; --j)
-        if (t.kk[j] > 0) { prev = reinterpret_cast<const float*>(tape + tp.blk[j].pol); break; }
-      TR_REQUIRE(hipMemsetAsync(dprev, 0, (size_t)M1 * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      uint16_t* d2 = dqkv;                    // scratch: [M1, Q] then reused
-      TR_TRY(tr_dyvit_decide_bwd(dpol, prev, reinterpret_cast<const float*>(tape + bt.hard), reinterpret_cast<const float*>(tape + bt.ysoft),
-                                 reinterpret_cast<const float*>(tape + bt.sm), U(tape + bt.ph2), Q, sw->w3, d2, dprev, F(sg->w3), F(sg->b3), acc, wsf,
-                                 wsn, B, Na, Cq, s));
-      TR_TRY(tr_gelu_bwd_bf16(U(tape + bt.ppre2), d2, (size_t)M1 * Q, s));
-      TR_TRY(tr_linear_bwd_params(d2, Q, 0, U(tape + bt.ph1), Hh, F(sg->w2), F(sg->b2), acc, wsf, wsn, M1, Cq, Hr, s));
-      uint16_t* d1 = dao;                     // [M1, Hh]
-      TR_TRY(tr_gemm_dgelu_bf16(d2, U(swt->w2), U(tape + bt.ppre1), d1, M1, Hh, Q, s));
-      TR_TRY(tr_linear_bwd_params(d1, Hh, 0, U(tape + bt.pcat), D, F(sg->w1), F(sg->b1), acc, wsf, wsn, M1, Hr, D, s));
-      TR_TRY(tr_gemm_bf16(d1, U(swt->w1), zeros, dxn, nullptr, 0, M1, D, Hh, TR_EPI_BF16, s));          // d [local | global]
-      uint16_t* d0 = dh;                      // [M1, D]
-      TR_TRY(tr_pool_policy_bwd(dxn, U(tape + bt.ppre0), U(tape + bt.pcat), prev, d0, dprev, B, Na, D, s));
-      TR_TRY(tr_gelu_bwd_bf16(U(tape + bt.ppre0), d0, (size_t)M1 * D, s));
-      TR_TRY(tr_linear_bwd_params(d0, D, 0, U(tape + bt.pu), D, F(sg->w0), F(sg->b0), acc, wsf, wsn, M1, D, D, s));
-      TR_TRY(tr_gemm_bf16(d0, U(swt->w0), zeros, dxn, nullptr, 0, M1, D, D, TR_EPI_BF16, s));
-      TR_TRY(tr_layernorm_bwd(dxn, reinterpret_cast<const float*>(tape + bt.x0), D, sw->ln_g, g, D, g, D, gb, nullptr, 0, 0, 0, nullptr, F(sg->ln_g),
-                              F(sg->ln_b), acc, wsf, wsn, M1, D, 1e-5f, s));
-      // what is left of the policy gradient belongs to the previous stage's decision
-      TR_REQUIRE(hipMemcpyAsync(dpol, dprev, (size_t)M1 * 4, hipMemcpyDeviceToDevice, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: copy failed");
-    }
-    if (trplan::soft_family(cfg->family) && K > 0) {
-      // soft-assignment stage before the block (sit.py:36-40, patchmerger.py:35-39, sinkhorn.py:66-86): g = d of the merged stream
-      // [B, K+1, D] -> the stream entering the stage [B, n_pre, D] + the stage's parameters (tr_soft_bwd.hip)
-      const tr_stage_weights* sw = &w->stage[i];
-      const tr_stage_weights* swt = &wt->stage[i];
-      const tr_stage_weights* sg = &grads->stage[i];
-      const int Np = t.n_pre[i], Mp = B * Np, ld = trplan::soft_ld(K), ld64 = trplan::soft_ld64(K);
-      const bool sit = cfg->family == TR_FAMILY_SIT, sink = cfg->family == TR_FAMILY_SINKHORN;
-      const float* x0 = reinterpret_cast<const float*>(tape + bt.x0);
-      const float* wts = reinterpret_cast<const float*>(tape + bt.swt);
-      const float* slog = reinterpret_cast<const float*>(tape + bt.slog);
-      const float* src = sit ? x0 : reinterpret_cast<const float*>(tape + bt.sxh);
-      float* dwt = reinterpret_cast<float*>(ws + bp.soft_dp);
-      uint16_t* ds = reinterpret_cast<uint16_t*>(ws + bp.soft_ds);
-      float* dsrc = sit ? g_alt : reinterpret_cast<float*>(ws + bp.soft_s);       // SiT sums the stream's own rows: d src IS a stream gradient
-      TR_REQUIRE(hipMemsetAsync(ds, 0, (size_t)Mp * ld64 * 2, st) == hipSuccess && hipMemsetAsync(dsrc, 0, (size_t)Mp * D * 4, st) == hipSuccess,
-                 TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      TR_TRY(tr_soft_dweights(g, src, dwt, ld, B, Np, K, D, s));
-      TR_TRY(tr_soft_dsrc(g, wts, ld, dsrc, B, Np, K, D, s));
-      if (sink)
-        TR_TRY(tr_sinkhorn_bwd(slog, dwt, ld, cfg->sinkhorn_eps > 0.f ? cfg->sinkhorn_eps : 1.0f, cfg->cluster_iters, ds, ld64, B, Np, K, s));
-      else
-        TR_TRY(tr_token_softmax_bwd(wts, dwt, slog, ld, sw->scale, ds, ld64, sit ? F(sg->b2) : nullptr, acc, wsf, wsn, B, Np, K, s));
-      if (sit) {
-        const int Hr = D / 2, Hh = (D / 2 + 63) / 64 * 64;     // real / packed hidden width (DeiT-T: 96 / 128)
-        uint16_t* d1 = dh;                    // [Mp, Hh]
-        TR_TRY(tr_linear_bwd_params(ds, ld64, 0, U(tape + bt.pcat), Hh, F(sg->w1), F(sg->b1), acc, wsf, wsn, Mp, ld, Hr, s));
-        TR_TRY(tr_gemm_dgelu_bf16(ds, U(swt->w1), U(tape + bt.ppre0), d1, Mp, Hh, ld64, s));
-        TR_TRY(tr_linear_bwd_params(d1, Hh, 0, U(tape + bt.pu), D, F(sg->w0), F(sg->b0), acc, wsf, wsn, Mp, Hr, D, s));
-        TR_TRY(tr_gemm_bf16(d1, U(swt->w0), zeros, dxn, nullptr, 0, Mp, D, Hh, TR_EPI_BF16, s));
-      } else {
-        // the similarity / score product: d queries (d centres) and d of its token operand
-        TR_TRY(tr_wgrad_bf16(ds, ld64, 0, U(tape + bt.pu), D, F(sg->w1), acc, wsf, wsn, Mp, ld, D, s));
-        TR_TRY(tr_gemm_bf16(ds, U(swt->w1), zeros, dxn, nullptr, 0, Mp, D, ld64, TR_EPI_BF16, s));
-      }
-      // the CLS row passes the stage untouched
-      if (!sit) TR_REQUIRE(hipMemsetAsync(g_alt, 0, (size_t)Mp * D * 4, st) == hipSuccess, TR_ERR_LAUNCH, "tr_vit_backward: memset failed");
-      if (sink) {
-        TR_TRY(tr_rownorm_bwd(x0, dsrc, dxn, g_alt, Mp, D, s));                  // d unit-norm rows = merge part + score-product part
-        TR_REQUIRE(hipMemcpy2DAsync(g_alt, (size_t)Np * D * 4, g, (size_t)(K + 1) * D * 4, (size_t)D * 4, B, hipMemcpyDeviceToDevice, st) == hipSuccess,
-                   TR_ERR_LAUNCH, "tr_vit_backward: copy failed");
-        TR_TRY(tr_f32_to_bf16(g_alt, gb_alt, (size_t)Mp * D, s));
-      } else {
-        TR_REQUIRE(hipMemcpy2DAsync(g_alt, (size_t)Np * D * 4, g, (size_t)(K + 1) * D * 4, (size_t)D * 4, B, hipMemcpyDeviceToDevice, st) == hipSuccess,
-                   TR_ERR_LAUNCH, "tr_vit_backward: copy failed");
-        if (!sit) TR_TRY(tr_add_into_bf16(dsrc, dxn, (size_t)Mp * D, s));        // PatchMerger sums the LayerNorm output: both uses meet here
-        TR_TRY(tr_layernorm_bwd(dxn, x0, D, sw->ln_g, g_alt, D, g_alt, D, gb_alt, nullptr, 0, 0, 0, nullptr, F(sg->ln_g), F(sg->ln_b), acc, wsf,
-                                wsn, Mp, D, 1e-5f, s));
-      }
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    }
-    if (cfg->family == TR_FAMILY_DPCKNN && K > 0) {
-      // CTM before the block (dpcknn.py:257-260): gradient of the merged tokens -> the tokens they were merged from + the score Linear
-      const tr_stage_weights* sw = &w->stage[i];
-      const tr_stage_weights* sg = &grads->stage[i];
-      TR_TRY(tr_cluster_merge_bwd(g, reinterpret_cast<const float*>(tape + bt.x0), x1, reinterpret_cast<const float*>(tape + bt.scores),
-                                  reinterpret_cast<const int32_t*>(tape + bt.idx2), sw->w3, g_alt, gb_alt, F(sg->w3), F(sg->b3), acc, wsf, wsn, B,
-                                  t.n_pre[i], K, D, s));
-      float* tg = g; g = g_alt; g_alt = tg;
-      uint16_t* tb = gb; gb = gb_alt; gb_alt = tb;
-    }
+    // Block, reversed: x += mlp(norm2(x)); [in-block reducer]; x += attn(norm1(x)); [stage reducer]
+    bool done = false;
+    b.begin_block(i);
+    TR_TRY(b.mlp_bwd(i));
+    TR_TRY(b.norm2_bwd(i));
+    TR_TRY(b.proj_bwd(i));
+    TR_TRY(b.attention_bwd(i));
+    TR_TRY(b.block_wgrads(i, &done));
+    if (done) break;
+    TR_TRY(b.qkv_norm1_bwd(i, &done));
+    if (done) break;
+    TR_TRY(b.stage_bwd(i));
   }
   TR_TRY(tr_ln_defer_flush());
   if (blk_lo > 0 || stop >= 0) return TR_OK;
-  // ---- embedding (topk.py:181-186): g is d x0 [B, N0, D]
-  if (dropout_keep != nullptr) {      // pos_drop (topk.py:186): on the stream gradient and on its bf16 copy (the patch projection's dY)
-    TR_TRY(tr_dropout_f32(g, g, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
-    TR_TRY(tr_dropout_bf16(gb, gb, dropout_keep, drop_mul, (size_t)B * t.N0 * D, s));
-  }
-  if (u_embed) TR_TRY(tr_embed_bwd(g, F(grads->pos_embed), F(grads->cls_token), acc, B, t.N0, D, s));
-  if (u_patch) TR_TRY(tr_linear_bwd_params(gb, D, t.P, U(tape + tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
-  // the input gradient: the patch projection's data gradient, folded back into the image (every element of dx written once)
-  if (dx != nullptr) TR_TRY(tr_patch_embed_dgrad(gb, D, U(wt->patch_w), dx, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
-  return TR_OK;
+  return b.embed_bwd();
 }
-}  // namespace
 
 extern "C" int tr_vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
                                const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
