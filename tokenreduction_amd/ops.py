@@ -695,14 +695,29 @@ def sit_merge(logits: torch.Tensor, scale: float, x: torch.Tensor, K: int, want_
 
 
 # ---------------------------------------------------------------------------------------- DPC-KNN (models/dpcknn.py)
-def dpcknn_cluster(x: torch.Tensor, K: int, noise: torch.Tensor = None, k: int = 5, fast_dist=False):
+def cluster_workspace_floats(B: int, N: int) -> int:
+    """fp32 elements of the workspace dpcknn_cluster, kmedoids and kmedoids_equal need for B images of N tokens."""
+    return int(_lib.load().tr_dpcknn_workspace_floats(B, N))
+
+
+def _cluster_ws(ws, B: int, N: int, device) -> torch.Tensor:
+    """The clustering workspace: a fresh one, or the caller's (whose stage intermediates the caller can then read back)."""
+    need = cluster_workspace_floats(B, N)
+    if ws is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.float32 and ws.is_contiguous() and ws.device == device and ws.numel() >= need):
+        raise ValueError(f"ws must be a contiguous fp32 tensor on {device} with at least {need} elements")
+    return ws
+
+
+def dpcknn_cluster(x: torch.Tensor, K: int, noise: torch.Tensor = None, k: int = 5, fast_dist=False, ws: torch.Tensor = None):
     """cluster_dpc_knn (dpcknn.py:44-100) on the patch rows of x fp32 [B,N,D] ->
     (centers int32 [B,K] in descending-score order, idx_cluster int32 [B,N-1], scores fp32 [B,N-1]).
     fast_dist: False / 0 = fp32 distances; True / 1 = split-bf16 MFMA distances, in ONE launch where the kernel applies; 2 = the same
-    distances through the staged launches."""
+    distances through the staged launches.  ws: caller-owned workspace (cluster_workspace_floats), None = a fresh one."""
     B, N, D = x.shape
     lib = _lib.load()
-    ws = torch.empty(lib.tr_dpcknn_workspace_floats(B, N), dtype=torch.float32, device=x.device)
+    ws = _cluster_ws(ws, B, N, x.device)
     centers = torch.empty(B, K, dtype=torch.int32, device=x.device)
     idx_cluster = torch.empty(B, N - 1, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, N - 1, dtype=torch.float32, device=x.device)
@@ -787,13 +802,13 @@ def weighted_merge(wt: torch.Tensor, x: torch.Tensor, src: torch.Tensor, K: int)
 
 
 # ---------------------------------------------------------------------------------------- K-Medoids (models/kmedoids.py)
-def kmedoids(x: torch.Tensor, colsum_part: torch.Tensor, K: int, iters: int, fast_dist: bool = False):
+def kmedoids(x: torch.Tensor, colsum_part: torch.Tensor, K: int, iters: int, fast_dist: bool = False, ws: torch.Tensor = None):
     """k_medoids_fit (kmedoids.py:40-85, weighted branch): x fp32 [B,N,D], colsum_part fp32 [B,H,4,N] (previous block's attention)
-    -> (centers int32 [B,K], assignment int32 [B,N-1])."""
+    -> (centers int32 [B,K], assignment int32 [B,N-1]).  ws: caller-owned workspace (cluster_workspace_floats), None = a fresh one."""
     B, N, D = x.shape
     H = colsum_part.shape[1]
     lib = _lib.load()
-    ws = torch.empty(lib.tr_dpcknn_workspace_floats(B, N), dtype=torch.float32, device=x.device)
+    ws = _cluster_ws(ws, B, N, x.device)
     centers = torch.empty(B, K, dtype=torch.int32, device=x.device)
     assign = torch.empty(B, N - 1, dtype=torch.int32, device=x.device)
     _lib.check(lib.tr_kmedoids(_dev(x, torch.float32, "x"), _dev(colsum_part, torch.float32, "colsum_part"), ws.data_ptr(),
@@ -801,11 +816,11 @@ def kmedoids(x: torch.Tensor, colsum_part: torch.Tensor, K: int, iters: int, fas
     return centers, assign
 
 
-def kmedoids_equal(x: torch.Tensor, first: int, K: int, iters: int, fast_dist: bool = False):
+def kmedoids_equal(x: torch.Tensor, first: int, K: int, iters: int, fast_dist: bool = False, ws: torch.Tensor = None):
     """k_medoids_fit with token_weight None (args.equal_weight, kmedoids.py:43-58): `first` = the np.random.choice draw."""
     B, N, D = x.shape
     lib = _lib.load()
-    ws = torch.empty(lib.tr_dpcknn_workspace_floats(B, N), dtype=torch.float32, device=x.device)
+    ws = _cluster_ws(ws, B, N, x.device)
     centers = torch.empty(B, K, dtype=torch.int32, device=x.device)
     assign = torch.empty(B, N - 1, dtype=torch.int32, device=x.device)
     _lib.check(lib.tr_kmedoids_equal(_dev(x, torch.float32, "x"), int(first), ws.data_ptr(), centers.data_ptr(), assign.data_ptr(), B, N, D, K,
