@@ -859,6 +859,23 @@ typedef struct tr_adamw_item { void* p; void* g; void* m; void* v; void* dst; vo
 int tr_adamw_step(const tr_adamw_item* items, const int* first, int n_items, int total_tiles, double beta1, double beta2, double eps,
                   float bias_correction1, float bias_correction2_sqrt, const double* lr8, const double* wd8, int zero_grads,
                   tr_stream_t s);
+/* LayerScale (timm's init_values: x + gamma o branch(x); csrc/tr_layerscale.hip).  The executor has no gamma: it reads the FOLDED
+ * operands W' = fl32(gamma[d] * W[d,k]), b' = fl32(gamma[d] * b[d]) of the Linear that ends a branch and produces their gradients.
+ * items: a DEVICE array, 16-byte aligned.  shapes: a HOST array of n_items (rows, cols) pairs -- the same values as in the items -- from
+ * which the grid is sized and which are refused (TR_ERR_SHAPE, before any launch) unless every one is a positive multiple of 64.
+ * first: the workgroups before the item -- (rows/64) * (cols/64) per item for the fold, rows/4 for the unfold.  Every pointer 16-byte aligned.
+ * tr_layerscale_fold, item i: w fp32 [rows, cols], b fp32 [rows], gamma fp32 [rows] -> dst [rows, cols] (bf16: the fp32 product rounded to
+ * nearest-even; fp32 when dst_is_f32; nullable), dst_t bf16 [cols, rows] (nullable), b_dst fp32 [rows] (nullable; b may then be NULL). */
+typedef struct tr_ls_fold_item { const void* w; const void* b; const void* gamma; void* dst; void* dst_t; void* b_dst; int rows, cols, first, pad_; } tr_ls_fold_item;
+int tr_layerscale_fold(const tr_ls_fold_item* items, const int* shapes, int n_items, int dst_is_f32, tr_stream_t s);
+/* The gradients of the real parameters from those of the folded operands.  Item i: dw_f fp32 [rows, cols], db_f fp32 [rows] (the executor's
+ * gradients of W', b'); w, b, gamma the fp32 parameters; dw [rows, cols], db [rows], dgamma [rows] fp32, each nullable (a frozen parameter):
+ *   dw = fl(gamma * dw_f), db = fl(gamma * db_f) -- under `accumulate` fl(old + fl(gamma * x)), two roundings;
+ *   dgamma[d] = sum_k dw_f[d,k] * w[d,k] + db_f[d] * b[d] in fp32 (under `accumulate` added to the old value), summed in an order that
+ *   depends on cols alone: the same bits on every launch.  dw_f / db_f are only read. */
+typedef struct tr_ls_unfold_item { const void* dw_f; const void* db_f; const void* w; const void* b; const void* gamma; void* dw; void* db; void* dgamma;
+                                   int rows, cols, first, pad_; } tr_ls_unfold_item;
+int tr_layerscale_unfold_grad(const tr_ls_unfold_item* items, const int* shapes, int n_items, int accumulate, tr_stream_t s);
 int tr_dropout_bf16(const uint16_t* src, uint16_t* dst, const uint8_t* keep, float mul, size_t n, tr_stream_t s);
 int tr_dropout_f32(const float* src, float* dst, const uint8_t* keep, float mul, size_t n, tr_stream_t s);
 /* Byte offsets of block blk's tape slots (x0,x1,xn1,qkv,ao,dattn,x2,xn2,pre,h,idx,idx2,scores,size) followed by its token counts

@@ -143,7 +143,9 @@ def load_finetune_checkpoint(model, checkpoint):
     DeiT-layout .pth ({"model": state_dict}) or the state dict itself.  A classifier whose shape does not fit the model is dropped,
     the position embedding is resized to the model's patch grid (class / distillation rows kept, the grid bicubically
     interpolated -- 14 x 14 -> 24 x 24 for a 224 -> 384 fine-tune), a model with global_pool='avg' takes a checkpoint's fc_norm.* as its
-    norm.* when the checkpoint has no norm.* of its own (timm's layout of MAE fine-tuned weights), everything else is loaded non-strictly.  Returns load_state_dict's
+    norm.* when the checkpoint has no norm.* of its own (timm's layout of MAE fine-tuned weights), everything else is loaded non-strictly.
+    A LayerScale model (init_values) takes a checkpoint's blocks.N.gamma_1 / gamma_2 (the DeiT-III repository's and older timm's names) as
+    ls1.gamma / ls2.gamma unless the new names are there; a no_embed_class model's table has no class row, so all of it is the grid.  Returns load_state_dict's
     (missing_keys, unexpected_keys).  Host-side only: the executor re-packs its operand copies at the next forward (new addresses
     and values are detected by the packing key)."""
     import torch.nn.functional as F
@@ -157,6 +159,14 @@ def load_finetune_checkpoint(model, checkpoint):
         for k in ("weight", "bias"):
             if f"fc_norm.{k}" in sd and f"norm.{k}" not in sd:
                 sd[f"norm.{k}"] = sd.pop(f"fc_norm.{k}")
+    if any(k.endswith(".ls1.gamma") for k in own):
+        # a LayerScale model: the DeiT-III repository and older timm releases call the two vectors blocks.N.gamma_1 / gamma_2 -- taken as
+        # ls1.gamma / ls2.gamma unless the checkpoint has the new names (sd is a copy: the caller's dict keeps its keys)
+        for k in [k for k in sd if k.startswith("blocks.") and k.endswith((".gamma_1", ".gamma_2"))]:
+            new = k[:-len("gamma_1")] + ("ls1.gamma" if k.endswith("1") else "ls2.gamma")
+            v = sd.pop(k)
+            if new not in sd:
+                sd[new] = v
     pos = sd.get("pos_embed")
     if pos is not None and pos.shape != model.pos_embed.shape:
         n_patches = model.patch_embed.num_patches

@@ -21,6 +21,9 @@ global_pool='avg' (constructor, create_model, reset_classifier; timm's average-p
 head -- or a headless model's output -- reads LayerNorm(weighted mean of the patch tokens after the last block) instead of the final-normed CLS
 row; the weights are ToMe's token sizes and the ATS padding mask, ones elsewhere.  Eval in all three precisions, training and backward; DyViT
 refuses it in train mode (its masked tokens stay in the stream).  '' and 'token' are the CLS row, the default.
+init_values (timm's LayerScale: blocks[i].ls1 / ls2, gamma [D]) and no_embed_class (pos_embed [1, P, D]) are the two options of a DeiT-III
+backbone: gamma reaches the executor folded into proj / fc2 (csrc/tr_layerscale.hip), its gradient is unfolded behind the backward (training.py);
+every family, eval in all three precisions, training and backward.
 Intermediate outputs of an eval forward: viz_mode (every row of every recorded block, on the host) or the output taps of forward_taps /
 forward_async -- the CLS rows after chosen blocks and the final-normed tokens, fp32 device tensors written while the fast path runs.
 The stages' decisions (which tokens each stage kept, which output every token went to) come the same two ways: viz_mode's viz_data, or
@@ -100,13 +103,28 @@ class Attention(nn.Module):
         self.init_n = 14 * 14   # topk.py:40 -- hard-coded in the reference, independent of img_size
 
 
-class Block(nn.Module):
-    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm, keep_rate=1.0):
+class LayerScale(nn.Module):
+    """timm's LayerScale (init_values; DeiT-III): the branch's output times a learnable per-channel `gamma` [D].  A parameter holder like
+    every module here: the executor reads gamma folded into the Linear that ends the branch (VisionTransformer._pack)."""
+
+    def __init__(self, dim, init_values=1e-5):
         super().__init__()
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
+
+
+class Block(nn.Module):
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm, keep_rate=1.0, init_values=None):
+        super().__init__()
+        # registration order is timm's: norm1, attn, ls1, norm2, mlp, ls2 -- and without init_values nothing is registered for ls1 / ls2 (not
+        # even an Identity): parameter order and state-dict keys of a plain block stay what they were
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads, qkv_bias, keep_rate)
+        if init_values:
+            self.ls1 = LayerScale(dim, init_values)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
+        if init_values:
+            self.ls2 = LayerScale(dim, init_values)
 
 
 def _init_vit_weights(m: nn.Module):
@@ -153,6 +171,7 @@ class _Packer:
         self.own = {p.untyped_storage().data_ptr() for p in model.parameters()}      # storages that ARE parameters
         self.calls = 0
         self.fused = []                  # (fp32 source, bf16 slot, transposed bf16 slot or None): one tr_cast_pack_bf16 launch for all
+        self.folds = []                  # (W, b, gamma, operand slot, transposed slot or None, bias slot): one tr_layerscale_fold launch for all
         self.keep_alive = []
         self.moved = False               # a slot was (re)allocated: addresses changed
         self.copied = False              # an operand copy the fused table does not cover (optim.FusedAdamW then leaves the refresh to _pack)
@@ -202,6 +221,19 @@ class _Packer:
                 ct.copy_(t.t())
         return (c.data_ptr(), ct) if transposed else c.data_ptr()
 
+    def folded(self, w, b, gamma):
+        """Weight and bias of the Linear that ends a LayerScale branch, as the executor reads them: (address of gamma[d] * w[d, k] in the operand
+        type, slot of its transposed bf16 copy or None, address of gamma o b in fp32).  Always slots, written by tr_layerscale_fold."""
+        self.calls += 1
+        w, b, gamma = w.detach(), b.detach(), gamma.detach()
+        if not (self._live(w) and self._live(b) and self._live(gamma)):
+            raise NotImplementedError("LayerScale: proj / fc2 and gamma must be fp32, contiguous parameters on the model's device")
+        c = self._slot("w", w.shape, self.wdt)
+        ct = self._slot("t", (w.shape[1], w.shape[0]), torch.bfloat16) if self.want_t else None
+        cb = self._slot("fb", b.shape, torch.float32)
+        self.folds.append((w, b, gamma, c, ct, cb))
+        return c.data_ptr(), ct, cb.data_ptr()
+
     def f32(self, t):
         self.calls += 1
         t = t.detach()
@@ -238,7 +270,7 @@ class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., embed_layer=None, norm_layer=None,
-                 act_layer=None, weight_init='', args=None, global_pool=''):
+                 act_layer=None, weight_init='', args=None, global_pool='', init_values=None, no_embed_class=False):
         super().__init__()
         _pool_code(global_pool)
         if distilled:
@@ -267,9 +299,13 @@ class VisionTransformer(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.dist_token = None
-        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + self.num_tokens, embed_dim))
+        # timm's no_embed_class (DeiT-III): the position table has the patch rows only; the class token is concatenated behind the addition
+        # and gets no position
+        self.no_embed_class = bool(no_embed_class)
+        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + (0 if self.no_embed_class else self.num_tokens), embed_dim))
         self.mlp_ratio, self.qkv_bias, self._norm_layer = mlp_ratio, qkv_bias, norm_layer
-        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer) for _ in range(depth)])
+        self.init_values = init_values   # timm's LayerScale: blocks[i].ls1 / ls2 (gamma [D]) scale the two branches; None / 0: no such modules
+        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer, init_values=init_values) for _ in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.pre_logits = nn.Identity()
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
@@ -303,6 +339,8 @@ class VisionTransformer(nn.Module):
         self._pack_slots = {}            # persistent operand copies {(call index, kind): tensor} (_Packer)
         self._pack_table = None          # device-side item table of the fused cast launch (_run_fused_pack)
         self._pack_all_fused = False     # that table covers every bf16 operand (optim.FusedAdamW may then refresh them itself)
+        self._ls_fold = None             # LayerScale: dict(sig, items, shapes, n, f32) -- the item table of tr_layerscale_fold (_run_layerscale_fold)
+        self._pos_table = None           # no_embed_class: the executor's [(P + 1), D] position table (row 0 zeros), a _Packer slot
         self._mlp_pack_items = None      # ([(fc1_w, fc2_w, fc2_b, pack buffer)], D, Hd) of _refresh_mlp_pack
         self._mlp_pk_stale = False       # the fragment-major Mlp copies are older than the bf16 copies
         self._want_transposed = False    # training asked for the transposed copies (dgrad operands)
@@ -457,7 +495,15 @@ class VisionTransformer(nn.Module):
         W.patch_w, tpatch = pk.w16(self.patch_embed.proj.weight.reshape(D, -1), True)      # (tpatch: the input gradient's operand, training.py)
         W.patch_b = pk.f32(self.patch_embed.proj.bias)
         W.cls_token = pk.f32(self.cls_token.reshape(-1))
-        W.pos_embed = pk.f32(self.pos_embed.reshape(-1, D))
+        if self.no_embed_class:
+            # the executor adds a [(P + 1), D] table to [cls; patches]: row 0 zeros (cls + 0 = cls), rows 1 .. P the parameter.  A slot of its
+            # own (born zeros), rewritten here and by _refresh_derived_operands
+            self._pos_table = pk.buffer("pe", (self.patch_embed.num_patches + 1, D), torch.float32)
+            self._pos_table[1:].copy_(self.pos_embed.detach()[0])
+            W.pos_embed = self._pos_table.data_ptr()
+        else:
+            self._pos_table = None
+            W.pos_embed = pk.f32(self.pos_embed.reshape(-1, D))
         W.norm_g, W.norm_b = pk.f32(self.norm.weight), pk.f32(self.norm.bias)
         cpad = self._classes_padded
         if not headless:             # headless: no classifier operands (tr_vit_weights.head_* stay NULL)
@@ -468,10 +514,17 @@ class VisionTransformer(nn.Module):
             b = W.blocks[i]
             b.ln1_g, b.ln1_b = pk.f32(blk.norm1.weight), pk.f32(blk.norm1.bias)
             (b.qkv_w, tq), b.qkv_b = pk.w16(blk.attn.qkv.weight, True), pk.f32(blk.attn.qkv.bias)
-            (b.proj_w, tp_), b.proj_b = pk.w16(blk.attn.proj.weight, True), pk.f32(blk.attn.proj.bias)
+            ls = hasattr(blk, "ls1")     # LayerScale: proj and fc2 reach the executor with gamma folded in (csrc/tr_layerscale.hip)
+            if ls:
+                b.proj_w, tp_, b.proj_b = pk.folded(blk.attn.proj.weight, blk.attn.proj.bias, blk.ls1.gamma)
+            else:
+                (b.proj_w, tp_), b.proj_b = pk.w16(blk.attn.proj.weight, True), pk.f32(blk.attn.proj.bias)
             b.ln2_g, b.ln2_b = pk.f32(blk.norm2.weight), pk.f32(blk.norm2.bias)
             (b.fc1_w, t1), b.fc1_b = pk.w16(blk.mlp.fc1.weight, True), pk.f32(blk.mlp.fc1.bias)
-            (b.fc2_w, t2), b.fc2_b = pk.w16(blk.mlp.fc2.weight, True), pk.f32(blk.mlp.fc2.bias)
+            if ls:
+                b.fc2_w, t2, b.fc2_b = pk.folded(blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.ls2.gamma)
+            else:
+                (b.fc2_w, t2), b.fc2_b = pk.w16(blk.mlp.fc2.weight, True), pk.f32(blk.mlp.fc2.bias)
             tblocks.append((tq, tp_, t1, t2))
             if wdt == torch.bfloat16 and mlp_pk_bytes:
                 # the fragment-major copy of the two Mlp matrices the fused eval Mlp kernel streams (csrc/tr_mlp_fused.hip), refreshed below /
@@ -486,6 +539,10 @@ class VisionTransformer(nn.Module):
                                 and type(self)._transposed_stage_weights is VisionTransformer._transposed_stage_weights)
         if pk.fused:
             self._run_fused_pack(pk.fused, dev)
+        if pk.folds:                 # before the fragment-major Mlp copies, which derive from the folded fc2 operand
+            self._run_layerscale_fold(pk.folds, dev, wdt == torch.float32)
+        else:
+            self._ls_fold = None
         self._mlp_pack_items = (mlp_items, D, Hd)
         if self.training:
             # a repack from the training forward (every step of a non-fused optimizer, every accumulation micro-step): the train executor
@@ -554,6 +611,32 @@ class VisionTransformer(nn.Module):
             _lib.check(_lib.load().tr_cast_pack_bf16(tab["items"].data_ptr(), tab["first"].data_ptr(), tab["n"], tab["tiles"],
                                                      torch.cuda.current_stream().cuda_stream), "tr_cast_pack_bf16")
 
+    def _run_layerscale_fold(self, folds, dev, f32):
+        """Every folded operand of the model (2 * depth matrices, their transposed copies and biases) through ONE tr_layerscale_fold launch;
+        like the cast table, the item table lives on the device and is rebuilt only when an address changed."""
+        from . import ops
+        tab = self._ls_fold
+        sig = (f32,) + tuple((w.data_ptr(), b.data_ptr(), g.data_ptr(), c.data_ptr(), 0 if ct is None else ct.data_ptr(), cb.data_ptr(),
+                              w.shape[0], w.shape[1]) for w, b, g, c, ct, cb in folds)
+        if tab is None or tab["sig"] != sig:
+            tab = self._ls_fold = dict(ops.layerscale_table(sig[1:], ops.LS_FOLD_ITEM, dev), sig=sig, f32=f32, dev=dev)
+        self._launch_layerscale_fold()
+
+    def _launch_layerscale_fold(self):
+        tab = self._ls_fold
+        with torch.cuda.device(tab["dev"]):
+            _lib.check(_lib.load().tr_layerscale_fold(tab["items"].data_ptr(), tab["shapes"], tab["n"], 1 if tab["f32"] else 0,
+                                                      torch.cuda.current_stream().cuda_stream), "tr_layerscale_fold")
+
+    def _refresh_derived_operands(self):
+        """The operand copies no optimizer table covers, rewritten in place from the current parameters: the LayerScale-folded proj / fc2
+        operands (one tr_layerscale_fold launch) and the [(P + 1), D] position table of a no_embed_class model.  optim.FusedAdamW calls this
+        behind its step, before it declares the operands fresh; a plain model has neither and launches nothing."""
+        if self._ls_fold is not None:
+            self._launch_layerscale_fold()
+        if self._pos_table is not None:
+            self._pos_table[1:].copy_(self.pos_embed.detach()[0])
+
     def _pack_stages(self, W, pk):
         """Families with learned reduction modules fill W.stage[blk] (tr_stage_weights) here."""
 
@@ -570,6 +653,8 @@ class VisionTransformer(nn.Module):
             return self._classes_padded * p.shape[1]
         if name == "head.bias":
             return self._classes_padded
+        if name == "pos_embed" and self.no_embed_class:
+            return p.numel() + self.embed_dim         # the executor writes a [(P + 1), D] gradient: row 0 is scratch, the parameter's view rows 1 .. P
         return p.numel()
 
     def _pre_pack(self):

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1549,4 +1550,75 @@ def adamw_step(items, lrs, wds, betas, eps: float, step: int, zero_grads: bool =
     with torch.cuda.device(dev):
         _lib.check(_lib.load().tr_adamw_step(d_items.data_ptr(), d_first.data_ptr(), n, first[-1], float(beta1), float(beta2), float(eps), bc1,
                                              bc2_sqrt, lr8, wd8, 1 if zero_grads else 0, _stream(items[0][0])), "tr_adamw_step")
+    torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch
+
+
+LS_FOLD_ITEM = np.dtype([("w", "<u8"), ("b", "<u8"), ("gamma", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("b_dst", "<u8"), ("rows", "<i4"),
+                         ("cols", "<i4"), ("first", "<i4"), ("pad", "<i4")])                                      # tr_ls_fold_item
+LS_UNFOLD_ITEM = np.dtype([("dw_f", "<u8"), ("db_f", "<u8"), ("w", "<u8"), ("b", "<u8"), ("gamma", "<u8"), ("dw", "<u8"), ("db", "<u8"),
+                           ("dgamma", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("first", "<i4"), ("pad", "<i4")])  # tr_ls_unfold_item
+
+
+def layerscale_table(rows, dtype, dev):
+    """The two halves of a tr_layerscale_fold / tr_layerscale_unfold_grad item table from `rows` = [(address, ..., rows, cols)] (the item's
+    fields up to `cols`; 0 = NULL): dict(items = the device array, shapes = the host (rows, cols) pairs, n).  `first` is filled in here:
+    the workgroups before the item, (rows/64) * (cols/64) each for the fold, rows/4 for the unfold.  Every address must be 16-byte aligned."""
+    arr = np.zeros(len(rows), dtype=dtype)
+    shapes = (ctypes.c_int * (2 * len(rows)))()
+    first = 0
+    for i, it in enumerate(rows):
+        r, c = int(it[-2]), int(it[-1])
+        if any(int(a) % 16 for a in it[:-2]):
+            raise ValueError(f"layerscale item {i}: every operand must start on a 16-byte boundary")
+        arr[i] = tuple(int(a) for a in it[:-2]) + (r, c, first, 0)
+        shapes[2 * i], shapes[2 * i + 1] = r, c
+        first += (r // 64) * (c // 64) if dtype is LS_FOLD_ITEM else r // 4
+    return dict(items=torch.from_numpy(arr.view(np.uint8).copy()).to(dev), shapes=shapes, n=len(rows))
+
+
+def layerscale_fold(items, dst_f32: bool = False) -> None:
+    """LayerScale folded into the Linear that ends a branch, every item in ONE launch (tr_layerscale_fold, csrc/tr_layerscale.hip).  items:
+    [(w fp32 [rows, cols], b fp32 [rows] | None, gamma fp32 [rows], dst [rows, cols] bf16 (fp32 with dst_f32) | None, dst_t bf16 [cols, rows]
+    | None, b_dst fp32 [rows] | None), ...]: dst = fl32(gamma[d] * w[d, k]) (rounded to nearest-even to bf16), dst_t its transpose, b_dst =
+    fl32(gamma o b).  rows and cols are multiples of 64; the tensors may be views that start on any 16-byte boundary of a buffer.
+    For tests and tools: the item table is built and uploaded per call and the stream is synchronised before it is freed (the models keep
+    persistent tables)."""
+    rows = []
+    ddt = torch.float32 if dst_f32 else torch.bfloat16
+    for i, (w, b, gamma, dst, dst_t, b_dst) in enumerate(items):
+        r, c = w.shape
+        _same_device(w, b, gamma, dst, dst_t, b_dst, items[0][0])
+        if gamma.shape != (r,) or (b is not None and b.shape != (r,)) or (b_dst is not None and (b is None or b_dst.shape != (r,))):
+            raise ValueError(f"layerscale_fold: item {i}: b, gamma and b_dst must have {r} entries (b_dst needs b)")
+        if dst is not None and tuple(dst.shape) != (r, c) or dst_t is not None and tuple(dst_t.shape) != (c, r):
+            raise ValueError(f"layerscale_fold: item {i}: destinations do not fit a [{r}, {c}] source")
+        rows.append((_view_ptr(w, torch.float32, "w"), 0 if b is None else _view_ptr(b, torch.float32, "b"), _view_ptr(gamma, torch.float32, "gamma"),
+                     0 if dst is None else _view_ptr(dst, ddt, "dst"), 0 if dst_t is None else _view_ptr(dst_t, torch.bfloat16, "dst_t"),
+                     0 if b_dst is None else _view_ptr(b_dst, torch.float32, "b_dst"), r, c))
+    dev = items[0][0].device
+    tab = layerscale_table(rows, LS_FOLD_ITEM, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tr_layerscale_fold(tab["items"].data_ptr(), tab["shapes"], tab["n"], 1 if dst_f32 else 0, _stream(items[0][0])),
+                   "tr_layerscale_fold")
+    torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch
+
+
+def layerscale_unfold_grad(items, accumulate: bool = False) -> None:
+    """Gradients of W, b and gamma from the gradients of the folded operands, every item in ONE launch (tr_layerscale_unfold_grad).  items:
+    [(dw_f fp32 [rows, cols], db_f fp32 [rows], w, b, gamma (the fp32 parameters), dw | None, db | None, dgamma | None), ...]: dw = fl(gamma
+    * dw_f), db = fl(gamma * db_f), dgamma[d] = sum_k dw_f[d,k] w[d,k] + db_f[d] b[d]; with `accumulate` each is added to what the output
+    holds (dw, db: fl(old + fl(gamma * x))).  A None output is not written.  Same table handling as layerscale_fold."""
+    rows = []
+    for i, (dw_f, db_f, w, b, gamma, dw, db, dgamma) in enumerate(items):
+        r, c = dw_f.shape
+        _same_device(dw_f, db_f, w, b, gamma, dw, db, dgamma, items[0][0])
+        if w.shape != (r, c) or (dw is not None and dw.shape != (r, c)) or any(t is not None and t.shape != (r,) for t in (db_f, b, gamma, db, dgamma)):
+            raise ValueError(f"layerscale_unfold_grad: item {i}: operands do not fit a [{r}, {c}] folded gradient")
+        rows.append(tuple(0 if t is None else _view_ptr(t, torch.float32, n)
+                          for t, n in zip((dw_f, db_f, w, b, gamma, dw, db, dgamma), ("dw_f", "db_f", "w", "b", "gamma", "dw", "db", "dgamma"))) + (r, c))
+    dev = items[0][0].device
+    tab = layerscale_table(rows, LS_UNFOLD_ITEM, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tr_layerscale_unfold_grad(tab["items"].data_ptr(), tab["shapes"], tab["n"], 1 if accumulate else 0,
+                                                         _stream(items[0][0])), "tr_layerscale_unfold_grad")
     torch.cuda.current_stream(dev).synchronize()          # the item table must outlive the launch

@@ -10,7 +10,8 @@ The reference builds `torch.optim.AdamW` (optim.py:102-140 through timm's factor
   * optionally (`zero_grads=True`) zeroes the gradient it consumed -- not needed for training.TrainState, whose backward overwrites
     the flat gradient buffer after `zero_grad(set_to_none=True)`,
   * rewrites the bf16 operand copy and the transposed copy of every matrix the executor reads, when constructed with `model=` -- the
-    next forward then finds its operands fresh and skips tr_cast_pack_bf16.
+    next forward then finds its operands fresh and skips tr_cast_pack_bf16.  The operands of a LayerScale model that carry gamma (proj,
+    fc2: models._Packer.folded) are not in the step's table; one tr_layerscale_fold launch behind the step rewrites them.
 
 Per training step of DeiT-B this replaces torch's multi_tensor_apply kernels, ~69 fill launches and the cast-pack pass.
 Not supported (raises): amsgrad, maximize, a gradient scaler, more than 8 parameter groups per step count.
@@ -56,7 +57,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _operand_slots(self):
         """{parameter storage address: (bf16 copy address, transposed copy address or 0)} of the model's packed matrices, if every bf16
-        operand of the model is refreshed by the fused pack table (else None: the model keeps refreshing them itself)."""
+        operand of the model is refreshed by the fused pack table (else None: the model keeps refreshing them itself).  The LayerScale-folded
+        operands are in no pack table and so not in here: step() refreshes them through the model (_refresh_derived_operands)."""
         m = self._model
         if m is None or getattr(m, "precision", "bf16") != "bf16":
             return None
@@ -141,6 +143,9 @@ class FusedAdamW(torch.optim.Optimizer):
             # left may be declared clean: a weights_changed() raised for another reason since (a manual p.data edit, an EMA / teacher copy
             # into a matrix this step did not touch) must survive
             if tab["refreshes"] and m._dirty_by_backward:
+                # what no table of this step covers -- a LayerScale model's folded proj / fc2 operands (one tr_layerscale_fold launch for all
+                # of them), a no_embed_class model's position table -- is rewritten by the model, from the parameters just stepped
+                m._refresh_derived_operands()
                 m._weights_dirty = False
                 m._dirty_by_backward = False
                 m._mlp_pk_stale = True             # the fused eval Mlp's fragment-major copies derive from the bf16 copies just rewritten

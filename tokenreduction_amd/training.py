@@ -67,7 +67,19 @@ class TrainState:
             self.offsets[n] = off
             off += _align4(model._grad_slot_numel(n, p))
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.views = {n: self.flat[o: o + p.numel()].view_as(p) for (n, p), o in zip(self.order, self.offsets.values())}
+        # where a parameter's view starts inside its slot: a no_embed_class model's pos_embed is rows 1 .. P of the [(P + 1), D] gradient
+        # the executor writes (D floats in: still 256-byte aligned); row 0, the class row's, is scratch
+        self.view_off = {"pos_embed": model.embed_dim} if getattr(model, "no_embed_class", False) else {}
+        self.views = {n: self.flat[o + self.view_off.get(n, 0): o + self.view_off.get(n, 0) + p.numel()].view_as(p)
+                      for (n, p), o in zip(self.order, self.offsets.values())}
+        self.slot_scratch = [self.flat[self.offsets[n]: self.offsets[n] + k] for n, k in self.view_off.items()]
+        # LayerScale: the executor's gradients of the FOLDED proj / fc2 operands land in a scratch buffer, depth * (D*D + D*Hd + 2D) floats;
+        # tr_layerscale_unfold_grad turns them into the gradients of W, b and gamma in the flat buffer (ls_unfold)
+        self.ls = None
+        if hasattr(model.blocks[0], "ls1"):
+            D, Hd = model.embed_dim, model.blocks[0].mlp.fc1.out_features
+            per = D * D + D * Hd + 2 * D
+            self.ls = dict(scratch=torch.zeros(model.depth * per, dtype=torch.float32, device=dev), per=per, D=D, Hd=Hd, items=[], tables={})
         # bucket boundaries: [head+norm+last block] ... per block ... [block 0 + embedding]; event index that completes each
         self.block_slices = self._block_slices(model)
         self.B = None
@@ -109,8 +121,8 @@ class TrainState:
         v = self.views
         named = dict(self.order)
 
-        def ptr(name):
-            return v[name].data_ptr()
+        def ptr(name):           # (the slot's start: what the executor writes)
+            return v[name].data_ptr() - 4 * self.view_off.get(name, 0)
 
         discarded = []
 
@@ -119,6 +131,23 @@ class TrainState:
                 return None, None
             discarded.extend(n for n in (a, b) if not named[n].requires_grad)
             return ptr(a), ptr(b)
+
+        ls = self.ls
+        if ls is not None:
+            ls["items"] = []
+
+        def folded_unit(blk, branch, w, b, g):
+            """The unit of a LayerScale branch: the executor writes the gradients of the folded operands into the scratch buffer (never into
+            the real slots), NULL only when W, b and gamma are all frozen; ls["items"] takes the unfold item (a frozen output is 0)."""
+            if not (named[w].requires_grad or named[b].requires_grad or named[g].requires_grad):
+                return None, None
+            D, Hd = ls["D"], ls["Hd"]
+            cols = Hd if branch else D
+            base = ls["scratch"].data_ptr() + 4 * (blk * ls["per"] + (D * D + D if branch else 0))
+            ls["items"].append((blk, (base, base + 4 * D * cols, named[w].data_ptr(), named[b].data_ptr(), named[g].data_ptr(),
+                                      ptr(w) if named[w].requires_grad else 0, ptr(b) if named[b].requires_grad else 0,
+                                      ptr(g) if named[g].requires_grad else 0, D, cols)))
+            return base, base + 4 * D * cols
 
         G.patch_w, G.patch_b = unit("patch_embed.proj.weight", "patch_embed.proj.bias")
         G.cls_token, G.pos_embed = unit("cls_token", "pos_embed")
@@ -129,10 +158,14 @@ class TrainState:
             b, pre = G.blocks[i], f"blocks.{i}."
             b.ln1_g, b.ln1_b = unit(pre + "norm1.weight", pre + "norm1.bias")
             b.qkv_w, b.qkv_b = unit(pre + "attn.qkv.weight", pre + "attn.qkv.bias")
-            b.proj_w, b.proj_b = unit(pre + "attn.proj.weight", pre + "attn.proj.bias")
             b.ln2_g, b.ln2_b = unit(pre + "norm2.weight", pre + "norm2.bias")
             b.fc1_w, b.fc1_b = unit(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
-            b.fc2_w, b.fc2_b = unit(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+            if self.ls is None:
+                b.proj_w, b.proj_b = unit(pre + "attn.proj.weight", pre + "attn.proj.bias")
+                b.fc2_w, b.fc2_b = unit(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+            else:
+                b.proj_w, b.proj_b = folded_unit(i, 0, pre + "attn.proj.weight", pre + "attn.proj.bias", pre + "ls1.gamma")
+                b.fc2_w, b.fc2_b = folded_unit(i, 1, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias", pre + "ls2.gamma")
         model._grad_stage_ptrs(G, ptr)
         stage_names = self._stage_names      # {block: names of the family's parameters behind G.stage[block]}: structure, not mask
         if stage_names is None:
@@ -164,6 +197,24 @@ class TrainState:
             else:
                 discarded.extend(n for n in names if not named[n].requires_grad)
         return G, discarded
+
+    def ls_unfold(self, hi, lo, accumulate, dev):
+        """LayerScale: the gradients of W, b and gamma of the blocks lo .. hi from the folded gradients the backward call just wrote -- one
+        tr_layerscale_unfold_grad launch (nothing for a model without LayerScale, or a range whose branches are all frozen).  The item
+        tables live on the device, one per (range, frozen pattern)."""
+        if self.ls is None:
+            return
+        rows = tuple(it for blk, it in self.ls["items"] if lo <= blk <= hi)
+        if not rows:
+            return
+        from . import ops
+        tab = self.ls["tables"].get(rows)
+        if tab is None:
+            if len(self.ls["tables"]) >= 64:
+                self.ls["tables"].clear()
+            tab = self.ls["tables"][rows] = ops.layerscale_table(rows, ops.LS_UNFOLD_ITEM, dev)
+        _lib.check(_lib.load().tr_layerscale_unfold_grad(tab["items"].data_ptr(), tab["shapes"], tab["n"], 1 if accumulate else 0,
+                                                         torch.cuda.current_stream().cuda_stream), "tr_layerscale_unfold_grad")
 
     def transposed(self, model, pk):
         """bf16 transposed copies of the block matrices (the dgrad GEMM operands): made by the model's own repack (models._pack with
@@ -394,6 +445,12 @@ class _VitTrainFn(torch.autograd.Function):
         if accumulate:
             for n in fresh + discarded:          # (a discarded slice is cleared so that it cannot grow without bound over the steps)
                 st.views[n].zero_()
+            for t in st.slot_scratch:            # (no_embed_class: the class row of the position gradient, discarded like them)
+                t.zero_()
+            if st.ls is not None:
+                # the executor ADDS to what its gradient pointers hold: the folded-gradient scratch must not carry the last backward's values
+                # into this one.  Cleared here, on accumulating calls only (a non-accumulating call overwrites it)
+                st.ls["scratch"].zero_()
         WT = st.transposed(model, pk)
         reducer = model._grad_reducer
         reduce_now = reducer is not None and reducer.sync
@@ -414,6 +471,7 @@ class _VitTrainFn(torch.autograd.Function):
                         None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(), float(model.drop_rate or 0.0))
                 rc = lib.tr_vit_backward(*args) if dx is None else lib.tr_vit_backward_dx(*args, dx.data_ptr())
                 _lib.check(rc, "tr_vit_backward")
+                st.ls_unfold(hi, lo, accumulate, dev)
                 if reduce_now:
                     reducer.reduce_slice(st.flat, start, stop)
         if reduce_now:
