@@ -781,6 +781,30 @@ int tr_stage_decisions(const int32_t* kept_idx, const int32_t* compl_idx, size_t
                        const tr_decision_stage* stages, int n_stages, int B, int N0, int32_t* kept_out, size_t kept_elems,
                        int32_t* count_out, int32_t* assign_out, size_t assign_elems, tr_stream_t s);
 
+/* Dense feature maps (csrc/tr_dense.hip): the final-normed rows of an eval forward (tr_vit_taps.final_tokens_out, fp32 [B, N_last, D]) back
+ * on the input's patch grid of P0 = h * w patches.  Two launches behind tr_stage_decisions on the same stream.
+ * tr_dense_index: index_out int32 [B, P0] = the row of the last stream (1 ... n_last-1; row 0 is the CLS token) that stands for grid patch
+ *   p, -1 where none does.  `kept` / `assign` are tr_stage_decisions' kept_out / assign_out with their lengths, `stages` the same HOST
+ *   table (kept_off / assign_off read, soft_off ignored; count_out is not needed: the entries behind a row's count are -1).  One
+ *   workgroup per image, P0 <= 1024.  A state cur[p] (patch-relative row, starting at cur[p] = p) walks the stages in block order:
+ *     CENTRES, TOME, SOFT   cur[p] = assign[b, cur[p]] where 0 <= cur[p] < n_in - 1 and the result lies in [0, n_out); -1 otherwise
+ *                           (SOFT: the hard argmax map; CENTRES: the assignment map, not the centre list)
+ *     PRUNE, EVIT, ATS      the list is absolute: cur[p] = the LOWEST j < n_out with kept[b, j] == p, -1 if there is none; entries < 0
+ *                           (EViT's fused token, padding, -2) or >= P0 own no patch.  Such a stage behind a stage with a map:
+ *                           TR_ERR_CONFIG.
+ *   n_out: PRUNE, CENTRES, SOFT k; EVIT k + 1; ATS k - 1; TOME n_in - 1 - min(k, (n_in-1)/2).  index = cur + 1 where cur >= 0.  The last
+ *   stage's n_out (P0 for n_stages == 0, which writes the identity 1 ... P0) must equal n_last - 1: TR_ERR_SHAPE.  Patches EViT fused or a
+ *   pruning stage dropped come out as -1; the fused token is not followed.  Errors as tr_stage_decisions, each before any launch.
+ * tr_dense_gather: out[b, :, p] = tokens[b, index[b, p], :] where 0 <= index[b, p] < n_rows (compared before the read), `fill` elsewhere.
+ *   tokens fp32 [B, n_rows, D] contiguous, index int32 [B, P]; out fp32, or bf16 when out_is_bf16 (round to nearest even: the bits of
+ *   torch's .to(bfloat16)); layout TR_LAYOUT_NHWC = [B, P, D] (channels last), TR_LAYOUT_NCHW = [B, D, P], anything else TR_ERR_CONFIG.
+ *   Every output element is written exactly once (no memset, no atomics).  D % 4 == 0, D <= 1024, 1 <= P <= 1024, n_rows >= 1:
+ *   TR_ERR_SHAPE otherwise; pointers 16-byte aligned.  NCHW stores 16 bytes (bf16: 8) along p when P % 4 == 0, single elements otherwise. */
+int tr_dense_index(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems, const tr_decision_stage* stages,
+                   int n_stages, int B, int P0, int n_last, int32_t* index_out, tr_stream_t s);
+int tr_dense_gather(const float* tokens, const int32_t* index, void* out, int layout, int out_is_bf16, float fill, int B, int P, int n_rows,
+                    int D, tr_stream_t s);
+
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
  * gradients), up to 640 tokens (224 x 224 and 384 x 384 inputs).  DyViT (dyvit.py:221-229): noise_in = the Gumbel noise of every stage, fp32 [B,P,2] back to back (torch's

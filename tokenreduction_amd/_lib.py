@@ -219,6 +219,8 @@ SIGNATURES = {
     "tr_vit_forward_pixels_taps": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                         C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
     "tr_stage_decisions": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "tr_dense_index": (_i, [_vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _i, _vp, _vp]),
+    "tr_dense_gather": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp]),
     "tr_cls_tap": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _i, _vp]),
     "tr_final_tokens_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "tr_token_pool": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),

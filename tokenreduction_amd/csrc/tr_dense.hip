@@ -1,0 +1,279 @@
+// Dense feature maps from the reduced token stream: the final-normed rows of an eval forward (the final_tokens tap, fp32 [B, N_last, D]) put
+// back on the input's patch grid.
+//   tr_dense_index    the record-form decisions of tr_stage_decisions composed across the stages into index[b, p]: the row of the last
+//                     stream (1 ... N_last-1, row 0 is the CLS token) that stands for grid patch p, -1 where none does.  One workgroup of
+//                     256 threads per image; the state cur[p] (patch-relative row, -1 = lost) and the inverse table of a kept list live in
+//                     LDS.  Pure index shuffling; every value is compared with the length of what it is about to index BEFORE the read.
+//   tr_dense_gather   features[b, :, p] = tokens[b, index[b, p], :] where 0 <= index < n_rows, `fill` elsewhere; fp32 or bf16 (round to
+//                     nearest even) output, channels-last [B, P, D] or NCHW [B, D, P].  Every output element is written exactly once: no
+//                     memset in front of it, no atomics.
+// The gather is the hot path: it writes the largest tensor of the forward once and reads at most as much.  Channels-last is a row copy in
+// the shape of tr_taps.hip (a wave per output row, 16-byte loads).  NCHW transposes a tile of 64 patches x 64 channels through LDS: rows
+// come in with 16-byte loads (a 256-byte piece of each gathered row), leave along p with 16-byte stores (8-byte for bf16) when P % 4 == 0,
+// 4-byte (2-byte) ones otherwise.  The tile's leading dimension is 65 floats -- one 4-byte access width of padding -- so a column read
+// (32 lanes of a half wave on 32 banks) is conflict-free; the row writes rotate each lane's four elements so that they are too.
+#include "tr_common.h"
+
+#include <climits>
+
+namespace {
+
+constexpr int DI_THREADS = 256;
+constexpr int DI_MAX_P = 1024;
+
+struct dense_table {
+  tr_decision_stage st[TR_MAX_DECISION_STAGES];
+  int n_out[TR_MAX_DECISION_STAGES];
+  int n;
+};
+
+__host__ __device__ inline bool stage_has_map(int kind) {
+  return kind == TR_DECISION_CENTRES || kind == TR_DECISION_TOME || kind == TR_DECISION_SOFT;
+}
+
+__global__ __launch_bounds__(DI_THREADS) void dense_index_kernel(const int32_t* __restrict__ kept, const int32_t* __restrict__ assign,
+                                                                 dense_table tab, int B, int P0, int32_t* __restrict__ index_out) {
+  __shared__ int cur[DI_MAX_P];
+  __shared__ int inv[DI_MAX_P];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int p = tid; p < P0; p += DI_THREADS) cur[p] = p;
+  for (int s = 0; s < tab.n; ++s) {
+    const tr_decision_stage st = tab.st[s];
+    const int n_out = tab.n_out[s];
+    if (stage_has_map(st.kind)) {
+      // cur[p] = assign[cur[p]]: a thread touches its own entries of cur only, no barrier needed between map stages
+      const int P_in = st.n_in - 1;
+      const int32_t* a = assign + st.assign_off + (size_t)b * P_in;
+      for (int p = tid; p < P0; p += DI_THREADS) {
+        const int c = cur[p];
+        int v = -1;
+        if (c >= 0 && c < P_in) {
+          v = a[c];
+          if (v < 0 || v >= n_out) v = -1;
+        }
+        cur[p] = v;
+      }
+    } else {
+      // the kept list is absolute: cur[p] = the lowest j with kept[j] == p (an LDS atomicMin: deterministic whatever the order)
+      const int W = n_out;
+      const int32_t* kp = kept + st.kept_off + (size_t)b * W;
+      for (int p = tid; p < P0; p += DI_THREADS) inv[p] = INT_MAX;
+      __syncthreads();
+      for (int j = tid; j < W; j += DI_THREADS) {
+        const int v = kp[j];
+        if (v >= 0 && v < P0) atomicMin(&inv[v], j);
+      }
+      __syncthreads();
+      for (int p = tid; p < P0; p += DI_THREADS) {
+        const int j = inv[p];
+        cur[p] = j == INT_MAX ? -1 : j;
+      }
+      __syncthreads();                                   // (inv is filled again by the next kept stage)
+    }
+  }
+  int32_t* out = index_out + (size_t)b * P0;
+  for (int p = tid; p < P0; p += DI_THREADS) {
+    const int c = cur[p];
+    out[p] = c >= 0 ? c + 1 : -1;
+  }
+}
+
+// ---- the gather ------------------------------------------------------------------------------------------------------------------------
+// fp32 -> bf16 bits, round to nearest even in integer arithmetic (the bits of tensor.to(torch.bfloat16): denormals are rounded like any
+// other value whatever the wave's denormal mode, a NaN becomes the quiet NaN 0x7fc0)
+__device__ __forceinline__ unsigned int bf16_rne_bits(float f) {
+  const unsigned int u = __builtin_bit_cast(unsigned int, f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+// Channels-last: one wave per output row (b, p), lane l on the 16-byte chunks l, l + 64, ...
+template <bool BF16>
+__global__ __launch_bounds__(256) void dense_gather_nhwc_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
+                                                                void* __restrict__ out, float fill, long rows, int P, int n_rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long b = row / P;
+  const int idx = index[row];
+  const bool ok = idx >= 0 && idx < n_rows;
+  const float* src = tokens + ((size_t)b * n_rows + (ok ? idx : 0)) * D;
+  for (int c = 4 * lane; c < D; c += 256) {
+    float4 v = make_float4(fill, fill, fill, fill);
+    if (ok) v = *reinterpret_cast<const float4*>(src + c);
+    if (BF16) {
+      uint2 o;
+      o.x = bf16_rne_bits(v.x) | (bf16_rne_bits(v.y) << 16);
+      o.y = bf16_rne_bits(v.z) | (bf16_rne_bits(v.w) << 16);
+      *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + (size_t)row * D + c) = o;
+    } else {
+      *reinterpret_cast<float4*>(static_cast<float*>(out) + (size_t)row * D + c) = v;
+    }
+  }
+}
+
+constexpr int DG_TP = 64;            // patches per tile
+constexpr int DG_TC = 64;            // channels per tile
+constexpr int DG_LD = DG_TC + 1;     // one 4-byte access width of padding: column reads hit 32 different banks
+
+// NCHW: tile (image b, patches p0 ... p0+63, channels c0 ... c0+63).  The tiles of one image are consecutive logical ids, and xcd_remap gives
+// each XCD a contiguous run of them: the rows of an image that many patches share (the merge families) are then read through one L2.
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(256) void dense_gather_nchw_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
+                                                                void* __restrict__ out, float fill, int P, int n_rows, int D, int ptiles,
+                                                                int ctiles) {
+  __shared__ float tile[DG_TP * DG_LD];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int ct = id % ctiles, pt = (id / ctiles) % ptiles, b = id / (ctiles * ptiles);
+  const int p0 = pt * DG_TP, c0 = ct * DG_TC;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+  // rows in: a wave instruction takes 4 rows x 64 channels, 16 lanes per row; all four loads of a wave are issued before the first write
+  const int l16 = lane & 15, c = c0 + 4 * l16;
+  float4 v[4];
+  int rr[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    rr[it] = wave * 16 + it * 4 + (lane >> 4);
+    const int p = p0 + rr[it];
+    int idx = -1;
+    if (p < P) idx = index[(size_t)b * P + p];
+    v[it] = make_float4(fill, fill, fill, fill);
+    if (idx >= 0 && idx < n_rows && c < D) v[it] = *reinterpret_cast<const float4*>(tokens + ((size_t)b * n_rows + idx) * D + c);
+  }
+  // a half wave writes rows r and r + 1 (65 floats apart: one bank on), 16 lanes each, lane l16 on elements 4 * l16 ... + 3.  With step i
+  // writing element (i + rot) % 4, rot = 0, 1, 1, 2 for the four groups of 8 lanes, the 32 lanes of a ds_write_b32 hit 32 different banks
+  const int rot = (((lane >> 3) & 3) + 1) >> 1;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const float e[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = (i + rot) & 3;
+      const float val = j == 0 ? e[0] : j == 1 ? e[1] : j == 2 ? e[2] : e[3];
+      tile[rr[it] * DG_LD + 4 * l16 + j] = val;
+    }
+  }
+  __syncthreads();
+
+  if (VEC) {
+    // columns out: a half wave takes 32 patches x 4 channels -- lane = (8 groups of 4 patches) x (4 channels): step j reads
+    // tile[4 * lp + j][cc], banks 4 * lp + j + cc -- and the two halves of a wave store the two 128-byte halves of the same channel rows
+    const int lp = lane & 7, cc = (lane >> 3) & 3, half = lane >> 5;
+    const int pr = 32 * half + 4 * lp, p = p0 + pr;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int cr = wave * 16 + it * 4 + cc, ch = c0 + cr;
+      float o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = tile[(pr + j) * DG_LD + cr];
+      if (ch < D && p < P) {                             // (P % 4 == 0: p < P means p + 3 < P)
+        const size_t at = ((size_t)b * D + ch) * P + p;
+        if (BF16) {
+          uint2 w;
+          w.x = bf16_rne_bits(o[0]) | (bf16_rne_bits(o[1]) << 16);
+          w.y = bf16_rne_bits(o[2]) | (bf16_rne_bits(o[3]) << 16);
+          *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + at) = w;
+        } else {
+          *reinterpret_cast<float4*>(static_cast<float*>(out) + at) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+      }
+    }
+  } else {
+    // P % 4 != 0: the channel rows of the output are not 16-byte aligned -- one element per lane, a wave on 64 patches of one channel
+    const int p = p0 + lane;
+#pragma unroll 4
+    for (int it = 0; it < 16; ++it) {
+      const int cr = wave * 16 + it, ch = c0 + cr;
+      const float o = tile[lane * DG_LD + cr];
+      if (ch < D && p < P) {
+        const size_t at = ((size_t)b * D + ch) * P + p;
+        if (BF16) static_cast<uint16_t*>(out)[at] = (uint16_t)bf16_rne_bits(o);
+        else static_cast<float*>(out)[at] = o;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int tr_dense_index(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems, const tr_decision_stage* stages,
+                              int n_stages, int B, int P0, int n_last, int32_t* index_out, tr_stream_t s) {
+  TR_REQUIRE(n_stages >= 0 && n_stages <= TR_MAX_DECISION_STAGES, TR_ERR_CONFIG, "tr_dense_index: %d stages (at most %d)", n_stages,
+             TR_MAX_DECISION_STAGES);
+  TR_REQUIRE(index_out && (n_stages == 0 || stages), TR_ERR_NULL, "tr_dense_index: null pointer");
+  TR_REQUIRE(B > 0 && P0 >= 1 && P0 <= DI_MAX_P && n_last >= 2, TR_ERR_SHAPE, "tr_dense_index: need B > 0, 1 <= P0 <= 1024, n_last >= 2 (B=%d P0=%d n_last=%d)",
+             B, P0, n_last);
+  dense_table tab;
+  tab.n = n_stages;
+  int last_block = -1, n_out = P0;
+  bool seen_map = false;
+  for (int i = 0; i < n_stages; ++i) {
+    const tr_decision_stage& st = stages[i];
+    TR_REQUIRE(st.kind >= TR_DECISION_PRUNE && st.kind <= TR_DECISION_SOFT, TR_ERR_CONFIG, "tr_dense_index: stage %d has kind %d", i, st.kind);
+    TR_REQUIRE(st.block > last_block && st.block < TR_MAX_DEPTH, TR_ERR_CONFIG,
+               "tr_dense_index: stage %d names block %d (ascending blocks below %d)", i, st.block, TR_MAX_DEPTH);
+    last_block = st.block;
+    TR_REQUIRE(st.n_in >= 2 && st.n_in <= P0 + 1 && st.k >= 1 && st.k < st.n_in, TR_ERR_SHAPE,
+               "tr_dense_index: stage %d needs 2 <= n_in <= P0 + 1 and 1 <= k < n_in (n_in=%d k=%d P0=%d)", i, st.n_in, st.k, P0);
+    TR_REQUIRE(st.kind != TR_DECISION_ATS || st.k >= 2, TR_ERR_SHAPE, "tr_dense_index: stage %d: an ATS stage needs k >= 2", i);
+    if (stage_has_map(st.kind)) {
+      seen_map = true;
+      n_out = st.kind == TR_DECISION_TOME ? st.n_in - 1 - (st.k < (st.n_in - 1) / 2 ? st.k : (st.n_in - 1) / 2) : st.k;
+      const size_t P_in = (size_t)st.n_in - 1;
+      TR_REQUIRE(assign, TR_ERR_NULL, "tr_dense_index: stage %d reads an assignment map, assign is NULL", i);
+      TR_REQUIRE(st.assign_off >= 0 && (size_t)st.assign_off + (size_t)B * P_in <= assign_elems, TR_ERR_SHAPE,
+                 "tr_dense_index: stage %d: map [%d, %zu] at %lld leaves assign (%zu elements)", i, B, P_in, (long long)st.assign_off, assign_elems);
+    } else {
+      // an absolute kept list overrides the state: behind a map stage the rows it names are no grid patches any more
+      TR_REQUIRE(!seen_map, TR_ERR_CONFIG, "tr_dense_index: stage %d has only a kept list and stands behind a stage with an assignment map", i);
+      n_out = st.kind == TR_DECISION_EVIT ? st.k + 1 : st.kind == TR_DECISION_ATS ? st.k - 1 : st.k;
+      TR_REQUIRE(kept, TR_ERR_NULL, "tr_dense_index: stage %d reads a kept list, kept is NULL", i);
+      TR_REQUIRE(st.kept_off >= 0 && (size_t)st.kept_off + (size_t)B * n_out <= kept_elems, TR_ERR_SHAPE,
+                 "tr_dense_index: stage %d: kept list [%d, %d] at %lld leaves kept (%zu elements)", i, B, n_out, (long long)st.kept_off, kept_elems);
+    }
+    tab.st[i] = st;
+    tab.n_out[i] = n_out;
+  }
+  TR_REQUIRE(n_out == n_last - 1, TR_ERR_SHAPE, "tr_dense_index: the stages end at %d patch rows, the last stream has %d", n_out, n_last - 1);
+  TR_REQUIRE(tr_aligned16(kept) && tr_aligned16(assign) && tr_aligned16(index_out), TR_ERR_ALIGN, "tr_dense_index: pointers must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  tr_prof_note("tr_dense_index", 0.0, 4.0 * B * P0 * (n_stages + 1));
+  hipLaunchKernelGGL(dense_index_kernel, dim3(B), dim3(DI_THREADS), 0, st, kept, assign, tab, B, P0, index_out);
+  TR_CHECK_LAUNCH("tr_dense_index");
+  return TR_OK;
+}
+
+extern "C" int tr_dense_gather(const float* tokens, const int32_t* index, void* out, int layout, int out_is_bf16, float fill, int B, int P,
+                               int n_rows, int D, tr_stream_t s) {
+  TR_REQUIRE(tokens && index && out, TR_ERR_NULL, "tr_dense_gather: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_CONFIG, "tr_dense_gather: layout %d (TR_LAYOUT_NCHW or TR_LAYOUT_NHWC)", layout);
+  TR_REQUIRE(B > 0 && P >= 1 && P <= DI_MAX_P && n_rows >= 1 && D > 0 && D % 4 == 0 && D <= 1024, TR_ERR_SHAPE,
+             "tr_dense_gather: need B > 0, 1 <= P <= 1024, n_rows >= 1, D %% 4 == 0, D <= 1024 (B=%d P=%d n_rows=%d D=%d)", B, P, n_rows, D);
+  TR_REQUIRE(tr_aligned16(tokens) && tr_aligned16(index) && tr_aligned16(out), TR_ERR_ALIGN, "tr_dense_gather: pointers must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const bool bf = out_is_bf16 != 0;
+  // required traffic: every output element once, at most as many token bytes, the index
+  tr_prof_note("tr_dense_gather", 0.0, (double)B * P * D * (4.0 + (bf ? 2.0 : 4.0)) + 4.0 * B * P);
+  if (layout == TR_LAYOUT_NHWC) {
+    const long rows = (long)B * P;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (bf) hipLaunchKernelGGL((dense_gather_nhwc_kernel<true>), grid, dim3(256), 0, st, tokens, index, out, fill, rows, P, n_rows, D);
+    else hipLaunchKernelGGL((dense_gather_nhwc_kernel<false>), grid, dim3(256), 0, st, tokens, index, out, fill, rows, P, n_rows, D);
+  } else {
+    const int ptiles = (P + DG_TP - 1) / DG_TP, ctiles = (D + DG_TC - 1) / DG_TC;
+    const long blocks = (long)B * ptiles * ctiles;
+    TR_REQUIRE(blocks <= INT_MAX, TR_ERR_SHAPE, "tr_dense_gather: %ld tiles", blocks);
+    const dim3 grid((unsigned)blocks);
+    const bool vec = P % 4 == 0;
+#define DG_LAUNCH(BF, VEC) \
+  hipLaunchKernelGGL((dense_gather_nchw_kernel<BF, VEC>), grid, dim3(256), 0, st, tokens, index, out, fill, P, n_rows, D, ptiles, ctiles)
+    if (bf && vec) DG_LAUNCH(true, true);
+    else if (bf) DG_LAUNCH(true, false);
+    else if (vec) DG_LAUNCH(false, true);
+    else DG_LAUNCH(false, false);
+#undef DG_LAUNCH
+  }
+  TR_CHECK_LAUNCH("tr_dense_gather");
+  return TR_OK;
+}

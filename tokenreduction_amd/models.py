@@ -29,6 +29,8 @@ forward_async -- the CLS rows after chosen blocks and the final-normed tokens, f
 The stages' decisions (which tokens each stage kept, which output every token went to) come the same two ways: viz_mode's viz_data, or
 forward_decisions / forward_async(decisions=True) -- int32 device tensors in the form of validate.py's per-image records, one launch
 (tr_stage_decisions) behind the fast-path forward.
+forward_dense / forward_async(dense=...) put the final-normed rows of the last block back on the input's patch grid ([B, D, h, w] or
+[B, h, w, D]) through those decisions: two more launches (tr_dense_index, tr_dense_gather), `fill` where no row stands for a patch.
 """
 from __future__ import annotations
 
@@ -790,7 +792,48 @@ class VisionTransformer(nn.Module):
         taps = self._tap_request(cls_blocks, final_tokens) if (cls_blocks is not None or final_tokens) else None
         return self._forward_eval(x, 0, taps, True)
 
-    def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False, decisions=False):
+    _DENSE_FORMATS = ("NCHW", "NHWC")
+
+    def _dense_request(self, x, what, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
+        """(format, dtype, fill) of a forward_dense / forward_async(dense=...) call, or the refusal."""
+        if self.training:
+            raise RuntimeError("dense feature maps are an eval feature: call model.eval() first (the training executor has no taps)")
+        if self.viz_mode:
+            raise RuntimeError("dense feature maps and viz_mode are two ways to the same rows: switch viz_mode off (viz_data['Features'] "
+                               "already holds every row of every recorded block)")
+        if self.dynamic_width:
+            raise RuntimeError(f"{what} cannot run under dynamic_width (the token counts of a stage are then data dependent and the executor "
+                               "synchronises mid-forward): switch dynamic_width off or use viz_mode")
+        if not x.is_cuda:
+            raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
+        if output_fmt not in self._DENSE_FORMATS:
+            raise ValueError(f"output_fmt must be one of {self._DENSE_FORMATS}, got {output_fmt!r}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+        if self.patch_embed.num_patches > 1024 or self.embed_dim % 4 or self.embed_dim > 1024:
+            raise ValueError(f"dense feature maps take at most 1024 patches and a width that is a multiple of 4 up to 1024 "
+                             f"({self.patch_embed.num_patches} patches, width {self.embed_dim})")
+        return output_fmt, dtype, float(fill)
+
+    def forward_dense(self, x: torch.Tensor, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
+        """Eval forward with a dense feature map: (logits, {"features", "index", "grid": (h, w)}).  `features` is the final norm of the last
+        block's rows (the final_tokens tap, fp32 arithmetic) put back on the input's patch grid: [B, D, h, w] for output_fmt "NCHW", [B, h, w,
+        D] for "NHWC", fp32 or bf16 (dtype; round to nearest even of the fp32 value).  `index` int32 [B, h * w] names, per grid patch, the row of
+        the reduced stream (1 ... N_last-1) that stands for it -- the stages' decisions composed on the device (tr_dense_index): an
+        assignment map sends a patch to the row it was merged into (ToMe, DPC-KNN, K-Medoids; the hard argmax map for the soft families), a
+        kept list to its position in the list.  A patch no row stands for has index -1 and `fill` in every channel: the patches a pruning
+        family dropped, and the patches EViT put into its fused token (the fused token is not followed; it is nobody's row).  DeiT and
+        Heuristic keep every row: the index is the identity.  The forward is that of forward_decisions(final_tokens=True) with two more
+        launches (tr_dense_index, tr_dense_gather) in the same stream and the same captured graph; the request is part of the graph key and
+        the logits are those of model(x).  The map and the index are static buffers per workspace slot, allocated on the first dense call
+        (at 512 x 512 inputs, DeiT-B width and batch 256 the fp32 map is about 0.8 GB per slot) and cloned out like the taps.  The taps and
+        decision records themselves are not returned: ask forward_decisions for them.  Intermediate blocks, a soft-weighted un-merge,
+        training and a gradient are not built.  Refuses train mode, viz_mode, dynamic_width."""
+        if isinstance(x, AugmentedBatch):
+            x = x.float()
+        return self._forward_eval(x, 0, dense=self._dense_request(x, "forward_dense", output_fmt, dtype, fill))
+
+    def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False, decisions=False, dense=None):
         """Eval forward that may run BESIDE the previous one: the call enqueues the forward on one of `pipeline_depth` (default 2) side streams
         -- each with its own workspace and captured hipGraph -- behind everything already enqueued on the caller's current stream, and
         returns a handle at once; `handle.result()` makes the caller's current stream wait for that forward and returns what `model(x)`
@@ -801,11 +844,17 @@ class VisionTransformer(nn.Module):
         Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete).
         cls_blocks / final_tokens: the output taps of forward_taps -- the result is then what forward_taps returns.  With taps, train mode,
         viz_mode and dynamic_width are refused instead of run synchronously.  decisions=True: the decision taps of forward_decisions, with
-        the same refusals -- the result is what forward_decisions returns."""
+        the same refusals -- the result is what forward_decisions returns.  dense=dict(output_fmt=..., dtype=..., fill=...) (any subset; {} for
+        the defaults): the dense feature map of forward_dense, with its refusals -- the result is what forward_dense returns; it does not
+        combine with the other keywords."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
         taps = None
-        if decisions:
+        if dense is not None:
+            if decisions or cls_blocks is not None or final_tokens:
+                raise ValueError("forward_async: dense= does not combine with cls_blocks / final_tokens / decisions")
+            dense = self._dense_request(x, "forward_async(dense=...)", **dict(dense))
+        elif decisions:
             self._decision_request(x, "forward_async(decisions=True)")
             if cls_blocks is not None or final_tokens:
                 taps = self._tap_request(cls_blocks, final_tokens)
@@ -832,13 +881,13 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(x.device)
         side.wait_stream(cur)                          # inputs and weights are ready where the forward runs
         with torch.cuda.stream(side):
-            out = self._forward_eval(x, slot + 1, taps, bool(decisions))
+            out = self._forward_eval(x, slot + 1, taps, bool(decisions), dense)
             done = torch.cuda.Event()
             done.record(side)
         x.record_stream(side)
         return _Pending(out, done)
 
-    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None, decisions=False):
+    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None, decisions=False, dense=None):
         if not x.is_cuda:
             raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
         lib = _lib.load()
@@ -851,6 +900,8 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"expected [B,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(x.shape)}")
         x, fmt, lut = self._executor_input(x)
         ws = self._workspace(B, x.device, slot)
+        if dense is not None:
+            taps, decisions = ((), True), True         # the rows of the final_tokens tap, placed by the stages' record-form decisions
         if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
             ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
         want_feat = (self.viz_mode or self._always_features) and taps is None
@@ -870,6 +921,14 @@ class VisionTransformer(nn.Module):
             tap_arg = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
                                      ws["tap_final"].data_ptr() if want_final else None)
         dec = self._decision_plan(ws, B, x.device) if decisions else None
+        if dense is not None:
+            # static per workspace slot: the index [B, P0] and one feature map per output dtype (either layout is B * P0 * D elements)
+            P0 = self.patch_embed.num_patches
+            if ws.get("dense_index") is None:
+                ws["dense_index"] = torch.empty(B * P0, dtype=torch.int32, device=x.device)
+            dense_feat = ws.setdefault("dense_feat", {}).get(dense[1])
+            if dense_feat is None:
+                dense_feat = ws["dense_feat"][dense[1]] = torch.empty(B * P0 * self.embed_dim, dtype=dense[1], device=x.device)
         soft = ws.get("soft") if dec is None or dec["soft"] is None else dec["soft"]      # (a buffer of its own: ws["soft"] stays viz_mode's)
         self._noise_slot = slot                      # (a static buffer per workspace slot: two forwards in flight must not share one)
         noise_ptr = self._noise_ptr(B, x.device)
@@ -896,6 +955,17 @@ class VisionTransformer(nn.Module):
                 rc = lib.tr_stage_decisions(ws["kept"].data_ptr(), ws["compl"].data_ptr(), ws["kept"].numel(), *dec["args"][0], dec["table"],
                                             dec["n"], B, self.patch_embed.num_patches + 1, *dec["args"][1], torch.cuda.current_stream().cuda_stream)
                 _lib.check(rc, "tr_stage_decisions")
+            if dense is not None:
+                # the decisions composed into one row per grid patch, then the un-reduce: two launches in the same stream (and graph)
+                stream, n_last = torch.cuda.current_stream().cuda_stream, tokens[self.depth - 1]
+                kept_out, kept_n, _, assign_out, assign_n = dec["args"][1]
+                rc = lib.tr_dense_index(kept_out, kept_n, assign_out, assign_n, dec["table"], dec["n"], B, P0, n_last,
+                                        ws["dense_index"].data_ptr(), stream)
+                _lib.check(rc, "tr_dense_index")
+                rc = lib.tr_dense_gather(ws["tap_final"].data_ptr(), ws["dense_index"].data_ptr(), dense_feat.data_ptr(),
+                                         _lib.TR_LAYOUT_NCHW if dense[0] == "NCHW" else _lib.TR_LAYOUT_NHWC, int(dense[1] == torch.bfloat16),
+                                         dense[2], B, P0, n_last, self.embed_dim, stream)
+                _lib.check(rc, "tr_dense_gather")
             return list(tokens)
 
         with torch.cuda.device(x.device):
@@ -903,12 +973,20 @@ class VisionTransformer(nn.Module):
             if (self.use_graph and not ws.get("graph_off") and not torch.cuda.is_current_stream_capturing()
                     and not self.dynamic_width):      # (ATS dynamic width: the executor reads a token count back mid-forward)
                 key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width,
-                       taps) + ((True,) if dec is not None else ())
+                       taps) + ((("dense",) + dense,) if dense is not None else ()) + ((True,) if dec is not None else ())
                 res = self._replay(ws, key, launch, B, x.device)
             logits, tokens = res if res is not None else self._plain_launch(launch, B, x.device)
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
         self._last_tokens = list(tokens)
         self._last_ws = ws
+        if dense is not None:
+            # cloned out of the static buffers in stream order, like the taps
+            if dec["static"] is None and not dec["checked"]:
+                self._decision_result(dec, B, list(tokens))     # (the stage table against the executor's token counts, once per workspace)
+            h, w = self.patch_embed.grid_size
+            feat = dense_feat.clone()
+            return logits, {"features": feat.view(B, self.embed_dim, h, w) if dense[0] == "NCHW" else feat.view(B, h, w, self.embed_dim),
+                            "index": ws["dense_index"].clone().view(B, h * w), "grid": (h, w)}
         if taps is not None:
             # cloned out of the static buffers in stream order, the way a replay's logits are: the next forward on this slot overwrites them
             blocks, want_final = taps

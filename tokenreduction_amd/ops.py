@@ -586,6 +586,50 @@ def stage_decisions(kept_idx: torch.Tensor, compl_idx: torch.Tensor, soft: torch
     return out
 
 
+def dense_index(kept: torch.Tensor, assign: torch.Tensor, stages, B: int, P0: int, n_last: int, table=None, out: torch.Tensor = None) -> torch.Tensor:
+    """index int32 [B, P0]: the row of the last stream (1 ... n_last-1) that stands for grid patch p, -1 where none does (tr_dense_index, one
+    launch).  kept / assign: the flat int32 buffers tr_stage_decisions wrote for `stages` [(blk, _lib.TR_DECISION_* kind, n_in, k)] laid out
+    by decision_table (either may be None where no stage has one); `table`: that ctypes table, built here when None.  No stage: the identity."""
+    _same_device(kept, assign, out)
+    if table is None:
+        table = decision_table(stages, B)[0]
+    if out is None:
+        dev = next((t.device for t in (kept, assign) if t is not None), torch.device("cuda", torch.cuda.current_device()))
+        out = torch.empty(B, P0, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tr_dense_index(_opt(kept, torch.int32, "kept"), 0 if kept is None else kept.numel(), _opt(assign, torch.int32, "assign"),
+                                          0 if assign is None else assign.numel(), table, len(stages), B, P0, n_last,
+                                          _dev(out, torch.int32, "out"), _stream(out)), "tr_dense_index")
+    return out
+
+
+DENSE_LAYOUTS = {"NCHW": _lib.TR_LAYOUT_NCHW, "NHWC": _lib.TR_LAYOUT_NHWC}
+
+
+def dense_gather(tokens: torch.Tensor, index: torch.Tensor, layout: str = "NCHW", dtype=torch.float32, fill: float = 0.0,
+                 out: torch.Tensor = None) -> torch.Tensor:
+    """features[b, :, p] = tokens[b, index[b, p], :] where 0 <= index < n_rows, `fill` elsewhere (tr_dense_gather, one launch): tokens fp32
+    [B, n_rows, D], index int32 [B, P]; the result is [B, D, P] (layout "NCHW") or [B, P, D] ("NHWC"), fp32 or bf16 (round to nearest even).
+    Every element of the result is written once."""
+    _same_device(tokens, index, out)
+    if layout not in DENSE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(DENSE_LAYOUTS)}, got {layout!r}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    B, n_rows, D = tokens.shape
+    P = index.shape[1]
+    if index.shape[0] != B:
+        raise ValueError(f"index must be [B, P] with B = {B}, got {tuple(index.shape)}")
+    shape = (B, D, P) if layout == "NCHW" else (B, P, D)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=tokens.device)
+    elif out.numel() != B * D * P:
+        raise ValueError(f"out must hold {B * D * P} elements, got {out.numel()}")
+    _lib.check(_lib.load().tr_dense_gather(_dev(tokens, torch.float32, "tokens"), _dev(index, torch.int32, "index"), _dev(out, dtype, "out"),
+                                           DENSE_LAYOUTS[layout], int(dtype == torch.bfloat16), float(fill), B, P, n_rows, D, _stream(tokens)),
+               "tr_dense_gather")
+    return out.view(shape)
+
+
 def attention_f32(qkv: torch.Tensor, B: int, N: int, H: int, want_cls: bool = False, size: torch.Tensor = None,
                   colsum_part: torch.Tensor = None, split: bool = False):
     out = torch.empty(B * N, H * 64, dtype=torch.float32, device=qkv.device)

@@ -1,0 +1,181 @@
+"""Dense feature maps against the torch restatement they replace, both sides in one process on one box (profiles/dense_lab.md).
+
+    python tools/dense_bench.py [--batch 256] [--steps 20] [--rounds 3] [--models deit topk tome sit dpcknn] [--fmt NCHW] [--dtype fp32]
+    python tools/dense_bench.py --kernels          # the same forwards under rocprofv3 --kernel-trace --stats: the gather's bytes/s
+
+Per model (DeiT-S width, 224 x 224: dense DeiT as the identity case, Top-K kr 0.7, ToMe, SiT, DPC-KNN; reduction at blocks 3 / 6 / 9) one
+JSON line with ms per batch, device events around `steps` forwards, the sides alternating within a round:
+  plain    model(x)
+  torch    model.forward_decisions(x, final_tokens=True), then the map on the device in torch: the decisions composed stage by stage with
+           torch.gather / scatter, the rows gathered per patch, masked with the fill, and permute().contiguous() for NCHW
+  dense    model.forward_dense(x)
+(gather_required_bytes: the upper bound of one fp32 row per patch; gather_distinct_bytes: the map plus every row of the last stream once.)
+The two maps are compared bit for bit before anything is timed.  --kernels runs a child process of this tool (leg `dense` only) under
+rocprofv3 and divides the bytes tr_dense_gather HAS to move -- every output element once, the rows it reads at most once per patch, the
+index: computed from the shapes here -- by the kernel's average duration, against the HBM rate a float4 copy reaches on this part."""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MODELS = {"deit": "deit_small_patch16_224_local", "topk": "topk_small_patch16_224", "tome": "tome_small_patch16_224", "sit": "sit_small_patch16_224",
+          "dpcknn": "dpcknn_small_patch16_224"}
+HBM_COPY_TBS = 6.29          # measured float4 copy on MI355X (8.0 TB/s on paper)
+
+
+def _args(**kw):
+    base = dict(keep_rate=[0.7], reduction_loc=[3, 6, 9], viz_mode=False, dyvit_distill=False, k_neighbors=5, equal_weight=False, cluster_iters=3,
+                sinkhorn_eps=1.0, heuristic_pattern="l2", not_contiguous=False, min_radius=None)
+    base.update(kw)
+    return types.SimpleNamespace(**base)
+
+
+def _create(tag):
+    import torch
+    import tokenreduction_amd as tra
+    torch.manual_seed(0)
+    args = _args(keep_rate=[1.0], reduction_loc=[]) if tag == "deit" else _args()
+    return tra.create_model(MODELS[tag], pretrained=False, num_classes=1000, drop_rate=0.0, drop_path_rate=0.0, drop_block_rate=None, img_size=224,
+                            args=args).cuda().eval()
+
+
+def _event_ms(fn, steps):
+    import torch
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(steps):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / steps
+
+
+def torch_dense(model, x, fmt, dtype, fill):
+    """The map through forward_decisions and torch ops on the device (the semantics of tr_dense_index / tr_dense_gather)."""
+    import torch
+    from tokenreduction_amd import _lib
+    logits, taps, dec = model.forward_decisions(x, final_tokens=True)
+    tokens = taps["final_tokens"]
+    B, n_last, D = tokens.shape
+    h, w = model.patch_embed.grid_size
+    P0 = h * w
+    cur = torch.arange(P0, device=x.device).expand(B, P0)
+    for blk, kind, n_in, k in model._decision_stages():
+        if kind in (_lib.TR_DECISION_CENTRES, _lib.TR_DECISION_TOME, _lib.TR_DECISION_SOFT):
+            n_out = n_in - 1 - min(k, (n_in - 1) // 2) if kind == _lib.TR_DECISION_TOME else k
+            ok = (cur >= 0) & (cur < n_in - 1)
+            nxt = torch.gather(dec["assign"][blk].long(), 1, cur.clamp(0, n_in - 2))
+            cur = torch.where(ok & (nxt >= 0) & (nxt < n_out), nxt, torch.full_like(nxt, -1))
+        else:
+            kept = dec["kept"][blk].long()
+            W = kept.shape[1]
+            valid = (kept >= 0) & (kept < P0)
+            inv = torch.full((B, P0 + 1), W, dtype=torch.long, device=x.device)
+            inv.scatter_reduce_(1, torch.where(valid, kept, torch.full_like(kept, P0)), torch.arange(W, device=x.device).expand(B, W), "amin")
+            cur = torch.where(inv[:, :P0] < W, inv[:, :P0], torch.full_like(inv[:, :P0], -1))
+    index = torch.where(cur >= 0, cur + 1, cur)
+    rows = torch.gather(tokens, 1, index.clamp(0, n_last - 1)[:, :, None].expand(B, P0, D))
+    feat = torch.where((index >= 0)[:, :, None], rows, torch.full_like(rows, fill)).to(dtype)
+    feat = feat.permute(0, 2, 1).contiguous().view(B, D, h, w) if fmt == "NCHW" else feat.view(B, h, w, D)
+    return logits, feat, index.int()
+
+
+def required_bytes(B, P0, D, out_bytes):
+    """What the gather has to move: the map once, one fp32 row per patch at most, the index."""
+    return B * P0 * D * (out_bytes + 4) + 4 * B * P0
+
+
+def run(tag, batch, steps, rounds, fmt, dtype, only_dense=False):
+    import torch
+    m = _create(tag)
+    tdtype = torch.bfloat16 if dtype == "bf16" else torch.float32
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(batch, 3, 224, 224, generator=g).cuda()
+    if tag == "dpcknn":
+        m.density_noise = {blk: torch.rand(batch, P, generator=g).cuda() for blk, _, P in m._stage_shapes()}
+    dense = lambda: m.forward_dense(x, output_fmt=fmt, dtype=tdtype, fill=0.0)
+    if only_dense:
+        m.use_graph = False                                    # plain launches: every kernel shows under its own name in the trace
+        for _ in range(steps + 2):
+            dense()
+        torch.cuda.synchronize()
+        m.check_status()
+        return
+    la, fa, ia = torch_dense(m, x, fmt, tdtype, 0.0)
+    lb, db = dense()
+    bits = torch.int16 if tdtype == torch.bfloat16 else torch.int32
+    same = bool(torch.equal(la, lb) and torch.equal(ia, db["index"]) and torch.equal(fa.view(bits), db["features"].view(bits)))
+    sides = {"plain": lambda: m(x), "torch": lambda: torch_dense(m, x, fmt, tdtype, 0.0), "dense": dense}
+    for fn in sides.values():
+        for _ in range(2):
+            fn()
+    ms = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, fn in sides.items():
+            ms[k].append(round(_event_ms(fn, steps), 4))
+    m.check_status()
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    P0, D = m.patch_embed.num_patches, m.embed_dim
+    print(json.dumps({"leg": "forward", "model": MODELS[tag], "B": batch, "fmt": fmt, "dtype": dtype, "steps": steps, "bitwise_equal": same,
+                      "n_last": int(m._last_tokens[-1]), "ms_per_batch": ms, "median_ms_per_batch": med,
+                      "extra_ms_over_plain": {k: round(med[k] - med["plain"], 4) for k in ("torch", "dense")},
+                      "gather_required_bytes": required_bytes(batch, P0, D, 2 if dtype == "bf16" else 4),
+                      "gather_distinct_bytes": batch * P0 * D * (2 if dtype == "bf16" else 4) + 4 * batch * int(m._last_tokens[-1]) * D}), flush=True)
+    assert same, "forward_dense and the torch restatement disagree"
+
+
+def kernels(a):
+    """rocprofv3 --kernel-trace --stats over a child that only runs forward_dense: one JSON line per model with the two kernels' average
+    duration and the gather's required bytes per second."""
+    for tag in a.models:
+        with tempfile.TemporaryDirectory() as tmp:
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
+                   "--child", "--models", tag, "--batch", str(a.batch), "--steps", str(a.steps), "--fmt", a.fmt, "--dtype", a.dtype]
+            subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
+            rows = []
+            for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+                rows += list(csv.DictReader(open(path)))
+        out = {"leg": "kernels", "model": MODELS[tag], "B": a.batch, "fmt": a.fmt, "dtype": a.dtype}
+        need = required_bytes(a.batch, 196, 384, 2 if a.dtype == "bf16" else 4)
+        for row in rows:
+            for key in ("dense_gather", "dense_index"):
+                if key in row["Name"]:
+                    calls = int(row["Calls"])
+                    avg_ns = float(row["AverageNs"]) if row.get("AverageNs") else float(row["TotalDurationNs"]) / calls
+                    out[key] = {"calls": calls, "average_us": round(avg_ns / 1e3, 3)}
+        if "dense_gather" in out:
+            tbs = need / (out["dense_gather"]["average_us"] * 1e-6) / 1e12
+            out["gather_required_bytes"] = need
+            out["gather_TB_per_s"] = round(tbs, 3)
+            out["of_hbm_copy_rate"] = round(tbs / HBM_COPY_TBS, 3)
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--models", nargs="+", default=list(MODELS), choices=list(MODELS))
+    ap.add_argument("--fmt", default="NCHW", choices=["NCHW", "NHWC"])
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.kernels:
+        kernels(a)
+    else:
+        import torch
+        assert torch.cuda.is_available(), "needs a GPU: nothing here is measured without one"
+        for tag in a.models:
+            run(tag, a.batch, a.steps, a.rounds, a.fmt, a.dtype, only_dense=a.child)
