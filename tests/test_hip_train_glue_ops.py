@@ -5,6 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _param_grad_ref as R
+from tests import _reduce_ref as RR
+from tests._reduce_ref import kernel_order_sum as _kernel_order_sum      # the reduces' fixed order, fp32 on the CPU
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 7.25
@@ -118,32 +122,6 @@ def test_f32_to_bf16_rounds_to_nearest_even(ops):
         ops.f32_to_bf16(torch.zeros(6, device="cuda"))
 
 
-def _kernel_order_sum(part, prefill):
-    """tr_reduce_partials_f32's documented fixed order in fp32 on the CPU: lane y of 4 adds partials y, y + 4, ... (whole groups of four
-    elements: sixteen partials at a time as (v0 + v1) + (v2 + v3); the ragged last group: one by one), the lanes are combined in lane
-    order, the destination is added last."""
-    S, count = part.shape
-    lanes_full, lanes_tail = [], []
-    for y in range(4):
-        a = torch.zeros_like(part[0])
-        s = y
-        while s + 12 < S:
-            a = a + ((part[s] + part[s + 4]) + (part[s + 8] + part[s + 12]))
-            s += 16
-        while s < S:
-            a = a + part[s]
-            s += 4
-        lanes_full.append(a)
-        t = torch.zeros_like(part[0])
-        for s in range(y, S, 4):
-            t = t + part[s]
-        lanes_tail.append(t)
-    full = ((lanes_full[0] + lanes_full[1]) + lanes_full[2]) + lanes_full[3]
-    tail = ((lanes_tail[0] + lanes_tail[1]) + lanes_tail[2]) + lanes_tail[3]
-    a = torch.where(torch.arange(count) < count // 4 * 4, full, tail)
-    return a if prefill is None else a + prefill
-
-
 @pytest.mark.parametrize("count", [1, 2, 255, 1027, 4096])
 @pytest.mark.parametrize("S", [1, 2, 37])
 def test_reduce_partials(ops, S, count):
@@ -174,6 +152,40 @@ def test_reduce_partials(ops, S, count):
                 assert torch.equal(got, _kernel_order_sum(part, pf)), f"accumulate={acc}: differs from the kernel's documented order"
                 want = part.double().sum(0) + (0 if pf is None else pf.double())
                 assert float((got.double() - want).abs().max()) <= 38 * 2.0 ** -24 * float(part.abs().sum(0).max() + 4)
+
+
+WS_SENT = -12345.5          # fills the workspace of the test below: a partial the first kernel did not write shows
+
+
+@pytest.mark.parametrize("M,D", RR.LN_REDUCE_SHAPES)
+def test_layernorm_param_reduce_order(ops, M, D):
+    """The pair reduce behind tr_layernorm_bwd in BOTH block layouts, bit for bit on Gaussian data: outside a deferred context the
+    [grid][D] partials of d_gamma and d_beta stay in the caller's workspace; their sum is restated on the CPU in the order of the layout the
+    call site must take (16 x 16 iff grid >= 64 and D <= 4096, 64 x 4 below) and compared with torch.equal, overwriting and accumulating
+    (the prior is added last).  Where the layouts differ on these very partials (tests/test_reduce_ref.py: they do at every S >= 64 on
+    the fp32 restatement of these inputs) the other layout's order fails this test."""
+    c = R.ln_case(M, D)
+    S = RR.ln_grid(M)
+    lanes = RR.layout_lanes(S, D)
+    g = _gen(M + D)
+    for acc in (False, True):
+        prior_g, prior_b = torch.randn(D, generator=g), torch.randn(D, generator=g)
+        ws = torch.full((2 * S * D,), WS_SENT, device="cuda")
+        _, _, dgamma, dbeta = ops.layernorm_bwd(c["dy"].cuda(), c["x"].cuda(), c["gamma"].cuda(), 1e-6, g_in=c["g_in"].cuda(), accumulate=acc,
+                                                dgamma=prior_g.clone().cuda(), dbeta=prior_b.clone().cuda(), ws=ws)
+        part = ws.cpu()
+        assert not bool((part == WS_SENT).any()), "a partial was not written"
+        pg, pb = part[:S * D].view(S, D), part[S * D:].view(S, D)
+        want_g = _kernel_order_sum(pg, prior_g if acc else None, lanes)
+        want_b = _kernel_order_sum(pb, prior_b if acc else None, lanes)
+        other = RR.TALL if lanes == RR.FLAT else RR.FLAT
+        differ = int((want_g != _kernel_order_sum(pg, prior_g if acc else None, other)).sum() +
+                     (want_b != _kernel_order_sum(pb, prior_b if acc else None, other)).sum())
+        print(f"M={M} D={D} S={S} lanes={lanes} accumulate={acc}: {differ} of {2 * D} sums would differ in the other layout")
+        if S >= 64 and D >= 64:      # a third of the sums and more on the CPU restatement; D = 4 has eight sums in all: held there only
+            assert differ >= 1, "the two layouts agree on these partials: the case cannot tell them apart"
+        assert torch.equal(dgamma.cpu(), want_g), f"accumulate={acc}: d_gamma differs from the {lanes}-lane order"
+        assert torch.equal(dbeta.cpu(), want_b), f"accumulate={acc}: d_beta differs from the {lanes}-lane order"
 
 
 # ------------------------------------------------------------------------------------------------------------------- LayerNorm variants

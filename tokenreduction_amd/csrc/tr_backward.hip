@@ -166,274 +166,109 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const uint16_t* __restric
     }
 }
 
-// dst[e] = (accumulate ? dst[e] : 0) + sum_s part[s][e].  Block = 64 float4 chunks x 4 partial-lanes: lane y sums partials
-// y, y+4, ... (independent loads, 4 in flight), the four lane sums are combined in lane order -- a fixed order, so the result is
-// bitwise reproducible.  (One thread per chunk walking all S partials was a chain of up to 1024 dependent round trips: 53 % of a
-// training step in the first profile.)
-__global__ __launch_bounds__(256) void partial_reduce_kernel(const float* __restrict__ part, int S, size_t count, float* __restrict__ dst,
-                                                             int accumulate) {
-  __shared__ float4 red[3][64];
-  const int cx = threadIdx.x & 63, y = threadIdx.x >> 6;
-  const size_t e = ((size_t)blockIdx.x * 64 + cx) * 4;
+// ---- "sum the partials": dst[e] = (accumulate ? dst[e] : 0) + sum_s part[s][e], the second stage of every two-stage reduction.
+// ONE body, ONE fixed order (bitwise reproducible, and equal wherever two entry points promise equal bits).  A block of 256 threads is
+// 256 / L float4 chunks x L partial-lanes: lane y sums partials y, y + L, ... four independent loads at a time as (v0 + v1) + (v2 + v3),
+// then one by one; lanes 1.. park their sums in LDS and lane 0 adds them in lane order; the destination is added LAST.  Two layouts:
+//   L = 4   64 chunks: long vectors.  (One thread per chunk walking all S partials was a chain of up to 1024 dependent round trips: 53 %
+//           of a training step in the first profile.)
+//   L = 16  16 chunks, "tall": many partials (S >= 64) of short vectors (<= 4096 elements; a LayerNorm's d_gamma / d_beta: 512 x D).  With
+//           L = 4 that job was 4 workgroups walking 128 partials each in 32 dependent round trips: 13 us, 26 times per training step.
+// The two layouts add in different orders: which call site takes which is part of its contract (DESIGN.md "Partial-sum reduces").
+
+// lanes 1.. park in LDS, lane 0 adds them in lane order; true for the threads that go on to store (lane 0 of a live chunk)
+template <int L>
+__device__ __forceinline__ bool combine_lanes(float4& a, int cx, int y, bool live) {
+  __shared__ float4 red[L - 1][256 / L];
+  if (y > 0) red[y - 1][cx] = a;
+  __syncthreads();
+  if (y > 0 || !live) return false;
+#pragma unroll
+  for (int w = 0; w < L - 1; ++w) {
+    const float4 v = red[w][cx];
+    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+  }
+  return true;
+}
+
+__device__ __forceinline__ void store_sum(float* __restrict__ dst, float4 a, int accumulate) {
+  if (accumulate) {
+    const float4 d = *reinterpret_cast<const float4*>(dst);
+    a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
+  }
+  *reinterpret_cast<float4*>(dst) = a;
+}
+
+// one result of a reduce launch, and the table of a launch: segment i owns the blocks from blk0[i] up to the next segment's first
+struct RSeg {
+  const float* part;       // [S][count]
+  float* dst;              // [count]
+  size_t count;
+  int S, accumulate;
+};
+template <int N>
+struct RSegs {
+  int blk0[N];             // unused entries: INT_MAX
+  RSeg s[N];
+};
+
+// block `b` of segment g.  A count that is no multiple of 4 ends in a ragged chunk, summed element by element in the same lane order.
+template <int L>
+__device__ __forceinline__ void reduce_block(const RSeg g, int b) {
+  constexpr int C = 256 / L;
+  const int cx = threadIdx.x % C, y = threadIdx.x / C;
+  const float* __restrict__ part = g.part;
+  const size_t count = g.count, e = ((size_t)b * C + cx) * 4;
+  const int S = g.S;
   const bool full = e + 4 <= count, any = e < count;
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
   if (full) {
     int s = y;
-    for (; s + 12 < S; s += 16) {
+    for (; s + 3 * L < S; s += 4 * L) {
       const float4 v0 = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + 4) * count + e);
-      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 8) * count + e);
-      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 12) * count + e);
+      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + L) * count + e);
+      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 2 * L) * count + e);
+      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 3 * L) * count + e);
       a.x += (v0.x + v1.x) + (v2.x + v3.x); a.y += (v0.y + v1.y) + (v2.y + v3.y);
       a.z += (v0.z + v1.z) + (v2.z + v3.z); a.w += (v0.w + v1.w) + (v2.w + v3.w);
     }
-    for (; s < S; s += 4) {
+    for (; s < S; s += L) {
       const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
       a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
     }
   } else if (any) {
     float t[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int s = y; s < S; s += 4)
+    for (int s = y; s < S; s += L)
       for (int i = 0; i < 4; ++i)
         if (e + i < count) t[i] += part[(size_t)s * count + e + i];
     a = make_float4(t[0], t[1], t[2], t[3]);
   }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || !any) return;
-#pragma unroll
-  for (int w = 0; w < 3; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
+  if (!combine_lanes<L>(a, cx, y, any)) return;
   if (full) {
-    if (accumulate) {
-      const float4 d = *reinterpret_cast<const float4*>(dst + e);
-      a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
-    }
-    *reinterpret_cast<float4*>(dst + e) = a;
+    store_sum(g.dst + e, a, g.accumulate);
   } else {
     const float t[4] = {a.x, a.y, a.z, a.w};
     for (int i = 0; i < 4; ++i)
-      if (e + i < count) dst[e + i] = (accumulate ? dst[e + i] : 0.f) + t[i];
+      if (e + i < count) g.dst[e + i] = (g.accumulate ? g.dst[e + i] : 0.f) + t[i];
   }
 }
 
-// the same for TWO results in one launch (a Linear's weight and bias gradient, a LayerNorm's d_gamma and d_beta): blocks
-// 0 .. nb0-1 reduce (part0, count0, dst0), the others (part1, count1, dst1); counts are multiples of 4
-__global__ __launch_bounds__(256) void partial_reduce2_kernel(const float* __restrict__ part0, size_t count0, float* __restrict__ dst0,
-                                                              const float* __restrict__ part1, size_t count1, float* __restrict__ dst1,
-                                                              int S, int nb0, int accumulate) {
-  __shared__ float4 red[3][64];
-  const bool second = (int)blockIdx.x >= nb0;
-  const float* part = second ? part1 : part0;
-  const size_t count = second ? count1 : count0;
-  float* dst = second ? dst1 : dst0;
-  const int cx = threadIdx.x & 63, y = threadIdx.x >> 6;
-  const size_t e = ((size_t)(second ? blockIdx.x - nb0 : blockIdx.x) * 64 + cx) * 4;
-  const bool ok = e + 4 <= count;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) {
-    int s = y;
-    for (; s + 12 < S; s += 16) {
-      const float4 v0 = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + 4) * count + e);
-      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 8) * count + e);
-      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 12) * count + e);
-      a.x += (v0.x + v1.x) + (v2.x + v3.x); a.y += (v0.y + v1.y) + (v2.y + v3.y);
-      a.z += (v0.z + v1.z) + (v2.z + v3.z); a.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; s < S; s += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-  }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || !ok) return;
+// Up to N results in one launch (a Linear's dW and db; the weight and bias gradients of up to four Linears whose weight gradients ran as one
+// launch; the d_gamma / d_beta of every LayerNorm of a backward pass).  Static indices only (a dynamically indexed kernel argument is
+// copied to scratch): the first blocks are walked with selects -- they load together, up front -- and the walk picks the ADDRESS of its
+// segment, whose five fields are then loaded once.  (Selecting the fields themselves entry by entry made every entry a load the next
+// compare waited for: 1 us more per launch at 8 entries, 2.4 us at 32.)
+template <int L, int N>
+__global__ __launch_bounds__(256) void partial_reduce_kernel(const RSegs<N> T) {
+  const RSeg* g = &T.s[0];
+  int b0 = 0;
 #pragma unroll
-  for (int w = 0; w < 3; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  if (accumulate) {
-    const float4 d = *reinterpret_cast<const float4*>(dst + e);
-    a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
-  }
-  *reinterpret_cast<float4*>(dst + e) = a;
-}
-
-// TALL variant of the two-result reduce: few elements (a LayerNorm's d_gamma / d_beta: D each), many partials (one per workgroup of the
-// producing kernel: 512).  Block = 16 float4 chunks x 16 partial-lanes: lane y sums partials y, y + 16, ... four loads in flight, the
-// sixteen lane sums are added in lane order (fixed).  With the 64 x 4 layout above the same job was 4 workgroups walking 128 partials each
-// in 32 dependent round trips: 13 us, 26 times per training step.
-__global__ __launch_bounds__(256) void partial_reduce2_tall_kernel(const float* __restrict__ part0, size_t count0, float* __restrict__ dst0,
-                                                                   const float* __restrict__ part1, size_t count1, float* __restrict__ dst1,
-                                                                   int S, int nb0, int accumulate) {
-  __shared__ float4 red[15][16];
-  const bool second = (int)blockIdx.x >= nb0;
-  const float* part = second ? part1 : part0;
-  const size_t count = second ? count1 : count0;
-  float* dst = second ? dst1 : dst0;
-  const int cx = threadIdx.x & 15, y = threadIdx.x >> 4;
-  const size_t e = ((size_t)(second ? blockIdx.x - nb0 : blockIdx.x) * 16 + cx) * 4;
-  const bool ok = e + 4 <= count;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) {
-    int s = y;
-    for (; s + 48 < S; s += 64) {
-      const float4 v0 = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + 16) * count + e);
-      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 32) * count + e);
-      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 48) * count + e);
-      a.x += (v0.x + v1.x) + (v2.x + v3.x); a.y += (v0.y + v1.y) + (v2.y + v3.y);
-      a.z += (v0.z + v1.z) + (v2.z + v3.z); a.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; s < S; s += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-  }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || !ok) return;
-#pragma unroll
-  for (int w = 0; w < 15; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  if (accumulate) {
-    const float4 d = *reinterpret_cast<const float4*>(dst + e);
-    a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
-  }
-  *reinterpret_cast<float4*>(dst + e) = a;
-}
-
-// The LayerNorm parameter gradients of a whole backward pass, reduced in ONE launch: every tr_layernorm_bwd of the pass leaves its
-// [grid][D] partials of d gamma and d beta in its own slice of a region and adds two segments here; the executor flushes after its
-// last block.  The per-call partial_reduce2_tall launch was 4.8 us x 24 per DeiT-B training step for a few hundred KB each.  Same block
-// layout and the same fixed summation order as partial_reduce2_tall_kernel, so the sums are bit-identical to the undeferred ones.
-constexpr int LN_DEFER_SEGS = 32;
-struct TallSegs {
-  const float* part[LN_DEFER_SEGS];
-  float* dst[LN_DEFER_SEGS];
-  int count[LN_DEFER_SEGS], S[LN_DEFER_SEGS], acc[LN_DEFER_SEGS];
-  int blk0[LN_DEFER_SEGS + 1];          // first block of segment i; blk0[n] = blocks in all
-};
-__global__ __launch_bounds__(256) void partial_reduce_tall_segs_kernel(const TallSegs T) {
-  __shared__ float4 red[15][16];
-  // static indices only (a dynamically indexed kernel argument is copied to scratch): walk the table with selects
-  const float* part = T.part[0];
-  float* dst = T.dst[0];
-  int count = T.count[0], S = T.S[0], accumulate = T.acc[0], b0 = 0;
-#pragma unroll
-  for (int i = 1; i < LN_DEFER_SEGS; ++i) {
+  for (int i = 1; i < N; ++i) {
     const bool in = (int)blockIdx.x >= T.blk0[i];
-    part = in ? T.part[i] : part;
-    dst = in ? T.dst[i] : dst;
-    count = in ? T.count[i] : count;
-    S = in ? T.S[i] : S;
-    accumulate = in ? T.acc[i] : accumulate;
+    g = in ? &T.s[i] : g;
     b0 = in ? T.blk0[i] : b0;
   }
-  const int cx = threadIdx.x & 15, y = threadIdx.x >> 4;
-  const size_t e = ((size_t)(blockIdx.x - b0) * 16 + cx) * 4;
-  const bool ok = e + 4 <= (size_t)count;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) {
-    int s = y;
-    for (; s + 48 < S; s += 64) {
-      const float4 v0 = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + 16) * count + e);
-      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 32) * count + e);
-      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 48) * count + e);
-      a.x += (v0.x + v1.x) + (v2.x + v3.x); a.y += (v0.y + v1.y) + (v2.y + v3.y);
-      a.z += (v0.z + v1.z) + (v2.z + v3.z); a.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; s < S; s += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-  }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || !ok) return;
-#pragma unroll
-  for (int w = 0; w < 15; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  if (accumulate) {
-    const float4 d = *reinterpret_cast<const float4*>(dst + e);
-    a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
-  }
-  *reinterpret_cast<float4*>(dst + e) = a;
-}
-
-// the same for up to EIGHT results with their own partial counts (the weight and bias gradients of up to four Linear layers whose weight
-// gradients ran as one launch): block ranges [0, nb0), [nb0, nb0 + nb1), ...; counts are multiples of 4; unused segments have nb = 0
-struct RSeg {
-  const float* part;
-  float* dst;
-  size_t count;
-  int S, nb;
-};
-struct RSegs {
-  RSeg s[8];
-};
-template <typename T>
-__device__ __forceinline__ T rsel8(int i, T a, T b, T c, T d, T e, T f, T g, T h) {      // by value (see qsel4 in tr_wgrad_pc.hip)
-  return i >= 4 ? (i >= 6 ? (i == 7 ? h : g) : (i == 5 ? f : e)) : (i >= 2 ? (i == 3 ? d : c) : (i ? b : a));
-}
-__global__ __launch_bounds__(256) void partial_reduce8_kernel(const RSegs segs, int accumulate) {
-  __shared__ float4 red[3][64];
-  int b = blockIdx.x, seg = 0;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int nb = segs.s[i].nb;
-    if (seg == i && b >= nb) {
-      b -= nb;
-      seg = i + 1;
-    }
-  }
-#define RS(f) rsel8(seg, segs.s[0].f, segs.s[1].f, segs.s[2].f, segs.s[3].f, segs.s[4].f, segs.s[5].f, segs.s[6].f, segs.s[7].f)
-  const float* part = RS(part);
-  float* dst = RS(dst);
-  const size_t count = RS(count);
-  const int S = RS(S);
-#undef RS
-  const int cx = threadIdx.x & 63, y = threadIdx.x >> 6;
-  const size_t e = ((size_t)b * 64 + cx) * 4;
-  const bool ok = e + 4 <= count;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) {
-    int s = y;
-    for (; s + 12 < S; s += 16) {
-      const float4 v0 = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      const float4 v1 = *reinterpret_cast<const float4*>(part + (size_t)(s + 4) * count + e);
-      const float4 v2 = *reinterpret_cast<const float4*>(part + (size_t)(s + 8) * count + e);
-      const float4 v3 = *reinterpret_cast<const float4*>(part + (size_t)(s + 12) * count + e);
-      a.x += (v0.x + v1.x) + (v2.x + v3.x); a.y += (v0.y + v1.y) + (v2.y + v3.y);
-      a.z += (v0.z + v1.z) + (v2.z + v3.z); a.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; s < S; s += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * count + e);
-      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-  }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || !ok) return;
-#pragma unroll
-  for (int w = 0; w < 3; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  if (accumulate) {
-    const float4 d = *reinterpret_cast<const float4*>(dst + e);
-    a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
-  }
-  *reinterpret_cast<float4*>(dst + e) = a;
+  reduce_block<L>(*g, (int)blockIdx.x - b0);
 }
 
 // column sums of a bf16 matrix: grid (ceil(N/512), S); thread = 2 adjacent columns; part[s][n]
@@ -688,34 +523,18 @@ __global__ __launch_bounds__(256) void head_dx_kernel(const float* __restrict__ 
 // ---- d pos_embed[n][:] = sum_b g[b][n][:], d cls_token = sum_b g[b][0][:]   (topk.py:183-186); block = 64 chunks x 4 batch lanes
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ g, float* __restrict__ dpos, float* __restrict__ dcls, int B,
                                                         int N, int D, int accumulate) {
-  __shared__ float4 red[3][64];
   const int cx = threadIdx.x & 63, y = threadIdx.x >> 6;
   const int t = blockIdx.x * 64 + cx;
   const int nch = N * (D >> 2);
   const int tc = min(t, nch - 1);
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b = y; b < B; b += 4) {
+  for (int b = y; b < B; b += 4) {      // plain sequential per lane: not the partial reduces' order
     const float4 v = *reinterpret_cast<const float4*>(g + (size_t)b * N * D + 4 * (size_t)tc);
     a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
   }
-  if (y > 0) red[y - 1][cx] = a;
-  __syncthreads();
-  if (y > 0 || t >= nch) return;
-#pragma unroll
-  for (int w = 0; w < 3; ++w) {
-    const float4 v = red[w][cx];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  float4* o = reinterpret_cast<float4*>(dpos + 4 * (size_t)t);
-  float4 r = a;
-  if (accumulate) { const float4 p = *o; r.x += p.x; r.y += p.y; r.z += p.z; r.w += p.w; }
-  *o = r;
-  if (t < (D >> 2)) {
-    float4* oc = reinterpret_cast<float4*>(dcls + 4 * (size_t)t);
-    float4 rc = a;
-    if (accumulate) { const float4 p = *oc; rc.x += p.x; rc.y += p.y; rc.z += p.z; rc.w += p.w; }
-    *oc = rc;
-  }
+  if (!combine_lanes<4>(a, cx, y, t < nch)) return;
+  store_sum(dpos + 4 * (size_t)t, a, accumulate);
+  if (t < (D >> 2)) store_sum(dcls + 4 * (size_t)t, a, accumulate);
 }
 
 // ---- EViT fused token backward (evit.py:117-120): extra = sum_j xm[1+c_j] * s[c_j], xm = x + delta (post-attention stream).
@@ -980,20 +799,32 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   *reinterpret_cast<uint2*>(dst + 4 * c) = pk;
 }
 
-inline int reduce_partials(const float* part, int S, size_t count, float* dst, int accumulate, hipStream_t st) {
-  const unsigned nb = (unsigned)(((count + 3) / 4 + 63) / 64);
-  hipLaunchKernelGGL(partial_reduce_kernel, dim3(nb), dim3(256), 0, st, part, S, count, dst, accumulate);
-  return 0;
+// ONE reduce launch for segs[0 .. n) (part, dst, count, S, accumulate filled by the caller), all in the tall or all in the 64 x 4 layout
+template <int L, int N>
+void launch_reduce_table(const RSeg* segs, int n, hipStream_t st) {
+  RSegs<N> T;
+  int blocks = 0;
+  for (int i = 0; i < N; ++i) {
+    T.s[i] = i < n ? segs[i] : RSeg{segs[0].part, segs[0].dst, 0, 0, 0};
+    T.blk0[i] = i < n ? blocks : 0x7fffffff;            // unused entries never match a block
+    if (i < n) blocks += (int)(((segs[i].count + 3) / 4 + 256 / L - 1) / (256 / L));
+  }
+  hipLaunchKernelGGL((partial_reduce_kernel<L, N>), dim3(blocks), dim3(256), 0, st, T);
+}
+constexpr int LN_DEFER_SEGS = 32;
+void launch_reduce(const RSeg* segs, int n, bool tall, hipStream_t st) {      // table sizes: a pair, the group's 8, the deferred 32
+  if (tall && n <= 2) launch_reduce_table<16, 2>(segs, n, st);
+  else if (tall) launch_reduce_table<16, LN_DEFER_SEGS>(segs, n, st);
+  else if (n <= 2) launch_reduce_table<4, 2>(segs, n, st);
+  else launch_reduce_table<4, 8>(segs, n, st);
 }
 
-inline void reduce_partials2(const float* p0, size_t c0, float* d0, const float* p1, size_t c1, float* d1, int S, int accumulate, hipStream_t st) {
-  if (S >= 64 && c0 <= 4096 && c1 <= 4096) {        // many partials of short vectors: spread the partials over the lanes
-    const int nb0 = (int)((c0 / 4 + 15) / 16), nb1 = (int)((c1 / 4 + 15) / 16);
-    hipLaunchKernelGGL(partial_reduce2_tall_kernel, dim3(nb0 + nb1), dim3(256), 0, st, p0, c0, d0, p1, c1, d1, S, nb0, accumulate);
-    return;
-  }
-  const int nb0 = (int)((c0 / 4 + 63) / 64), nb1 = (int)((c1 / 4 + 63) / 64);
-  hipLaunchKernelGGL(partial_reduce2_kernel, dim3(nb0 + nb1), dim3(256), 0, st, p0, c0, d0, p1, c1, d1, S, nb0, accumulate);
+// the tall layout's domain: many partials of a short vector (`count`: the longest of the launch)
+inline bool reduce_tall(int S, size_t count) { return S >= 64 && count <= 4096; }
+
+inline void reduce_partials(const float* part, int S, size_t count, float* dst, int accumulate, hipStream_t st) {
+  const RSeg g{part, dst, count, S, accumulate};
+  launch_reduce(&g, 1, false, st);
 }
 
 }  // namespace
@@ -1029,71 +860,57 @@ extern "C" size_t tr_wgrad_workspace_floats(int M, int N, int K) {
   return (size_t)S * N * K + (size_t)S * N;         // weight partials, then the bias partials of tr_linear_bwd_params
 }
 
-extern "C" int tr_wgrad_bf16(const uint16_t* dY, long ldy, int yskip, const uint16_t* X, long ldx, float* dW, int accumulate, float* ws,
-                             size_t ws_floats, int M, int N, int K, tr_stream_t s) {
-  TR_REQUIRE(dY && X && dW && ws, TR_ERR_NULL, "tr_wgrad_bf16: null pointer");
+// The host path of tr_wgrad_bf16 (db == NULL) and tr_linear_bwd_params (the bias sums come out of the weight-gradient kernel's staging
+// registers): split plan, weight-gradient launch, ONE reduce launch.  `fn` / `fn_reduce`: the entry point's name in errors and profiles.
+// dW is reduced in the same layout with and without db -- tall iff S >= 64 and N K <= 4096 (N <= 4096 follows) -- so it is bit-equal
+// between the two entry points at every shape.
+static int linear_params(const char* fn, const char* fn_reduce, const uint16_t* dY, long ldy, int yskip, const uint16_t* X, long ldx, float* dW,
+                         float* db, int accumulate, float* ws, size_t ws_floats, int M, int N, int K, tr_stream_t s) {
   TR_REQUIRE(M > 0 && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0 && ldy % 8 == 0 && ldx % 8 == 0 && ldy >= N && ldx >= K && yskip >= 0,
-             TR_ERR_SHAPE, "tr_wgrad_bf16: need N,K,ldy,ldx multiples of 8 (M=%d N=%d K=%d ldy=%ld ldx=%ld)", M, N, K, ldy, ldx);
-  TR_REQUIRE(tr_aligned16(dY) && tr_aligned16(X) && tr_aligned16(dW) && tr_aligned16(ws), TR_ERR_ALIGN, "tr_wgrad_bf16: pointers must be 16-byte aligned");
+             TR_ERR_SHAPE, "%s: need N,K,ldy,ldx multiples of 8 (M=%d N=%d K=%d ldy=%ld ldx=%ld)", fn, M, N, K, ldy, ldx);
+  TR_REQUIRE(tr_aligned16(dY) && tr_aligned16(X) && tr_aligned16(dW) && tr_aligned16(db) && tr_aligned16(ws), TR_ERR_ALIGN,
+             "%s: pointers must be 16-byte aligned", fn);
   const int nNt = (N + WB - 1) / WB, nKt = (K + WB - 1) / WB, tiles = nNt * nKt;
   const int nslab = (M + WM - 1) / WM;
   int S = wgrad_splits(M, N, K);
-  const size_t fit = ws_floats / ((size_t)N * K);
-  TR_REQUIRE(fit >= 1, TR_ERR_SHAPE, "tr_wgrad_bf16: workspace of %zu floats cannot hold one %d x %d partial", ws_floats, N, K);
+  const size_t nk = (size_t)N * K, fit = ws_floats / (nk + (db ? (size_t)N : 0));      // partials the workspace holds
+  if (db) TR_REQUIRE(fit >= 1, TR_ERR_SHAPE, "%s: workspace of %zu floats cannot hold one partial", fn, ws_floats);
+  else TR_REQUIRE(fit >= 1, TR_ERR_SHAPE, "%s: workspace of %zu floats cannot hold one %d x %d partial", fn, ws_floats, N, K);
   if ((size_t)S > fit) S = (int)fit;
   const int sps = (nslab + S - 1) / S;
   S = (nslab + sps - 1) / sps;                 // every split owns at least one slab
-  hipStream_t st = static_cast<hipStream_t>(s);
-  if (tr_wgrad_pc_fits(M, N, K, ldy, ldx, yskip)) {
-    tr_prof_note("wgrad_pc_kernel", 2.0 * M * N * K, 2.0 * ((double)M * N + (double)M * K) + 4.0 * S * N * K);
-    S = tr_wgrad_pc_launch(dY, ldy, yskip, X, ldx, ws, nullptr, M, N, K, (int)min(fit, (size_t)1 << 20), st);
-  } else {
-    tr_prof_note("wgrad_kernel", 2.0 * M * N * K, 2.0 * ((double)M * N + (double)M * K) + 4.0 * S * N * K);
-    hipLaunchKernelGGL(wgrad_kernel<false>, dim3(tiles, S), dim3(256), 0, st, dY, ldy, yskip, X, ldx, ws, static_cast<float*>(nullptr), M, N, K, nNt, sps);
-  }
-  TR_CHECK_LAUNCH("tr_wgrad_bf16");
-  // many partials of a small matrix: the tall order tr_linear_bwd_params' reduce takes there (second result empty), so that dW stays
-  // bit-equal to the fused call's at every shape; the 64 x 4 order otherwise (the same in both reduces)
-  if (S >= 64 && (size_t)N * K <= 4096) reduce_partials2(ws, (size_t)N * K, dW, ws, (size_t)0, dW, S, accumulate, st);
-  else reduce_partials(ws, S, (size_t)N * K, dW, accumulate, st);
-  TR_CHECK_LAUNCH("tr_wgrad_bf16 (reduce)");
-  return TR_OK;
-}
-
-// nn.Linear parameter gradients in one pass over dY: dW[N,K] (+)= dY^T X and db[N] (+)= column sums of dY (tr_wgrad_bf16 +
-// tr_colsum_bf16 fused: the bias sums come out of the weight-gradient kernel's staging registers), one reduce launch for both.
-extern "C" int tr_linear_bwd_params(const uint16_t* dY, long ldy, int yskip, const uint16_t* X, long ldx, float* dW, float* db, int accumulate,
-                                    float* ws, size_t ws_floats, int M, int N, int K, tr_stream_t s) {
-  TR_REQUIRE(dY && X && dW && db && ws, TR_ERR_NULL, "tr_linear_bwd_params: null pointer");
-  TR_REQUIRE(M > 0 && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0 && ldy % 8 == 0 && ldx % 8 == 0 && ldy >= N && ldx >= K && yskip >= 0,
-             TR_ERR_SHAPE, "tr_linear_bwd_params: need N,K,ldy,ldx multiples of 8 (M=%d N=%d K=%d ldy=%ld ldx=%ld)", M, N, K, ldy, ldx);
-  TR_REQUIRE(tr_aligned16(dY) && tr_aligned16(X) && tr_aligned16(dW) && tr_aligned16(db) && tr_aligned16(ws), TR_ERR_ALIGN,
-             "tr_linear_bwd_params: pointers must be 16-byte aligned");
-  const int nNt = (N + WB - 1) / WB, nKt = (K + WB - 1) / WB, tiles = nNt * nKt;
-  const int nslab = (M + WM - 1) / WM;
-  int S = wgrad_splits(M, N, K);
-  const size_t per = (size_t)N * K + (size_t)N;
-  const size_t fit = ws_floats / per;
-  TR_REQUIRE(fit >= 1, TR_ERR_SHAPE, "tr_linear_bwd_params: workspace of %zu floats cannot hold one partial", ws_floats);
-  if ((size_t)S > fit) S = (int)fit;
-  const int sps = (nslab + S - 1) / S;
-  S = (nslab + sps - 1) / sps;
-  float* bpart = ws + (size_t)S * N * K;
+  float* bpart = db ? ws + (size_t)S * nk : nullptr;
   hipStream_t st = static_cast<hipStream_t>(s);
   if (tr_wgrad_pc_fits(M, N, K, ldy, ldx, yskip)) {
     // the bias partials sit behind the weight partials of the LARGEST split count the workspace admits (the launch may pick fewer)
     const int S_max = (int)min(fit, (size_t)1 << 20);
-    bpart = ws + (size_t)S_max * N * K;
+    if (db) bpart = ws + (size_t)S_max * nk;
     tr_prof_note("wgrad_pc_kernel", 2.0 * M * N * K, 2.0 * ((double)M * N + (double)M * K) + 4.0 * S * N * K);
     S = tr_wgrad_pc_launch(dY, ldy, yskip, X, ldx, ws, bpart, M, N, K, S_max, st);
   } else {
     tr_prof_note("wgrad_kernel", 2.0 * M * N * K, 2.0 * ((double)M * N + (double)M * K) + 4.0 * S * N * K);
-    hipLaunchKernelGGL(wgrad_kernel<true>, dim3(tiles, S), dim3(256), 0, st, dY, ldy, yskip, X, ldx, ws, bpart, M, N, K, nNt, sps);
+    if (db) hipLaunchKernelGGL(wgrad_kernel<true>, dim3(tiles, S), dim3(256), 0, st, dY, ldy, yskip, X, ldx, ws, bpart, M, N, K, nNt, sps);
+    else hipLaunchKernelGGL(wgrad_kernel<false>, dim3(tiles, S), dim3(256), 0, st, dY, ldy, yskip, X, ldx, ws, bpart, M, N, K, nNt, sps);
   }
-  TR_CHECK_LAUNCH("tr_linear_bwd_params");
-  reduce_partials2(ws, (size_t)N * K, dW, bpart, (size_t)N, db, S, accumulate, st);
-  TR_CHECK_LAUNCH("tr_linear_bwd_params (reduce)");
+  TR_CHECK_LAUNCH(fn);
+  const RSeg segs[2] = {{ws, dW, nk, S, accumulate}, {bpart, db, (size_t)N, S, accumulate}};
+  launch_reduce(segs, db ? 2 : 1, reduce_tall(S, nk), st);
+  TR_CHECK_LAUNCH(fn_reduce);
   return TR_OK;
+}
+
+extern "C" int tr_wgrad_bf16(const uint16_t* dY, long ldy, int yskip, const uint16_t* X, long ldx, float* dW, int accumulate, float* ws,
+                             size_t ws_floats, int M, int N, int K, tr_stream_t s) {
+  TR_REQUIRE(dY && X && dW && ws, TR_ERR_NULL, "tr_wgrad_bf16: null pointer");
+  return linear_params("tr_wgrad_bf16", "tr_wgrad_bf16 (reduce)", dY, ldy, yskip, X, ldx, dW, nullptr, accumulate, ws, ws_floats, M, N, K, s);
+}
+
+// nn.Linear parameter gradients in one pass over dY: dW[N,K] (+)= dY^T X and db[N] (+)= column sums of dY (tr_wgrad_bf16 +
+// tr_colsum_bf16 fused), one reduce launch for both.
+extern "C" int tr_linear_bwd_params(const uint16_t* dY, long ldy, int yskip, const uint16_t* X, long ldx, float* dW, float* db, int accumulate,
+                                    float* ws, size_t ws_floats, int M, int N, int K, tr_stream_t s) {
+  TR_REQUIRE(dY && X && dW && db && ws, TR_ERR_NULL, "tr_linear_bwd_params: null pointer");
+  return linear_params("tr_linear_bwd_params", "tr_linear_bwd_params (reduce)", dY, ldy, yskip, X, ldx, dW, db, accumulate, ws, ws_floats, M, N, K, s);
 }
 
 void tr_wgrad_pc_group_splits(const int (*mnk)[3], int n, int* S);
@@ -1172,20 +989,12 @@ extern "C" int tr_linear_bwd_group(const tr_linear_grad* layers, int n, int accu
   const bool stored = tr_wgrad_pc_group_launch(dY, ldy, X, ldx, mnk, n, ws, S, part, bpart, accumulate ? nullptr : dW, accumulate ? nullptr : db, st);
   TR_CHECK_LAUNCH("tr_linear_bwd_group");
   if (stored) return TR_OK;
-  RSegs segs;
-  int nb = 0;
-  for (int i = 0; i < 8; ++i) {
-    const int l = i & 3, bias = i >> 2;        // segments: dW of layers 0..3, then db of layers 0..3
-    RSeg& g = segs.s[i];
-    if (l >= n) { g.part = nullptr; g.dst = nullptr; g.count = 0; g.S = 0; g.nb = 0; continue; }
-    g.part = bias ? bpart[l] : part[l];
-    g.dst = bias ? layers[l].db : layers[l].dW;
-    g.count = bias ? (size_t)layers[l].N : (size_t)layers[l].N * layers[l].K;
-    g.S = S[l];
-    g.nb = (int)((g.count / 4 + 63) / 64);
-    nb += g.nb;
+  RSeg segs[8];                                // dW of layers 0..n-1, then db of layers 0..n-1; always the 64 x 4 layout
+  for (int l = 0; l < n; ++l) {
+    segs[l] = RSeg{part[l], layers[l].dW, (size_t)layers[l].N * layers[l].K, S[l], accumulate};
+    segs[n + l] = RSeg{bpart[l], layers[l].db, (size_t)layers[l].N, S[l], accumulate};
   }
-  hipLaunchKernelGGL(partial_reduce8_kernel, dim3(nb), dim3(256), 0, st, segs, accumulate);
+  launch_reduce(segs, 2 * n, false, st);
   TR_CHECK_LAUNCH("tr_linear_bwd_group (reduce)");
   return TR_OK;
 }
@@ -1260,14 +1069,17 @@ static inline int ln_bwd_grid(int M) {
 
 extern "C" size_t tr_layernorm_bwd_workspace_floats(int M, int D) { return (size_t)ln_bwd_grid(M) * 2 * D; }
 
-// ---- deferred reduction of the LayerNorm parameter gradients (see partial_reduce_tall_segs_kernel).  One context per host thread: the
-// backward executor opens it around its block loop; calls outside a context, calls whose partials do not fit the region, and calls with
-// few partials or long rows (which the tall layout does not serve) reduce at once as before.
+// ---- deferred reduction of the LayerNorm parameter gradients: every tr_layernorm_bwd of a backward pass leaves its [grid][D] partials of
+// d gamma and d beta in its own slice of a region and adds two segments to a table; the executor flushes after its last block, ONE tall
+// reduce launch (one per call was 4.8 us x 24 per DeiT-B training step for a few hundred KB each).  The same body and layout as the
+// reduce at once, so the sums are bit-identical.  One context per host thread: the backward executor opens it around its block loop;
+// calls outside a context, calls whose partials do not fit the region, and calls with few partials or long rows (which the tall layout
+// does not serve) reduce at once.
 namespace {
 struct LnDefer {
   float* region = nullptr;
   size_t cap = 0, used = 0;
-  TallSegs T;
+  RSeg segs[LN_DEFER_SEGS];
   int n = 0;
   hipStream_t st = nullptr;
 };
@@ -1278,25 +1090,16 @@ thread_local LnDefer g_ln_defer_store;
 int tr_ln_defer_flush() {
   LnDefer* c = g_ln_defer;
   if (c == nullptr || c->n == 0) return TR_OK;
-  const int blocks = c->T.blk0[c->n];
-  for (int i = c->n; i < LN_DEFER_SEGS; ++i) {          // unused entries never match a block
-    c->T.part[i] = c->T.part[0]; c->T.dst[i] = c->T.dst[0]; c->T.count[i] = 0; c->T.S[i] = 0; c->T.acc[i] = 0;
-    c->T.blk0[i] = 0x7fffffff;
-  }
-  c->T.blk0[LN_DEFER_SEGS] = blocks;
-  hipLaunchKernelGGL(partial_reduce_tall_segs_kernel, dim3(blocks), dim3(256), 0, c->st, c->T);
+  launch_reduce(c->segs, c->n, true, c->st);
   c->n = 0;
   c->used = 0;                 // the reduce is ordered before every later launch of this stream: the slices may be rewritten
-  c->T.blk0[0] = 0;
   TR_CHECK_LAUNCH("tr_layernorm_bwd (deferred reduce)");
   return TR_OK;
 }
 void tr_ln_defer_begin(float* region, size_t floats, hipStream_t st) {
   LnDefer* c = &g_ln_defer_store;
   c->region = region; c->cap = floats; c->used = 0; c->n = 0; c->st = st;
-  c->T.blk0[0] = 0;
-  static const bool off = getenv("TR_LN_DEFER_OFF") != nullptr;       // lab switch: same-box A/B against the per-call reduce
-  g_ln_defer = (region != nullptr && floats > 0 && !off) ? c : nullptr;
+  g_ln_defer = (region != nullptr && floats > 0) ? c : nullptr;
 }
 void tr_ln_defer_end() { g_ln_defer = nullptr; }           // drops what was not flushed (error paths)
 
@@ -1351,20 +1154,13 @@ static int layernorm_bwd_impl(const uint16_t* dy, const float* x, long ldx, cons
     TR_DISPATCH_NCH(D, hipLaunchKernelGGL((ln_bwd_kernel<NCH, false, true>), dim3(grid), dim3(256), 0, st, dy, x, ldx, gamma, g_in, ldgi, g_out, ldgo, gb_out,
                                           idx, K, n_in, n_out, g_fused, ws, M, D, eps));
   TR_CHECK_LAUNCH("tr_layernorm_bwd");
-  if (defer) {
-    const int nb = (D / 4 + 15) / 16;
-    for (int k = 0; k < 2; ++k) {
-      const int i = dc->n++;
-      dc->T.part[i] = ws + (size_t)k * grid * D;
-      dc->T.dst[i] = k ? dbeta : dgamma;
-      dc->T.count[i] = D;
-      dc->T.S[i] = grid;
-      dc->T.acc[i] = accumulate;
-      dc->T.blk0[i + 1] = dc->T.blk0[i] + nb;
-    }
+  const RSeg segs[2] = {{ws, dgamma, (size_t)D, grid, accumulate}, {ws + (size_t)grid * D, dbeta, (size_t)D, grid, accumulate}};
+  if (defer) {      // grid >= 64 and D <= 4096: the tall layout, as the reduce below would take for these two
+    dc->segs[dc->n++] = segs[0];
+    dc->segs[dc->n++] = segs[1];
     return TR_OK;
   }
-  reduce_partials2(ws, (size_t)D, dgamma, ws + (size_t)grid * D, (size_t)D, dbeta, grid, accumulate, st);
+  launch_reduce(segs, 2, reduce_tall(grid, (size_t)D), st);
   TR_CHECK_LAUNCH("tr_layernorm_bwd (reduce)");
   return TR_OK;
 }
@@ -1492,7 +1288,7 @@ extern "C" int tr_ats_scatter(const float* g, const uint16_t* dao_s, const int32
 }
 
 // dst[e] = (accumulate ? dst[e] : 0) + sum_{s < S} part[s][e]: the deterministic second stage of the two-stage reductions
-// The order is fixed but NOT sequential in s (partial_reduce_kernel): lane y of four adds partials y, y + 4, y + 8, ... -- for whole groups of
+// The order is fixed but NOT sequential in s (reduce_block, L = 4): lane y of four adds partials y, y + 4, y + 8, ... -- for whole groups of
 // four elements sixteen partials at a time as (v0 + v1) + (v2 + v3), for the ragged last group one by one --, the result is
 // ((lane0 + lane1) + lane2) + lane3, and the destination is added LAST when accumulating.
 extern "C" int tr_reduce_partials_f32(const float* part, int S, size_t count, float* dst, int accumulate, tr_stream_t s) {
