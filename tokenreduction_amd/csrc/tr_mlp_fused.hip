@@ -147,6 +147,13 @@ constexpr int MF_ENTRY = MF_FR * 1024;         // 48 KiB
 constexpr int MF_NSLOT = 3;
 constexpr int MF_HBUF = 2048;                  // one hidden fragment pair (2 token groups x 64 lanes x 16 B)
 constexpr int MF_LDS = MF_NSLOT * MF_ENTRY + 4 * 2 * MF_HBUF;     // 163,840 B: all of the CU's LDS
+constexpr int MF_LNX = 2 * MF_ENTRY;           // NP, a workgroup's first block: the C waves' normalised rows (4 pairs x 12 KiB) cross here -- ring
+                                               // slot 2, whose first DMA (entry 2) goes out behind the barrier in front of time step 0
+static_assert(4 * MF_KS * 1024 <= MF_ENTRY, "the hand-over rows of the four pairs fit one ring slot");
+constexpr int MF_LNP = MF_NSLOT * MF_ENTRY;    // ... and the norm's weight and bias (2 x 1,536 B) lie in the hidden buffers, first written in time step 0
+static_assert(2 * MF_D * 4 <= 4 * 2 * MF_HBUF, "the norm's two vectors fit the hidden buffers");
+template <bool V>
+struct MfFlag { static constexpr bool value = V; };
 constexpr int MF_ROWS = 128;                   // token rows per block (4 wave pairs x 32)
 #ifndef MF_PQ
 #define MF_PQ 0                                // DMA pieces of an entry a P wave issues (0..6, lab: -DMF_PQ=..); a C wave issues 12 - MF_PQ.  0: the P
@@ -286,6 +293,10 @@ struct MfResid {
 // `sub` = 8 (ks & 3) + 2 q + h holds the chunks ks, ks + 4, ks + 8 of half h; its butterfly xor 16, 8 is in-lane here, xor 4, 2 are this
 // wave's lane ^ 32, ^ 16, xor 1 is the in-lane half h), with its contractions spelled out.  Removes the lazy-norm2 launch in front of the
 // Mlp (8 B per element through HBM) and the bf16 round trip of the normalised rows.
+// At a workgroup's FIRST block the pair shares the prologue: the P wave normalises row group 0, its C partner -- whose accumulator
+// registers are not live yet -- row group 1 and hands it over through ring slot 2 (free until time step 0's DMA), and both read the
+// norm's weight and bias from a copy in LDS.  Later blocks of a workgroup are normalised by the P wave alone, parameters from memory.
+// Where the prologue's time goes and what each step saved: profiles/mlp_ln_pair_lab.md.
 struct MfNorm {
   const float* x;        // [M, 384] fp32 residual stream (not written)
   const uint16_t* d;     // [M, 384] bf16 pending residual (the attention branch)
@@ -368,6 +379,115 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(const uint16_t* __res
     ld_cur = mf_next(q, ld_cur, NS);
     ld_w1 = ld_cur.s;
     ld_slot = (ld_slot + 1 == MF_NSLOT) ? 0 : ld_slot + 1;
+  };
+
+  // NP: LayerNorm(x + d) of 16-row group j of this wave pair's 32 rows of block blk, as the twelve B-operand fragments of the fc1 wave
+  // (lane (frow, fq), k-step ks: row frow + 16 j, columns 32 ks + 8 fq ..), handed to emit(ks, fragment) one by one; 96 fp32 values per
+  // lane live.  Runs on either wave of the pair: a row's arithmetic stays in four lanes of ONE wave, so the bits do not depend on which.
+  // The sched_barriers pin the phases: left alone, hipcc issues all loads and all 48 parameter loads up front (121 spilled registers).
+  // first (MfFlag<true>: a workgroup's first block): the norm's weight and bias come through LDS -- every wave copies the two vectors
+  // (3 KiB) by DMA to MF_LNP ahead of its row loads and reads its fragments from there: as global loads, one k-step ahead, they are
+  // twelve dependent L2 round trips behind the statistics (measured: 5.5 of a 12-us prologue).  All eight waves write the SAME bytes to
+  // the same place and each reads behind its own vmcnt wait, so no barrier is needed.  after_loads() runs once the row loads are out.
+  [[maybe_unused]] auto ln_group = [&](int blk, const int j, auto first, auto&& after_loads, auto&& emit) __attribute__((always_inline)) {
+    constexpr bool FIRST = decltype(first)::value;
+    const int m = min(blk * MF_ROWS + pr * 32 + frow + 16 * j, M - 1);
+    const float* xr = nm.x + (size_t)m * MF_D + 8 * fq;
+    const uint16_t* dr = nm.d + (size_t)m * MF_D + 8 * fq;
+    f32x4 v[MF_KS][2];
+    u32x4 dq[2][4];
+    if constexpr (FIRST) {
+      mf_piece(reinterpret_cast<const unsigned char*>(nm.g), lane16, lds0 + MF_LNP);
+      mf_piece(reinterpret_cast<const unsigned char*>(nm.b), lane16, lds0 + MF_LNP + MF_D * 4);
+      if (lane < 32) {            // floats 256..383
+        mf_piece(reinterpret_cast<const unsigned char*>(nm.g) + 1024, lane16, lds0 + MF_LNP + 1024);
+        mf_piece(reinterpret_cast<const unsigned char*>(nm.b) + 1024, lane16, lds0 + MF_LNP + MF_D * 4 + 1024);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dq[0][i] = *reinterpret_cast<const u32x4*>(dr + 32 * i);
+#pragma unroll
+    for (int ks = 0; ks < MF_KS; ++ks) {
+      v[ks][0] = *reinterpret_cast<const f32x4*>(xr + 32 * ks);
+      v[ks][1] = *reinterpret_cast<const f32x4*>(xr + 32 * ks + 4);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    after_loads();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (c + 1 < 3) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dq[(c + 1) & 1][i] = *reinterpret_cast<const u32x4*>(dr + 32 * (4 * (c + 1) + i));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const u32x4 dd = dq[c & 1][i];
+        const int ks = 4 * c + i;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          v[ks][h][0] += __uint_as_float(dd[2 * h] << 16); v[ks][h][1] += __uint_as_float(dd[2 * h] & 0xffff0000u);
+          v[ks][h][2] += __uint_as_float(dd[2 * h + 1] << 16); v[ks][h][3] += __uint_as_float(dd[2 * h + 1] & 0xffff0000u);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // the row sum: per (ks & 3, h) the three chunks in order, then the tree (see the header of MfNorm)
+    float sp[4][2];
+#pragma unroll
+    for (int ks = 0; ks < MF_KS; ++ks)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float t = (v[ks][h][0] + v[ks][h][1]) + (v[ks][h][2] + v[ks][h][3]);
+        sp[ks & 3][h] = (ks < 4 ? 0.f : sp[ks & 3][h]) + t;
+      }
+    float c0 = (sp[0][0] + sp[2][0]) + (sp[1][0] + sp[3][0]), c1 = (sp[0][1] + sp[2][1]) + (sp[1][1] + sp[3][1]);
+    c0 += __shfl_xor(c0, 32); c1 += __shfl_xor(c1, 32);
+    c0 += __shfl_xor(c0, 16); c1 += __shfl_xor(c1, 16);
+    const float mean = (c0 + c1) / (float)MF_D;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < MF_KS; ++ks)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 t = v[ks][h];
+        t[0] -= mean; t[1] -= mean; t[2] -= mean; t[3] -= mean;
+        v[ks][h] = t;
+        const float u = __builtin_fmaf(t[0], t[0], t[1] * t[1]) + __builtin_fmaf(t[2], t[2], t[3] * t[3]);
+        sp[ks & 3][h] = (ks < 4 ? 0.f : sp[ks & 3][h]) + u;
+      }
+    c0 = (sp[0][0] + sp[2][0]) + (sp[1][0] + sp[3][0]); c1 = (sp[0][1] + sp[2][1]) + (sp[1][1] + sp[3][1]);
+    c0 += __shfl_xor(c0, 32); c1 += __shfl_xor(c1, 32);
+    c0 += __shfl_xor(c0, 16); c1 += __shfl_xor(c1, 16);
+    const float rstd = rsqrtf((c0 + c1) / (float)MF_D + nm.eps);
+    // (FIRST: the vectors' DMA is older than the row loads, which have all arrived -- the wait costs nothing and says so)
+    if constexpr (FIRST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const float* gr = FIRST ? reinterpret_cast<const float*>(smem + MF_LNP) + 8 * fq : nm.g + 8 * fq;
+    const float* br = FIRST ? reinterpret_cast<const float*>(smem + MF_LNP) + MF_D + 8 * fq : nm.b + 8 * fq;
+    // normalise, scale, round: the parameters of chunk ks + 1 are requested before chunk ks is computed (two sets of 16 registers)
+    f32x4 gb[2][4];
+    gb[0][0] = *reinterpret_cast<const f32x4*>(gr); gb[0][1] = *reinterpret_cast<const f32x4*>(gr + 4);
+    gb[0][2] = *reinterpret_cast<const f32x4*>(br); gb[0][3] = *reinterpret_cast<const f32x4*>(br + 4);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < MF_KS; ++ks) {
+      if (ks + 1 < MF_KS) {
+        gb[(ks + 1) & 1][0] = *reinterpret_cast<const f32x4*>(gr + 32 * (ks + 1)); gb[(ks + 1) & 1][1] = *reinterpret_cast<const f32x4*>(gr + 32 * (ks + 1) + 4);
+        gb[(ks + 1) & 1][2] = *reinterpret_cast<const f32x4*>(br + 32 * (ks + 1)); gb[(ks + 1) & 1][3] = *reinterpret_cast<const f32x4*>(br + 32 * (ks + 1) + 4);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      u32x4 o;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x4 gg = gb[ks & 1][h], bb = gb[ks & 1][2 + h];
+        const f32x4 t = v[ks][h];
+        o[2 * h] = pack_bf16x2(__builtin_fmaf(rstd * t[0], gg[0], bb[0]), __builtin_fmaf(rstd * t[1], gg[1], bb[1]));
+        o[2 * h + 1] = pack_bf16x2(__builtin_fmaf(rstd * t[2], gg[2], bb[2]), __builtin_fmaf(rstd * t[3], gg[3], bb[3]));
+      }
+      emit(ks, o);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   };
 
 #ifdef MF_P32
@@ -549,101 +669,25 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(const uint16_t* __res
 #define MF_RELOAD_X(ks)                        \
   mf_reload_x<(ks) * 64>(x0[ks], xn, xo0);     \
   mf_reload_x<(ks) * 64>(x1[ks], xn, xo1)
-    // NP: x0 / x1 <- LayerNorm(x + d) of block blk's rows, one 16-row group at a time (96 fp32 values per lane live).  The sched_barriers
-    // pin the phases: left alone, hipcc issues both groups' loads and all 48 parameter loads up front (121 spilled registers).
+    // NP: x0 / x1 <- LayerNorm(x + d) of block blk's rows, one 16-row group at a time (ln_group above)
     auto ln_fill = [&](int blk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int m = min(blk * MF_ROWS + pr * 32 + frow + 16 * j, M - 1);
-        const float* xr = nm.x + (size_t)m * MF_D + 8 * fq;
-        const uint16_t* dr = nm.d + (size_t)m * MF_D + 8 * fq;
-        f32x4 v[MF_KS][2];
-        u32x4 dq[2][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dq[0][i] = *reinterpret_cast<const u32x4*>(dr + 32 * i);
-#pragma unroll
-        for (int ks = 0; ks < MF_KS; ++ks) {
-          v[ks][0] = *reinterpret_cast<const f32x4*>(xr + 32 * ks);
-          v[ks][1] = *reinterpret_cast<const f32x4*>(xr + 32 * ks + 4);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (c + 1 < 3) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dq[(c + 1) & 1][i] = *reinterpret_cast<const u32x4*>(dr + 32 * (4 * (c + 1) + i));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const u32x4 dd = dq[c & 1][i];
-            const int ks = 4 * c + i;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              v[ks][h][0] += __uint_as_float(dd[2 * h] << 16); v[ks][h][1] += __uint_as_float(dd[2 * h] & 0xffff0000u);
-              v[ks][h][2] += __uint_as_float(dd[2 * h + 1] << 16); v[ks][h][3] += __uint_as_float(dd[2 * h + 1] & 0xffff0000u);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        // the row sum: per (ks & 3, h) the three chunks in order, then the tree (see the header of MfNorm)
-        float sp[4][2];
-#pragma unroll
-        for (int ks = 0; ks < MF_KS; ++ks)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const float t = (v[ks][h][0] + v[ks][h][1]) + (v[ks][h][2] + v[ks][h][3]);
-            sp[ks & 3][h] = (ks < 4 ? 0.f : sp[ks & 3][h]) + t;
-          }
-        float c0 = (sp[0][0] + sp[2][0]) + (sp[1][0] + sp[3][0]), c1 = (sp[0][1] + sp[2][1]) + (sp[1][1] + sp[3][1]);
-        c0 += __shfl_xor(c0, 32); c1 += __shfl_xor(c1, 32);
-        c0 += __shfl_xor(c0, 16); c1 += __shfl_xor(c1, 16);
-        const float mean = (c0 + c1) / (float)MF_D;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < MF_KS; ++ks)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            f32x4 t = v[ks][h];
-            t[0] -= mean; t[1] -= mean; t[2] -= mean; t[3] -= mean;
-            v[ks][h] = t;
-            const float u = __builtin_fmaf(t[0], t[0], t[1] * t[1]) + __builtin_fmaf(t[2], t[2], t[3] * t[3]);
-            sp[ks & 3][h] = (ks < 4 ? 0.f : sp[ks & 3][h]) + u;
-          }
-        c0 = (sp[0][0] + sp[2][0]) + (sp[1][0] + sp[3][0]); c1 = (sp[0][1] + sp[2][1]) + (sp[1][1] + sp[3][1]);
-        c0 += __shfl_xor(c0, 32); c1 += __shfl_xor(c1, 32);
-        c0 += __shfl_xor(c0, 16); c1 += __shfl_xor(c1, 16);
-        const float rstd = rsqrtf((c0 + c1) / (float)MF_D + nm.eps);
-        const float* gr = nm.g + 8 * fq;
-        const float* br = nm.b + 8 * fq;
-        // normalise, scale, round: the parameters of chunk ks + 1 are requested before chunk ks is computed (two sets of 16 registers)
-        f32x4 gb[2][4];
-        gb[0][0] = *reinterpret_cast<const f32x4*>(gr); gb[0][1] = *reinterpret_cast<const f32x4*>(gr + 4);
-        gb[0][2] = *reinterpret_cast<const f32x4*>(br); gb[0][3] = *reinterpret_cast<const f32x4*>(br + 4);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < MF_KS; ++ks) {
-          if (ks + 1 < MF_KS) {
-            gb[(ks + 1) & 1][0] = *reinterpret_cast<const f32x4*>(gr + 32 * (ks + 1)); gb[(ks + 1) & 1][1] = *reinterpret_cast<const f32x4*>(gr + 32 * (ks + 1) + 4);
-            gb[(ks + 1) & 1][2] = *reinterpret_cast<const f32x4*>(br + 32 * (ks + 1)); gb[(ks + 1) & 1][3] = *reinterpret_cast<const f32x4*>(br + 32 * (ks + 1) + 4);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          u32x4 o;
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const f32x4 gg = gb[ks & 1][h], bb = gb[ks & 1][2 + h];
-            const f32x4 t = v[ks][h];
-            o[2 * h] = pack_bf16x2(__builtin_fmaf(rstd * t[0], gg[0], bb[0]), __builtin_fmaf(rstd * t[1], gg[1], bb[1]));
-            o[2 * h + 1] = pack_bf16x2(__builtin_fmaf(rstd * t[2], gg[2], bb[2]), __builtin_fmaf(rstd * t[3], gg[3], bb[3]));
-          }
-          if (j == 0) x0[ks] = __builtin_bit_cast(bf16x8, o);
-          else x1[ks] = __builtin_bit_cast(bf16x8, o);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
+      ln_group(blk, 0, MfFlag<false>{}, [] {}, [&](int ks, const u32x4 o) __attribute__((always_inline)) { x0[ks] = __builtin_bit_cast(bf16x8, o); });
+      ln_group(blk, 1, MfFlag<false>{}, [] {}, [&](int ks, const u32x4 o) __attribute__((always_inline)) { x1[ks] = __builtin_bit_cast(bf16x8, o); });
     };
     if constexpr (NP) {
-      ln_fill(mf_block(q, mf_first(q, NS)));
+      // The workgroup's FIRST block: the pair shares the norm.  This wave normalises row group 0, the partner -- whose accumulator
+      // registers are not live yet -- row group 1, which crosses LDS in this wave's fragment layout (C side: below).  The weights of
+      // entries 0 and 1 are requested first, so that they land under the norm.
+      issue_all();
+      advance_entry();
+      issue_all();
+      advance_entry();
+      ln_group(mf_block(q, mf_first(q, NS)), 0, MfFlag<true>{}, [] {}, [&](int ks, const u32x4 o) __attribute__((always_inline)) { x0[ks] = __builtin_bit_cast(bf16x8, o); });
+      __builtin_amdgcn_s_barrier();             // the partner's rows are in LDS
+      asm volatile("" ::: "memory");
+      const unsigned char* hx = smem + MF_LNX + pr * (MF_KS * 1024) + lane16;
+#pragma unroll
+      for (int ks = 0; ks < MF_KS; ++ks) x1[ks] = *reinterpret_cast<const bf16x8*>(hx + ks * 1024);
     } else {
       unsigned xo0, xo1;
       x_offsets(mf_block(q, mf_first(q, NS)), xo0, xo1);
@@ -652,10 +696,13 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(const uint16_t* __res
     }
     bn0 = mf_load_f4<0>(b1 + 32 * mf_first(q, NS).s, boff);
     bn1 = mf_load_f4<16>(b1 + 32 * mf_first(q, NS).s, boff);
-    issue_all();
-    advance_entry();
-    issue_all();
-    advance_entry();
+    if constexpr (!NP) {
+      issue_all();
+      advance_entry();
+      issue_all();
+      advance_entry();
+    }
+    // (NP: the tied x1 registers are the LDS reads above, so they have arrived -- and the hand-over rows are free -- before the barrier)
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(bn0), "+v"(bn1), MF_TIE_X(x0), MF_TIE_X(x1)::"memory");
     __builtin_amdgcn_s_barrier();               // entries 0 and 1 have landed
     asm volatile("" ::: "memory");
@@ -821,6 +868,25 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(const uint16_t* __res
                                                                          RL ? (int)(2u * out_bytes) : MF_NI * 2 * 1024, 0x00020000);
   // a lane's first element of block blk in the stream: row blk * 128 + pr * 32 + (lane & 15) [+ 16 j], column 4 (lane >> 4) [+ 16 i]
   auto x_row_off = [&](int blk) __attribute__((always_inline)) { return ((unsigned)(blk * MF_ROWS + pr * 32 + frow) * MF_D + 4u * fq) * 4u; };
+  if constexpr (NP) {
+    // The workgroup's first block: this wave normalises row group 1 of the pair's 32 rows in the registers that become accumulators
+    // below, while the fc1 partner normalises group 0 (half the prologue each instead of the whole on one wave beside an idle one).  The
+    // twelve fragments go to the partner lane-linear through LDS (MF_LNX: 1 KiB per k-step, a lane's 16 bytes at 16 * lane = exactly what
+    // the partner's lane holds as x1[ks]); a barrier of their own publishes them, the partner has read them by the barrier in front of
+    // time step 0, and only behind that barrier does this wave's DMA of entry 2 write the slot.  Later blocks of the workgroup are
+    // normalised by the fc1 wave alone: the accumulator registers are live then and the ring has no free slot.
+    // The weights of entries 0 and 1 are requested right behind the row loads -- in front of them they hold this wave's loads back
+    // behind the partner's in the CU's memory pipeline (measured: the norm began 4.7 us late) -- and land under the norm.
+    unsigned char* const hx = smem + MF_LNX + pr * (MF_KS * 1024) + lane16;
+    ln_group(mf_block(q, mf_first(q, NS)), 1, MfFlag<true>{},
+             [&]() __attribute__((always_inline)) {
+               issue_all();
+               advance_entry();
+               issue_all();
+               advance_entry();
+             },
+             [&](int ks, const u32x4 o) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(hx + ks * 1024) = o; });
+  }
   if constexpr (RL) {
     const unsigned vo = x_row_off(mf_block(q, mf_first(q, NS)));
 #pragma unroll
@@ -835,10 +901,17 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(const uint16_t* __res
       for (int j = 0; j < 2; ++j)
         acc[i][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, lane16 + (unsigned)((i * 2 + j) * 1024), 0, 0));
   }
-  issue_all();
-  advance_entry();
-  issue_all();
-  advance_entry();
+  if constexpr (NP) {
+    // (behind the accumulator's loads, so that they travel while the partner fetches the rows)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();               // the normalised rows are in LDS
+    asm volatile("" ::: "memory");
+  } else {
+    issue_all();
+    advance_entry();
+    issue_all();
+    advance_entry();
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // entries 0 and 1 have landed
   asm volatile("" ::: "memory");
