@@ -60,9 +60,10 @@ def ats_cdf(normed: Tensor, mask: Tensor) -> Tensor:
 
 
 def ats_ids_from_cdf(cdf: Tensor, steps: Tensor, pad_to: Optional[int] = None):
-    """ats.py:73-84: nearest cdf entry per grid point (torch.cdist -- its matmul form |a|^2+|b|^2-2ab since P > 25, whose
-    rounding decides among candidates closer than ~3e-4 to a grid point), per-image sorted unique, zero padding, CLS id 0 in
-    front.  Returns (ids [B,K'], new_mask [B,K'])."""
+    """ats.py:73-84: nearest cdf entry per grid point (torch.cdist in its default mode: with more than 25 cdf entries or more than
+    25 grid points its matmul form |a|^2+|b|^2-2ab, whose rounding decides among candidates closer than ~3e-4 to a grid point;
+    with at most 25 of both its direct form sqrt((a-b)^2)), per-image sorted unique, zero padding, CLS id 0 in front.
+    Returns (ids [B,K'], new_mask [B,K'])."""
     dist = torch.cdist(steps.unsqueeze(0).unsqueeze(2), cdf.unsqueeze(2))
     sampled = torch.argmin(dist, dim=-1) + 1
     uniq = [torch.unique(t, sorted=True) for t in torch.unbind(sampled)]

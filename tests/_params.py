@@ -442,8 +442,9 @@ def assert_valid_ranking(idx, ref_scores, tol):
 def assert_valid_sampling(kept, cdf, steps, tol):
     """ATS (ats.py:73-77): `kept` [B,W] (0-based patch ids, -1 = pad) is a correct set of inverse-CDF samples of `cdf` [B,P]
     up to `tol` in the distance |step - cdf|: every grid point has a kept id within tol of its nearest cdf entry, and every
-    kept id is within tol of nearest for some grid point.  (The reference's cdist takes its matmul form, whose fp32 rounding
-    decides among candidates closer than ~3e-4 to a grid point.)"""
+    kept id is within tol of nearest for some grid point.  (With more than 25 cdf entries or grid points the reference's cdist
+    takes its matmul form, whose fp32 rounding decides among candidates closer than ~3e-4 to a grid point; with at most 25 of
+    both it takes the direct form, which needs no such slack.  Exact decisions: tests/test_hip_ats_edges.py.)"""
     kept, cdf, steps = np.asarray(kept), np.asarray(cdf, dtype=np.float64), np.asarray(steps, dtype=np.float64)
     for b in range(kept.shape[0]):
         ids = kept[b][kept[b] >= 0]

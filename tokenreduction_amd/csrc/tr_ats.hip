@@ -8,15 +8,20 @@
 //                   One workgroup per image; everything after the |v| pass lives in LDS.
 //   tr_ats_gather   x = batched_index_select(x, ids) (ats.py:157) and new_attn @ v = rows `ids` of attn @ v (ats.py:86,129):
 //                   row gather of the fp32 residual stream and of the attention output.
-// The nearest-entry search mirrors torch.cdist's matmul form (|a|^2 + |b|^2 - 2ab as a 3-term dot product, clamp 1e-30, sqrt):
-// its fp32 rounding -- not the exact |a - b| -- decides among candidates closer than ~3e-4 to a grid point.
+// The nearest-entry search mirrors torch.cdist (ats.py:73, default compute mode) in whichever form cdist itself takes.  With more than 25
+// cdf entries or more than 25 grid points that is the matmul form (|a|^2 + |b|^2 - 2ab as a 3-term dot product, clamp 1e-30, sqrt): its
+// fp32 rounding -- not the exact |a - b| -- decides among candidates closer than ~3e-4 to a grid point.  With at most 25 of both (the
+// late stages of low keep rates, 80x80 inputs) it is the direct form sqrt((a - b)^2), which decides nearly exactly.  The two pick
+// different tokens among near-equidistant entries, so the threshold is part of the result (tests/_ats_ref.py).
 #include "tr_common.h"
 
 namespace {
 
 constexpr int ATS_MAX_P = 1024;
+constexpr int ATS_DIRECT_MAX = 25;                    // torch.cdist: direct form while both row counts are <= 25
 
-template <bool F32>
+// DIRECT: the form of the search, chosen by the host -- the matmul-form instantiations are the code they were before the direct form existed
+template <bool F32, bool DIRECT>
 __global__ __launch_bounds__(256) void ats_sample_kernel(const float* __restrict__ cls_rows, const void* __restrict__ qkv,
                                                          const float* __restrict__ mask, const float* __restrict__ steps,
                                                          int n_steps, int32_t* __restrict__ ids, float* __restrict__ new_mask,
@@ -95,24 +100,32 @@ __global__ __launch_bounds__(256) void ats_sample_kernel(const float* __restrict
     if (cdf_out != nullptr) cdf_out[(size_t)b * P + p] = c;
   }
   __syncthreads();
-  // nearest cdf entry per grid point; torch.cdist matmul form: [-2s, s^2, 1] . [c, 1, c^2], clamp_min(1e-30), sqrt; argmin
-  // keeps the first minimum.  Four lanes per grid point, each walking every fourth entry; (distance, index) minima combined
-  // lexicographically, which is the first minimum of the whole row.
+  // nearest cdf entry per grid point; torch.cdist matmul form: [-2s, s^2, 1] . [c, 1, c^2], clamp_min(1e-30), sqrt -- or, for at most
+  // 25 entries and 25 grid points, its direct form sqrt((s - c)^2); argmin keeps the first minimum.  Four lanes per grid point, each
+  // walking every fourth entry; (distance, index) minima combined lexicographically, which is the first minimum of the whole row.
   {
     const int q4 = tid & 3;
     for (int t = tid >> 2; t < ((n_steps + 63) & ~63); t += 64) {
       const float s = steps[min(t, n_steps - 1)];
-      const float a0 = -2.0f * s, a1 = __fmul_rn(s, s);
       float best = INFINITY;
       int arg = 0x7fffffff;
-      for (int p = q4; p < P; p += 4) {
-        const float c = s_cdf[p];
-        // k = 0,1,2 of the 3-term dot product, each product/sum rounded once (no contraction: c^2 is a rounded operand)
-        float r = __fmul_rn(a0, c);
-        r = __fadd_rn(r, a1);
-        r = __fadd_rn(r, __fmul_rn(c, c));
-        const float d = sqrtf(fmaxf(r, 1e-30f));
-        if (d < best) { best = d; arg = p; }
+      if (DIRECT) {
+        for (int p = q4; p < P; p += 4) {
+          const float x = __fsub_rn(s, s_cdf[p]);     // difference and square rounded once each
+          const float d = sqrtf(__fmul_rn(x, x));
+          if (d < best) { best = d; arg = p; }
+        }
+      } else {
+        const float a0 = -2.0f * s, a1 = __fmul_rn(s, s);
+        for (int p = q4; p < P; p += 4) {
+          const float c = s_cdf[p];
+          // k = 0,1,2 of the 3-term dot product, each product/sum rounded once (no contraction: c^2 is a rounded operand)
+          float r = __fmul_rn(a0, c);
+          r = __fadd_rn(r, a1);
+          r = __fadd_rn(r, __fmul_rn(c, c));
+          const float d = sqrtf(fmaxf(r, 1e-30f));
+          if (d < best) { best = d; arg = p; }
+        }
       }
 #pragma unroll
       for (int o = 1; o < 4; o <<= 1) {
@@ -204,6 +217,17 @@ __global__ __launch_bounds__(256) void ats_gather_kernel(const float* __restrict
   }
 }
 
+template <bool F32, bool DIRECT>
+int launch_ats_sample(const float* cls_rows, const void* qkv, const float* mask, const float* steps, int n_steps, int32_t* ids, float* new_mask,
+                      float* cdf_out, int B, int N, int H, int K, size_t lds, hipStream_t st) {
+  // more than the default 64 KiB of dynamic LDS (16 heads x 1024 tokens = 64 KiB; the CU has 160): raise the kernel's limit on demand
+  TR_RESERVE_LDS(reinterpret_cast<const void*>(ats_sample_kernel<F32, DIRECT>), lds, "tr_ats_sample");
+  hipLaunchKernelGGL((ats_sample_kernel<F32, DIRECT>), dim3(B), dim3(256), lds, st, cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, N,
+                     H, K, 1e-6f);
+  TR_CHECK_LAUNCH("tr_ats_sample");
+  return TR_OK;
+}
+
 }  // namespace
 
 extern "C" int tr_ats_sample(const float* cls_rows, const void* qkv, int qkv_is_f32, const float* mask, const float* steps,
@@ -217,17 +241,13 @@ extern "C" int tr_ats_sample(const float* cls_rows, const void* qkv, int qkv_is_
   hipStream_t st = static_cast<hipStream_t>(s);
   const size_t lds = (size_t)H * (N - 1) * sizeof(float);            // one term per (head, token)
   TR_REQUIRE(lds <= 128 * 1024, TR_ERR_SHAPE, "tr_ats_sample: %d heads x %d tokens do not fit the per-head scratch (128 KiB of LDS)", H, N - 1);
-  // more than the default 64 KiB of dynamic LDS (16 heads x 1024 tokens = 64 KiB; the CU has 160): raise the kernel's limit on demand
-  if (qkv_is_f32) TR_RESERVE_LDS(reinterpret_cast<const void*>(ats_sample_kernel<true>), lds, "tr_ats_sample");
-  else TR_RESERVE_LDS(reinterpret_cast<const void*>(ats_sample_kernel<false>), lds, "tr_ats_sample");
+  // torch.cdist's own choice of form: direct while neither side has more than 25 rows
+  const bool direct = N - 1 <= ATS_DIRECT_MAX && n_steps <= ATS_DIRECT_MAX;
   if (qkv_is_f32)
-    hipLaunchKernelGGL(ats_sample_kernel<true>, dim3(B), dim3(256), lds, st, cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, N,
-                       H, K, 1e-6f);
-  else
-    hipLaunchKernelGGL(ats_sample_kernel<false>, dim3(B), dim3(256), lds, st, cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out,
-                       N, H, K, 1e-6f);
-  TR_CHECK_LAUNCH("tr_ats_sample");
-  return TR_OK;
+    return direct ? launch_ats_sample<true, true>(cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, B, N, H, K, lds, st)
+                  : launch_ats_sample<true, false>(cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, B, N, H, K, lds, st);
+  return direct ? launch_ats_sample<false, true>(cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, B, N, H, K, lds, st)
+                : launch_ats_sample<false, false>(cls_rows, qkv, mask, steps, n_steps, ids, new_mask, cdf_out, B, N, H, K, lds, st);
 }
 
 extern "C" int tr_ats_gather(const float* x, const void* ao, int ao_is_f32, const int32_t* ids, float* x_out, void* ao_out, int B,
