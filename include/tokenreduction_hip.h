@@ -737,6 +737,32 @@ int tr_vit_forward_pixels_taps(const tr_vit_config* cfg, const tr_vit_weights* w
                                float* soft_out, const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s,
                                const tr_vit_taps* taps);
 
+/* Level taps: EVERY row of the residual stream after caller-chosen blocks, written by the eval forward while it runs (fp32, device memory) --
+ * the tokens of the multi-level dense feature maps below.
+ *   blocks        bit i set: the stream after block i -- x plus the residuals still pending there, added in fp32 in the order the next norm
+ *                 adds them: (x + attention branch) + mlp branch
+ *   norm          0: those rows as they are, the rows features_out holds for that block, bit for bit; 1: the model's final LayerNorm (norm_g,
+ *                 norm_b, ln_eps) of those rows in fp32 arithmetic (tr_final_tokens_f32)
+ *   tokens_out    fp32: the l-th set block's slab starts at l * B * N0 * D (N0 = patch tokens + 1) and holds [B, N_l, D] contiguous, N_l the
+ *                 stream's token count after that block (tokens_out[i] of the forward)
+ *   tokens_elems  the length of tokens_out in elements, at least popcount(blocks) * B * N0 * D
+ * tr_vit_forward_levels is tr_vit_forward_pixels (any input_format) with that struct and, nullable, a tr_vit_taps.  A tapped block writes its
+ * slab with ONE launch where its CLS tap would run; the stream is not written and nothing else about the launch sequence changes: lazy norms,
+ * the fused Mlp and the `concurrent` hint stay, and so does the CLS tail unless block depth-1 is tapped -- that needs every row of the last
+ * block, which then runs full width, as under final_tokens_out.  blocks == 0: the launches are those of tr_vit_forward.  A bit at or above
+ * depth, blocks without tokens_out, norm outside 0 / 1, levels together with features_out or a training tape: TR_ERR_CONFIG; tokens_elems too
+ * short: TR_ERR_SHAPE; tokens_out not 16-byte aligned: TR_ERR_ALIGN -- each before any launch.  Eval only. */
+typedef struct {
+  uint32_t blocks;
+  int32_t norm;
+  float* tokens_out;
+  size_t tokens_elems;
+} tr_vit_levels;
+int tr_vit_forward_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                          float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
+                          const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, const tr_vit_taps* taps,
+                          const tr_vit_levels* levels);
+
 /* Decision taps (csrc/tr_decisions.hip): the raw stage slabs of an eval forward -> the per-image decisions of validate.py's `Stage-{loc}`
  * records (validate.py:199-229 on the viz_data of topk.py:196, evit.py:123, tome.py:91-99, sit.py:122, ats.py:78,253, dpcknn.py / kmedoids.py),
  * on the device: ONE launch behind tr_vit_forward* on the same stream, one workgroup per image, the stages walked in block order; no launch
@@ -800,6 +826,24 @@ int tr_stage_decisions(const int32_t* kept_idx, const int32_t* compl_idx, size_t
  *   torch's .to(bfloat16)); layout TR_LAYOUT_NHWC = [B, P, D] (channels last), TR_LAYOUT_NCHW = [B, D, P], anything else TR_ERR_CONFIG.
  *   Every output element is written exactly once (no memset, no atomics).  D % 4 == 0, D <= 1024, 1 <= P <= 1024, n_rows >= 1:
  *   TR_ERR_SHAPE otherwise; pointers 16-byte aligned.  NCHW stores 16 bytes (bf16: 8) along p when P % 4 == 0, single elements otherwise. */
+/* The same for L levels -- the streams after L blocks (tr_vit_levels), each behind its own prefix of the stages -- in ONE launch each.
+ * tr_dense_index_levels: index_out int32 [L, B, P0].  One workgroup per image walks the stage table once, with tr_dense_index's semantics per
+ *   stage kind, and writes level l's index (cur + 1, or -1) behind the last stage whose block is <= level_blocks[l]: a stage reduces in front
+ *   of or inside its block, so the stream after block i is behind every stage with block <= i.  A level in front of every stage is the identity
+ *   1 ... P0.  level_blocks / level_rows: HOST arrays of L entries (they travel as kernel arguments: a captured graph holds them), the
+ *   blocks strictly ascending inside [0, TR_MAX_DEPTH), 1 <= L <= 32 (TR_ERR_CONFIG); level_rows[l] = the token count of the stream after that
+ *   block, CLS included: the rows its prefix of stages leaves must equal level_rows[l] - 1 (TR_ERR_SHAPE -- a wrong idea of where a family
+ *   reduces does not go unnoticed).  Everything else as tr_dense_index, each refusal before any launch.
+ * tr_dense_gather_levels: out[l][b, :, p] = tokens[l * level_stride + (b * level_rows[l] + index[l, b, p]) * D ...] where the index lies in
+ *   [0, level_rows[l]), `fill` elsewhere.  tokens: fp32 slabs of level_stride elements (a multiple of 4, at least B * level_rows[l] * D:
+ *   tr_vit_levels.tokens_out with level_stride = B * N0 * D), index int32 [L, B, P], out [L, B, P * D] in tr_dense_gather's layouts and
+ *   dtypes; per level the bits of tr_dense_gather.  Every element is written exactly once (no memset, no atomics) by one launch whose tile
+ *   order has the level as its slowest coordinate. */
+int tr_dense_index_levels(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems, const tr_decision_stage* stages,
+                          int n_stages, int B, int P0, const int32_t* level_blocks, const int32_t* level_rows, int L, int32_t* index_out,
+                          tr_stream_t s);
+int tr_dense_gather_levels(const float* tokens, size_t level_stride, const int32_t* level_rows, int L, const int32_t* index, void* out, int layout,
+                           int out_is_bf16, float fill, int B, int P, int D, tr_stream_t s);
 int tr_dense_index(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems, const tr_decision_stage* stages,
                    int n_stages, int B, int P0, int n_last, int32_t* index_out, tr_stream_t s);
 int tr_dense_gather(const float* tokens, const int32_t* index, void* out, int layout, int out_is_bf16, float fill, int B, int P, int n_rows,

@@ -54,6 +54,10 @@ class TrVitTaps(C.Structure):        # tr_vit_taps: the output taps of tr_vit_fo
     _fields_ = [("cls_blocks", C.c_uint32), ("cls_out", _vp), ("final_tokens_out", _vp)]
 
 
+class TrVitLevels(C.Structure):      # tr_vit_levels: the level taps of tr_vit_forward_levels (24 bytes)
+    _fields_ = [("blocks", C.c_uint32), ("norm", C.c_int32), ("tokens_out", _vp), ("tokens_elems", _sz)]
+
+
 class TrDecisionStage(C.Structure):  # tr_decision_stage: one row of tr_stage_decisions' stage table (40 bytes)
     _fields_ = [("block", C.c_int32), ("kind", C.c_int32), ("n_in", C.c_int32), ("k", C.c_int32), ("kept_off", C.c_int64),
                 ("assign_off", C.c_int64), ("soft_off", C.c_int64)]
@@ -218,9 +222,14 @@ SIGNATURES = {
                                  C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
     "tr_vit_forward_pixels_taps": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                         C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps)]),
+    "tr_vit_forward_levels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(_i), _i, _vp, C.POINTER(TrVitTaps), C.POINTER(TrVitLevels)]),
     "tr_stage_decisions": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "tr_dense_index": (_i, [_vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, _i, _vp, _vp]),
     "tr_dense_gather": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp]),
+    "tr_dense_index_levels": (_i, [_vp, _sz, _vp, _sz, C.POINTER(TrDecisionStage), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp,
+                                   _vp]),
+    "tr_dense_gather_levels": (_i, [_vp, _sz, C.POINTER(C.c_int32), _i, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "tr_cls_tap": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _i, _vp]),
     "tr_final_tokens_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "tr_token_pool": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),

@@ -7,6 +7,9 @@
 //   tr_dense_gather   features[b, :, p] = tokens[b, index[b, p], :] where 0 <= index < n_rows, `fill` elsewhere; fp32 or bf16 (round to
 //                     nearest even) output, channels-last [B, P, D] or NCHW [B, D, P].  Every output element is written exactly once: no
 //                     memset in front of it, no atomics.
+//   tr_dense_index_levels / tr_dense_gather_levels   the same two steps for L levels (the streams after L chosen blocks, each behind its own
+//                     prefix of the stages) in ONE launch each: the index kernel walks the stage table once and writes a level's index where
+//                     its prefix ends; the gather's tile order has the level as its slowest coordinate.
 // The gather is the hot path: it writes the largest tensor of the forward once and reads at most as much.  Channels-last is a row copy in
 // the shape of tr_taps.hip (a wave per output row, 16-byte loads).  NCHW transposes a tile of 64 patches x 64 channels through LDS: rows
 // come in with 16-byte loads (a 256-byte piece of each gathered row), leave along p with 16-byte stores (8-byte for bf16) when P % 4 == 0,
@@ -31,50 +34,77 @@ __host__ __device__ inline bool stage_has_map(int kind) {
   return kind == TR_DECISION_CENTRES || kind == TR_DECISION_TOME || kind == TR_DECISION_SOFT;
 }
 
+// the levels of tr_dense_index_levels: level l's index is the state behind the first after[l] stages (ascending; 0 = in front of every stage)
+struct level_table {
+  int after[TR_MAX_DEPTH];
+  int n;
+};
+
+// one stage applied to the state cur[] of image b (every thread of the workgroup calls it)
+__device__ __forceinline__ void dense_index_stage(const int32_t* __restrict__ kept, const int32_t* __restrict__ assign, const tr_decision_stage& st,
+                                                  int n_out, int b, int P0, int tid, int* cur, int* inv) {
+  if (stage_has_map(st.kind)) {
+    // cur[p] = assign[cur[p]]: a thread touches its own entries of cur only, no barrier needed between map stages
+    const int P_in = st.n_in - 1;
+    const int32_t* a = assign + st.assign_off + (size_t)b * P_in;
+    for (int p = tid; p < P0; p += DI_THREADS) {
+      const int c = cur[p];
+      int v = -1;
+      if (c >= 0 && c < P_in) {
+        v = a[c];
+        if (v < 0 || v >= n_out) v = -1;
+      }
+      cur[p] = v;
+    }
+  } else {
+    // the kept list is absolute: cur[p] = the lowest j with kept[j] == p (an LDS atomicMin: deterministic whatever the order)
+    const int W = n_out;
+    const int32_t* kp = kept + st.kept_off + (size_t)b * W;
+    for (int p = tid; p < P0; p += DI_THREADS) inv[p] = INT_MAX;
+    __syncthreads();
+    for (int j = tid; j < W; j += DI_THREADS) {
+      const int v = kp[j];
+      if (v >= 0 && v < P0) atomicMin(&inv[v], j);
+    }
+    __syncthreads();
+    for (int p = tid; p < P0; p += DI_THREADS) {
+      const int j = inv[p];
+      cur[p] = j == INT_MAX ? -1 : j;
+    }
+    __syncthreads();                                     // (inv is filled again by the next kept stage)
+  }
+}
+
+// index = cur + 1 where a row stands for the patch (a thread reads the entries of cur it wrote itself)
+__device__ __forceinline__ void dense_index_store(const int* cur, int32_t* __restrict__ out, int P0, int tid) {
+  for (int p = tid; p < P0; p += DI_THREADS) {
+    const int c = cur[p];
+    out[p] = c >= 0 ? c + 1 : -1;
+  }
+}
+
 __global__ __launch_bounds__(DI_THREADS) void dense_index_kernel(const int32_t* __restrict__ kept, const int32_t* __restrict__ assign,
                                                                  dense_table tab, int B, int P0, int32_t* __restrict__ index_out) {
   __shared__ int cur[DI_MAX_P];
   __shared__ int inv[DI_MAX_P];
   const int b = blockIdx.x, tid = threadIdx.x;
   for (int p = tid; p < P0; p += DI_THREADS) cur[p] = p;
-  for (int s = 0; s < tab.n; ++s) {
-    const tr_decision_stage st = tab.st[s];
-    const int n_out = tab.n_out[s];
-    if (stage_has_map(st.kind)) {
-      // cur[p] = assign[cur[p]]: a thread touches its own entries of cur only, no barrier needed between map stages
-      const int P_in = st.n_in - 1;
-      const int32_t* a = assign + st.assign_off + (size_t)b * P_in;
-      for (int p = tid; p < P0; p += DI_THREADS) {
-        const int c = cur[p];
-        int v = -1;
-        if (c >= 0 && c < P_in) {
-          v = a[c];
-          if (v < 0 || v >= n_out) v = -1;
-        }
-        cur[p] = v;
-      }
-    } else {
-      // the kept list is absolute: cur[p] = the lowest j with kept[j] == p (an LDS atomicMin: deterministic whatever the order)
-      const int W = n_out;
-      const int32_t* kp = kept + st.kept_off + (size_t)b * W;
-      for (int p = tid; p < P0; p += DI_THREADS) inv[p] = INT_MAX;
-      __syncthreads();
-      for (int j = tid; j < W; j += DI_THREADS) {
-        const int v = kp[j];
-        if (v >= 0 && v < P0) atomicMin(&inv[v], j);
-      }
-      __syncthreads();
-      for (int p = tid; p < P0; p += DI_THREADS) {
-        const int j = inv[p];
-        cur[p] = j == INT_MAX ? -1 : j;
-      }
-      __syncthreads();                                   // (inv is filled again by the next kept stage)
-    }
-  }
-  int32_t* out = index_out + (size_t)b * P0;
-  for (int p = tid; p < P0; p += DI_THREADS) {
-    const int c = cur[p];
-    out[p] = c >= 0 ? c + 1 : -1;
+  for (int s = 0; s < tab.n; ++s) dense_index_stage(kept, assign, tab.st[s], tab.n_out[s], b, P0, tid, cur, inv);
+  dense_index_store(cur, index_out + (size_t)b * P0, P0, tid);
+}
+
+// L levels in one walk: before stage s is applied, every level whose prefix is the first s stages takes the state as it stands
+__global__ __launch_bounds__(DI_THREADS) void dense_index_levels_kernel(const int32_t* __restrict__ kept, const int32_t* __restrict__ assign,
+                                                                        dense_table tab, level_table lev, int B, int P0,
+                                                                        int32_t* __restrict__ index_out) {
+  __shared__ int cur[DI_MAX_P];
+  __shared__ int inv[DI_MAX_P];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int p = tid; p < P0; p += DI_THREADS) cur[p] = p;
+  int l = 0;
+  for (int s = 0; s <= tab.n; ++s) {
+    for (; l < lev.n && lev.after[l] == s; ++l) dense_index_store(cur, index_out + ((size_t)l * B + b) * P0, P0, tid);
+    if (s < tab.n) dense_index_stage(kept, assign, tab.st[s], tab.n_out[s], b, P0, tid, cur, inv);
   }
 }
 
@@ -89,11 +119,9 @@ __device__ __forceinline__ unsigned int bf16_rne_bits(float f) {
 
 // Channels-last: one wave per output row (b, p), lane l on the 16-byte chunks l, l + 64, ...
 template <bool BF16>
-__global__ __launch_bounds__(256) void dense_gather_nhwc_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
-                                                                void* __restrict__ out, float fill, long rows, int P, int n_rows, int D) {
+__device__ __forceinline__ void gather_row_nhwc(const float* __restrict__ tokens, const int32_t* __restrict__ index, void* __restrict__ out,
+                                                float fill, long row, int P, int n_rows, int D) {
   const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
   const long b = row / P;
   const int idx = index[row];
   const bool ok = idx >= 0 && idx < n_rows;
@@ -112,6 +140,33 @@ __global__ __launch_bounds__(256) void dense_gather_nhwc_kernel(const float* __r
   }
 }
 
+template <bool BF16>
+__global__ __launch_bounds__(256) void dense_gather_nhwc_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
+                                                                void* __restrict__ out, float fill, long rows, int P, int n_rows, int D) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  gather_row_nhwc<BF16>(tokens, index, out, fill, row, P, n_rows, D);
+}
+
+// the rows of a level, per level of tr_dense_gather_levels (a kernel argument: a captured graph holds it)
+struct level_rows_table {
+  int rows[TR_MAX_DEPTH];
+};
+
+// ... for L levels: the rows of level l are l * B * P ... (l + 1) * B * P - 1 of one launch; a level's tokens, index and map are slabs of
+// level_stride, B * P and B * P * D elements
+template <bool BF16>
+__global__ __launch_bounds__(256) void dense_gather_levels_nhwc_kernel(const float* __restrict__ tokens, size_t level_stride, level_rows_table lr,
+                                                                       const int32_t* __restrict__ index, void* __restrict__ out, float fill,
+                                                                       long rows_per_level, long rows, int P, int D) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int l = (int)(row / rows_per_level);
+  const size_t o = (size_t)l * rows_per_level * D;
+  void* out_l = BF16 ? static_cast<void*>(static_cast<uint16_t*>(out) + o) : static_cast<void*>(static_cast<float*>(out) + o);
+  gather_row_nhwc<BF16>(tokens + l * level_stride, index + (size_t)l * rows_per_level, out_l, fill, row - l * rows_per_level, P, lr.rows[l], D);
+}
+
 constexpr int DG_TP = 64;            // patches per tile
 constexpr int DG_TC = 64;            // channels per tile
 constexpr int DG_LD = DG_TC + 1;     // one 4-byte access width of padding: column reads hit 32 different banks
@@ -119,13 +174,8 @@ constexpr int DG_LD = DG_TC + 1;     // one 4-byte access width of padding: colu
 // NCHW: tile (image b, patches p0 ... p0+63, channels c0 ... c0+63).  The tiles of one image are consecutive logical ids, and xcd_remap gives
 // each XCD a contiguous run of them: the rows of an image that many patches share (the merge families) are then read through one L2.
 template <bool BF16, bool VEC>
-__global__ __launch_bounds__(256) void dense_gather_nchw_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
-                                                                void* __restrict__ out, float fill, int P, int n_rows, int D, int ptiles,
-                                                                int ctiles) {
-  __shared__ float tile[DG_TP * DG_LD];
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
-  const int ct = id % ctiles, pt = (id / ctiles) % ptiles, b = id / (ctiles * ptiles);
-  const int p0 = pt * DG_TP, c0 = ct * DG_TC;
+__device__ __forceinline__ void gather_tile_nchw(const float* __restrict__ tokens, const int32_t* __restrict__ index, void* __restrict__ out,
+                                                 float fill, int P, int n_rows, int D, int b, int p0, int c0, float* tile) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   // rows in: a wave instruction takes 4 rows x 64 channels, 16 lanes per row; all four loads of a wave are issued before the first write
@@ -195,7 +245,69 @@ __global__ __launch_bounds__(256) void dense_gather_nchw_kernel(const float* __r
   }
 }
 
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(256) void dense_gather_nchw_kernel(const float* __restrict__ tokens, const int32_t* __restrict__ index,
+                                                                void* __restrict__ out, float fill, int P, int n_rows, int D, int ptiles,
+                                                                int ctiles) {
+  __shared__ float tile[DG_TP * DG_LD];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int ct = id % ctiles, pt = (id / ctiles) % ptiles, b = id / (ctiles * ptiles);
+  gather_tile_nchw<BF16, VEC>(tokens, index, out, fill, P, n_rows, D, b, pt * DG_TP, ct * DG_TC, tile);
+}
+
+// ... for L levels in one launch: the logical tile order is (level, image, patch tile, channel tile), the level slowest, and xcd_remap gives
+// each XCD a contiguous run of it -- inside a level the tiles of an image stay neighbours on one L2, as in the single-level kernel
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(256) void dense_gather_levels_nchw_kernel(const float* __restrict__ tokens, size_t level_stride, level_rows_table lr,
+                                                                       const int32_t* __restrict__ index, void* __restrict__ out, float fill,
+                                                                       int B, int P, int D, int ptiles, int ctiles) {
+  __shared__ float tile[DG_TP * DG_LD];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int per_image = ctiles * ptiles;
+  const int ct = id % ctiles, pt = (id / ctiles) % ptiles, b = (id / per_image) % B, l = id / (per_image * B);
+  const size_t o = (size_t)l * B * P * D;
+  void* out_l = BF16 ? static_cast<void*>(static_cast<uint16_t*>(out) + o) : static_cast<void*>(static_cast<float*>(out) + o);
+  gather_tile_nchw<BF16, VEC>(tokens + l * level_stride, index + (size_t)l * B * P, out_l, fill, P, lr.rows[l], D, b, pt * DG_TP, ct * DG_TC, tile);
+}
+
 }  // namespace
+
+// the stage table checked and copied into `tab` with every stage's n_out (tr_dense_index's rules, for both index entry points)
+static int dense_build_table(const char* who, const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems,
+                             const tr_decision_stage* stages, int n_stages, int B, int P0, dense_table* tab_out) {
+  dense_table& tab = *tab_out;
+  tab.n = n_stages;
+  int last_block = -1, n_out = P0;
+  bool seen_map = false;
+  for (int i = 0; i < n_stages; ++i) {
+    const tr_decision_stage& st = stages[i];
+    TR_REQUIRE(st.kind >= TR_DECISION_PRUNE && st.kind <= TR_DECISION_SOFT, TR_ERR_CONFIG, "%s: stage %d has kind %d", who, i, st.kind);
+    TR_REQUIRE(st.block > last_block && st.block < TR_MAX_DEPTH, TR_ERR_CONFIG, "%s: stage %d names block %d (ascending blocks below %d)", who, i,
+               st.block, TR_MAX_DEPTH);
+    last_block = st.block;
+    TR_REQUIRE(st.n_in >= 2 && st.n_in <= P0 + 1 && st.k >= 1 && st.k < st.n_in, TR_ERR_SHAPE,
+               "%s: stage %d needs 2 <= n_in <= P0 + 1 and 1 <= k < n_in (n_in=%d k=%d P0=%d)", who, i, st.n_in, st.k, P0);
+    TR_REQUIRE(st.kind != TR_DECISION_ATS || st.k >= 2, TR_ERR_SHAPE, "%s: stage %d: an ATS stage needs k >= 2", who, i);
+    if (stage_has_map(st.kind)) {
+      seen_map = true;
+      n_out = st.kind == TR_DECISION_TOME ? st.n_in - 1 - (st.k < (st.n_in - 1) / 2 ? st.k : (st.n_in - 1) / 2) : st.k;
+      const size_t P_in = (size_t)st.n_in - 1;
+      TR_REQUIRE(assign, TR_ERR_NULL, "%s: stage %d reads an assignment map, assign is NULL", who, i);
+      TR_REQUIRE(st.assign_off >= 0 && (size_t)st.assign_off + (size_t)B * P_in <= assign_elems, TR_ERR_SHAPE,
+                 "%s: stage %d: map [%d, %zu] at %lld leaves assign (%zu elements)", who, i, B, P_in, (long long)st.assign_off, assign_elems);
+    } else {
+      // an absolute kept list overrides the state: behind a map stage the rows it names are no grid patches any more
+      TR_REQUIRE(!seen_map, TR_ERR_CONFIG, "%s: stage %d has only a kept list and stands behind a stage with an assignment map", who, i);
+      n_out = st.kind == TR_DECISION_EVIT ? st.k + 1 : st.kind == TR_DECISION_ATS ? st.k - 1 : st.k;
+      TR_REQUIRE(kept, TR_ERR_NULL, "%s: stage %d reads a kept list, kept is NULL", who, i);
+      TR_REQUIRE(st.kept_off >= 0 && (size_t)st.kept_off + (size_t)B * n_out <= kept_elems, TR_ERR_SHAPE,
+                 "%s: stage %d: kept list [%d, %d] at %lld leaves kept (%zu elements)", who, i, B, n_out, (long long)st.kept_off, kept_elems);
+    }
+    tab.st[i] = st;
+    tab.n_out[i] = n_out;
+  }
+  return TR_OK;
+}
 
 extern "C" int tr_dense_index(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems, const tr_decision_stage* stages,
                               int n_stages, int B, int P0, int n_last, int32_t* index_out, tr_stream_t s) {
@@ -205,42 +317,48 @@ extern "C" int tr_dense_index(const int32_t* kept, size_t kept_elems, const int3
   TR_REQUIRE(B > 0 && P0 >= 1 && P0 <= DI_MAX_P && n_last >= 2, TR_ERR_SHAPE, "tr_dense_index: need B > 0, 1 <= P0 <= 1024, n_last >= 2 (B=%d P0=%d n_last=%d)",
              B, P0, n_last);
   dense_table tab;
-  tab.n = n_stages;
-  int last_block = -1, n_out = P0;
-  bool seen_map = false;
-  for (int i = 0; i < n_stages; ++i) {
-    const tr_decision_stage& st = stages[i];
-    TR_REQUIRE(st.kind >= TR_DECISION_PRUNE && st.kind <= TR_DECISION_SOFT, TR_ERR_CONFIG, "tr_dense_index: stage %d has kind %d", i, st.kind);
-    TR_REQUIRE(st.block > last_block && st.block < TR_MAX_DEPTH, TR_ERR_CONFIG,
-               "tr_dense_index: stage %d names block %d (ascending blocks below %d)", i, st.block, TR_MAX_DEPTH);
-    last_block = st.block;
-    TR_REQUIRE(st.n_in >= 2 && st.n_in <= P0 + 1 && st.k >= 1 && st.k < st.n_in, TR_ERR_SHAPE,
-               "tr_dense_index: stage %d needs 2 <= n_in <= P0 + 1 and 1 <= k < n_in (n_in=%d k=%d P0=%d)", i, st.n_in, st.k, P0);
-    TR_REQUIRE(st.kind != TR_DECISION_ATS || st.k >= 2, TR_ERR_SHAPE, "tr_dense_index: stage %d: an ATS stage needs k >= 2", i);
-    if (stage_has_map(st.kind)) {
-      seen_map = true;
-      n_out = st.kind == TR_DECISION_TOME ? st.n_in - 1 - (st.k < (st.n_in - 1) / 2 ? st.k : (st.n_in - 1) / 2) : st.k;
-      const size_t P_in = (size_t)st.n_in - 1;
-      TR_REQUIRE(assign, TR_ERR_NULL, "tr_dense_index: stage %d reads an assignment map, assign is NULL", i);
-      TR_REQUIRE(st.assign_off >= 0 && (size_t)st.assign_off + (size_t)B * P_in <= assign_elems, TR_ERR_SHAPE,
-                 "tr_dense_index: stage %d: map [%d, %zu] at %lld leaves assign (%zu elements)", i, B, P_in, (long long)st.assign_off, assign_elems);
-    } else {
-      // an absolute kept list overrides the state: behind a map stage the rows it names are no grid patches any more
-      TR_REQUIRE(!seen_map, TR_ERR_CONFIG, "tr_dense_index: stage %d has only a kept list and stands behind a stage with an assignment map", i);
-      n_out = st.kind == TR_DECISION_EVIT ? st.k + 1 : st.kind == TR_DECISION_ATS ? st.k - 1 : st.k;
-      TR_REQUIRE(kept, TR_ERR_NULL, "tr_dense_index: stage %d reads a kept list, kept is NULL", i);
-      TR_REQUIRE(st.kept_off >= 0 && (size_t)st.kept_off + (size_t)B * n_out <= kept_elems, TR_ERR_SHAPE,
-                 "tr_dense_index: stage %d: kept list [%d, %d] at %lld leaves kept (%zu elements)", i, B, n_out, (long long)st.kept_off, kept_elems);
-    }
-    tab.st[i] = st;
-    tab.n_out[i] = n_out;
-  }
+  const int rc = dense_build_table("tr_dense_index", kept, kept_elems, assign, assign_elems, stages, n_stages, B, P0, &tab);
+  if (rc != TR_OK) return rc;
+  const int n_out = n_stages > 0 ? tab.n_out[n_stages - 1] : P0;
   TR_REQUIRE(n_out == n_last - 1, TR_ERR_SHAPE, "tr_dense_index: the stages end at %d patch rows, the last stream has %d", n_out, n_last - 1);
   TR_REQUIRE(tr_aligned16(kept) && tr_aligned16(assign) && tr_aligned16(index_out), TR_ERR_ALIGN, "tr_dense_index: pointers must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(s);
   tr_prof_note("tr_dense_index", 0.0, 4.0 * B * P0 * (n_stages + 1));
   hipLaunchKernelGGL(dense_index_kernel, dim3(B), dim3(DI_THREADS), 0, st, kept, assign, tab, B, P0, index_out);
   TR_CHECK_LAUNCH("tr_dense_index");
+  return TR_OK;
+}
+
+extern "C" int tr_dense_index_levels(const int32_t* kept, size_t kept_elems, const int32_t* assign, size_t assign_elems,
+                                     const tr_decision_stage* stages, int n_stages, int B, int P0, const int32_t* level_blocks,
+                                     const int32_t* level_rows, int L, int32_t* index_out, tr_stream_t s) {
+  TR_REQUIRE(n_stages >= 0 && n_stages <= TR_MAX_DECISION_STAGES, TR_ERR_CONFIG, "tr_dense_index_levels: %d stages (at most %d)", n_stages,
+             TR_MAX_DECISION_STAGES);
+  TR_REQUIRE(L >= 1 && L <= TR_MAX_DEPTH, TR_ERR_CONFIG, "tr_dense_index_levels: %d levels (1 ... %d)", L, TR_MAX_DEPTH);
+  TR_REQUIRE(index_out && level_blocks && level_rows && (n_stages == 0 || stages), TR_ERR_NULL, "tr_dense_index_levels: null pointer");
+  TR_REQUIRE(B > 0 && P0 >= 1 && P0 <= DI_MAX_P, TR_ERR_SHAPE, "tr_dense_index_levels: need B > 0, 1 <= P0 <= 1024 (B=%d P0=%d)", B, P0);
+  for (int l = 0; l < L; ++l)
+    TR_REQUIRE(level_blocks[l] >= 0 && level_blocks[l] < TR_MAX_DEPTH && (l == 0 || level_blocks[l] > level_blocks[l - 1]), TR_ERR_CONFIG,
+               "tr_dense_index_levels: level %d names block %d (strictly ascending blocks in 0 ... %d)", l, level_blocks[l], TR_MAX_DEPTH - 1);
+  dense_table tab;
+  const int rc = dense_build_table("tr_dense_index_levels", kept, kept_elems, assign, assign_elems, stages, n_stages, B, P0, &tab);
+  if (rc != TR_OK) return rc;
+  // a level's prefix: the stages at or before its block.  What that prefix leaves must be the rows the caller saw in the stream there
+  level_table lev;
+  lev.n = L;
+  for (int l = 0, after = 0; l < L; ++l) {
+    while (after < n_stages && stages[after].block <= level_blocks[l]) ++after;
+    lev.after[l] = after;
+    const int n_out = after > 0 ? tab.n_out[after - 1] : P0;
+    TR_REQUIRE(n_out == level_rows[l] - 1, TR_ERR_SHAPE, "tr_dense_index_levels: the stages up to block %d leave %d patch rows, level %d has %d",
+               level_blocks[l], n_out, l, level_rows[l] - 1);
+  }
+  TR_REQUIRE(tr_aligned16(kept) && tr_aligned16(assign) && tr_aligned16(index_out), TR_ERR_ALIGN,
+             "tr_dense_index_levels: pointers must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  tr_prof_note("tr_dense_index_levels", 0.0, 4.0 * B * P0 * (n_stages + L));
+  hipLaunchKernelGGL(dense_index_levels_kernel, dim3(B), dim3(DI_THREADS), 0, st, kept, assign, tab, lev, B, P0, index_out);
+  TR_CHECK_LAUNCH("tr_dense_index_levels");
   return TR_OK;
 }
 
@@ -275,5 +393,52 @@ extern "C" int tr_dense_gather(const float* tokens, const int32_t* index, void* 
 #undef DG_LAUNCH
   }
   TR_CHECK_LAUNCH("tr_dense_gather");
+  return TR_OK;
+}
+
+extern "C" int tr_dense_gather_levels(const float* tokens, size_t level_stride, const int32_t* level_rows, int L, const int32_t* index, void* out,
+                                      int layout, int out_is_bf16, float fill, int B, int P, int D, tr_stream_t s) {
+  TR_REQUIRE(tokens && level_rows && index && out, TR_ERR_NULL, "tr_dense_gather_levels: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_CONFIG, "tr_dense_gather_levels: layout %d (TR_LAYOUT_NCHW or TR_LAYOUT_NHWC)",
+             layout);
+  TR_REQUIRE(L >= 1 && L <= TR_MAX_DEPTH, TR_ERR_CONFIG, "tr_dense_gather_levels: %d levels (1 ... %d)", L, TR_MAX_DEPTH);
+  TR_REQUIRE(B > 0 && P >= 1 && P <= DI_MAX_P && D > 0 && D % 4 == 0 && D <= 1024, TR_ERR_SHAPE,
+             "tr_dense_gather_levels: need B > 0, 1 <= P <= 1024, D %% 4 == 0, D <= 1024 (B=%d P=%d D=%d)", B, P, D);
+  level_rows_table lr;
+  for (int l = 0; l < L; ++l) {
+    // a level's rows [B, n_rows, D] lie inside its slab; slabs start 16-byte aligned
+    TR_REQUIRE(level_rows[l] >= 1 && (size_t)B * level_rows[l] * D <= level_stride, TR_ERR_SHAPE,
+               "tr_dense_gather_levels: level %d has %d rows: [%d, %d, %d] does not fit a slab of %zu elements", l, level_rows[l], B, level_rows[l],
+               D, level_stride);
+    lr.rows[l] = level_rows[l];
+  }
+  TR_REQUIRE(level_stride % 4 == 0, TR_ERR_ALIGN, "tr_dense_gather_levels: level_stride %zu is not a multiple of 4 elements", level_stride);
+  TR_REQUIRE(tr_aligned16(tokens) && tr_aligned16(index) && tr_aligned16(out), TR_ERR_ALIGN,
+             "tr_dense_gather_levels: pointers must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const bool bf = out_is_bf16 != 0;
+  tr_prof_note("tr_dense_gather_levels", 0.0, (double)L * ((double)B * P * D * (4.0 + (bf ? 2.0 : 4.0)) + 4.0 * B * P));
+  if (layout == TR_LAYOUT_NHWC) {
+    const long per_level = (long)B * P, rows = per_level * L;
+    TR_REQUIRE((rows + 3) / 4 <= INT_MAX, TR_ERR_SHAPE, "tr_dense_gather_levels: %ld rows", rows);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (bf) hipLaunchKernelGGL((dense_gather_levels_nhwc_kernel<true>), grid, dim3(256), 0, st, tokens, level_stride, lr, index, out, fill, per_level, rows, P, D);
+    else hipLaunchKernelGGL((dense_gather_levels_nhwc_kernel<false>), grid, dim3(256), 0, st, tokens, level_stride, lr, index, out, fill, per_level, rows, P, D);
+  } else {
+    const int ptiles = (P + DG_TP - 1) / DG_TP, ctiles = (D + DG_TC - 1) / DG_TC;
+    const long blocks = (long)L * B * ptiles * ctiles;
+    TR_REQUIRE(blocks <= INT_MAX, TR_ERR_SHAPE, "tr_dense_gather_levels: %ld tiles", blocks);
+    const dim3 grid((unsigned)blocks);
+    const bool vec = P % 4 == 0;
+#define DG_LAUNCH(BF, VEC)                                                                                                                   \
+  hipLaunchKernelGGL((dense_gather_levels_nchw_kernel<BF, VEC>), grid, dim3(256), 0, st, tokens, level_stride, lr, index, out, fill, B, P, D, \
+                     ptiles, ctiles)
+    if (bf && vec) DG_LAUNCH(true, true);
+    else if (bf) DG_LAUNCH(true, false);
+    else if (vec) DG_LAUNCH(false, true);
+    else DG_LAUNCH(false, false);
+#undef DG_LAUNCH
+  }
+  TR_CHECK_LAUNCH("tr_dense_gather_levels");
   return TR_OK;
 }

@@ -256,6 +256,12 @@ struct Fwd {
   uint32_t tap_mask = 0;
   int n_taps = 0, tap_i = 0;
   float *cls_out = nullptr, *final_tokens_out = nullptr;
+  // level taps (eval, tr_vit_forward_levels): EVERY row of the stream after the blocks of level_mask, plus what is pending there, goes to the
+  // next slab of level_out (level_i; a slab is B * N0 * D elements and holds [B, N, D]) -- as it stands (the rows of features_out) or through
+  // the final norm.  Like a CLS tap it reads what is there; a tapped last block needs every row and so runs full width (begin_block)
+  uint32_t level_mask = 0;
+  int level_norm = 0, level_i = 0;
+  float* level_out = nullptr;
   // ---- the block being enqueued (pre_block, begin_block) ------------------------------------------------------------------------------
   bool have_xn = false;         // norm1(x) already in xn (written by a pre-block reducer)
   bool tail = false;            // this block runs as the CLS tail
@@ -267,7 +273,7 @@ struct Fwd {
       const trplan::TapePlan* tp_, const void* img_, int input_format_, const float* pixel_lut_, const tr_augment_rec* aug_,
       const float* aug_noise_, long aug_noise_len_, float* logits_, int32_t* kept_idx_, int32_t* compl_idx_, float* soft_out_,
       const float* noise_in_, float* features_out_, int* tokens_out_, const float* drop_scale_, const uint8_t* drop_keep_, float drop_rate,
-      const tr_vit_taps* taps)
+      const tr_vit_taps* taps, const tr_vit_levels* levels)
       : cfg(cfg_), w(w_), p(plan), B(B_), D(plan.D), H(plan.H), prec(cfg_->precision), s(s_), f32(cfg_->precision != TR_PREC_BF16),
         train(tape_ != nullptr), ws(static_cast<char*>(workspace)), tape(tape_), tp(tp_), img(img_), input_format(input_format_),
         pixel_lut(pixel_lut_), aug_noise(aug_noise_), aug(aug_), aug_noise_len(aug_noise_len_), drop_scale(drop_scale_),
@@ -278,6 +284,11 @@ struct Fwd {
       n_taps = __builtin_popcount(tap_mask);
       cls_out = tap_mask != 0 ? taps->cls_out : nullptr;
       final_tokens_out = taps->final_tokens_out;
+    }
+    if (levels != nullptr && levels->blocks != 0) {
+      level_mask = levels->blocks;
+      level_norm = levels->norm;
+      level_out = levels->tokens_out;
     }
     lazy_base = !train && !f32 && !lab().ln_eager && features_out == nullptr;
     rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
@@ -686,12 +697,12 @@ struct Fwd {
       r = cfg->keep[i] < (N - 1) / 2 ? cfg->keep[i] : (N - 1) / 2;
     }
     // CLS tail: the last block of an eval forward that reduces nothing from its attention onward and whose stream nobody reads (no Features,
-    // no final tokens, no average pool).
+    // no final tokens, no level tap of this block, no average pool).
     // K and V still come from every row (norm1 and the qkv GEMM stay full width); the attention computes the CLS query only, and proj, norm2,
     // fc1, fc2 run on the B CLS rows: per-row operations of the same kernels, so these rows come out bit for bit as in the full-width block.
     // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
-    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr && !pool && K == 0 &&
-           r == 0 && Ks == 0 &&
+    tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr &&
+           ((level_mask >> i) & 1u) == 0 && !pool && K == 0 && r == 0 && Ks == 0 &&
            drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0 &&
            tr_attention_cls_available() != 0;
     norm2_in_mlp = false;
@@ -749,12 +760,30 @@ struct Fwd {
   // CLS tap after block i: the CLS rows of x plus what is still pending, in the order the next norm adds it -- (x + attention branch) + mlp
   // branch, the fp32 additions behind viz_data["Features"][i][:, 0].  Under the CLS tail the pending rows are the compact [B, D] buffers.
   int tap_cls(int i) {
+    TR_TRY(tap_level(i));
     if (cls_out == nullptr || ((tap_mask >> i) & 1u) == 0) return TR_OK;
     const long ld = (long)N * D, ldp = pending_ld > 0 ? pending_ld : ld;
     const void* first = pending_attn != nullptr ? pending_attn : pending;
     const void* second = pending_attn != nullptr ? pending : nullptr;
     TR_TRY(tr_cls_tap(x, ld, first, ldp, second, ldp, f32 ? 1 : 0, cls_out + (size_t)tap_i * D, (long)n_taps * D, B, D, s));
     ++tap_i;
+    return TR_OK;
+  }
+
+  // Level tap after block i: every row of the stream plus what is still pending, added in fp32 in the order the next norm adds it -- the rows
+  // of viz_data["Features"][i] (tr_cls_tap at row stride D: its arithmetic is tr_residual_snapshot's behind an eager norm2) -- or their final
+  // norm (tr_final_tokens_f32).  One launch; x is not written.  Behind a fused block tail nothing is pending: the rows are x itself.
+  int tap_level(int i) {
+    if (level_out == nullptr || ((level_mask >> i) & 1u) == 0) return TR_OK;
+    TR_REQUIRE(pending_ld == 0, TR_ERR_CONFIG, "tr_vit_forward_levels: internal: level tap of block %d behind a CLS tail", i);
+    const void* first = pending_attn != nullptr ? pending_attn : pending;
+    const void* second = pending_attn != nullptr ? pending : nullptr;
+    float* dst = level_out + (size_t)level_i * B * p.N0 * D;
+    if (level_norm != 0)
+      TR_TRY(tr_final_tokens_f32(x, first, second, f32 ? 1 : 0, w->norm_g, w->norm_b, dst, B * N, D, cfg->ln_eps, s));
+    else
+      TR_TRY(tr_cls_tap(x, D, first, D, second, D, f32 ? 1 : 0, dst, D, B * N, D, s));
+    ++level_i;
     return TR_OK;
   }
 
@@ -975,7 +1004,7 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
                             const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
-                            const tr_vit_taps* taps = nullptr) {
+                            const tr_vit_taps* taps = nullptr, const tr_vit_levels* levels = nullptr) {
   Plan p;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
@@ -1000,10 +1029,24 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
     TR_REQUIRE(tr_aligned16(taps->cls_out) && tr_aligned16(taps->final_tokens_out), TR_ERR_ALIGN,
                "tr_vit_forward_taps: tap buffers must be 16-byte aligned");
   }
+  if (levels != nullptr && (levels->blocks != 0 || levels->tokens_out != nullptr)) {
+    const int n_levels = __builtin_popcount(levels->blocks);
+    const size_t slab = (size_t)B * p.N0 * p.D;
+    TR_REQUIRE(tape == nullptr, TR_ERR_CONFIG, "tr_vit_forward_levels: level taps are an eval feature");
+    TR_REQUIRE(features_out == nullptr, TR_ERR_CONFIG, "tr_vit_forward_levels: level taps and features_out in one call");
+    TR_REQUIRE(levels->blocks == 0 || levels->tokens_out != nullptr, TR_ERR_CONFIG, "tr_vit_forward_levels: blocks 0x%x without tokens_out",
+               levels->blocks);
+    TR_REQUIRE(cfg->depth >= 32 || (levels->blocks >> cfg->depth) == 0, TR_ERR_CONFIG,
+               "tr_vit_forward_levels: blocks 0x%x names a block outside 0 ... %d", levels->blocks, cfg->depth - 1);
+    TR_REQUIRE(levels->norm == 0 || levels->norm == 1, TR_ERR_CONFIG, "tr_vit_forward_levels: norm %d (0 or 1)", levels->norm);
+    TR_REQUIRE(levels->tokens_elems >= n_levels * slab, TR_ERR_SHAPE, "tr_vit_forward_levels: tokens_out holds %zu elements, %d levels need %zu",
+               levels->tokens_elems, n_levels, n_levels * slab);
+    TR_REQUIRE(tr_aligned16(levels->tokens_out), TR_ERR_ALIGN, "tr_vit_forward_levels: tokens_out must be 16-byte aligned");
+  }
   tr_prof_restart();
 
   Fwd f(cfg, w, p, B, s, workspace, tape, tp, img, input_format, pixel_lut, aug, aug_noise, aug_noise_len, logits, kept_idx, compl_idx, soft_out,
-        noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate, taps);
+        noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate, taps, levels);
 
   // patch_embed -> cat(cls) + pos_embed -> depth x Block -> norm -> x[:,0] -> head, with
   // Block: [stage reducer]; x += attn(norm1(x)); [in-block reducer]; x += mlp(norm2(x))
@@ -1072,6 +1115,15 @@ extern "C" int tr_vit_forward_pixels_taps(const tr_vit_config* cfg, const tr_vit
   TR_REQUIRE(taps != nullptr, TR_ERR_NULL, "tr_vit_forward_pixels_taps: null tr_vit_taps");
   return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
                           features_out, tokens_out, B, s, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, 0, taps);
+}
+
+extern "C" int tr_vit_forward_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                                     float* logits, void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
+                                     const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, const tr_vit_taps* taps,
+                                     const tr_vit_levels* levels) {
+  TR_REQUIRE(levels != nullptr, TR_ERR_NULL, "tr_vit_forward_levels: null tr_vit_levels");
+  return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, kept_idx, compl_idx, soft_out, noise_in,
+                          features_out, tokens_out, B, s, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, 0, taps, levels);
 }
 
 extern "C" size_t tr_vit_tape_bytes(const tr_vit_config* cfg, int B) {

@@ -31,6 +31,9 @@ forward_decisions / forward_async(decisions=True) -- int32 device tensors in the
 (tr_stage_decisions) behind the fast-path forward.
 forward_dense / forward_async(dense=...) put the final-normed rows of the last block back on the input's patch grid ([B, D, h, w] or
 [B, h, w, D]) through those decisions: two more launches (tr_dense_index, tr_dense_gather), `fill` where no row stands for a patch.
+forward_dense(blocks=...) / get_intermediate_layers do the same for chosen intermediate blocks: the executor writes every row of those
+blocks while the fast path runs (tr_vit_forward_levels), each level is placed by the stages at or before its block, and one index launch and
+one gather launch serve all levels (tr_dense_index_levels, tr_dense_gather_levels).
 """
 from __future__ import annotations
 
@@ -794,8 +797,9 @@ class VisionTransformer(nn.Module):
 
     _DENSE_FORMATS = ("NCHW", "NHWC")
 
-    def _dense_request(self, x, what, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
-        """(format, dtype, fill) of a forward_dense / forward_async(dense=...) call, or the refusal."""
+    def _dense_request(self, x, what, output_fmt="NCHW", dtype=torch.float32, fill=0.0, blocks=None, norm=True):
+        """(format, dtype, fill) of a forward_dense / forward_async(dense=...) call -- with blocks: (format, dtype, fill, ascending block tuple,
+        norm) -- or the refusal."""
         if self.training:
             raise RuntimeError("dense feature maps are an eval feature: call model.eval() first (the training executor has no taps)")
         if self.viz_mode:
@@ -813,9 +817,21 @@ class VisionTransformer(nn.Module):
         if self.patch_embed.num_patches > 1024 or self.embed_dim % 4 or self.embed_dim > 1024:
             raise ValueError(f"dense feature maps take at most 1024 patches and a width that is a multiple of 4 up to 1024 "
                              f"({self.patch_embed.num_patches} patches, width {self.embed_dim})")
-        return output_fmt, dtype, float(fill)
+        if blocks is None:
+            return output_fmt, dtype, float(fill)
+        if isinstance(blocks, (int, np.integer)):
+            blocks = (blocks,)
+        asked = [int(b) for b in blocks]
+        if not asked:
+            raise ValueError("blocks is empty: name at least one block (blocks=None is the last block's map)")
+        if any(not -self.depth <= b < self.depth for b in asked):
+            raise ValueError(f"blocks {tuple(asked)} names a block outside {-self.depth} ... {self.depth - 1}")
+        levels = sorted(b % self.depth for b in asked)
+        if len(set(levels)) != len(levels):
+            raise ValueError(f"blocks {tuple(asked)} names a block twice")
+        return output_fmt, dtype, float(fill), tuple(levels), bool(norm)
 
-    def forward_dense(self, x: torch.Tensor, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
+    def forward_dense(self, x: torch.Tensor, blocks=None, norm=True, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
         """Eval forward with a dense feature map: (logits, {"features", "index", "grid": (h, w)}).  `features` is the final norm of the last
         block's rows (the final_tokens tap, fp32 arithmetic) put back on the input's patch grid: [B, D, h, w] for output_fmt "NCHW", [B, h, w,
         D] for "NHWC", fp32 or bf16 (dtype; round to nearest even of the fp32 value).  `index` int32 [B, h * w] names, per grid patch, the row of
@@ -827,11 +843,37 @@ class VisionTransformer(nn.Module):
         launches (tr_dense_index, tr_dense_gather) in the same stream and the same captured graph; the request is part of the graph key and
         the logits are those of model(x).  The map and the index are static buffers per workspace slot, allocated on the first dense call
         (at 512 x 512 inputs, DeiT-B width and batch 256 the fp32 map is about 0.8 GB per slot) and cloned out like the taps.  The taps and
-        decision records themselves are not returned: ask forward_decisions for them.  Intermediate blocks, a soft-weighted un-merge,
-        training and a gradient are not built.  Refuses train mode, viz_mode, dynamic_width."""
+        decision records themselves are not returned: ask forward_decisions for them.
+        blocks=(...) asks for the maps of chosen blocks instead (ints in [-depth, depth), negative ones count from the end, no duplicates;
+        results in ascending block order): (logits, {"features": [L maps], "index": [L int32 [B, h * w]], "blocks", "grid", "cls": fp32 [B, L,
+        D]}).  Level l is the stream after block blocks[l] -- every row, with the residuals pending there, bit for bit the rows of viz_mode's
+        Features[blocks[l]] -- through the model's final norm (norm=True) or as it stands (norm=False), put on the grid by the decisions of
+        the stages at or before that block: a block in front of every stage has the identity as its index.  `cls` is row 0 of each level.
+        The forward stays on the fast path (tr_vit_forward_levels: one launch per level where its CLS tap would run; the CLS tail stays unless
+        the last block is asked for), followed by tr_stage_decisions and ONE tr_dense_index_levels and ONE tr_dense_gather_levels for all
+        levels; blocks and norm are part of the graph key.  blocks=None is the call described first, unchanged.
+        A soft-weighted un-merge, following EViT's fused token, training and a gradient are not built.  Refuses train mode, viz_mode,
+        dynamic_width and a block out of range."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        return self._forward_eval(x, 0, dense=self._dense_request(x, "forward_dense", output_fmt, dtype, fill))
+        return self._forward_eval(x, 0, dense=self._dense_request(x, "forward_dense", output_fmt, dtype, fill, blocks, norm))
+
+    def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape=False, return_class_token=False, norm=False, dtype=torch.float32, fill=0.0):
+        """timm's VisionTransformer.get_intermediate_layers on the fast path: the patch tokens after the last `n` blocks (int n) or after the
+        blocks `n` names (a sequence; negative entries count from the end), in ascending block order -- a tuple of [B, h * w, D] tensors, of
+        [B, D, h, w] with reshape=True; norm=True applies the model's final norm; with return_class_token a tuple of (tokens, cls [B, D])
+        pairs.  A thin wrapper over forward_dense(blocks=...), with its refusals.  Unlike a dense ViT, a reduced stream has no row for every
+        patch: a patch whose row was pruned (or went into EViT's fused token) shows `fill` in every channel, and the patches merged into one
+        row all show that row."""
+        blocks = tuple(range(self.depth - int(n), self.depth)) if isinstance(n, (int, np.integer)) else tuple(n)
+        if isinstance(n, (int, np.integer)) and not 1 <= int(n) <= self.depth:
+            raise ValueError(f"n = {n}: the model has {self.depth} blocks")
+        _, out = self.forward_dense(x, blocks=blocks, norm=norm, output_fmt="NCHW" if reshape else "NHWC", dtype=dtype, fill=fill)
+        B, D = x.shape[0], self.embed_dim
+        feats = out["features"] if reshape else [f.view(B, -1, D) for f in out["features"]]
+        if return_class_token:
+            return tuple((f, out["cls"][:, l]) for l, f in enumerate(feats))
+        return tuple(feats)
 
     def forward_async(self, x: torch.Tensor, cls_blocks=None, final_tokens=False, decisions=False, dense=None):
         """Eval forward that may run BESIDE the previous one: the call enqueues the forward on one of `pipeline_depth` (default 2) side streams
@@ -844,9 +886,9 @@ class VisionTransformer(nn.Module):
         Train mode, viz_mode and ATS's dynamic width run synchronously (the handle is already complete).
         cls_blocks / final_tokens: the output taps of forward_taps -- the result is then what forward_taps returns.  With taps, train mode,
         viz_mode and dynamic_width are refused instead of run synchronously.  decisions=True: the decision taps of forward_decisions, with
-        the same refusals -- the result is what forward_decisions returns.  dense=dict(output_fmt=..., dtype=..., fill=...) (any subset; {} for
-        the defaults): the dense feature map of forward_dense, with its refusals -- the result is what forward_dense returns; it does not
-        combine with the other keywords."""
+        the same refusals -- the result is what forward_decisions returns.  dense=dict(output_fmt=..., dtype=..., fill=..., blocks=...,
+        norm=...) (any subset; {} for the defaults): the dense feature map(s) of forward_dense, with its refusals -- the result is what
+        forward_dense returns; it does not combine with the other keywords."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
         taps = None
@@ -900,7 +942,10 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"expected [B,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(x.shape)}")
         x, fmt, lut = self._executor_input(x)
         ws = self._workspace(B, x.device, slot)
-        if dense is not None:
+        levels = dense[3] if dense is not None and len(dense) > 3 else None       # forward_dense(blocks=...): the ascending block tuple
+        if levels is not None:
+            decisions = True                           # the rows of the level taps, placed by the stages' record-form decisions
+        elif dense is not None:
             taps, decisions = ((), True), True         # the rows of the final_tokens tap, placed by the stages' record-form decisions
         if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
             ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
@@ -921,7 +966,20 @@ class VisionTransformer(nn.Module):
             tap_arg = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
                                      ws["tap_final"].data_ptr() if want_final else None)
         dec = self._decision_plan(ws, B, x.device) if decisions else None
-        if dense is not None:
+        if levels is not None:
+            # static per workspace slot and level count: the level slabs [L, B * N0 * D] fp32, the indices [L, B, P0], one map buffer per dtype
+            P0, L = self.patch_embed.num_patches, len(levels)
+            slab = B * (P0 + 1) * self.embed_dim
+            lv = ws.setdefault("levels", {}).get(L)
+            if lv is None:
+                lv = ws["levels"][L] = dict(tokens=torch.empty(L * slab, dtype=torch.float32, device=x.device),
+                                            index=torch.empty(L * B * P0, dtype=torch.int32, device=x.device), feat={})
+            dense_feat = lv["feat"].get(dense[1])
+            if dense_feat is None:
+                dense_feat = lv["feat"][dense[1]] = torch.empty(L * B * P0 * self.embed_dim, dtype=dense[1], device=x.device)
+            level_arg = _lib.TrVitLevels(sum(1 << b for b in levels), int(dense[4]), lv["tokens"].data_ptr(), lv["tokens"].numel())
+            level_blocks = (C.c_int32 * L)(*levels)
+        elif dense is not None:
             # static per workspace slot: the index [B, P0] and one feature map per output dtype (either layout is B * P0 * D elements)
             P0 = self.patch_embed.num_patches
             if ws.get("dense_index") is None:
@@ -941,7 +999,9 @@ class VisionTransformer(nn.Module):
             rest = (out.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
                     None if soft is None else soft.data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
                     torch.cuda.current_stream().cuda_stream)
-            if tap_arg is not None and fmt == _lib.TR_INPUT_F32:
+            if levels is not None:
+                rc = lib.tr_vit_forward_levels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest, None, C.byref(level_arg))
+            elif tap_arg is not None and fmt == _lib.TR_INPUT_F32:
                 rc = lib.tr_vit_forward_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest, C.byref(tap_arg))
             elif tap_arg is not None:
                 rc = lib.tr_vit_forward_pixels_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest, C.byref(tap_arg))
@@ -955,7 +1015,19 @@ class VisionTransformer(nn.Module):
                 rc = lib.tr_stage_decisions(ws["kept"].data_ptr(), ws["compl"].data_ptr(), ws["kept"].numel(), *dec["args"][0], dec["table"],
                                             dec["n"], B, self.patch_embed.num_patches + 1, *dec["args"][1], torch.cuda.current_stream().cuda_stream)
                 _lib.check(rc, "tr_stage_decisions")
-            if dense is not None:
+            if levels is not None:
+                # every level's prefix of the decisions composed, then every level's un-reduce: two launches in the same stream (and graph)
+                stream = torch.cuda.current_stream().cuda_stream
+                level_rows = (C.c_int32 * L)(*[tokens[b] for b in levels])
+                kept_out, kept_n, _, assign_out, assign_n = dec["args"][1]
+                rc = lib.tr_dense_index_levels(kept_out, kept_n, assign_out, assign_n, dec["table"], dec["n"], B, P0, level_blocks, level_rows, L,
+                                               lv["index"].data_ptr(), stream)
+                _lib.check(rc, "tr_dense_index_levels")
+                rc = lib.tr_dense_gather_levels(lv["tokens"].data_ptr(), slab, level_rows, L, lv["index"].data_ptr(), dense_feat.data_ptr(),
+                                                _lib.TR_LAYOUT_NCHW if dense[0] == "NCHW" else _lib.TR_LAYOUT_NHWC,
+                                                int(dense[1] == torch.bfloat16), dense[2], B, P0, self.embed_dim, stream)
+                _lib.check(rc, "tr_dense_gather_levels")
+            elif dense is not None:
                 # the decisions composed into one row per grid patch, then the un-reduce: two launches in the same stream (and graph)
                 stream, n_last = torch.cuda.current_stream().cuda_stream, tokens[self.depth - 1]
                 kept_out, kept_n, _, assign_out, assign_n = dec["args"][1]
@@ -985,6 +1057,14 @@ class VisionTransformer(nn.Module):
                 self._decision_result(dec, B, list(tokens))     # (the stage table against the executor's token counts, once per workspace)
             h, w = self.patch_embed.grid_size
             feat = dense_feat.clone()
+            if levels is not None:
+                D, n0 = self.embed_dim, self.patch_embed.num_patches + 1
+                feat = feat.view(L, B, D, h, w) if dense[0] == "NCHW" else feat.view(L, B, h, w, D)
+                index = lv["index"].clone().view(L, B, h * w)
+                # row 0 of every level's [B, N_l, D] rows: a strided copy out of the static slabs
+                cls = torch.stack([lv["tokens"][l * slab: l * slab + B * tokens[b] * D].view(B, tokens[b], D)[:, 0] for l, b in enumerate(levels)], dim=1)
+                return logits, {"features": [feat[l] for l in range(L)], "index": [index[l] for l in range(L)], "blocks": levels, "grid": (h, w),
+                                "cls": cls}
             return logits, {"features": feat.view(B, self.embed_dim, h, w) if dense[0] == "NCHW" else feat.view(B, h, w, self.embed_dim),
                             "index": ws["dense_index"].clone().view(B, h * w), "grid": (h, w)}
         if taps is not None:

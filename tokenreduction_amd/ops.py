@@ -630,6 +630,66 @@ def dense_gather(tokens: torch.Tensor, index: torch.Tensor, layout: str = "NCHW"
     return out.view(shape)
 
 
+def _level_array(values, what):
+    vals = [int(v) for v in values]
+    if not 1 <= len(vals) <= _lib.TR_MAX_DEPTH:
+        raise ValueError(f"{what}: {len(vals)} levels (1 ... {_lib.TR_MAX_DEPTH})")
+    return (ctypes.c_int32 * len(vals))(*vals)
+
+
+def dense_index_levels(kept: torch.Tensor, assign: torch.Tensor, stages, B: int, P0: int, level_blocks, level_rows, table=None,
+                       out: torch.Tensor = None) -> torch.Tensor:
+    """index int32 [L, B, P0]: per level l -- the stream after block level_blocks[l], level_rows[l] tokens with the CLS token -- the row
+    (1 ... level_rows[l]-1) that stands for grid patch p, -1 where none does (tr_dense_index_levels, one launch for all levels).  Level l sits
+    behind the stages with block <= level_blocks[l]; a level in front of every stage is the identity.  kept / assign / stages / table as
+    dense_index; level_blocks strictly ascending."""
+    _same_device(kept, assign, out)
+    if len(level_blocks) != len(level_rows):
+        raise ValueError(f"{len(level_blocks)} level blocks, {len(level_rows)} level rows")
+    blocks, rows = _level_array(level_blocks, "level_blocks"), _level_array(level_rows, "level_rows")
+    L = len(blocks)
+    if table is None:
+        table = decision_table(stages, B)[0]
+    if out is None:
+        dev = next((t.device for t in (kept, assign) if t is not None), torch.device("cuda", torch.cuda.current_device()))
+        out = torch.empty(L, B, P0, dtype=torch.int32, device=dev)
+    elif out.numel() != L * B * P0:
+        raise ValueError(f"out must hold {L * B * P0} elements, got {out.numel()}")
+    _lib.check(_lib.load().tr_dense_index_levels(_opt(kept, torch.int32, "kept"), 0 if kept is None else kept.numel(),
+                                                 _opt(assign, torch.int32, "assign"), 0 if assign is None else assign.numel(), table, len(stages),
+                                                 B, P0, blocks, rows, L, _dev(out, torch.int32, "out"), _stream(out)), "tr_dense_index_levels")
+    return out.view(L, B, P0)
+
+
+def dense_gather_levels(tokens: torch.Tensor, level_stride: int, level_rows, index: torch.Tensor, D: int, layout: str = "NCHW",
+                        dtype=torch.float32, fill: float = 0.0, out: torch.Tensor = None) -> torch.Tensor:
+    """features[l][b, :, p] = the row index[l, b, p] of level l's tokens where 0 <= index < level_rows[l], `fill` elsewhere
+    (tr_dense_gather_levels, one launch for all levels): tokens fp32, flat, level l's rows [B, level_rows[l], D] at l * level_stride; index
+    int32 [L, B, P]; the result is [L, B, D, P] (layout "NCHW") or [L, B, P, D] ("NHWC"), fp32 or bf16.  Per level the bits of dense_gather."""
+    _same_device(tokens, index, out)
+    if layout not in DENSE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(DENSE_LAYOUTS)}, got {layout!r}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    rows = _level_array(level_rows, "level_rows")
+    L = len(rows)
+    if index.dim() != 3 or index.shape[0] != L:
+        raise ValueError(f"index must be [L, B, P] with L = {L}, got {tuple(index.shape)}")
+    _, B, P = index.shape
+    need = max(l * level_stride + B * rows[l] * D for l in range(L))
+    if tokens.numel() < need:
+        raise ValueError(f"tokens holds {tokens.numel()} elements, {L} levels at stride {level_stride} need {need}")
+    shape = (L, B, D, P) if layout == "NCHW" else (L, B, P, D)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=tokens.device)
+    elif out.numel() != L * B * D * P:
+        raise ValueError(f"out must hold {L * B * D * P} elements, got {out.numel()}")
+    _lib.check(_lib.load().tr_dense_gather_levels(_dev(tokens, torch.float32, "tokens"), level_stride, rows, L, _dev(index, torch.int32, "index"),
+                                                  _dev(out, dtype, "out"), DENSE_LAYOUTS[layout], int(dtype == torch.bfloat16), float(fill), B, P, D,
+                                                  _stream(tokens)), "tr_dense_gather_levels")
+    return out.view(shape)
+
+
 def attention_f32(qkv: torch.Tensor, B: int, N: int, H: int, want_cls: bool = False, size: torch.Tensor = None,
                   colsum_part: torch.Tensor = None, split: bool = False):
     out = torch.empty(B * N, H * 64, dtype=torch.float32, device=qkv.device)
