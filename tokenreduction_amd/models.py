@@ -41,7 +41,7 @@ import copy
 import ctypes as C
 import warnings
 from functools import partial
-from typing import List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -151,6 +151,43 @@ def _pad8(n):
 def _pad64(n):
     """Widths the bf16 GEMMs reduce over (K-step 64): hidden layers of the reduction modules, leading dimensions of their transposed copies."""
     return (n + 63) // 64 * 64
+
+
+class Op(NamedTuple):
+    """One operand of the executor's weight structs (tr_vit_weights / tr_block_weights / tr_stage_weights): THE declaration the pack (W), the
+    gradient pointers (G), the gradient slot sizes and the transposed dgrad operands (WT) are all derived from.  Trunk and block rows come in
+    pairs, the two gradients one launch of the backward produces (a unit)."""
+    field: str                          # member of the struct
+    name: Optional[str] = None          # the parameter behind it, relative to the model / "blocks.i." / the stage's module; None: no parameter
+    kind: str = "f32"                   # "f32": fp32 as it is | "w": matrix in the operand type | "wt": ... with a transposed bf16 copy made by
+                                        # the packer | "grad": no operand, the field takes the parameter's gradient only | "f32_row0": fp32 table
+                                        # of `rows` rows in a buffer of its own, born zeros: row 0 stays zero, the parameter is rows 1 ..
+    rows: int = 0                       # the operand is a zero-padded copy with this many rows / columns (0: the value's own)
+    cols: int = 0
+    grad_rows: int = 0                  # rows of the gradient the kernels write: the parameter's slot in the flat buffer (0: the parameter's own)
+    t_rows: Optional[int] = None        # stage rows: the dgrad operand is the transposed bf16 copy of the value padded to this many rows, its
+                                        # leading dimension (0: the operand's rows; None: no such copy)
+    value: Optional[Callable] = None    # value() -> fp32 tensor, for an operand that is not the parameter as it stands
+    gamma: Optional[str] = None         # block rows: the LayerScale gamma folded into this Linear when the model has one
+    grad: bool = True                   # the field of the gradient struct points at the parameter's slot
+
+
+def _unit(field, path, kind="f32", gamma=None):
+    """The two rows of a LayerNorm ("f32": <field>_g, <field>_b) or a Linear (<field>_w, <field>_b) at module `path`."""
+    return Op(field + ("_g" if kind == "f32" else "_w"), path + ".weight", kind, gamma=gamma), Op(field + "_b", path + ".bias")
+
+
+# tr_block_weights: the six units of a block, names relative to "blocks.i." (mlp_pk, the fragment-major Mlp buffer, derives from fc1 / fc2)
+_BLOCK_UNITS = (_unit("ln1", "norm1"), _unit("qkv", "attn.qkv", "wt"), _unit("proj", "attn.proj", "wt", "ls1.gamma"),
+                _unit("ln2", "norm2"), _unit("fc1", "mlp.fc1", "wt"), _unit("fc2", "mlp.fc2", "wt", "ls2.gamma"))
+
+
+def _padded(t, rows=0, cols=0):
+    """Detached fp32 copy of a vector [n] / matrix [r, c] with zeros appended up to `rows` (and `cols`); 0 keeps the size."""
+    shape = (rows or t.shape[0],) + ((cols or t.shape[1],) if t.dim() > 1 else ())
+    out = torch.zeros(shape, dtype=torch.float32, device=t.device)
+    out[tuple(slice(n) for n in t.shape)] = t.detach()
+    return out
 
 
 def _expand_schedule(values, locs, expand, what):
@@ -345,6 +382,8 @@ class VisionTransformer(nn.Module):
         self._pack_table = None          # device-side item table of the fused cast launch (_run_fused_pack)
         self._pack_all_fused = False     # that table covers every bf16 operand (optim.FusedAdamW may then refresh them itself)
         self._ls_fold = None             # LayerScale: dict(sig, items, shapes, n, f32) -- the item table of tr_layerscale_fold (_run_layerscale_fold)
+        self._grad_rows = None           # {parameter name: rows of its gradient slot} where the declaration pads them (_grad_slot_numel)
+        self._stage_t = {}               # {(block, field): transposed bf16 dgrad operand of a reduction stage} (_pack_stages)
         self._pos_table = None           # no_embed_class: the executor's [(P + 1), D] position table (row 0 zeros), a _Packer slot
         self._mlp_pack_items = None      # ([(fc1_w, fc2_w, fc2_b, pack buffer)], D, Hd) of _refresh_mlp_pack
         self._mlp_pk_stale = False       # the fragment-major Mlp copies are older than the bf16 copies
@@ -415,6 +454,7 @@ class VisionTransformer(nn.Module):
         self.head = (nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()).to(dev)
         self._packed = None
         self._tstate = None          # the flat gradient buffer is laid out for the old head
+        self._grad_rows = None
 
     def _pool_mode(self):
         """tr_vit_config.global_pool of this model (ValueError for a value written into the attribute that is none of '', 'token', 'avg')."""
@@ -472,7 +512,9 @@ class VisionTransformer(nn.Module):
     def _pack(self, need_transposed=False):
         """bf16 (or fp32) operand copies of every parameter the executor reads + the C structs.  The copies live in PERSISTENT buffers:
         a repack after an optimizer step rewrites them in place -- one fused launch for all matrices (tr_cast_pack_bf16), transposed
-        copies for the data-gradient GEMMs included once training asked for them -- so addresses, workspaces and captured graphs survive."""
+        copies for the data-gradient GEMMs included once training asked for them -- so addresses, workspaces and captured graphs survive.
+        Which parameter goes into which member, in which type and padding, is read off the operand rows (Op: _trunk_units, _BLOCK_UNITS and
+        the families' _stage_operands); a slot's identity is the index of its packer call, so the rows' order must not depend on values."""
         if self.precision not in ("bf16", "fp32", "bf16x3"):
             raise ValueError("precision must be 'bf16', 'bf16x3' or 'fp32'")
         self._pre_pack()
@@ -497,51 +539,28 @@ class VisionTransformer(nn.Module):
         lib = _lib.load()
         mlp_pk_bytes = int(lib.tr_mlp_pack_bytes(D, Hd)) if lib.tr_mlp_fused_supported(D, Hd) else 0
         mlp_items = []
-        W.patch_w, tpatch = pk.w16(self.patch_embed.proj.weight.reshape(D, -1), True)      # (tpatch: the input gradient's operand, training.py)
-        W.patch_b = pk.f32(self.patch_embed.proj.bias)
-        W.cls_token = pk.f32(self.cls_token.reshape(-1))
-        if self.no_embed_class:
-            # the executor adds a [(P + 1), D] table to [cls; patches]: row 0 zeros (cls + 0 = cls), rows 1 .. P the parameter.  A slot of its
-            # own (born zeros), rewritten here and by _refresh_derived_operands
-            self._pos_table = pk.buffer("pe", (self.patch_embed.num_patches + 1, D), torch.float32)
-            self._pos_table[1:].copy_(self.pos_embed.detach()[0])
-            W.pos_embed = self._pos_table.data_ptr()
-        else:
-            self._pos_table = None
-            W.pos_embed = pk.f32(self.pos_embed.reshape(-1, D))
-        W.norm_g, W.norm_b = pk.f32(self.norm.weight), pk.f32(self.norm.bias)
-        cpad = self._classes_padded
-        if not headless:             # headless: no classifier operands (tr_vit_weights.head_* stay NULL)
-            W.head_w = pk.w16(self.head.weight if cpad == self.num_classes else _pad_rows(self.head.weight, cpad))
-            W.head_b = pk.f32(self.head.bias if cpad == self.num_classes else _pad_vec(self.head.bias, cpad))
+        named = dict(self.named_parameters())
+        self._pos_table = None
+        tpatch = None
+        for u in self._trunk_units():
+            t = self._pack_unit(pk, W, named, "", u)
+            if u[0].field == "patch_w":      # (its transposed copy: the input gradient's operand, training.py)
+                tpatch = t
         tblocks = []
-        for i, blk in enumerate(self.blocks):
+        for i in range(self.depth):
             b = W.blocks[i]
-            b.ln1_g, b.ln1_b = pk.f32(blk.norm1.weight), pk.f32(blk.norm1.bias)
-            (b.qkv_w, tq), b.qkv_b = pk.w16(blk.attn.qkv.weight, True), pk.f32(blk.attn.qkv.bias)
-            ls = hasattr(blk, "ls1")     # LayerScale: proj and fc2 reach the executor with gamma folded in (csrc/tr_layerscale.hip)
-            if ls:
-                b.proj_w, tp_, b.proj_b = pk.folded(blk.attn.proj.weight, blk.attn.proj.bias, blk.ls1.gamma)
-            else:
-                (b.proj_w, tp_), b.proj_b = pk.w16(blk.attn.proj.weight, True), pk.f32(blk.attn.proj.bias)
-            b.ln2_g, b.ln2_b = pk.f32(blk.norm2.weight), pk.f32(blk.norm2.bias)
-            (b.fc1_w, t1), b.fc1_b = pk.w16(blk.mlp.fc1.weight, True), pk.f32(blk.mlp.fc1.bias)
-            if ls:
-                b.fc2_w, t2, b.fc2_b = pk.folded(blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.ls2.gamma)
-            else:
-                (b.fc2_w, t2), b.fc2_b = pk.w16(blk.mlp.fc2.weight, True), pk.f32(blk.mlp.fc2.bias)
-            tblocks.append((tq, tp_, t1, t2))
+            ts = [self._pack_unit(pk, b, named, f"blocks.{i}.", u) for u in _BLOCK_UNITS]
+            tblocks.append(tuple(t for (a, _), t in zip(_BLOCK_UNITS, ts) if a.kind == "wt"))
             if wdt == torch.bfloat16 and mlp_pk_bytes:
                 # the fragment-major copy of the two Mlp matrices the fused eval Mlp kernel streams (csrc/tr_mlp_fused.hip), refreshed below /
                 # by _refresh_mlp_pack() whenever the bf16 copies were rewritten
                 pkb = pk.buffer("p", (mlp_pk_bytes,), torch.uint8)
                 b.mlp_pk = pkb.data_ptr()
                 mlp_items.append((b.fc1_w, b.fc2_w, b.fc2_b, pkb))
-        self._pack_stages(W, pk)
+        stages = self._pack_stages(W, pk, named)
         # may an optimizer that rewrites the fused table's copies itself declare the operands fresh?  Only if that table is all there is:
-        # no copied operand, and no reduction module whose transposed matrices training.TrainState keys on the pack generation
-        self._pack_all_fused = (not pk.copied and wdt == torch.bfloat16
-                                and type(self)._transposed_stage_weights is VisionTransformer._transposed_stage_weights)
+        # no copied operand, and no reduction stage whose dgrad operand is made here, at every repack
+        self._pack_all_fused = not pk.copied and wdt == torch.bfloat16 and not self._stages_transposed(stages)
         if pk.fused:
             self._run_fused_pack(pk.fused, dev)
         if pk.folds:                 # before the fragment-major Mlp copies, which derive from the folded fc2 operand
@@ -642,34 +661,110 @@ class VisionTransformer(nn.Module):
         if self._pos_table is not None:
             self._pos_table[1:].copy_(self.pos_embed.detach()[0])
 
-    def _pack_stages(self, W, pk):
-        """Families with learned reduction modules fill W.stage[blk] (tr_stage_weights) here."""
+    # ---- the operand declaration: rows (Op) -> W, G, WT and the gradient slot sizes -------------------------------
+    def _trunk_units(self):
+        """tr_vit_weights: the trunk's units.  The classifier's rows are padded to a multiple of 8; a no_embed_class model's position operand
+        and gradient are [(P + 1), D] tables (row 0: zeros / scratch); a headless model has no classifier unit."""
+        P, cpad = self.patch_embed.num_patches, self._classes_padded
+        pad = cpad if cpad != self.num_classes else 0
+        pos = dict(kind="f32_row0", rows=P + 1, grad_rows=P + 1) if self.no_embed_class else {}
+        units = [(Op("patch_w", "patch_embed.proj.weight", "wt"), Op("patch_b", "patch_embed.proj.bias")),
+                 (Op("cls_token", "cls_token"), Op("pos_embed", "pos_embed", **pos)),
+                 (Op("norm_g", "norm.weight"), Op("norm_b", "norm.bias"))]
+        if isinstance(self.head, nn.Linear):
+            units.append((Op("head_w", "head.weight", "w", rows=pad, grad_rows=cpad), Op("head_b", "head.bias", rows=pad, grad_rows=cpad)))
+        return units
+
+    def _stage_operands(self, j, loc):
+        """(name prefix of the stage's module, rows, scalar members) of tr_stage_weights for reduction stage j at block loc: what a family
+        with operands of its own declares.  A scalar may be a callable, read when the operands are packed."""
+        return "", (), {}
+
+    def _stages(self):
+        """{block: _stage_operands} of every reduction stage."""
+        return {loc: self._stage_operands(j, loc) for j, loc in enumerate(self.get_reduction_count())}
+
+    def _operand_rows(self, blocks=True):
+        """Every row of the declaration as (struct, parameter name or None, row); struct: "trunk", ("blocks", i) or ("stage", block)."""
+        for u in self._trunk_units():
+            for r in u:
+                yield "trunk", r.name, r
+        for i in range(self.depth if blocks else 0):
+            for u in _BLOCK_UNITS:
+                for r in u:
+                    yield ("blocks", i), f"blocks.{i}.{r.name}", r
+        for loc, (pre, rows, _) in self._stages().items():
+            for r in rows:
+                yield ("stage", loc), r.name and pre + r.name, r
+
+    def _stages_transposed(self, stages=None):
+        """A reduction stage has a dgrad operand of its own (_pack_stages makes them: not something an optimizer's table refreshes)."""
+        return any(r.t_rows is not None for _, rows, _ in (stages or self._stages()).values() for r in rows)
+
+    def _pack_row(self, pk, row, src):
+        """One operand through the packer: (address, slot of the packer's transposed copy or None)."""
+        if row.kind == "f32_row0":
+            # no_embed_class: the executor adds a [(P + 1), D] table to [cls; patches]: row 0 zeros (cls + 0 = cls), rows 1 .. P the parameter.  A slot of its
+            # own (born zeros), rewritten here and by _refresh_derived_operands
+            self._pos_table = pk.buffer("pe", (row.rows, src.shape[-1]), torch.float32)
+            self._pos_table[1:].copy_(src.detach()[0])
+            return self._pos_table.data_ptr(), None
+        if src.dim() > 2:               # the convolution's weight as [D, C*p*p]; cls_token / pos_embed as rows of D
+            src = src.reshape(-1, src.shape[-1]) if row.kind == "f32" else src.reshape(src.shape[0], -1)
+        if row.rows or row.cols:
+            src = _padded(src, row.rows, row.cols)
+        if row.kind == "f32":
+            return pk.f32(src), None
+        return pk.w16(src, True) if row.kind == "wt" else (pk.w16(src), None)
+
+    def _pack_unit(self, pk, S, named, pre, unit):
+        """The two operands of a trunk / block unit into struct S; returns the slot of the matrix's transposed copy (or None).  LayerScale: proj and
+        fc2 reach the executor with gamma folded in (csrc/tr_layerscale.hip)."""
+        a, b = unit
+        if a.gamma and pre + a.gamma in named:
+            wa, t, wb = pk.folded(named[pre + a.name], named[pre + b.name], named[pre + a.gamma])
+        else:
+            (wa, t), (wb, _) = self._pack_row(pk, a, named[pre + a.name]), self._pack_row(pk, b, named[pre + b.name])
+        setattr(S, a.field, wa)
+        setattr(S, b.field, wb)
+        return t
+
+    def _pack_stages(self, W, pk, named=None):
+        """The reduction stages' operands and scalar members (W.stage[block]) from the families' rows -- and, once training asked for transposed
+        copies, the stages' dgrad operands from the same values (self._stage_t: training.TrainState.transposed points WT at them and keeps
+        them alive).  Returns the stages' declaration it went through."""
+        named = named or dict(self.named_parameters())
+        self._stage_t = {}
+        stages = self._stages()
+        for loc, (pre, rows, scalars) in stages.items():
+            st = W.stage[loc]
+            for k, v in scalars.items():
+                setattr(st, k, v() if callable(v) else v)
+            for row in rows:
+                if row.kind == "grad":
+                    continue
+                src = row.value() if row.value else named[pre + row.name]
+                setattr(st, row.field, self._pack_row(pk, row, src)[0])
+                if row.t_rows is not None and pk.want_t:
+                    self._stage_t[loc, row.field] = _padded(src, row.t_rows or row.rows, row.cols).t().to(torch.bfloat16).contiguous()
+        return stages
+
+    def _grad_slot_numel(self, name, p):
+        """fp32 elements reserved for parameter `name` in the flat gradient buffer (>= p.numel(): the rows its declaration pads the gradient to)."""
+        if self._grad_rows is None:
+            self._grad_rows = {n: r.grad_rows for _, n, r in self._operand_rows(blocks=False) if r.grad_rows}
+        rows = self._grad_rows.get(name)
+        return rows * (p.shape[-1] if p.dim() > 1 else 1) if rows else p.numel()
 
     def _noise_ptr(self, B, dev):
         """Device pointer of the per-stage random inputs (DPC-KNN density noise), None for deterministic families."""
         return None
-
-    def _grad_stage_ptrs(self, G, ptr):
-        """Families with learned reduction modules point G.stage[blk] (tr_stage_weights layout) at their gradient views."""
-
-    def _grad_slot_numel(self, name, p):
-        """fp32 elements reserved for parameter `name` in the flat gradient buffer (>= p.numel(): matrices whose rows the kernels pad)."""
-        if name == "head.weight":
-            return self._classes_padded * p.shape[1]
-        if name == "head.bias":
-            return self._classes_padded
-        if name == "pos_embed" and self.no_embed_class:
-            return p.numel() + self.embed_dim         # the executor writes a [(P + 1), D] gradient: row 0 is scratch, the parameter's view rows 1 .. P
-        return p.numel()
 
     def _pre_pack(self):
         """Parameter maintenance the reference does inside forward() (Sinkhorn re-normalises its centres in place)."""
 
     def _per_forward_config(self, cfg):
         """Host-side random draws of a forward that the executor takes as inputs (K-Medoids equal_weight)."""
-
-    def _transposed_stage_weights(self, WT, t16):
-        """Families whose reduction modules have a backward: transposed bf16 copies of their matrices (dgrad operands)."""
 
     def _soft_elems(self, B):
         """fp32 elements of the soft-assignment output (SiT), 0 for families without one."""
@@ -1396,22 +1491,15 @@ class ToMeVisionTransformer(VisionTransformer):
 
 
 def _pad_rows(w, rows):
-    """[r, c] -> [rows, c] with zero rows appended (detached fp32 copy)."""
-    out = torch.zeros(rows, w.shape[1], dtype=torch.float32, device=w.device)
-    out[:w.shape[0]] = w.detach()
-    return out
+    return _padded(w, rows)
 
 
 def _pad_cols(w, cols):
-    out = torch.zeros(w.shape[0], cols, dtype=torch.float32, device=w.device)
-    out[:, :w.shape[1]] = w.detach()
-    return out
+    return _padded(w, 0, cols)
 
 
 def _pad_vec(b, n):
-    out = torch.zeros(n, dtype=torch.float32, device=b.device)
-    out[:b.shape[0]] = b.detach()
-    return out
+    return _padded(b, n)
 
 
 def _ln_default(dim):
@@ -1475,23 +1563,6 @@ class DynamicVisionTransformer(VisionTransformer):
             buf.exponential_().log_().neg_()          # F.gumbel_softmax: -empty_like(logits).exponential_().log()
         return buf.data_ptr()
 
-    def _grad_stage_ptrs(self, G, ptr):
-        for j, loc in enumerate(self.pruning_loc):
-            g, pre = G.stage[loc], f"score_predictor.{j}."
-            g.ln_g, g.ln_b = ptr(pre + "in_conv.0.weight"), ptr(pre + "in_conv.0.bias")
-            g.w0, g.b0 = ptr(pre + "in_conv.1.weight"), ptr(pre + "in_conv.1.bias")
-            g.w1, g.b1 = ptr(pre + "out_conv.0.weight"), ptr(pre + "out_conv.0.bias")
-            g.w2, g.b2 = ptr(pre + "out_conv.2.weight"), ptr(pre + "out_conv.2.bias")
-            g.w3, g.b3 = ptr(pre + "out_conv.4.weight"), ptr(pre + "out_conv.4.bias")
-
-    def _transposed_stage_weights(self, WT, t16):
-        hh, qq = self._hidden_pad()
-        for j, loc in enumerate(self.pruning_loc):
-            sp, st = self.score_predictor[j], WT.stage[loc]
-            st.w0 = t16(sp.in_conv[1].weight)                                              # [D, D]^T
-            st.w1 = t16(_pad_rows(sp.out_conv[0].weight, hh))                              # [Hh, D]^T -> [D, Hh]
-            st.w2 = t16(_pad_rows(_pad_cols(sp.out_conv[2].weight, hh), qq))               # [Q, Hh]^T -> [Hh, Q]
-
     def get_reduction_count(self):
         return self.pruning_loc
 
@@ -1500,17 +1571,14 @@ class DynamicVisionTransformer(VisionTransformer):
         (DeiT-T: 96 -> 128); the training path's GEMMs reduce over the D/4 rows too."""
         return _pad64(self.embed_dim // 2), _pad64(self.embed_dim // 4)
 
-    def _pack_stages(self, W, pk):
-        hh, qq = self._hidden_pad()
-        for j, loc in enumerate(self.pruning_loc):
-            sp, st = self.score_predictor[j], W.stage[loc]
-            st.ln_g, st.ln_b = pk.f32(sp.in_conv[0].weight), pk.f32(sp.in_conv[0].bias)
-            st.w0, st.b0 = pk.w16(sp.in_conv[1].weight), pk.f32(sp.in_conv[1].bias)
-            st.w1, st.b1 = pk.w16(_pad_rows(sp.out_conv[0].weight, hh)), pk.f32(_pad_vec(sp.out_conv[0].bias, hh))
-            st.w2, st.b2 = pk.w16(_pad_rows(_pad_cols(sp.out_conv[2].weight, hh), qq)), pk.f32(_pad_vec(sp.out_conv[2].bias, qq))
-            st.h_pad = hh
-            st.reserved_ = qq
-            st.w3, st.b3 = pk.f32(sp.out_conv[4].weight), pk.f32(sp.out_conv[4].bias)
+    def _stage_operands(self, j, loc):
+        hh, qq = self._hidden_pad()      # (w0 .. w2 have a backward: transposed copies of the operands as padded)
+        rows = (Op("ln_g", "in_conv.0.weight"), Op("ln_b", "in_conv.0.bias"),
+                Op("w0", "in_conv.1.weight", "w", t_rows=0), Op("b0", "in_conv.1.bias"),
+                Op("w1", "out_conv.0.weight", "w", rows=hh, t_rows=0), Op("b1", "out_conv.0.bias", rows=hh),
+                Op("w2", "out_conv.2.weight", "w", rows=qq, cols=hh, t_rows=0), Op("b2", "out_conv.2.bias", rows=qq),
+                Op("w3", "out_conv.4.weight"), Op("b3", "out_conv.4.bias"))
+        return f"score_predictor.{j}.", rows, dict(h_pad=hh, reserved_=qq)
 
     def _viz_data(self, ws, B, tokens):
         kept = ws["kept"].cpu().numpy()
@@ -1599,50 +1667,20 @@ class SelfSlimmedVisionTransformer(_ClusterBase):
     def _make_cluster_layer(self, count):
         return TokenSlimmingModule(self.embed_dim, count)
 
-    def _pack_stages(self, W, pk):
-        for j, loc in enumerate(self.cluster_loc):
-            m, st = self.cluster_layers[j], W.stage[loc]
-            K = self.cluster_count[j]
-            n_pad = self._soft_pad(K)[0]
-            w1 = torch.zeros(n_pad, m.weight[3].in_features, dtype=torch.float32, device=m.weight[3].weight.device)
-            w1[:K] = m.weight[3].weight.detach()
-            b1 = torch.zeros(n_pad, dtype=torch.float32, device=w1.device)
-            b1[:K] = m.weight[3].bias.detach()
-            st.ln_g, st.ln_b = pk.f32(m.weight[0].weight), pk.f32(m.weight[0].bias)
-            hh = _pad64(m.weight[1].out_features)     # hidden width padded with zero weights (DeiT-T: 96 -> 128)
-            st.w0, st.b0 = pk.w16(_pad_rows(m.weight[1].weight, hh)), pk.f32(_pad_vec(m.weight[1].bias, hh))
-            st.w1, st.b1 = pk.w16(_pad_cols(w1, hh)), pk.f32(b1)
-            st.scale = float(m.scale.detach().reshape(-1)[0])
-            st.n_pad = n_pad
-            st.h_pad = hh
+    def _stage_operands(self, j, loc):
+        m = self.cluster_layers[j]
+        n_pad, ld = self._soft_pad(self.cluster_count[j])
+        hh = _pad64(m.weight[1].out_features)     # hidden width padded with zero weights (DeiT-T: 96 -> 128)
+        rows = (Op("ln_g", "weight.0.weight"), Op("ln_b", "weight.0.bias"),
+                Op("w0", "weight.1.weight", "w", rows=hh, t_rows=0), Op("b0", "weight.1.bias", rows=hh),
+                # the last Linear's rows are padded to a multiple of 8 by the weight-gradient kernel too (rows >= K receive zeros)
+                Op("w1", "weight.3.weight", "w", rows=n_pad, cols=hh, grad_rows=n_pad, t_rows=ld), Op("b1", "weight.3.bias", rows=n_pad, grad_rows=n_pad),
+                Op("b2", "scale", "grad"))       # the operand is the scalar member; d scale (sit.py:34), fp32[1], lands in b2
+        return f"cluster_layers.{j}.", rows, dict(scale=lambda: float(m.scale.detach().reshape(-1)[0]), n_pad=n_pad, h_pad=hh)
 
     def _soft_pad(self, K):
         """(rows, leading dimension of the transposed copy) of a soft-assignment matrix with K outputs, as the kernels pad them."""
         return _pad8(K), _pad64(K)
-
-    def _grad_slot_numel(self, name, p):
-        # the last Linear's rows are padded to a multiple of 8 by the weight-gradient kernel (rows >= K receive zeros)
-        for j, K in enumerate(self.cluster_count):
-            if name == f"cluster_layers.{j}.weight.3.weight":
-                return self._soft_pad(K)[0] * p.shape[1]
-            if name == f"cluster_layers.{j}.weight.3.bias":
-                return self._soft_pad(K)[0]
-        return super()._grad_slot_numel(name, p)
-
-    def _grad_stage_ptrs(self, G, ptr):
-        for j, loc in enumerate(self.cluster_loc):
-            g, pre = G.stage[loc], f"cluster_layers.{j}."
-            g.ln_g, g.ln_b = ptr(pre + "weight.0.weight"), ptr(pre + "weight.0.bias")
-            g.w0, g.b0 = ptr(pre + "weight.1.weight"), ptr(pre + "weight.1.bias")
-            g.w1, g.b1 = ptr(pre + "weight.3.weight"), ptr(pre + "weight.3.bias")
-            g.b2 = ptr(pre + "scale")                                    # d scale (sit.py:34), fp32[1]
-
-    def _transposed_stage_weights(self, WT, t16):
-        for j, loc in enumerate(self.cluster_loc):
-            m, st = self.cluster_layers[j], WT.stage[loc]
-            hh = _pad64(m.weight[1].out_features)                                     # hidden width as packed (DeiT-T: 96 -> 128)
-            st.w0 = t16(_pad_rows(m.weight[1].weight, hh))                            # [Hh, D]^T
-            st.w1 = t16(_pad_rows(_pad_cols(m.weight[3].weight, hh), self._soft_pad(self.cluster_count[j])[1]))   # [K -> ld64, Hh]^T
 
     def _soft_elems(self, B):
         return sum(B * K * P for _, K, P in self._stage_shapes())
@@ -1688,18 +1726,10 @@ class DPCKNNVisionTransformer(_ClusterBase):
     def _make_cluster_layer(self, count):
         return CTM(self.embed_dim, count, self.k_neighbors, self.equal_weight)
 
-    def _pack_stages(self, W, pk):
-        if self.equal_weight:
-            return
-        for j, loc in enumerate(self.cluster_loc):
-            st = W.stage[loc]
-            st.w3, st.b3 = pk.f32(self.cluster_layers[j].score.weight), pk.f32(self.cluster_layers[j].score.bias)
-
-    def _grad_stage_ptrs(self, G, ptr):
-        if self.equal_weight:
-            return
-        for j, loc in enumerate(self.cluster_loc):
-            G.stage[loc].w3, G.stage[loc].b3 = ptr(f"cluster_layers.{j}.score.weight"), ptr(f"cluster_layers.{j}.score.bias")
+    def _stage_operands(self, j, loc):
+        if self.equal_weight:            # (no score layer: CTM registers none)
+            return "", (), {}
+        return f"cluster_layers.{j}.", (Op("w3", "score.weight"), Op("b3", "score.bias")), {}
 
     def _noise_ptr(self, B, dev):
         shapes = self._stage_shapes()
@@ -1759,12 +1789,9 @@ class ATSVisionTransformer(VisionTransformer):
         """ats.py:48, verbatim."""
         return torch.arange(1 / (2 * sample_count), (2 * sample_count - 1) / (2 * sample_count), 2 / (2 * sample_count))
 
-    def _pack_stages(self, W, pk):
-        for blk, K in enumerate(self.sample_count):
-            if K:
-                steps = self.sample_steps(K).to(self.pos_embed.device)
-                W.stage[blk].w3 = pk.f32(steps)
-                W.stage[blk].n_pad = steps.numel()
+    def _stage_operands(self, j, loc):
+        steps = lambda: self.sample_steps(self.sample_count[loc]).to(self.pos_embed.device)
+        return "", (Op("w3", value=steps, grad=False),), dict(n_pad=self._keep[loc] - 1)       # (_keep: one token per grid point + CLS)
 
     def _decision_stages(self):
         out, n = [], self.patch_embed.num_patches + 1
@@ -1815,30 +1842,13 @@ class SinkhornVisionTransformer(SelfSlimmedVisionTransformer):
                 for m in self.cluster_layers:
                     m.v.copy_(torch.nn.functional.normalize(m.v, p=2, dim=-1))
 
-    def _grad_slot_numel(self, name, p):
-        for j, K in enumerate(self.cluster_count):
-            if name == f"cluster_layers.{j}.v":
-                return self._soft_pad(K)[0] * p.shape[1]
-        return VisionTransformer._grad_slot_numel(self, name, p)
-
-    def _grad_stage_ptrs(self, G, ptr):
-        for j, loc in enumerate(self.cluster_loc):
-            G.stage[loc].w1 = ptr(f"cluster_layers.{j}.v")               # the gradient reaches v as if it were the unit vector (sinkhorn.py:76-77)
-
-    def _transposed_stage_weights(self, WT, t16):
-        for j, loc in enumerate(self.cluster_loc):
-            v = torch.nn.functional.normalize(self.cluster_layers[j].v.detach().float(), p=2, dim=-1)
-            WT.stage[loc].w1 = t16(_pad_rows(v, self._soft_pad(self.cluster_count[j])[1]))
-
-    def _pack_stages(self, W, pk):
-        for j, loc in enumerate(self.cluster_loc):
-            v, st = self.cluster_layers[j].v.detach(), W.stage[loc]
-            K = self.cluster_count[j]
-            n_pad = self._soft_pad(K)[0]
-            w1 = torch.zeros(n_pad, v.shape[1], dtype=torch.float32, device=v.device)
-            w1[:K] = torch.nn.functional.normalize(v.float(), p=2, dim=-1)
-            st.w1, st.b1 = pk.w16(w1), pk.f32(torch.zeros(n_pad, dtype=torch.float32, device=v.device))
-            st.n_pad = n_pad
+    def _stage_operands(self, j, loc):
+        v = self.cluster_layers[j].v
+        n_pad, ld = self._soft_pad(self.cluster_count[j])
+        # the operand is the unit-norm v, made once per repack for both copies; the gradient reaches v as if it were the unit vector (sinkhorn.py:76-77)
+        rows = (Op("w1", "v", "w", rows=n_pad, grad_rows=n_pad, t_rows=ld, value=lambda: torch.nn.functional.normalize(v.detach().float(), p=2, dim=-1)),
+                Op("b1", value=lambda: torch.zeros(n_pad, dtype=torch.float32, device=v.device), grad=False))
+        return f"cluster_layers.{j}.", rows, dict(n_pad=n_pad)
 
 
 class KMedoids(nn.Module):
@@ -1899,33 +1909,12 @@ class PatchMergerVisionTransformer(SelfSlimmedVisionTransformer):
     def _make_cluster_layer(self, count):
         return PatchMerger(self.embed_dim, count)
 
-    def _grad_slot_numel(self, name, p):
-        for j, K in enumerate(self.cluster_count):
-            if name == f"cluster_layers.{j}.queries":
-                return self._soft_pad(K)[0] * p.shape[1]
-        return VisionTransformer._grad_slot_numel(self, name, p)
-
-    def _grad_stage_ptrs(self, G, ptr):
-        for j, loc in enumerate(self.cluster_loc):
-            g, pre = G.stage[loc], f"cluster_layers.{j}."
-            g.ln_g, g.ln_b = ptr(pre + "norm.weight"), ptr(pre + "norm.bias")
-            g.w1 = ptr(pre + "queries")
-
-    def _transposed_stage_weights(self, WT, t16):
-        for j, loc in enumerate(self.cluster_loc):
-            WT.stage[loc].w1 = t16(_pad_rows(self.cluster_layers[j].queries, self._soft_pad(self.cluster_count[j])[1]))
-
-    def _pack_stages(self, W, pk):
-        for j, loc in enumerate(self.cluster_loc):
-            m, st = self.cluster_layers[j], W.stage[loc]
-            K = self.cluster_count[j]
-            n_pad = self._soft_pad(K)[0]
-            w1 = torch.zeros(n_pad, self.embed_dim, dtype=torch.float32, device=m.queries.device)
-            w1[:K] = m.queries.detach()
-            st.ln_g, st.ln_b = pk.f32(m.norm.weight), pk.f32(m.norm.bias)
-            st.w1, st.b1 = pk.w16(w1), pk.f32(torch.zeros(n_pad, dtype=torch.float32, device=w1.device))
-            st.scale = float(m.scale)
-            st.n_pad = n_pad
+    def _stage_operands(self, j, loc):
+        m = self.cluster_layers[j]
+        n_pad, ld = self._soft_pad(self.cluster_count[j])
+        rows = (Op("ln_g", "norm.weight"), Op("ln_b", "norm.bias"), Op("w1", "queries", "w", rows=n_pad, grad_rows=n_pad, t_rows=ld),
+                Op("b1", value=lambda: torch.zeros(n_pad, dtype=torch.float32, device=m.queries.device), grad=False))
+        return f"cluster_layers.{j}.", rows, dict(scale=float(m.scale), n_pad=n_pad)
 
 
 class HeuristicVisionTransformer(VisionTransformer):
@@ -2003,12 +1992,9 @@ class HeuristicVisionTransformer(VisionTransformer):
     def _block_mask(self, idx):
         return (self.distances <= self.threshold[idx]).reshape(self.P * self.P)
 
-    def _pack_stages(self, W, pk):
-        dev = self.pos_embed.device
-        for idx in self.reduction_loc:
-            m = torch.cat([torch.ones(1), self._block_mask(idx).float()]).to(dev)
-            W.stage[idx].w3 = pk.f32(m)
-            W.stage[idx].n_pad = m.numel()
+    def _stage_operands(self, j, loc):
+        mask = lambda: torch.cat([torch.ones(1), self._block_mask(loc).float()]).to(self.pos_embed.device)      # CLS, then the patches in reach
+        return "", (Op("w3", value=mask, grad=False),), dict(n_pad=self.P * self.P + 1)
 
     def _feature_blocks(self, tokens):
         return sorted(set(int(b) for b in self.reduction_loc) | {self.depth - 1})

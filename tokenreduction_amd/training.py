@@ -22,7 +22,7 @@ from typing import List, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, models
 from .augment import AugmentedBatch
 
 
@@ -62,10 +62,12 @@ class TrainState:
     def __init__(self, model):
         dev = model.pos_embed.device
         self.order = backward_order(model)
+        self.named = dict(self.order)
+        self.slots = {n: _align4(model._grad_slot_numel(n, p)) for n, p in self.order}
         self.offsets, off = {}, 0
-        for n, p in self.order:
+        for n in self.slots:
             self.offsets[n] = off
-            off += _align4(model._grad_slot_numel(n, p))
+            off += self.slots[n]
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         # where a parameter's view starts inside its slot: a no_embed_class model's pos_embed is rows 1 .. P of the [(P + 1), D] gradient
         # the executor writes (D floats in: still 256-byte aligned); row 0, the class row's, is scratch
@@ -86,98 +88,73 @@ class TrainState:
         self.tape = self.bws = None
         self.key = None
         self.events = None
-        self._stage_names = None
+        # the gradient side of the model's operand declaration (models.Op rows), read once.  ptr: the slot's start of every parameter, what the
+        # executor writes; units: (block or None for the trunk, (field, name) of the two rows, gamma's name under LayerScale, where the unit's
+        # folded gradients start inside the block's part of the scratch buffer); stage_grads: {block: [(field, name)]} of a family's stages
+        self.ptr = {n: self.flat.data_ptr() + 4 * o for n, o in self.offsets.items()}
+        self.units = [(None, (a.field, a.name), (b.field, b.name), None, 0) for a, b in model._trunk_units()]
+        for i in range(model.depth):
+            pre, off = f"blocks.{i}.", 0
+            for a, b in models._BLOCK_UNITS:
+                gamma = pre + a.gamma if a.gamma and self.ls is not None else None
+                self.units.append((i, (a.field, pre + a.name), (b.field, pre + b.name), gamma, off))
+                off += self.named[pre + a.name].numel() + self.named[pre + b.name].numel() if gamma else 0
+        self.stage_grads = {loc: [(r.field, pre + r.name) for r in rows if r.grad] for loc, (pre, rows, _) in model._stages().items()}
+        self._stage_names = {loc: [n for _, n in rows] for loc, rows in self.stage_grads.items() if rows}      # structure, not mask
+        self._stage_of = {n: loc for loc, names in self._stage_names.items() for n in names}
         self.gen = 0                 # counts training forwards: the tape belongs to the LAST one (see _VitTrainFn.backward)
 
     def _block_slices(self, model):
         """[(event_index, start, stop)] over the flat buffer: the slice event `e` of tr_vit_backward completes."""
-        names = [n for n, _ in self.order]
         ends = {}
-        for n, p in self.order:
+        for n in self.slots:
             if n.startswith("blocks."):
                 e = int(n.split(".")[1])
             elif n.startswith(("head", "norm")):
                 e = model.depth - 1                     # finished before the last block's event
             else:
                 e = model.depth                          # embedding + family modules: the final event
-            ends[e] = self.offsets[n] + _align4(model._grad_slot_numel(n, p))
+            ends[e] = self.offsets[n] + self.slots[n]
         out, start = [], 0
         for e in sorted(ends, key=lambda k: ends[k]):
             out.append((e, start, ends[e]))
             start = ends[e]
-        del names
         return out
 
     def grads_struct(self, model, want_dx=False):
         """tr_vit_weights-shaped struct whose pointers are the gradient views, read off `requires_grad` as it is NOW (built per
-        backward, nothing cached).  A unit of tr_vit_backward (the two gradients one launch produces) whose parameters are all frozen
-        is NULL: the executor leaves its work out.  A mixed unit (pos_embed trainable, cls_token frozen) keeps both pointers; the frozen
-        half lands in its slot of the flat buffer and is discarded.  The pointers of a family's reduction stage are NULL only where
+        backward, nothing cached but the declaration's rows).  A unit of tr_vit_backward (the two gradients one launch produces) whose
+        parameters are all frozen is NULL: the executor leaves its work out.  A mixed unit (pos_embed trainable, cls_token frozen) keeps both
+        pointers; the frozen half lands in its slot of the flat buffer and is discarded.  The unit of a LayerScale branch points into the scratch
+        buffer instead (never at the real slots): the executor writes the gradients of the FOLDED operands there, NULL only when W, b and gamma are
+        all frozen, and ls["items"] takes the unfold item (a frozen output is 0).  The pointers of a family's reduction stage are NULL only where
         the backward never arrives: below the lowest block that has a trainable parameter at or below it.
         want_dx: the input takes a gradient, so the backward goes all the way whatever is frozen (the floor is -1): every reduction stage is
         reached and keeps its pointers, a frozen stage parameter's slice is computed and discarded.
         Returns (struct, names of the frozen parameters the executor still writes)."""
         G = _lib.TrVitWeights()
-        v = self.views
-        named = dict(self.order)
-
-        def ptr(name):           # (the slot's start: what the executor writes)
-            return v[name].data_ptr() - 4 * self.view_off.get(name, 0)
-
+        named, ptr, ls = self.named, self.ptr, self.ls
         discarded = []
-
-        def unit(a, b):
-            if not (named[a].requires_grad or named[b].requires_grad):
-                return None, None
-            discarded.extend(n for n in (a, b) if not named[n].requires_grad)
-            return ptr(a), ptr(b)
-
-        ls = self.ls
         if ls is not None:
             ls["items"] = []
-
-        def folded_unit(blk, branch, w, b, g):
-            """The unit of a LayerScale branch: the executor writes the gradients of the folded operands into the scratch buffer (never into
-            the real slots), NULL only when W, b and gamma are all frozen; ls["items"] takes the unfold item (a frozen output is 0)."""
-            if not (named[w].requires_grad or named[b].requires_grad or named[g].requires_grad):
-                return None, None
-            D, Hd = ls["D"], ls["Hd"]
-            cols = Hd if branch else D
-            base = ls["scratch"].data_ptr() + 4 * (blk * ls["per"] + (D * D + D if branch else 0))
-            ls["items"].append((blk, (base, base + 4 * D * cols, named[w].data_ptr(), named[b].data_ptr(), named[g].data_ptr(),
-                                      ptr(w) if named[w].requires_grad else 0, ptr(b) if named[b].requires_grad else 0,
-                                      ptr(g) if named[g].requires_grad else 0, D, cols)))
-            return base, base + 4 * D * cols
-
-        G.patch_w, G.patch_b = unit("patch_embed.proj.weight", "patch_embed.proj.bias")
-        G.cls_token, G.pos_embed = unit("cls_token", "pos_embed")
-        G.norm_g, G.norm_b = unit("norm.weight", "norm.bias")
-        if "head.weight" in v:       # headless models (num_classes == 0) have no classifier slices: the head pointers stay NULL
-            G.head_w, G.head_b = unit("head.weight", "head.bias")
-        for i in range(model.depth):
-            b, pre = G.blocks[i], f"blocks.{i}."
-            b.ln1_g, b.ln1_b = unit(pre + "norm1.weight", pre + "norm1.bias")
-            b.qkv_w, b.qkv_b = unit(pre + "attn.qkv.weight", pre + "attn.qkv.bias")
-            b.ln2_g, b.ln2_b = unit(pre + "norm2.weight", pre + "norm2.bias")
-            b.fc1_w, b.fc1_b = unit(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
-            if self.ls is None:
-                b.proj_w, b.proj_b = unit(pre + "attn.proj.weight", pre + "attn.proj.bias")
-                b.fc2_w, b.fc2_b = unit(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+        for blk, (fa, a), (fb, b), g, off in self.units:
+            ps = [named[n] for n in ((a, b) if g is None else (a, b, g))]
+            if not any(p.requires_grad for p in ps):
+                continue
+            if g is None:
+                discarded.extend(n for n in (a, b) if not named[n].requires_grad)
+                ga, gb = ptr[a], ptr[b]
             else:
-                b.proj_w, b.proj_b = folded_unit(i, 0, pre + "attn.proj.weight", pre + "attn.proj.bias", pre + "ls1.gamma")
-                b.fc2_w, b.fc2_b = folded_unit(i, 1, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias", pre + "ls2.gamma")
-        model._grad_stage_ptrs(G, ptr)
-        stage_names = self._stage_names      # {block: names of the family's parameters behind G.stage[block]}: structure, not mask
-        if stage_names is None:
-            by_ptr = {ptr(n): n for n, _ in self.order}
-            stage_names = self._stage_names = {}
-            for loc in range(model.depth):
-                names = [by_ptr[a] for a in (getattr(G.stage[loc], f) for f in _STAGE_PTRS) if a]
-                if names:
-                    stage_names[loc] = names
+                D, cols = ps[0].shape
+                ga = ls["scratch"].data_ptr() + 4 * (blk * ls["per"] + off)
+                gb = ga + 4 * D * cols
+                ls["items"].append((blk, (ga, gb) + tuple(p.data_ptr() for p in ps)
+                                    + tuple(ptr[n] if p.requires_grad else 0 for n, p in zip((a, b, g), ps)) + (D, cols)))
+            S = G if blk is None else G.blocks[blk]
+            setattr(S, fa, ga)
+            setattr(S, fb, gb)
         # the floor: the lowest block with a trainable parameter at or below it (-1: the embedding trains, the backward goes all the way).
         # Conservative for family modules: a stage's parameter counts at the stage's block, any other family parameter at block 0.
-        at = {n: loc for loc, names in stage_names.items() for n in names}
         floor = model.depth
         for n, p in self.order:
             if not p.requires_grad or n.startswith(("head.", "norm.")):
@@ -187,14 +164,13 @@ class TrainState:
             elif n.startswith(("pos_embed", "cls_token", "patch_embed")):
                 floor = -1
             else:
-                floor = min(floor, at.get(n, 0))
+                floor = min(floor, self._stage_of.get(n, 0))
         if want_dx:
             floor = -1
-        for loc, names in stage_names.items():
-            if loc < floor or (loc == floor and not any(named[n].requires_grad for n in names)):
-                for f in _STAGE_PTRS:
-                    setattr(G.stage[loc], f, None)
-            else:
+        for loc, names in self._stage_names.items():
+            if loc > floor or (loc == floor and any(named[n].requires_grad for n in names)):
+                for f, n in self.stage_grads[loc]:
+                    setattr(G.stage[loc], f, ptr[n])
                 discarded.extend(n for n in names if not named[n].requires_grad)
         return G, discarded
 
@@ -217,26 +193,21 @@ class TrainState:
                                                          torch.cuda.current_stream().cuda_stream), "tr_layerscale_unfold_grad")
 
     def transposed(self, model, pk):
-        """bf16 transposed copies of the block matrices (the dgrad GEMM operands): made by the model's own repack (models._pack with
-        need_transposed: persistent buffers rewritten by the same fused launch as the operand copies); the reduction modules' few small
-        matrices are transposed here whenever the pack generation changes."""
+        """The dgrad GEMM operands, all made by the model's own repack (models._pack with need_transposed): the bf16 transposed copies of
+        the block matrices and of the patch weight are persistent buffers rewritten by the same fused launch as the operand copies; the reduction
+        modules' few small matrices are transposed there too (models._pack_stages).  The struct is rebuilt whenever the pack generation changes."""
         if self.key == pk["gen"]:
             return self.wt
         WT = _lib.TrVitWeights()
-        keep = []
-
-        def t16(w):
-            c = w.detach().t().to(torch.bfloat16).contiguous()
-            keep.append(c)
-            return c.data_ptr()
-
-        for i, (tq, tp_, t1, t2) in enumerate(pk["tblocks"]):
-            b = WT.blocks[i]
-            b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w = tq.data_ptr(), tp_.data_ptr(), t1.data_ptr(), t2.data_ptr()
+        wt_fields = [a.field for a, _ in models._BLOCK_UNITS if a.kind == "wt"]
+        for i, ts in enumerate(pk["tblocks"]):
+            for f, t in zip(wt_fields, ts):
+                setattr(WT.blocks[i], f, t.data_ptr())
         if pk.get("tpatch") is not None:      # the patch weight transposed [C*p*p, D]: the operand of the input gradient (tr_vit_backward_dx)
             WT.patch_w = pk["tpatch"].data_ptr()
-        model._transposed_stage_weights(WT, t16)
-        self.wt, self.wt_keep, self.key = WT, keep, pk["gen"]
+        for (loc, f), t in model._stage_t.items():
+            setattr(WT.stage[loc], f, t.data_ptr())
+        self.wt, self.wt_keep, self.key = WT, dict(model._stage_t), pk["gen"]      # (the struct points into the stage tensors: kept with it)
         return WT
 
     def buffers(self, model, pk, B, dev):
@@ -253,8 +224,6 @@ class TrainState:
             self.B = B
         return self.tape, self.bws
 
-
-_STAGE_PTRS = ("ln_g", "ln_b", "w0", "b0", "w1", "b1", "w2", "b2", "w3", "b3")
 
 TAPE_FIELDS = ("x0", "x1", "xn1", "qkv", "ao", "dattn", "x2", "xn2", "pre", "h", "idx", "idx2", "scores", "size",
                "n_pre", "n_att", "n_mlp", "kk")
