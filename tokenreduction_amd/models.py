@@ -39,6 +39,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import types
 import warnings
 from functools import partial
 from typing import Callable, List, NamedTuple, Optional
@@ -49,6 +50,7 @@ import torch.nn as nn
 
 from . import _lib, pixels
 from .augment import AugmentedBatch
+from .eval_request import REFUSALS, REFUSE_CPU, DenseOutput, EvalRequest, Levels
 
 
 def _pair(v):
@@ -840,17 +842,26 @@ class VisionTransformer(nn.Module):
             return training.train_forward(self, x)
         return self._forward_eval(x, 0)
 
-    def _tap_request(self, cls_blocks, final_tokens):
-        """(ascending block tuple, bool) of a forward_taps / forward_async call, or the refusal."""
-        if self.training:
-            raise RuntimeError("output taps are an eval feature: call model.eval() first (the training executor has no taps)")
-        if self.viz_mode:
-            raise RuntimeError("output taps and viz_mode are two ways to the same rows: switch viz_mode off (viz_data['Features'] "
-                               "already holds every row of every recorded block)")
-        blocks = tuple(sorted({int(b) for b in (cls_blocks or ())}))
-        if blocks and not (0 <= blocks[0] and blocks[-1] < self.depth):
-            raise ValueError(f"cls_blocks {blocks} names a block outside 0 ... {self.depth - 1}")
-        return blocks, bool(final_tokens)
+    def _eval_request(self, x, what, cls_blocks=None, final_tokens=False, decisions=False, dense=None, dynamic_width_ok=False):
+        """The EvalRequest of the public entry `what` -- every entry builds its request here -- or the refusal: eval_request.REFUSALS' checks
+        of the request's feature, the first that applies wins.  dense: forward_dense's keywords (any subset), which stand alone."""
+        feature = "dense" if dense is not None else "decisions" if decisions else "taps"
+        applies = {"train": self.training, "viz_mode": self.viz_mode, "dynamic_width": self.dynamic_width and not dynamic_width_ok,
+                   "cpu": not x.is_cuda}
+        for check, message in REFUSALS[feature].items():
+            if check != "args":
+                if applies[check]:
+                    raise RuntimeError(message.format(what=what, device=x.device))
+            elif dense is not None:
+                request = EvalRequest(None, False, False, *self._dense_arguments(**dict(dense)))
+            else:
+                blocks = None
+                if cls_blocks is not None or final_tokens:
+                    blocks = tuple(sorted({int(b) for b in (cls_blocks or ())}))
+                    if blocks and not (0 <= blocks[0] and blocks[-1] < self.depth):
+                        raise ValueError(f"cls_blocks {blocks} names a block outside 0 ... {self.depth - 1}")
+                request = EvalRequest(blocks, bool(final_tokens), bool(decisions))
+        return request
 
     def forward_taps(self, x: torch.Tensor, cls_blocks=(3, 6, 9, 11), final_tokens=False):
         """Eval forward with output taps: (logits, {"cls", "blocks", "final_tokens"}).  taps["cls"] is fp32 [B, n, D]: the CLS row of the
@@ -862,20 +873,7 @@ class VisionTransformer(nn.Module):
         viz_mode and a block index outside 0 ... depth-1."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        return self._forward_eval(x, 0, self._tap_request(cls_blocks, final_tokens))
-
-    def _decision_request(self, x, what):
-        """The refusals of a forward that asks for the stages' decisions."""
-        if self.training:
-            raise RuntimeError("decision taps are an eval feature: call model.eval() first (the training executor records no decisions)")
-        if self.viz_mode:
-            raise RuntimeError("decision taps and viz_mode are two ways to the same records: switch viz_mode off (viz_data already holds "
-                               "Kept_Tokens / Assignment_Maps on the host)")
-        if self.dynamic_width:
-            raise RuntimeError(f"{what} cannot run under dynamic_width (the token counts of a stage are then data dependent and the executor "
-                               "synchronises mid-forward): switch dynamic_width off or use viz_mode")
-        if not x.is_cuda:
-            raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
+        return self._forward_eval(x, 0, self._eval_request(x, "forward_taps", tuple(cls_blocks or ()), final_tokens, dynamic_width_ok=True))
 
     def forward_decisions(self, x: torch.Tensor, cls_blocks=None, final_tokens=False):
         """Eval forward with decision taps: (logits, dec), dec = {"stages": (blk, ...), "kept": {blk: int32 [B, W]}, "kept_count": {blk: int32
@@ -886,25 +884,12 @@ class VisionTransformer(nn.Module):
         final_tokens the output taps of forward_taps ride along: (logits, taps, dec).  Refuses train mode, viz_mode, dynamic_width."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        self._decision_request(x, "forward_decisions")
-        taps = self._tap_request(cls_blocks, final_tokens) if (cls_blocks is not None or final_tokens) else None
-        return self._forward_eval(x, 0, taps, True)
+        return self._forward_eval(x, 0, self._eval_request(x, "forward_decisions", cls_blocks, final_tokens, decisions=True))
 
     _DENSE_FORMATS = ("NCHW", "NHWC")
 
-    def _dense_request(self, x, what, output_fmt="NCHW", dtype=torch.float32, fill=0.0, blocks=None, norm=True):
-        """(format, dtype, fill) of a forward_dense / forward_async(dense=...) call -- with blocks: (format, dtype, fill, ascending block tuple,
-        norm) -- or the refusal."""
-        if self.training:
-            raise RuntimeError("dense feature maps are an eval feature: call model.eval() first (the training executor has no taps)")
-        if self.viz_mode:
-            raise RuntimeError("dense feature maps and viz_mode are two ways to the same rows: switch viz_mode off (viz_data['Features'] "
-                               "already holds every row of every recorded block)")
-        if self.dynamic_width:
-            raise RuntimeError(f"{what} cannot run under dynamic_width (the token counts of a stage are then data dependent and the executor "
-                               "synchronises mid-forward): switch dynamic_width off or use viz_mode")
-        if not x.is_cuda:
-            raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
+    def _dense_arguments(self, output_fmt="NCHW", dtype=torch.float32, fill=0.0, blocks=None, norm=True):
+        """(DenseOutput, Levels or None) of forward_dense's keywords: the blocks ascending and counted from the front."""
         if output_fmt not in self._DENSE_FORMATS:
             raise ValueError(f"output_fmt must be one of {self._DENSE_FORMATS}, got {output_fmt!r}")
         if dtype not in (torch.float32, torch.bfloat16):
@@ -912,8 +897,9 @@ class VisionTransformer(nn.Module):
         if self.patch_embed.num_patches > 1024 or self.embed_dim % 4 or self.embed_dim > 1024:
             raise ValueError(f"dense feature maps take at most 1024 patches and a width that is a multiple of 4 up to 1024 "
                              f"({self.patch_embed.num_patches} patches, width {self.embed_dim})")
+        out = DenseOutput(output_fmt, dtype, float(fill))
         if blocks is None:
-            return output_fmt, dtype, float(fill)
+            return out, None
         if isinstance(blocks, (int, np.integer)):
             blocks = (blocks,)
         asked = [int(b) for b in blocks]
@@ -924,7 +910,7 @@ class VisionTransformer(nn.Module):
         levels = sorted(b % self.depth for b in asked)
         if len(set(levels)) != len(levels):
             raise ValueError(f"blocks {tuple(asked)} names a block twice")
-        return output_fmt, dtype, float(fill), tuple(levels), bool(norm)
+        return out, Levels(tuple(levels), bool(norm))
 
     def forward_dense(self, x: torch.Tensor, blocks=None, norm=True, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
         """Eval forward with a dense feature map: (logits, {"features", "index", "grid": (h, w)}).  `features` is the final norm of the last
@@ -951,7 +937,8 @@ class VisionTransformer(nn.Module):
         dynamic_width and a block out of range."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        return self._forward_eval(x, 0, dense=self._dense_request(x, "forward_dense", output_fmt, dtype, fill, blocks, norm))
+        dense = dict(output_fmt=output_fmt, dtype=dtype, fill=fill, blocks=blocks, norm=norm)
+        return self._forward_eval(x, 0, self._eval_request(x, "forward_dense", dense=dense))
 
     def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape=False, return_class_token=False, norm=False, dtype=torch.float32, fill=0.0):
         """timm's VisionTransformer.get_intermediate_layers on the fast path: the patch tokens after the last `n` blocks (int n) or after the
@@ -986,24 +973,16 @@ class VisionTransformer(nn.Module):
         forward_dense returns; it does not combine with the other keywords."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
-        taps = None
-        if dense is not None:
-            if decisions or cls_blocks is not None or final_tokens:
-                raise ValueError("forward_async: dense= does not combine with cls_blocks / final_tokens / decisions")
-            dense = self._dense_request(x, "forward_async(dense=...)", **dict(dense))
-        elif decisions:
-            self._decision_request(x, "forward_async(decisions=True)")
-            if cls_blocks is not None or final_tokens:
-                taps = self._tap_request(cls_blocks, final_tokens)
-        elif cls_blocks is not None or final_tokens:
-            taps = self._tap_request(cls_blocks, final_tokens)
-            if not x.is_cuda:
-                raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
-            if self.dynamic_width:
-                raise RuntimeError("forward_async with output taps cannot run under dynamic_width (the executor synchronises mid-forward): "
-                                   "use forward_taps")
+        asked = decisions or cls_blocks is not None or final_tokens
+        if dense is not None and asked:
+            raise ValueError("forward_async: dense= does not combine with cls_blocks / final_tokens / decisions")
+        if dense is not None or asked:
+            what = "forward_async" + ("(dense=...)" if dense is not None else "(decisions=True)" if decisions else "")
+            request = self._eval_request(x, what, cls_blocks, final_tokens, decisions, dense)
         elif self.training or self.viz_mode or self.dynamic_width or not x.is_cuda:
             return _Pending(self(x), None)
+        else:
+            request = EvalRequest()
         depth = max(1, int(self.pipeline_depth))
         st = self._pipe_streams
         key = x.device
@@ -1018,16 +997,17 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(x.device)
         side.wait_stream(cur)                          # inputs and weights are ready where the forward runs
         with torch.cuda.stream(side):
-            out = self._forward_eval(x, slot + 1, taps, bool(decisions), dense)
+            out = self._forward_eval(x, slot + 1, request)
             done = torch.cuda.Event()
             done.record(side)
         x.record_stream(side)
         return _Pending(out, done)
 
-    def _forward_eval(self, x: torch.Tensor, slot: int, taps=None, decisions=False, dense=None):
+    def _forward_eval(self, x: torch.Tensor, slot: int, request: EvalRequest = EvalRequest()):
+        """One eval forward on workspace slot `slot`: the request's static buffers, then the executor call and the request's launches behind
+        it -- as one hipGraph replay where the workspace allows, plain launches otherwise -- then the request's result."""
         if not x.is_cuda:
-            raise RuntimeError(f"input is on {x.device}: tokenreduction_amd has no CPU path (HIP kernels only)")
-        lib = _lib.load()
+            raise RuntimeError(REFUSE_CPU.format(device=x.device))
         pk = self._pack()
         if self._mlp_pk_stale:
             self._refresh_mlp_pack(x.device)
@@ -1035,147 +1015,145 @@ class VisionTransformer(nn.Module):
         B, Cc, Hh, Ww = x.shape
         if (Cc, Hh, Ww) != (cfg.in_chans, cfg.img_size, cfg.img_size):
             raise ValueError(f"expected [B,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(x.shape)}")
-        x, fmt, lut = self._executor_input(x)
+        image = self._executor_input(x)
+        x = image[0]
         ws = self._workspace(B, x.device, slot)
-        levels = dense[3] if dense is not None and len(dense) > 3 else None       # forward_dense(blocks=...): the ascending block tuple
-        if levels is not None:
-            decisions = True                           # the rows of the level taps, placed by the stages' record-form decisions
-        elif dense is not None:
-            taps, decisions = ((), True), True         # the rows of the final_tokens tap, placed by the stages' record-form decisions
-        if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
-            ws["soft"] = torch.empty(self._soft_elems(B), dtype=torch.float32, device=x.device)
-        want_feat = (self.viz_mode or self._always_features) and taps is None
-        if want_feat and ws.get("feat") is None:
-            # viz_data["Features"]: the residual stream after every block (upper bound depth * B * N0 * D fp32)
-            n0 = self.patch_embed.num_patches + 1
-            ws["feat"] = torch.empty(self.depth * B * n0 * self.embed_dim, dtype=torch.float32, device=x.device)
-        tap_arg = None
-        if taps is not None:
-            # static per workspace slot like every other output: the CLS taps [B, n, D] (room for every block), the final tokens [B, N0, D]
-            blocks, want_final = taps
-            D, n0 = self.embed_dim, self.patch_embed.num_patches + 1
-            if blocks and ws.get("tap_cls") is None:
-                ws["tap_cls"] = torch.empty(B * self.depth * D, dtype=torch.float32, device=x.device)
-            if want_final and ws.get("tap_final") is None:
-                ws["tap_final"] = torch.empty(B * n0 * D, dtype=torch.float32, device=x.device)
-            tap_arg = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
-                                     ws["tap_final"].data_ptr() if want_final else None)
-        dec = self._decision_plan(ws, B, x.device) if decisions else None
-        if levels is not None:
-            # static per workspace slot and level count: the level slabs [L, B * N0 * D] fp32, the indices [L, B, P0], one map buffer per dtype
-            P0, L = self.patch_embed.num_patches, len(levels)
-            slab = B * (P0 + 1) * self.embed_dim
-            lv = ws.setdefault("levels", {}).get(L)
-            if lv is None:
-                lv = ws["levels"][L] = dict(tokens=torch.empty(L * slab, dtype=torch.float32, device=x.device),
-                                            index=torch.empty(L * B * P0, dtype=torch.int32, device=x.device), feat={})
-            dense_feat = lv["feat"].get(dense[1])
-            if dense_feat is None:
-                dense_feat = lv["feat"][dense[1]] = torch.empty(L * B * P0 * self.embed_dim, dtype=dense[1], device=x.device)
-            level_arg = _lib.TrVitLevels(sum(1 << b for b in levels), int(dense[4]), lv["tokens"].data_ptr(), lv["tokens"].numel())
-            level_blocks = (C.c_int32 * L)(*levels)
-        elif dense is not None:
-            # static per workspace slot: the index [B, P0] and one feature map per output dtype (either layout is B * P0 * D elements)
-            P0 = self.patch_embed.num_patches
-            if ws.get("dense_index") is None:
-                ws["dense_index"] = torch.empty(B * P0, dtype=torch.int32, device=x.device)
-            dense_feat = ws.setdefault("dense_feat", {}).get(dense[1])
-            if dense_feat is None:
-                dense_feat = ws["dense_feat"][dense[1]] = torch.empty(B * P0 * self.embed_dim, dtype=dense[1], device=x.device)
-        soft = ws.get("soft") if dec is None or dec["soft"] is None else dec["soft"]      # (a buffer of its own: ws["soft"] stays viz_mode's)
+        out = self._request_buffers(ws, request, B, x.device)
         self._noise_slot = slot                      # (a static buffer per workspace slot: two forwards in flight must not share one)
         noise_ptr = self._noise_ptr(B, x.device)
         self._kmed_draws = None
         self._per_forward_config(cfg)
         cfg.concurrent = 1 if slot > 0 else 0        # forward_async: other forwards run beside this one (a scheduling hint, same bits)
 
-        def launch(out):
-            tokens = (C.c_int * self.depth)()
-            rest = (out.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(),
-                    None if soft is None else soft.data_ptr(), noise_ptr, ws["feat"].data_ptr() if want_feat else None, tokens, B,
-                    torch.cuda.current_stream().cuda_stream)
-            if levels is not None:
-                rc = lib.tr_vit_forward_levels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest, None, C.byref(level_arg))
-            elif tap_arg is not None and fmt == _lib.TR_INPUT_F32:
-                rc = lib.tr_vit_forward_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest, C.byref(tap_arg))
-            elif tap_arg is not None:
-                rc = lib.tr_vit_forward_pixels_taps(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest, C.byref(tap_arg))
-            elif fmt == _lib.TR_INPUT_F32:
-                rc = lib.tr_vit_forward(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), *rest)
-            else:
-                rc = lib.tr_vit_forward_pixels(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, *rest)
-            _lib.check(rc, "tr_vit_forward")
-            if dec is not None and dec["n"]:
-                # the raw slabs -> record form, in the forward's stream (and its graph): one launch
-                rc = lib.tr_stage_decisions(ws["kept"].data_ptr(), ws["compl"].data_ptr(), ws["kept"].numel(), *dec["args"][0], dec["table"],
-                                            dec["n"], B, self.patch_embed.num_patches + 1, *dec["args"][1], torch.cuda.current_stream().cuda_stream)
-                _lib.check(rc, "tr_stage_decisions")
-            if levels is not None:
-                # every level's prefix of the decisions composed, then every level's un-reduce: two launches in the same stream (and graph)
-                stream = torch.cuda.current_stream().cuda_stream
-                level_rows = (C.c_int32 * L)(*[tokens[b] for b in levels])
-                kept_out, kept_n, _, assign_out, assign_n = dec["args"][1]
-                rc = lib.tr_dense_index_levels(kept_out, kept_n, assign_out, assign_n, dec["table"], dec["n"], B, P0, level_blocks, level_rows, L,
-                                               lv["index"].data_ptr(), stream)
-                _lib.check(rc, "tr_dense_index_levels")
-                rc = lib.tr_dense_gather_levels(lv["tokens"].data_ptr(), slab, level_rows, L, lv["index"].data_ptr(), dense_feat.data_ptr(),
-                                                _lib.TR_LAYOUT_NCHW if dense[0] == "NCHW" else _lib.TR_LAYOUT_NHWC,
-                                                int(dense[1] == torch.bfloat16), dense[2], B, P0, self.embed_dim, stream)
-                _lib.check(rc, "tr_dense_gather_levels")
-            elif dense is not None:
-                # the decisions composed into one row per grid patch, then the un-reduce: two launches in the same stream (and graph)
-                stream, n_last = torch.cuda.current_stream().cuda_stream, tokens[self.depth - 1]
-                kept_out, kept_n, _, assign_out, assign_n = dec["args"][1]
-                rc = lib.tr_dense_index(kept_out, kept_n, assign_out, assign_n, dec["table"], dec["n"], B, P0, n_last,
-                                        ws["dense_index"].data_ptr(), stream)
-                _lib.check(rc, "tr_dense_index")
-                rc = lib.tr_dense_gather(ws["tap_final"].data_ptr(), ws["dense_index"].data_ptr(), dense_feat.data_ptr(),
-                                         _lib.TR_LAYOUT_NCHW if dense[0] == "NCHW" else _lib.TR_LAYOUT_NHWC, int(dense[1] == torch.bfloat16),
-                                         dense[2], B, P0, n_last, self.embed_dim, stream)
-                _lib.check(rc, "tr_dense_gather")
+        def launch(logits):
+            tokens = self._launch_executor(pk, ws, out, image, noise_ptr, logits, B)
+            self._launch_outputs(ws, request, out, tokens, B)
             return list(tokens)
 
         with torch.cuda.device(x.device):
             res = None
             if (self.use_graph and not ws.get("graph_off") and not torch.cuda.is_current_stream_capturing()
                     and not self.dynamic_width):      # (ATS dynamic width: the executor reads a token count back mid-forward)
-                key = (x.data_ptr(), x.dtype, fmt, lut, bool(want_feat), ws.get("soft") is not None, noise_ptr, self._kmed_draws, self._out_width,
-                       taps) + ((("dense",) + dense,) if dense is not None else ()) + ((True,) if dec is not None else ())
+                key = (x.data_ptr(), x.dtype, *image[1:], out.features is not None, ws.get("soft") is not None, noise_ptr, self._kmed_draws,
+                       self._out_width) + request.graph_key()
                 res = self._replay(ws, key, launch, B, x.device)
             logits, tokens = res if res is not None else self._plain_launch(launch, B, x.device)
         cfg.concurrent = 0                           # (the packed configuration is compared byte-wise on a repack: leave no per-call state in it)
         self._last_tokens = list(tokens)
         self._last_ws = ws
-        if dense is not None:
-            # cloned out of the static buffers in stream order, like the taps
+        return self._eval_result(ws, request, out, logits, list(tokens), B)
+
+    def _request_buffers(self, ws, req, B, dev):
+        """The outputs of a request beside the logits -- static per workspace slot like every other output, allocated by the first request that
+        asks for them -- and the executor's structs over them: features (viz_data["Features"]: the stream after every block, upper bound depth
+        * B * N0 * D fp32), soft, taps (a TrVitTaps or None: the CLS taps [B, n, D] with room for every block, the final tokens [B, N0, D]),
+        dec (the decision plan or None), and for a dense request maps = ws["levels"][L] (per level count; 0: the single map of the
+        final_tokens tap): the level slabs [L, B * N0 * D] fp32, the indices [L, B, P0] and one map buffer per output dtype (either layout is
+        L * B * P0 * D elements), of which feat is the request's; levels is the TrVitLevels over the slabs (zeroed: no level taps)."""
+        D, P0 = self.embed_dim, self.patch_embed.num_patches
+        empty = lambda n, dtype=torch.float32: torch.empty(n, dtype=dtype, device=dev)
+        if self.viz_mode and self._soft_elems(B) and ws.get("soft") is None:      # viz_mode switched on after the first call
+            ws["soft"] = empty(self._soft_elems(B))
+        out = types.SimpleNamespace(features=None, soft=ws.get("soft"), taps=None, dec=None, maps=None, feat=None, levels=_lib.TrVitLevels())
+        if (self.viz_mode or self._always_features) and req.taps is None:
+            if ws.get("feat") is None:
+                ws["feat"] = empty(self.depth * B * (P0 + 1) * D)
+            out.features = ws["feat"]
+        if req.taps is not None:
+            blocks, final = req.taps
+            if blocks and ws.get("tap_cls") is None:
+                ws["tap_cls"] = empty(B * self.depth * D)
+            if final and ws.get("tap_final") is None:
+                ws["tap_final"] = empty(B * (P0 + 1) * D)
+            out.taps = _lib.TrVitTaps(sum(1 << b for b in blocks), ws["tap_cls"].data_ptr() if blocks else None,
+                                      ws["tap_final"].data_ptr() if final else None)
+        if req.wants_decisions:
+            out.dec = self._decision_plan(ws, B, dev)
+            if out.dec["soft"] is not None:
+                out.soft = out.dec["soft"]             # (a buffer of its own: ws["soft"] stays viz_mode's)
+        if req.dense is not None:
+            L = len(req.levels.blocks) if req.levels is not None else 0
+            out.maps = ws.setdefault("levels", {}).get(L)
+            if out.maps is None:
+                out.maps = ws["levels"][L] = dict(tokens=empty(L * B * (P0 + 1) * D) if L else None, index=empty(max(L, 1) * B * P0, torch.int32),
+                                                  feat={})
+            out.feat = out.maps["feat"].get(req.dense.dtype)
+            if out.feat is None:
+                out.feat = out.maps["feat"][req.dense.dtype] = empty(max(L, 1) * B * P0 * D, req.dense.dtype)
+            if L:
+                out.levels = _lib.TrVitLevels(sum(1 << b for b in req.levels.blocks), int(req.levels.norm), out.maps["tokens"].data_ptr(),
+                                              out.maps["tokens"].numel())
+        return out
+
+    def _launch_executor(self, pk, ws, out, image, noise_ptr, logits, B):
+        """The eval path's one executor call -> the token count after every block.  tr_vit_forward_levels is the superset entry point: a float
+        image is TR_INPUT_F32 without a LUT, no output taps a NULL tr_vit_taps, no level taps a zeroed tr_vit_levels."""
+        x, fmt, lut = image
+        tokens = (C.c_int * self.depth)()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = _lib.load().tr_vit_forward_levels(C.byref(pk["cfg"]), C.byref(pk["W"]), x.data_ptr(), fmt, lut, logits.data_ptr(), ws["buf"].data_ptr(),
+                                               ws["nbytes"], ws["kept"].data_ptr(), ws["compl"].data_ptr(), ptr(out.soft), noise_ptr,
+                                               ptr(out.features), tokens, B, torch.cuda.current_stream().cuda_stream,
+                                               None if out.taps is None else C.byref(out.taps), C.byref(out.levels))
+        _lib.check(rc, "tr_vit_forward")
+        return tokens
+
+    def _launch_outputs(self, ws, req, out, tokens, B):
+        """The request's launches behind the executor, in the forward's stream (and its graph): the raw decision slabs -> record form
+        (tr_stage_decisions), then for a dense request the decisions composed into one row per grid patch and the un-reduce -- of the
+        final_tokens tap, or of every level at once (the _levels forms: every level's prefix of the decisions)."""
+        lib, dec, stream = _lib.load(), out.dec, torch.cuda.current_stream().cuda_stream
+        D, P0 = self.embed_dim, self.patch_embed.num_patches
+        if dec is not None and dec["n"]:
+            rc = lib.tr_stage_decisions(ws["kept"].data_ptr(), ws["compl"].data_ptr(), ws["kept"].numel(), dec["soft_ptr"], dec["soft_elems"],
+                                        dec["table"], dec["n"], B, P0 + 1, dec["kept_ptr"], dec["kept_elems"], dec["count_ptr"],
+                                        dec["assign_ptr"], dec["assign_elems"], stream)
+            _lib.check(rc, "tr_stage_decisions")
+        if req.dense is None:
+            return
+        records = (dec["kept_ptr"], dec["kept_elems"], dec["assign_ptr"], dec["assign_elems"], dec["table"], dec["n"], B, P0)
+        layout = (_lib.TR_LAYOUT_NCHW if req.dense.fmt == "NCHW" else _lib.TR_LAYOUT_NHWC, int(req.dense.dtype == torch.bfloat16), req.dense.fill)
+        index, feat = out.maps["index"].data_ptr(), out.feat.data_ptr()
+        if req.levels is None:
+            n_last = tokens[self.depth - 1]
+            _lib.check(lib.tr_dense_index(*records, n_last, index, stream), "tr_dense_index")
+            _lib.check(lib.tr_dense_gather(ws["tap_final"].data_ptr(), index, feat, *layout, B, P0, n_last, D, stream), "tr_dense_gather")
+        else:
+            L = len(req.levels.blocks)
+            blocks, rows = (C.c_int32 * L)(*req.levels.blocks), (C.c_int32 * L)(*[tokens[b] for b in req.levels.blocks])
+            _lib.check(lib.tr_dense_index_levels(*records, blocks, rows, L, index, stream), "tr_dense_index_levels")
+            _lib.check(lib.tr_dense_gather_levels(out.maps["tokens"].data_ptr(), B * (P0 + 1) * D, rows, L, index, feat, *layout, B, P0, D, stream),
+                       "tr_dense_gather_levels")
+
+    def _eval_result(self, ws, req, out, logits, tokens, B):
+        """What the request's entry returns, one section per output kind.  Every output is cloned out of its static buffer in stream order, the
+        way a replay's logits are: the next forward on this slot overwrites them."""
+        D, dec = self.embed_dim, out.dec
+        if req.dense is not None:
             if dec["static"] is None and not dec["checked"]:
-                self._decision_result(dec, B, list(tokens))     # (the stage table against the executor's token counts, once per workspace)
-            h, w = self.patch_embed.grid_size
-            feat = dense_feat.clone()
-            if levels is not None:
-                D, n0 = self.embed_dim, self.patch_embed.num_patches + 1
-                feat = feat.view(L, B, D, h, w) if dense[0] == "NCHW" else feat.view(L, B, h, w, D)
-                index = lv["index"].clone().view(L, B, h * w)
-                # row 0 of every level's [B, N_l, D] rows: a strided copy out of the static slabs
-                cls = torch.stack([lv["tokens"][l * slab: l * slab + B * tokens[b] * D].view(B, tokens[b], D)[:, 0] for l, b in enumerate(levels)], dim=1)
-                return logits, {"features": [feat[l] for l in range(L)], "index": [index[l] for l in range(L)], "blocks": levels, "grid": (h, w),
-                                "cls": cls}
-            return logits, {"features": feat.view(B, self.embed_dim, h, w) if dense[0] == "NCHW" else feat.view(B, h, w, self.embed_dim),
-                            "index": ws["dense_index"].clone().view(B, h * w), "grid": (h, w)}
-        if taps is not None:
-            # cloned out of the static buffers in stream order, the way a replay's logits are: the next forward on this slot overwrites them
-            blocks, want_final = taps
-            D, n_last = self.embed_dim, tokens[-1]
-            out = {"cls": ws["tap_cls"][:B * len(blocks) * D].view(B, len(blocks), D).clone() if blocks else None, "blocks": blocks,
-                   "final_tokens": ws["tap_final"][:B * n_last * D].view(B, n_last, D).clone() if want_final else None}
-            if dec is not None:
-                return logits, out, self._decision_result(dec, B, list(tokens))
-            return logits, out
+                self._decision_result(dec, B, tokens)           # (the stage table against the executor's token counts, once per workspace)
+            (h, w), levels = self.patch_embed.grid_size, req.levels
+            n = len(levels.blocks) if levels is not None else 1
+            feat = out.feat.clone().view((n, B, D, h, w) if req.dense.fmt == "NCHW" else (n, B, h, w, D))
+            index = out.maps["index"].clone().view(n, B, h * w)
+            if levels is None:
+                return logits, {"features": feat[0], "index": index[0], "grid": (h, w)}
+            # row 0 of every level's [B, N_l, D] rows: a strided copy out of the static slabs
+            slabs = out.maps["tokens"].view(n, -1)
+            cls = torch.stack([slabs[l, :B * tokens[b] * D].view(B, tokens[b], D)[:, 0] for l, b in enumerate(levels.blocks)], dim=1)
+            return logits, {"features": list(feat), "index": list(index), "blocks": levels.blocks, "grid": (h, w), "cls": cls}
+        result = (logits,)
+        if req.taps is not None:
+            blocks, final = req.taps
+            result += ({"cls": ws["tap_cls"][:B * len(blocks) * D].view(B, len(blocks), D).clone() if blocks else None, "blocks": blocks,
+                        "final_tokens": ws["tap_final"][:B * tokens[-1] * D].view(B, tokens[-1], D).clone() if final else None},)
         if dec is not None:
-            return logits, self._decision_result(dec, B, list(tokens))
+            result += (self._decision_result(dec, B, tokens),)
+        if len(result) > 1:
+            return result
         if self.viz_mode:
-            viz = self._viz_data(ws, B, list(tokens))
-            viz["Features"] = self._features(ws, B, list(tokens))
+            viz = self._viz_data(ws, B, tokens)
+            viz["Features"] = self._features(ws, B, tokens)
             return logits, viz
         return logits
 
@@ -1271,9 +1249,10 @@ class VisionTransformer(nn.Module):
                                static=self._static_decisions(B, dev), checked=False)
         ptr = lambda t: None if t is None else t.data_ptr()
         size = lambda t: 0 if t is None else t.numel()
-        # tr_stage_decisions' arguments around the table: (soft, soft_elems), (kept_out, kept_elems, count_out, assign_out, assign_elems)
-        dec["args"] = ((ptr(dec["soft"]), size(dec["soft"])),
-                       (ptr(dec["kept"]), size(dec["kept"]), dec["count"].data_ptr(), ptr(dec["assign"]), size(dec["assign"])))
+        # the buffers as tr_stage_decisions and the dense index launches take them: address and element count, NULL and 0 where a family has none
+        for name in ("soft", "kept", "assign"):
+            dec[name + "_ptr"], dec[name + "_elems"] = ptr(dec[name]), size(dec[name])
+        dec["count_ptr"] = dec["count"].data_ptr()
         return dec
 
     def _decision_result(self, dec, B, tokens):
