@@ -16,6 +16,8 @@ MAX_SMALL_SHARE = 0.02
 SHAPES = {"bwd": [(2, 197, 6), (3, 50, 3), (1, 224, 2), (2, 17, 1), (2, 139, 12), (1, 64, 1), (4, 98, 3)],
           "long": [(2, 577, 3), (1, 290, 2), (2, 197, 6), (1, 65, 1), (3, 64, 2), (1, 640, 1), (2, 17, 1)],
           "policy": [(2, 577, 2), (1, 300, 3), (2, 197, 6), (2, 138, 2), (1, 40, 1), (1, 640, 1)]}
+# one N per count of 32-key blocks, 1..7: every instantiation the register-resident kernels are dispatched to (plain, bias and policy form)
+SHAPES["bwd_blocks"] = SHAPES["policy_blocks"] = [(2, 17, 1), (1, 50, 2), (1, 81, 2), (1, 98, 2), (1, 139, 2), (1, 177, 2), (1, 197, 2)]
 
 
 class _RoundGrad(torch.autograd.Function):
@@ -132,10 +134,23 @@ def _size(B, N):
     return size
 
 
+def _bwd_cases(group):
+    return [(_randn(20, B * N, 3 * H * 64, dtype=torch.bfloat16), _randn(21, B * N, H * 64, dtype=torch.bfloat16), B, N, H,
+             _size(B, N) if bias else None, None, None) for B, N, H in SHAPES[group] for bias in (False, True)]
+
+
+def _policy_cases(group):
+    cases = []
+    for B, N, H in SHAPES[group]:
+        policy = (torch.rand(B, N, generator=torch.Generator().manual_seed(5)) > 0.4).float()
+        policy[:, 0] = 1.0
+        cases.append((_randn(40, B * N, 3 * H * 64, dtype=torch.bfloat16), _randn(41, B * N, H * 64, dtype=torch.bfloat16), B, N, H, None, None, policy))
+    return cases
+
+
 def _measure():
-    cases = [(_randn(20, B * N, 3 * H * 64, dtype=torch.bfloat16), _randn(21, B * N, H * 64, dtype=torch.bfloat16), B, N, H,
-              _size(B, N) if bias else None, None, None) for B, N, H in SHAPES["bwd"] for bias in (False, True)]
-    print("test_attention_bwd:", _worst(cases))
+    print("test_attention_bwd:", _worst(_bwd_cases("bwd")))
+    print("test_attention_bwd_blocks:", _worst(_bwd_cases("bwd_blocks")))
     B, N, H = 2, 139, 6
     dcls = _randn(24, B, N)
     dcls[:, 0] = 0
@@ -149,12 +164,8 @@ def _measure():
             cases.append((_randn(30, B * N, 3 * H * 64, dtype=torch.bfloat16), _randn(31, B * N, H * 64, dtype=torch.bfloat16), B, N, H,
                           _size(B, N) if bias else None, dcls, None))
     print("test_attention_bwd_long:", _worst(cases))
-    cases = []
-    for B, N, H in SHAPES["policy"]:
-        policy = (torch.rand(B, N, generator=torch.Generator().manual_seed(5)) > 0.4).float()
-        policy[:, 0] = 1.0
-        cases.append((_randn(40, B * N, 3 * H * 64, dtype=torch.bfloat16), _randn(41, B * N, H * 64, dtype=torch.bfloat16), B, N, H, None, None, policy))
-    print("test_attention_policy_bwd:", _worst(cases))
+    print("test_attention_policy_bwd:", _worst(_policy_cases("policy")))
+    print("test_attention_policy_bwd_blocks:", _worst(_policy_cases("policy_blocks")))
 
 
 if __name__ == "__main__":

@@ -111,6 +111,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.tr_version() >= 100
 
 
+def test_library_reads_one_environment_variable():
+    """The library keeps no lab switch in the environment: the only getenv( of csrc is TR_MLP_FUSED_GRID (tr_mlp_fused.hip), which the
+    fused-Mlp tests use to run the stream-K hand-over over several rounds."""
+    import glob
+    csrc = os.path.join(ROOT, "tokenreduction_amd", "csrc")
+    found = []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        for ln in open(path):
+            if "getenv(" in ln:
+                found.append((os.path.basename(path), re.search(r'getenv\(\s*"?(\w*)', ln).group(1)))
+    assert found == [("tr_mlp_fused.hip", "TR_MLP_FUSED_GRID")], found
+
+
 def test_struct_layout_matches_header():
     assert ctypes.sizeof(_lib.TrBlockWeights) == 13 * 8          # 12 parameter pointers + mlp_pk
     assert ctypes.sizeof(_lib.TrStageWeights) == 10 * 8 + 16

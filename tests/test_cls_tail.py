@@ -249,10 +249,11 @@ def test_attention_cls_equals_row_0_of_the_full_attention(N, H, masked):
     assert torch.equal(got.view(torch.int16), full.view(B, N, H * 64)[:, 0].contiguous().view(torch.int16))
 
 
-@pytest.mark.parametrize("N", [1, 16, 17, 32, 33, 224, 225, 256, 257, 1025])
+@pytest.mark.parametrize("N", [1, 16, 17, 32, 33, 98, 177, 224, 225, 256, 257, 1025])
 def test_attention_cls_equals_row_0_at_the_block_edges(N):
     """The first query block alone at the 16- and 32-query block edges and both sides of the 224-token dispatch, with and without a key
-    bias, on the shifted and masked inputs of tests/_attn_fwd_ref.py as well (a masked key 25 above every real one)."""
+    bias, on the shifted and masked inputs of tests/_attn_fwd_ref.py as well (a masked key 25 above every real one).  98 and 177: the
+    CLS instantiations for 4 and 6 key blocks, which no other N of this file reaches."""
     from tokenreduction_amd import ops
     from tests import _attn_fwd_ref as R
     B, H = R.shape_of(N)

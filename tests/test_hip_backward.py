@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 # over each test's own shapes and seeds -- measured on the CPU by `python -m tests._attn_bwd_ref` -- and 2 x that for the kernels (bf16
 # output rounding plus fp32 order).  The whole-tensor bound of 1.2e-2 stays; one block of 577 rows off by 10 % passes it.
 ATTN_MEASURED = {"bwd": {"q": 2.53e-3, "k": 2.29e-3, "v": 2.30e-3}, "cls": {"q": 2.62e-3, "k": 1.85e-3, "v": 1.77e-3},
-                 "long": {"q": 2.39e-3, "k": 2.44e-3, "v": 1.98e-3}, "policy": {"q": 2.59e-3, "k": 2.39e-3, "v": 2.18e-3}}
+                 "long": {"q": 2.39e-3, "k": 2.44e-3, "v": 1.98e-3}, "policy": {"q": 2.59e-3, "k": 2.39e-3, "v": 2.18e-3},
+                 "bwd_blocks": {"q": 2.53e-3, "k": 1.97e-3, "v": 2.39e-3}, "policy_blocks": {"q": 3.13e-3, "k": 2.33e-3, "v": 1.81e-3}}
 ATTN_BLOCK_BOUND = {t: {nm: 2 * v for nm, v in m.items()} for t, m in ATTN_MEASURED.items()}
 # d policy is evaluated in fp32 by the kernels (no bf16 intermediate) and by the fp32 reference: each entry sums N * H <= 3500 signed terms
 # that exceed the result by the cancellation of a random sum (~ sqrt(count) ~ 60): 2^-24 * 60 * a few = ~1e-5 per side and per operation
@@ -218,6 +219,17 @@ def _attn_ref(qkv, B, N, H, size=None):
 @pytest.mark.parametrize("B,N,H", ATTN_SHAPES["bwd"])
 @pytest.mark.parametrize("bias", [False, True])
 def test_attention_bwd(ops, B, N, H, bias):
+    _check_attention_bwd(ops, B, N, H, bias, "bwd")
+
+
+@pytest.mark.parametrize("B,N,H", ATTN_SHAPES["bwd_blocks"])
+@pytest.mark.parametrize("bias", [False, True])
+def test_attention_bwd_blocks(ops, B, N, H, bias):
+    """One N per count of 32-key blocks, 1..7: every instantiation the dispatch of the register-resident kernel can reach."""
+    _check_attention_bwd(ops, B, N, H, bias, "bwd_blocks")
+
+
+def _check_attention_bwd(ops, B, N, H, bias, group):
     qkv = _randn(20, B * N, 3 * H * 64, dtype=torch.bfloat16)
     dout = _randn(21, B * N, H * 64, dtype=torch.bfloat16)
     size = None
@@ -234,7 +246,7 @@ def test_attention_bwd(ops, B, N, H, bias):
         r = rel_l2(gv[:, i], want[:, i])
         # P and dS pass through bf16 (2^-9 relative rounding each) before the three products; the result is rounded to bf16
         assert r <= 1.2e-2, f"d{nm}: rel L2 {r:.3e}"
-    assert_blocks(got, qf.grad, B, N, H, ATTN_BLOCK_BOUND["bwd"], f"attention_bwd B={B} N={N} H={H} bias={bias}:")
+    assert_blocks(got, qf.grad, B, N, H, ATTN_BLOCK_BOUND[group], f"attention_bwd B={B} N={N} H={H} bias={bias}:")
 
 
 def test_attention_bwd_cls_gradient(ops):
@@ -286,6 +298,16 @@ def test_attention_policy_bwd(ops, B, N, H):
     """Backward of DyViT's training-time attention (Policy_Attention.softmax_with_policy, dyvit.py:39-67) against torch.autograd over
     the oracle's restatement: d qkv and the per-key policy gradient (the straight-through Gumbel sample upstream makes the policy
     differentiable, dyvit.py:223-224).  N <= 224: the register-resident kernel; beyond (384 x 384 inputs): the key-blocked one."""
+    _check_attention_policy_bwd(ops, B, N, H, "policy")
+
+
+@pytest.mark.parametrize("B,N,H", ATTN_SHAPES["policy_blocks"])
+def test_attention_policy_bwd_blocks(ops, B, N, H):
+    """One N per count of 32-key blocks, 1..7: every instantiation of the register-resident policy kernels, backward and forward."""
+    _check_attention_policy_bwd(ops, B, N, H, "policy_blocks")
+
+
+def _check_attention_policy_bwd(ops, B, N, H, group):
     import oracle
     qkv = _randn(40, B * N, 3 * H * 64, dtype=torch.bfloat16)
     dout = _randn(41, B * N, H * 64, dtype=torch.bfloat16)
@@ -305,7 +327,7 @@ def test_attention_policy_bwd(ops, B, N, H):
         assert r <= 1.2e-2, f"d{nm}: rel L2 {r:.3e}"
     r = rel_l2(dpart.sum(1).cpu(), pol.grad)
     assert r <= 1.2e-2, f"d policy: rel L2 {r:.3e}"
-    assert_blocks(got, qf.grad, B, N, H, ATTN_BLOCK_BOUND["policy"], f"attention_policy_bwd B={B} N={N} H={H}:")
+    assert_blocks(got, qf.grad, B, N, H, ATTN_BLOCK_BOUND[group], f"attention_policy_bwd B={B} N={N} H={H}:")
     dp, wp = dpart.sum(1).cpu().double(), pol.grad.double()
     for b in range(B):                                                # d policy per image, and entry by entry with an absolute floor
         rb_ = rel_l2(dp[b], wp[b])

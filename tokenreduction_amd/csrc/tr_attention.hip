@@ -5,20 +5,18 @@
 // and emits the CLS query's softmax row per head (attn[:, :, 0, :], topk.py:59) as a side output, so the
 // B*H*N*N matrix the reference keeps alive for the Top-K score is never materialised.
 //
-// One workgroup (4 waves) per (image, head).  K [N][64] is staged once into LDS row-major with the
-// 16-byte chunk index XOR-swizzled by (key>>1)&7; V is staged TRANSPOSED (Vt[d][key]) so that both
-// MFMA operands are 16-byte LDS reads (tools/lds_sim.py: all reads/writes conflict-free).
-// Each wave owns 32-query blocks and keeps the WHOLE score row in registers (no online softmax):
-//   S^T[key][q] = K Q^T       v_mfma_f32_32x32x16_bf16, lane = query, 16 keys per lane per 32-key block
-//   softmax over keys         lane-local over registers + one exchange with lane^32
-//   O^T[d][q]  = Vt P^T       the exponentiated S^T accumulator is fed straight back as the MFMA B operand
-//                             ("accumulator tile as the next MFMA's operand", cdna guide section 3); the k-order
-//                             permutation this implies (key bits 2<->3 inside each 32-key block) is applied
-//                             once, when V is transposed into LDS.
+// Which kernel serves which call (one workgroup per (image, head) unless noted; NP = NKB = ceil(N/32), from TR_DISPATCH_NKB):
+//   tr_attention_bf16         N <= 224   attention16_kernel<NP, COLSUM, BIAS>: 16-query blocks, the whole score row in registers.
+//                                        COLSUM = column sums wanted (colsum_part), BIAS = key bias / mask given (size)
+//                             N >= 225   attention_flash_kernel<false>: online softmax over 128-key chunks, one workgroup per four
+//                                        32-query blocks; column sums by a second pass (attention_colsum_kernel)
+//                                        -- except column sums TOGETHER with a key bias: attention_long_kernel<COLSUM> (two passes, N <= 608)
+//   tr_attention_cls_bf16     the same two with CLS = true: query block 0 only, row 0 stored
+//   tr_attention_policy_bf16  N <= 224   attention_policy_kernel<NKB>: DyViT's softmax_with_policy on 32-query blocks
+//                             N >= 225   attention_flash_kernel<true>
 // Arithmetic: bf16 operands, fp32 accumulate/softmax; P is rounded to bf16 for P.V, the normaliser is the
 // fp32 sum of the un-rounded exponentials (same rounding points as oracle precision="bf16").
 #include "tr_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -38,32 +36,31 @@ __device__ __forceinline__ void colsum_step(float* v, int ql) {
   }
 }
 
-// COLSUM: also emit, per (image, head, wave), the column sums over this wave's queries of the softmax matrix -- the token
-// weights K-Medoids needs from the previous block's attention (kmedoids.py:240) -- without materialising B*H*N*N.
-// POLICY: DyViT's training-time softmax_with_policy (dyvit.py:39-51): `size` then carries the keep policy [B,N] of 1/0 and
+// DyViT's training-time softmax_with_policy (dyvit.py:39-51), N <= 224, on 32-QUERY blocks: `size` carries the keep policy [B,N] of 1/0 and
 //   attn = (exp(s - max) * pol + eps/N) / (sum_k exp(s - max) * pol + eps),  pol[q][k] = policy[k], 1 on the diagonal.
-template <int NKB, bool COLSUM, bool POLICY, bool BIAS>
-__global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
-                                                           float* __restrict__ cls_rows, const float* __restrict__ size,
-                                                           float* __restrict__ colsum_part, int N, int H) {
+// One workgroup (4 waves) per (image, head).  K [N][64] is staged once into LDS row-major with the 16-byte chunk index XOR-swizzled by
+// (key>>1)&7; V is staged TRANSPOSED (Vt[d][key]) so that both MFMA operands are 16-byte LDS reads (tools/lds_sim.py: conflict-free).
+// Each wave owns 32-query blocks and keeps the WHOLE score row in registers (no online softmax):
+//   S^T[key][q] = K Q^T       v_mfma_f32_32x32x16_bf16, lane = query, 16 keys per lane per 32-key block
+//   softmax over keys         lane-local over registers + one exchange with lane^32
+//   O^T[d][q]  = Vt P^T       the exponentiated S^T accumulator is fed straight back as the MFMA B operand ("accumulator tile as the next
+//                             MFMA's operand", cdna guide section 3); the k-order permutation this implies (key bits 2<->3 inside each
+//                             32-key block) is applied once, when V is transposed into LDS.
+// (cls_rows and colsum_part keep the parameter list of the other forward kernels; the policy entry point passes neither.)
+template <int NKB>
+__global__ __launch_bounds__(256, 2) void attention_policy_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
+                                                                  float* __restrict__ cls_rows, const float* __restrict__ size,
+                                                                  float* __restrict__ colsum_part, int N, int H) {
   constexpr int RS = NKB * 64 + 16;  // Vt row stride in bytes: odd multiple of 16 -> conflict-free b128 column reads
   __shared__ __attribute__((aligned(16))) unsigned char sK[NKB * 32 * 128];
   __shared__ __attribute__((aligned(16))) unsigned char sVt[64 * RS];
-  __shared__ __attribute__((aligned(16))) float sLB[NKB * 32];   // log2(size[key]): ToMe's proportional attention (tome.py:48-49), 0 without sizes
+  __shared__ __attribute__((aligned(16))) float sLB[NKB * 32];   // the keep policy of the keys, 0 past N
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
   const int ldq = 3 * H * 64;
   const uint16_t* base = qkv + (size_t)b * N * ldq;
   const int qcol = h * 64, kcol = H * 64 + h * 64, vcol = 2 * H * 64 + h * 64;
-#ifdef TR_ATT_STAMPS   // diagnostic build (tools/attn_stamps.py): clock64 stamps of the first query block go to cls_rows
-  long long stamp[8];
-  int nst = 0;
-#define TR_STAMP() do { if (nst < 8) stamp[nst++] = clock64(); } while (0)
-  TR_STAMP();
-#else
-#define TR_STAMP() do { } while (0)
-#endif
 
   // ---- stage K (row-major, swizzled) and V transposed; keys >= N are zero rows.  All 2 * NKB 16-byte loads of a thread are
   // issued BEFORE the first LDS write: as rolled loops (load, wait, write, next) the 2 * NKB global round trips ran back to
@@ -105,18 +102,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
       dst[(e * RS) >> 1] = (unsigned short)((e & 1) ? (word >> 16) : (word & 0xffffu));
     }
   }
-  for (int key = tid; key < NKB * 32; key += 256)
-    sLB[key] = POLICY ? (key < N ? size[(size_t)b * N + key] : 0.f)
-                      : ((size != nullptr && key < N) ? __builtin_amdgcn_logf(size[(size_t)b * N + key]) : 0.f);   // v_log_f32 = log2
+  for (int key = tid; key < NKB * 32; key += 256) sLB[key] = key < N ? size[(size_t)b * N + key] : 0.f;
   __syncthreads();
-  TR_STAMP();
 
   const int ql = lane & 31, hh = lane >> 5;
   const int nqb = (N + 31) >> 5;
   const float c_exp = 0.125f * 1.44269504088896340736f;  // dh^-0.5 * log2(e), dh = 64
-  float colacc[NKB];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) colacc[kb] = 0.f;
 
   for (int qb = wave; qb < nqb; qb += 4) {
     const int q = qb * 32 + ql;
@@ -124,10 +115,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
     bf16x8 qf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qrow + 16 * s);
-#ifdef TR_ATT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    TR_STAMP();
 
     f32x16 sacc[NKB];
 #pragma unroll
@@ -141,87 +128,15 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
       }
       __builtin_amdgcn_sched_barrier(0);  // keep K-fragment reads per key block: bounds live registers
     }
-    TR_STAMP();
     // ---- softmax over keys (rows of S^T): registers of this lane + the other half-wave
     float mx = -INFINITY;
     float l = 0.f;
-    if (!POLICY && !BIAS) {
-      // no key bias (DeiT / Top-K / EViT / DyViT ...): the maximum is taken on the raw scores and the scale folded into the
-      // exponent's fma, exp2(s * c - max * c), on register PAIRS (v_pk_fma_f32, v_pk_add_f32): 3 VALU instructions per element
-      // instead of 5 (scale, max3, sub, exp, add -> max3, half a pk_fma, exp, half a pk_add).  The softmax is the longer half
-      // of a query block (stamps: 4.1 k of 8 k cycles), so this is what the kernel's time follows.
-      typedef __attribute__((ext_vector_type(2))) float f32x2;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = (NKB - 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        if (key >= N) sacc[NKB - 1][r] = -INFINITY;
-      }
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float nm = -mx * c_exp;
-      f32x2 l2 = {0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          f32x2 t = {sacc[kb][r], sacc[kb][r + 1]};
-          t = t * c_exp + nm;
-          f32x2 pp;
-          pp[0] = __builtin_amdgcn_exp2f(t[0]);
-          pp[1] = __builtin_amdgcn_exp2f(t[1]);
-          sacc[kb][r] = pp[0];
-          sacc[kb][r + 1] = pp[1];
-          l2 += pp;
-        }
-      l = l2[0] + l2[1];
-    } else if (!POLICY) {
-      // key bias log2(size[key]) (ToMe's proportional attention, ATS / heuristic masks as log2 0 = -inf): same packed arithmetic,
-      // the bias comes from LDS four keys at a time (registers 4g..4g+3 of a block hold keys 8g + 4hh + 0..3)
-      typedef __attribute__((ext_vector_type(2))) float f32x2;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 b4 = *reinterpret_cast<const float4*>(&sLB[kb * 32 + 8 * g + 4 * hh]);
-          f32x2 t0 = {sacc[kb][4 * g], sacc[kb][4 * g + 1]}, t1 = {sacc[kb][4 * g + 2], sacc[kb][4 * g + 3]};
-          t0 = t0 * c_exp + f32x2{b4.x, b4.y};
-          t1 = t1 * c_exp + f32x2{b4.z, b4.w};
-          float e[4] = {t0[0], t0[1], t1[0], t1[1]};
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (kb == NKB - 1 && kb * 32 + 8 * g + 4 * hh + u >= N) e[u] = -INFINITY;
-            sacc[kb][4 * g + u] = e[u];
-            mx = fmaxf(mx, e[u]);
-          }
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float nm = (mx == -INFINITY) ? 0.f : -mx;         // every key masked: all weights exp2(-inf) = 0, as before
-      f32x2 l2 = {0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          f32x2 t = {sacc[kb][r], sacc[kb][r + 1]};
-          t = t + nm;
-          f32x2 pp;
-          pp[0] = __builtin_amdgcn_exp2f(t[0]);
-          pp[1] = __builtin_amdgcn_exp2f(t[1]);
-          sacc[kb][r] = pp[0];
-          sacc[kb][r + 1] = pp[1];
-          l2 += pp;
-        }
-      l = l2[0] + l2[1];
-    } else {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        // logits in the log2 domain: (q.k) * dh^-0.5 * log2(e) + log2(size[key])
-        sacc[kb][r] = POLICY ? sacc[kb][r] * c_exp : sacc[kb][r] * c_exp + sLB[key];
+        sacc[kb][r] = sacc[kb][r] * c_exp;                       // logits in the log2 domain: (q.k) * dh^-0.5 * log2(e)
         if (kb == NKB - 1 && key >= N) sacc[kb][r] = -INFINITY;
         mx = fmaxf(mx, sacc[kb][r]);
       }
@@ -230,18 +145,15 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
     for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
         float p = __builtin_amdgcn_exp2f(sacc[kb][r] - mx);
-        if (POLICY) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-          p *= (key == q) ? 1.0f : sLB[key];                     // attn_policy = policy + (1 - policy) * eye
-        }
+        p *= (key == q) ? 1.0f : sLB[key];                       // attn_policy = policy + (1 - policy) * eye
         sacc[kb][r] = p;
         l += p;
       }
-    }
     l += __shfl_xor(l, 32, 64);
-    const float inv = POLICY ? 1.0f / (l + 1e-6f) : 1.0f / l;
-    if (POLICY) {                                                // (attn + eps/N) / (sum + eps); padded keys stay 0
+    const float inv = 1.0f / (l + 1e-6f);
+    {                                                            // (attn + eps/N) / (sum + eps); padded keys stay 0
       const float add = 1e-6f / (float)N;
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb)
@@ -252,7 +164,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
         }
     }
 
-    TR_STAMP();
     // ---- O^T = Vt P^T
     f32x16 o[2];
 #pragma unroll
@@ -272,10 +183,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
         __builtin_amdgcn_sched_barrier(0);
       }
 
-    TR_STAMP();
-#ifdef TR_ATT_NO_STORE
-    if (q == 0 && o[0][0] == 123.456f) out[0] = 1;
-#else
     if (q < N) {
       uint16_t* orow = out + ((size_t)b * N + q) * (H * 64) + h * 64 + 4 * hh;
 #pragma unroll
@@ -288,23 +195,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
           *reinterpret_cast<uint2*>(orow + db * 32 + 8 * g) = pk;
         }
     }
-#endif
-    TR_STAMP();
-    if (COLSUM) {
-      const float wq = q < N ? inv : 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = sacc[kb][r] * wq;
-        colsum_step<16, 1>(v, ql);
-        colsum_step<8, 2>(v, ql);
-        colsum_step<4, 4>(v, ql);
-        colsum_step<2, 8>(v, ql);
-        colacc[kb] += v[0] + __shfl_xor(v[0], 16, 64);
-      }
-    }
-#ifndef TR_ATT_STAMPS
     if (cls_rows != nullptr && qb == 0 && ql == 0) {
       float* crow = cls_rows + ((size_t)b * H + h) * N;
 #pragma unroll
@@ -315,30 +205,14 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const uint16_t* __res
           if (key < N) crow[key] = sacc[kb][r] * inv;
         }
     }
-#endif
-  }
-#ifdef TR_ATT_STAMPS
-  if (lane == 0 && cls_rows != nullptr) {
-    long long* dbg = reinterpret_cast<long long*>(cls_rows) + ((size_t)blockIdx.x * 4 + wave) * 8;
-    for (int i = 0; i < 8; ++i) dbg[i] = i < nst ? stamp[i] - stamp[0] : -1;
-  }
-#endif
-  if (COLSUM && (ql & 16) == 0) {
-    // after the transpose-reduce, lane bits (b0,b1,b2,b3) of ql select register r = 8 b0 + 4 b1 + 2 b2 + b3
-    const int r = ((ql & 1) << 3) | ((ql & 2) << 1) | ((ql & 4) >> 1) | ((ql & 8) >> 3);
-    float* crow = colsum_part + (((size_t)b * H + h) * 4 + wave) * N;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-      if (key < N) crow[key] = colacc[kb];
-    }
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// N <= 224, round 3: the same whole-row-in-registers softmax on 16-QUERY blocks (v_mfma_f32_16x16x32_bf16), three workgroups per CU.
+// N <= 224, every form but the policy one: the same whole-row-in-registers softmax on 16-QUERY blocks (v_mfma_f32_16x16x32_bf16), three
+// workgroups per CU.
 //
-// Why (profiles/r02_final_pmc_sq.json): attention_kernel above keeps 32 queries x 224 keys = 112 score registers per
+// Why (profiles/r02_final_pmc_sq.json): the 32-query scheme above keeps 32 queries x 224 keys = 112 score registers per
 // lane, so two waves per SIMD is all the register file takes, two workgroups per CU is all the LDS takes (K + V^T = 58 KB), and a
 // wave spends its 2 x 8 k cycles per workgroup in order: matrix pipe busy 15 %, HBM at 3.1 TB/s -- bound by neither.  Here:
 //   * S^T block = 16 keys x 16 queries: a lane holds 4 consecutive keys of ONE query per block, 56 registers for 224 keys, so three
@@ -391,8 +265,11 @@ __device__ __forceinline__ float quad_rows_sum(float v) {
 constexpr int A16_NW = TR_ATT16_WAVES, A16_NT = 64 * A16_NW;     // waves / threads per workgroup
 // CLS (tr_attention_cls_bf16: the last block of the eval forward, whose other rows nobody reads): all waves stage K and V as always, then
 // wave 0 alone runs query block 0 -- the same instructions as in the full launch -- and stores only query 0, into a compact [B, H*64] buffer
-template <int NP, bool COLSUM, bool POLICY, bool BIAS, bool CLS = false>
-__global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention16_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
+// COLSUM: also emit, per (image, head, wave), the column sums over this wave's queries of the softmax matrix -- the token weights K-Medoids
+// needs from the previous block's attention (kmedoids.py:240) -- without materialising B*H*N*N.
+// BIAS: the keys carry log2(size[key]) (ToMe's proportional attention, tome.py:48-49; ATS / heuristic masks as log2 0 = -inf).
+template <int NP, bool COLSUM, bool BIAS, bool CLS = false>
+__global__ __launch_bounds__(A16_NT, COLSUM ? 2 : 3) void attention16_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                              float* __restrict__ cls_rows, const float* __restrict__ size,
                                                              float* __restrict__ colsum_part, int N, int H) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
@@ -400,7 +277,7 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
   const int R = ((N + 15) >> 4) << 4;               // key rows held in LDS
   unsigned char* sK = smem16;
   unsigned char* sV = sK + R * 128;
-  float* sLB = reinterpret_cast<float*>(sV + R * 128);     // POLICY: keep policy; BIAS: log2(size[key]) (ToMe / key masks)
+  float* sLB = reinterpret_cast<float*>(sV + R * 128);     // BIAS: log2(size[key]) (ToMe / key masks)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int li = lane & 15, g = lane >> 4;
@@ -439,10 +316,9 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
       *reinterpret_cast<uint4*>(sV + key * 128 + ((ch ^ (((key >> 1) & 1) << 2)) << 4)) = v4;
     }
   }
-  if (POLICY || BIAS) {
+  if (BIAS) {
     for (int key = tid; key < R; key += A16_NT)
-      sLB[key] = POLICY ? (key < N ? size[(size_t)b * N + key] : 0.f)
-                        : ((size != nullptr && key < N) ? __builtin_amdgcn_logf(size[(size_t)b * N + key]) : 0.f);   // v_log_f32 = log2
+      sLB[key] = (size != nullptr && key < N) ? __builtin_amdgcn_logf(size[(size_t)b * N + key]) : 0.f;   // v_log_f32 = log2
   }
   __syncthreads();
 
@@ -487,7 +363,7 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
     }
     // ---- softmax over keys: this lane's registers, then the four lanes (g = 0..3) that share the query
     float mx = -INFINITY, l = 0.f;
-    if (!POLICY && !BIAS) {
+    if (!BIAS) {
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -518,11 +394,11 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb) {
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!POLICY && (kb < NKB - 1 || !last_empty)) b4 = *reinterpret_cast<const float4*>(&sLB[kb * 16 + 4 * g]);
+        if (kb < NKB - 1 || !last_empty) b4 = *reinterpret_cast<const float4*>(&sLB[kb * 16 + 4 * g]);
         const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          // logits in the log2 domain: (q.k) * dh^-0.5 * log2(e) [+ log2(size[key])]
+          // logits in the log2 domain: (q.k) * dh^-0.5 * log2(e) + log2(size[key])
           sacc[kb][r] = sacc[kb][r] * c_exp + bb[r];
           if (kb >= NKB - 2 && kb * 16 + 4 * g + r >= N) sacc[kb][r] = -INFINITY;
           mx = fmaxf(mx, sacc[kb][r]);
@@ -531,29 +407,16 @@ __global__ __launch_bounds__(A16_NT, (COLSUM || POLICY) ? 2 : 3) void attention1
       mx = quad_rows_max(mx);
       const float nm = (mx == -INFINITY) ? 0.f : -mx;          // every key masked: all weights exp2(-inf) = 0
 #pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        float4 p4v = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (POLICY && (kb < NKB - 1 || !last_empty)) p4v = *reinterpret_cast<const float4*>(&sLB[kb * 16 + 4 * g]);
-        const float pw[4] = {p4v.x, p4v.y, p4v.z, p4v.w};
+      for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float pv = __builtin_amdgcn_exp2f(sacc[kb][r] + nm);
-          if (POLICY) pv *= (kb * 16 + 4 * g + r == q) ? 1.0f : pw[r];      // attn_policy = policy + (1 - policy) * eye
+          const float pv = __builtin_amdgcn_exp2f(sacc[kb][r] + nm);
           sacc[kb][r] = pv;
           l += pv;
         }
-      }
     }
     l = quad_rows_sum(l);
-    const float inv = POLICY ? 1.0f / (l + 1e-6f) : 1.0f / l;
-    if (POLICY) {                                                // (attn + eps/N) / (sum + eps); padded keys stay 0
-      const float add = 1e-6f / (float)N;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (kb < NKB - 2 || kb * 16 + 4 * g + r < N) sacc[kb][r] += add;
-    }
+    const float inv = 1.0f / l;
 
     // ---- O^T = V^T P^T
     f32x4 o[4];
@@ -1050,7 +913,7 @@ __global__ __launch_bounds__(256, TR_FLASH_WGS) void attention_flash_kernel(cons
 // which leaves every query's reference point m and 1 / normaliser in rows 0 and 1 of the [B,H,4,N] partial buffer.  One workgroup
 // per (image, head, chunk of 128 keys) holds the K chunk in LDS and walks ALL query blocks: S^T = K Q^T again (half the FLOPs of
 // the attention itself), p = exp2(s * c - m_q) / l_q, summed over the queries of each wave by the same transpose-reduce as
-// attention_kernel<COLSUM>.  Waves 0,2 and 1,3 are combined (fixed order) into rows 2 and 3; the launcher zeroes rows 0 and 1
+// attention_long_kernel<true>.  Waves 0,2 and 1,3 are combined (fixed order) into rows 2 and 3; the launcher zeroes rows 0 and 1
 // afterwards, so the consumer's sum over the four rows is unchanged.
 __global__ __launch_bounds__(256, 3) void attention_colsum_kernel(const uint16_t* __restrict__ qkv, float* __restrict__ part, int N,
                                                                   int H, int nkc) {
@@ -1136,62 +999,42 @@ __global__ __launch_bounds__(256, 3) void attention_colsum_kernel(const uint16_t
   }
 }
 
-template <int NP>
-int launch_attention16(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B, int N, int H,
-                       hipStream_t st, bool policy = false) {
+// ---- N <= 224: the kernel's instantiation by key-block count (TR_DISPATCH_NKB) and by which pointers are given:
+// colsum_part -> COLSUM, size -> BIAS.  LDS of the 16-query kernel: K and V rows of ceil(N/16)*16 keys, plus the bias row.
+void launch_attention16(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B, int N, int H,
+                        hipStream_t st) {
   const int R = ((N + 15) >> 4) << 4;
-  const size_t lds = (size_t)R * 256 + ((policy || size) ? (size_t)R * 4 : 0);
-  if (policy)
-    hipLaunchKernelGGL((attention16_kernel<NP, false, true, false>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (colsum_part && size)
-    hipLaunchKernelGGL((attention16_kernel<NP, true, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (colsum_part)
-    hipLaunchKernelGGL((attention16_kernel<NP, true, false, false>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (size)
-    hipLaunchKernelGGL((attention16_kernel<NP, false, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else
-    hipLaunchKernelGGL((attention16_kernel<NP, false, false, false>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  return 0;
+  const size_t lds = (size_t)R * 256 + (size ? (size_t)R * 4 : 0);
+  TR_DISPATCH_NKB(N, {
+    if (colsum_part && size)
+      hipLaunchKernelGGL((attention16_kernel<NKB, true, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
+    else if (colsum_part)
+      hipLaunchKernelGGL((attention16_kernel<NKB, true, false>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
+    else if (size)
+      hipLaunchKernelGGL((attention16_kernel<NKB, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
+    else
+      hipLaunchKernelGGL((attention16_kernel<NKB, false, false>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, cls_rows, size, colsum_part, N, H);
+  });
 }
 
-template <int NP>
-int launch_attention16_cls(const uint16_t* qkv, uint16_t* out, const float* size, int B, int N, int H, hipStream_t st) {
+void launch_attention16_cls(const uint16_t* qkv, uint16_t* out, const float* size, int B, int N, int H, hipStream_t st) {
   const int R = ((N + 15) >> 4) << 4;
   const size_t lds = (size_t)R * 256 + (size ? (size_t)R * 4 : 0);
   float* const none = nullptr;
-  if (size)
-    hipLaunchKernelGGL((attention16_kernel<NP, false, false, true, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
-  else
-    hipLaunchKernelGGL((attention16_kernel<NP, false, false, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
-  return 0;
+  TR_DISPATCH_NKB(N, {
+    if (size)
+      hipLaunchKernelGGL((attention16_kernel<NKB, false, true, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
+    else
+      hipLaunchKernelGGL((attention16_kernel<NKB, false, false, true>), dim3(B * H), dim3(A16_NT), lds, st, qkv, out, none, size, none, N, H);
+  });
 }
 
-template <int NKB>
-int launch_attention(const uint16_t* qkv, uint16_t* out, float* cls_rows, const float* size, float* colsum_part, int B, int N, int H,
-                     hipStream_t st, bool policy = false) {
-  // BIAS: the keys carry log2(size) / a mask (ToMe, ATS, heuristic masks); without it the softmax takes its packed fast path
-  if (policy)
-    hipLaunchKernelGGL((attention_kernel<NKB, false, true, true>), dim3(B * H), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (colsum_part && size)
-    hipLaunchKernelGGL((attention_kernel<NKB, true, false, true>), dim3(B * H), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (colsum_part)
-    hipLaunchKernelGGL((attention_kernel<NKB, true, false, false>), dim3(B * H), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else if (size)
-    hipLaunchKernelGGL((attention_kernel<NKB, false, false, true>), dim3(B * H), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  else
-    hipLaunchKernelGGL((attention_kernel<NKB, false, false, false>), dim3(B * H), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H);
-  return 0;
-}
-
-bool att_use_old() {
-  static const bool use_old = [] { const char* e = getenv("TR_ATT_OLD"); return e && atoi(e) != 0; }();   // lab: the 32-query kernel
-  return use_old;
+void launch_attention_policy(const uint16_t* qkv, uint16_t* out, const float* policy, int B, int N, int H, hipStream_t st) {
+  float* const none = nullptr;
+  TR_DISPATCH_NKB(N, hipLaunchKernelGGL(attention_policy_kernel<NKB>, dim3(B * H), dim3(256), 0, st, qkv, out, none, policy, none, N, H));
 }
 
 }  // namespace
-
-// 0 where tr_attention_bf16 runs a kernel that has no CLS-only form (the lab's 32-query kernel): the executor keeps the full launch there
-int tr_attention_cls_available() { return att_use_old() ? 0 : 1; }
 
 // The attention of a block whose output is read on the CLS rows only: out bf16 [B, H*64] = row 0 of every image of what tr_attention_bf16
 // writes, bit for bit.  K and V of all N rows are read as always; q and the output of the first query block only.
@@ -1199,7 +1042,6 @@ extern "C" int tr_attention_cls_bf16(const uint16_t* qkv, uint16_t* out, const f
   TR_REQUIRE(qkv && out, TR_ERR_NULL, "tr_attention_cls_bf16: null pointer");
   TR_REQUIRE(B > 0 && H > 0 && N >= 1, TR_ERR_SHAPE, "tr_attention_cls_bf16: bad shape B=%d N=%d H=%d", B, N, H);
   TR_REQUIRE(tr_aligned16(qkv) && tr_aligned16(out), TR_ERR_ALIGN, "tr_attention_cls_bf16: pointers must be 16-byte aligned");
-  TR_REQUIRE(tr_attention_cls_available(), TR_ERR_CONFIG, "tr_attention_cls_bf16: not available beside TR_ATT_OLD");
   hipStream_t st = static_cast<hipStream_t>(s);
   // one query block per (image, head): 16 (N <= 224) or 32 queries against all keys; K, V and the block's q rows in, B rows out
   const double qrows = N <= 224 ? 16.0 : 32.0;
@@ -1211,15 +1053,7 @@ extern "C" int tr_attention_cls_bf16(const uint16_t* qkv, uint16_t* out, const f
     TR_CHECK_LAUNCH("tr_attention_cls_bf16");
     return TR_OK;
   }
-  switch ((N + 31) / 32) {
-    case 1: launch_attention16_cls<1>(qkv, out, size, B, N, H, st); break;
-    case 2: launch_attention16_cls<2>(qkv, out, size, B, N, H, st); break;
-    case 3: launch_attention16_cls<3>(qkv, out, size, B, N, H, st); break;
-    case 4: launch_attention16_cls<4>(qkv, out, size, B, N, H, st); break;
-    case 5: launch_attention16_cls<5>(qkv, out, size, B, N, H, st); break;
-    case 6: launch_attention16_cls<6>(qkv, out, size, B, N, H, st); break;
-    default: launch_attention16_cls<7>(qkv, out, size, B, N, H, st); break;
-  }
+  launch_attention16_cls(qkv, out, size, B, N, H, st);
   TR_CHECK_LAUNCH("tr_attention_cls_bf16");
   return TR_OK;
 }
@@ -1233,14 +1067,7 @@ extern "C" int tr_attention_bf16(const uint16_t* qkv, uint16_t* out, float* cls_
   TR_REQUIRE(tr_aligned16(qkv) && tr_aligned16(out), TR_ERR_ALIGN, "tr_attention_bf16: pointers must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(s);
   tr_prof_note(N <= 224 ? "attention_kernel" : "attention_flash_kernel", 4.0 * B * H * (double)N * N * 64, 2.0 * B * N * 4.0 * H * 64);
-#ifdef TR_ATT_LAB          // lab builds only (tools/attn_lab.py): smallest N that takes the online-softmax kernel, from the environment
-  static const int flash_min = [] {
-    const char* e = getenv("TR_ATT_FLASH_MIN");
-    return e ? atoi(e) : 225;
-  }();
-#else
   constexpr int flash_min = 225;   // N <= 224: whole score row in registers; beyond: online softmax over 128-key chunks
-#endif
   if (N >= flash_min && (colsum_part == nullptr || size == nullptr)) {
     const int nqg = ((N + 31) / 32 + 3) / 4;
     hipLaunchKernelGGL(attention_flash_kernel<false>, dim3(B * H * nqg), dim3(256), 0, st, qkv, out, cls_rows, size, colsum_part, N, H, nqg);
@@ -1267,28 +1094,7 @@ extern "C" int tr_attention_bf16(const uint16_t* qkv, uint16_t* out, float* cls_
     TR_CHECK_LAUNCH("tr_attention_bf16");
     return TR_OK;
   }
-  if (!att_use_old()) {
-    switch ((N + 31) / 32) {
-      case 1: launch_attention16<1>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      case 2: launch_attention16<2>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      case 3: launch_attention16<3>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      case 4: launch_attention16<4>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      case 5: launch_attention16<5>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      case 6: launch_attention16<6>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-      default: launch_attention16<7>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    }
-    TR_CHECK_LAUNCH("tr_attention_bf16");
-    return TR_OK;
-  }
-  switch ((N + 31) / 32) {
-    case 1: launch_attention<1>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    case 2: launch_attention<2>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    case 3: launch_attention<3>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    case 4: launch_attention<4>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    case 5: launch_attention<5>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    case 6: launch_attention<6>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-    default: launch_attention<7>(qkv, out, cls_rows, size, colsum_part, B, N, H, st); break;
-  }
+  launch_attention16(qkv, out, cls_rows, size, colsum_part, B, N, H, st);
   TR_CHECK_LAUNCH("tr_attention_bf16");
   return TR_OK;
 }
@@ -1308,15 +1114,7 @@ extern "C" int tr_attention_policy_bf16(const uint16_t* qkv, uint16_t* out, cons
     TR_CHECK_LAUNCH("tr_attention_policy_bf16");
     return TR_OK;
   }
-  switch ((N + 31) / 32) {
-    case 1: launch_attention<1>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    case 2: launch_attention<2>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    case 3: launch_attention<3>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    case 4: launch_attention<4>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    case 5: launch_attention<5>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    case 6: launch_attention<6>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-    default: launch_attention<7>(qkv, out, nullptr, policy, nullptr, B, N, H, st, true); break;
-  }
+  launch_attention_policy(qkv, out, policy, B, N, H, st);
   TR_CHECK_LAUNCH("tr_attention_policy_bf16");
   return TR_OK;
 }

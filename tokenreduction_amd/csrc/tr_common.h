@@ -61,6 +61,21 @@ void tr_prof_note(const char* label, double flops, double bytes);
     }                                                                                                                           \
   } while (0)
 
+// run the statement(s) with NKB = ceil(N / 32) in 1..7 as a compile-time constant: the 32-key blocks of the register-resident attention
+// kernels, forward and backward (N <= 224; the callers check the bound).  Same form as TR_DISPATCH_NCH (tr_rowops.h).
+#define TR_DISPATCH_NKB(N_, ...)                          \
+  do {                                                    \
+    switch (((N_) + 31) / 32) {                           \
+      case 1: { constexpr int NKB = 1; __VA_ARGS__; } break;  \
+      case 2: { constexpr int NKB = 2; __VA_ARGS__; } break;  \
+      case 3: { constexpr int NKB = 3; __VA_ARGS__; } break;  \
+      case 4: { constexpr int NKB = 4; __VA_ARGS__; } break;  \
+      case 5: { constexpr int NKB = 5; __VA_ARGS__; } break;  \
+      case 6: { constexpr int NKB = 6; __VA_ARGS__; } break;  \
+      default: { constexpr int NKB = 7; __VA_ARGS__; } break; \
+    }                                                     \
+  } while (0)
+
 static inline bool tr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---- device helpers -------------------------------------------------------------------------

@@ -462,8 +462,6 @@ __global__ __launch_bounds__(768, 3) void lnlin_kernel(const LlArgs a) {
 extern "C" int tr_lnlin_supported(int D, int N) { return (D == LL_D && N >= 128 && N % 64 == 0 && N <= LL_BIAS_MAX) ? 1 : 0; }      // (N / 64 >= 2 steps per block)
 
 static int ll_grid() {
-  static const int forced = [] { const char* e = getenv("TR_LNLIN_GRID"); return e ? atoi(e) : 0; }();
-  if (forced > 0) return forced;
   static std::atomic<int> cached[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;

@@ -465,8 +465,7 @@ static int layernorm_impl(bool f32, const float* x, long ldx, float* x_out, long
                                             (delta2 ? (double)M * D * 2.0 : 0.0) + ((delta && write_x) ? (double)M * D * 4.0 : 0.0));
 #ifndef TR_LN_NO_HALF
   if (!f32 && D == 384) {
-    static const int lnb = [] { const char* e = getenv("TR_LN_BLOCK"); const int b = e ? atoi(e) : 0; return (b == 64 || b == 128) ? b : 256; }();   // lab: waves per workgroup
-    const int rpb = lnb / 32;
+    constexpr int lnb = 256, rpb = lnb / 32;      // threads per workgroup; half a wave per row
     if (out32)
       hipLaunchKernelGGL((layernorm_half_kernel<3, float>), dim3((M + rpb - 1) / rpb), dim3(lnb), 0, st, x, ldx, x_out, ldxo,
                          static_cast<const uint16_t*>(delta), ldd, delta2, ldd2, write_x, gamma, beta, static_cast<float*>(y), M, eps);

@@ -841,8 +841,7 @@ extern "C" int tr_sinkhorn(const float* scores, int ldl, float eps, int iters, f
   const size_t lds = ((size_t)K * (N - 1) + K + (N - 1)) * sizeof(float);
   hipStream_t st = static_cast<hipStream_t>(s);
   if (lds > 158 * 1024) {
-    static const bool regs_off = getenv("TR_SINKHORN_REGS_OFF") != nullptr;       // lab switch (same-box A/B)
-    if (!regs_off && K <= 64 * SR_KC && N - 1 == SR_NW * SR_RPW) {                   // the plan fits the register file of one CU
+    if (K <= 64 * SR_KC && N - 1 == SR_NW * SR_RPW) {                   // the plan fits the register file of one CU
       hipLaunchKernelGGL(sinkhorn_regs_kernel, dim3(B), dim3(64 * SR_NW), 0, st, scores, ldl, eps, iters, wt, soft, N, K);
       TR_CHECK_LAUNCH("tr_sinkhorn");
       return TR_OK;

@@ -26,7 +26,6 @@ int tr_mlp_fused_resid_ln_bf16_set(const uint16_t* xn, const void* packed, const
                                    const float* next_b, float eps, uint16_t* xn_next, void* scratch, size_t scratch_bytes, int M, int D, int Hd,
                                    int cset, tr_stream_t s);
 int tr_mlp_ln_wanted(int M, int D, int Hd, int have_scratch, int concurrent);         // tr_mlp_fused.hip: ... with the norm2 in front of it inside the launch (tr_set_mlp_ln)
-int tr_attention_cls_available();                                     // tr_attention.hip: tr_attention_bf16 has its CLS-only form (tr_attention_cls_bf16)
 
 // CLS tail (eval, bf16): after the last block's attention no row mixes with another one again, and the forward returns head(norm(x)[:, 0]) --
 // so from that attention's output onward only the B CLS rows are computed (see vit_forward_impl).  1 (default) / 0: today's full-width block.
@@ -176,17 +175,6 @@ namespace {
 inline const uint16_t* u16(const void* p) { return static_cast<const uint16_t*>(p); }
 inline uint16_t* u16(void* p) { return static_cast<uint16_t*>(p); }
 
-// Lab A/B switches of this file, read once per process: the eager norm2 (no lazy residual), the three-launch patch embedding, a memset
-// node in front of every fused-Mlp launch, whole blocks round-robin (no stream-K hand-over).
-struct Lab { bool ln_eager, patch_unfused, mlp_memset_each, mlp_no_streamk; };
-const Lab& lab() {
-  static const Lab l = [] {
-    auto on = [](const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; };
-    return Lab{on("TR_LN_EAGER"), on("TR_PATCH_UNFUSED"), on("TR_MLP_MEMSET_EACH"), on("TR_MLP_NO_STREAMK")};
-  }();
-  return l;
-}
-
 // One forward being enqueued: vit_forward_impl builds it and calls its steps in the reference forward's order.
 // tape != nullptr: TRAINING forward -- every activation the backward pass needs goes to its own slot of the tape (tr_plan.h)
 // instead of the shared scratch, the residual stream is written out of place (the inputs of norm1 / norm2 of every block stay),
@@ -290,12 +278,12 @@ struct Fwd {
       level_norm = levels->norm;
       level_out = levels->tokens_out;
     }
-    lazy_base = !train && !f32 && !lab().ln_eager && features_out == nullptr;
+    lazy_base = !train && !f32 && features_out == nullptr;
     rl_base = lazy_base && drop_keep == nullptr && drop_scale == nullptr && tr_mlp_resid_ln_enabled();
     conc = (!train && cfg->concurrent) ? 1 : 0;
     pool = cfg->global_pool == 1;
-    sk_ok = p.mlp_sk_bytes > 0 && !lab().mlp_no_streamk && !conc;
-    one_memset = !train && prec == TR_PREC_BF16 && sk_ok && w->blocks[0].mlp_pk != nullptr && !lab().mlp_memset_each;
+    sk_ok = p.mlp_sk_bytes > 0 && !conc;
+    one_memset = !train && prec == TR_PREC_BF16 && sk_ok && w->blocks[0].mlp_pk != nullptr;
     x = scratch(p.off_x0);
     x_alt = scratch(p.off_x1);
     xn = xn_shared = ws + p.off_xn;
@@ -379,7 +367,7 @@ struct Fwd {
     const float* fimg = static_cast<const float*>(img);
     const int layout = input_format == TR_INPUT_U8_NHWC ? TR_LAYOUT_NHWC : TR_LAYOUT_NCHW;
     const int C = cfg->in_chans, S = cfg->img_size, patch = cfg->patch;
-    if (!train && !f32 && !lab().patch_unfused && tr_patch_embed_supported(C, S, patch, D)) {
+    if (!train && !f32 && tr_patch_embed_supported(C, S, patch, D)) {
       // eval: unfold + GEMM + cls/pos in one launch (tr_patch.hip), at every batch size (the two paths differ in the last bit: an image's
       // tokens must not depend on its batch); training keeps the column matrix (PatchEmbed's weight-gradient operand)
       if (pixels)
@@ -703,8 +691,7 @@ struct Fwd {
     // bf16 executor only: TR_PREC_FP32 / TR_PREC_BF16X3 (validation paths) keep the full-width block.
     tail = !train && i == cfg->depth - 1 && prec == TR_PREC_BF16 && features_out == nullptr && final_tokens_out == nullptr &&
            ((level_mask >> i) & 1u) == 0 && !pool && K == 0 && r == 0 && Ks == 0 &&
-           drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0 &&
-           tr_attention_cls_available() != 0;
+           drop_keep == nullptr && drop_scale == nullptr && policy_cur == nullptr && g_cls_tail.load(std::memory_order_relaxed) != 0;
     norm2_in_mlp = false;
     if (train) {
       const trplan::BlockTape& bt = tp->blk[i];

@@ -32,5 +32,5 @@ for rep in range(12):
     torch.cuda.synchronize()
     res.append((ev[0].elapsed_time(ev[1]) * 1e3, ev[0].elapsed_time(ev[2]) * 1e3))
 res.sort()
-tag = os.path.basename(os.environ.get("TOKENREDUCTION_HIP_LIB", "product")) + " ln-block " + os.environ.get("TR_LN_BLOCK", "256")
+tag = os.path.basename(os.environ.get("TOKENREDUCTION_HIP_LIB", "product"))
 print(tag, "| GEMM ends at / LayerNorm ends at (us after the common start), 12 runs:", " ".join(f"{a:.0f}/{b:.0f}" for a, b in res), flush=True)

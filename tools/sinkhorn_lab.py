@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Time tr_sinkhorn in isolation: python3 tools/sinkhorn_lab.py [B N K iters]   (default: the first stage of sinkhorn_base at 384^2, B = 64).
-TR_SINKHORN_REGS_OFF=1: the kernel that keeps the transport plan in global memory."""
+"""Time tr_sinkhorn in isolation: python3 tools/sinkhorn_lab.py [B N K iters]   (default: the first stage of sinkhorn_base at 384^2, B = 64)."""
 import os
 import sys
 
