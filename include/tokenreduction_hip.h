@@ -848,6 +848,16 @@ int tr_dense_index(const int32_t* kept, size_t kept_elems, const int32_t* assign
                    int n_stages, int B, int P0, int n_last, int32_t* index_out, tr_stream_t s);
 int tr_dense_gather(const float* tokens, const int32_t* index, void* out, int layout, int out_is_bf16, float fill, int B, int P, int n_rows,
                     int D, tr_stream_t s);
+/* tr_dense_scatter: the adjoint of tr_dense_gather, the gradient of a map back on the token rows (one launch, no scratch):
+ *   dtokens[b, r, :] = sum of dmap[b, :, p] over the patches p with index[b, p] == r, for 0 <= r < n_rows -- row 0 included, as the gather
+ *   reads it.  An index entry outside [0, n_rows) (-1, -2, a row too many) owns nothing: it is compared, never used as an address.  dmap in
+ *   tr_dense_gather's layouts ([B, D, P] for TR_LAYOUT_NCHW, [B, P, D] for TR_LAYOUT_NHWC; anything else TR_ERR_CONFIG), fp32 or bf16
+ *   (dmap_is_bf16); dtokens [B, n_rows, D] fp32, or bf16 when out_is_bf16 (the fp32 sum rounded once, to nearest even) -- the form
+ *   tr_vit_backward_dense consumes directly.  The sum is in fp32, one addition after the other in ascending p starting from +0; a row nobody
+ *   names is zero; every output element is written exactly once (no memset, no floating-point atomics): the same bits on every launch.
+ *   Shapes, alignment and refusals are tr_dense_gather's, each before any launch. */
+int tr_dense_scatter(const void* dmap, const int32_t* index, void* dtokens, int layout, int dmap_is_bf16, int out_is_bf16, int B, int P,
+                     int n_rows, int D, tr_stream_t s);
 
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
@@ -909,6 +919,45 @@ int tr_vit_forward_train_aug(const tr_vit_config* cfg, const tr_vit_weights* w, 
  * bytes in the order the forward consumes them -- the embedded tokens [B,N0,D], then per block proj's output rows, the Mlp's hidden
  * layer and its output: the order in which the reference module draws them.  Survivors are scaled by 1 / (1 - drop_rate).
  * (attn_drop_rate -- dropout on the attention probabilities, topk.py:49 -- is not built; the reference's CLI cannot set it either.) */
+/* Dense feature maps in training: tr_vit_forward_train_dense is the superset training forward -- input_format TR_INPUT_F32 (no LUT), a uint8
+ * format (tr_vit_forward_train_pixels) or a uint8 format with aug != NULL (tr_vit_forward_train_aug) -- that also leaves, in caller-owned
+ * buffers, what a dense map of the last stream and its gradient need (tr_vit_dense_train):
+ *   tokens_out   fp32 [B, N0, D] holding [B, N_last, D]: the final norm of every row, in fp32 arithmetic (the arithmetic of DyViT's
+ *                features_out) -- the `tokens` of tr_dense_gather
+ *   stream_out   fp32 [B, N0, D] holding [B, N_last, D]: the stream entering the final norm (what DyViT keeps on the tape as xfin_all; the
+ *                tape's layout is untouched), the `stream` of tr_vit_backward_dense
+ *   kept_idx / compl_idx (int32, depth * B * N0 each: idx_elems) and soft_out (fp32, soft_elems; NULL for a family without soft stages):
+ *                the decisions in the eval slab format of tr_stage_decisions, slab of block blk at blk * B * N0 -- device-to-device copies
+ *                of the tape's decision slots on the stream, behind the forward; both NULL: no copies
+ * No host synchronisation.  The logits, the tape and every launch in front of the final norm are tr_vit_forward_train's.  DyViT (every token
+ * stays under a policy; it has features_out): TR_ERR_CONFIG.  A NULL struct, tokens_out or stream_out: TR_ERR_NULL; a buffer too small:
+ * TR_ERR_SHAPE; not 16-byte aligned: TR_ERR_ALIGN -- each before any launch.
+ * tr_vit_backward_dense: tr_vit_backward_dx (dx nullable) plus dtokens, the gradient with respect to tokens_out [B, N_last, D] -- bf16
+ *   (dtokens_is_bf16: tr_dense_scatter's output, read as it is) or fp32 (rounded to bf16 first, as dfeat is) -- and `stream`, the forward's
+ *   stream_out.  The call with blk_hi == depth-1 runs a second pass of the final norm's backward over all rows behind the head's (behind
+ *   tr_token_pool_bwd's spread with global_pool == 1), adding into the stream gradient and into the norm's parameter gradients; the other
+ *   range calls take the same arguments and do not read them.  With dtokens == NULL the call IS tr_vit_backward_dx.  dtokens without stream:
+ *   TR_ERR_NULL; DyViT: TR_ERR_CONFIG; not 16-byte aligned: TR_ERR_ALIGN. */
+typedef struct {
+  float* tokens_out;
+  float* stream_out;
+  size_t rows_elems;    /* elements of tokens_out and of stream_out: at least B * N0 * D */
+  int32_t* kept_idx;
+  int32_t* compl_idx;
+  size_t idx_elems;     /* elements of kept_idx and of compl_idx: at least depth * B * N0 */
+  float* soft_out;
+  size_t soft_elems;
+} tr_vit_dense_train;
+int tr_vit_forward_train_dense(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                               const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len, float* logits, void* workspace,
+                               size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, const float* drop_scale,
+                               int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate,
+                               const tr_vit_dense_train* dense);
+int tr_vit_backward_dense(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                          const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape,
+                          size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                          tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens, int dtokens_is_bf16,
+                          const float* stream);
 size_t tr_vit_dropout_mask_bytes(const tr_vit_config* cfg, int B);
 /* fp32 master parameters -> the bf16 operand copies of the GEMMs, every matrix of a model in ONE launch (an optimizer step changes them
  * all: engine.py:76-91).  Item i: src fp32 [rows, cols] contiguous -> dst bf16 [rows, cols] (nullable) and dst_t bf16 [cols, rows]

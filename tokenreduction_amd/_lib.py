@@ -58,6 +58,11 @@ class TrVitLevels(C.Structure):      # tr_vit_levels: the level taps of tr_vit_f
     _fields_ = [("blocks", C.c_uint32), ("norm", C.c_int32), ("tokens_out", _vp), ("tokens_elems", _sz)]
 
 
+class TrVitDenseTrain(C.Structure):  # tr_vit_dense_train: the caller-owned outputs of tr_vit_forward_train_dense (64 bytes)
+    _fields_ = [("tokens_out", _vp), ("stream_out", _vp), ("rows_elems", _sz), ("kept_idx", _vp), ("compl_idx", _vp), ("idx_elems", _sz),
+                ("soft_out", _vp), ("soft_elems", _sz)]
+
+
 class TrDecisionStage(C.Structure):  # tr_decision_stage: one row of tr_stage_decisions' stage table (40 bytes)
     _fields_ = [("block", C.c_int32), ("kind", C.c_int32), ("n_in", C.c_int32), ("k", C.c_int32), ("kept_off", C.c_int64),
                 ("assign_off", C.c_int64), ("soft_off", C.c_int64)]
@@ -238,6 +243,11 @@ SIGNATURES = {
                                          C.POINTER(_i), _i, _vp, _vp, _f]),
     "tr_vit_forward_train_aug": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,
                                       _vp, _vp, C.POINTER(_i), _i, _vp, _vp, _f]),
+    "tr_dense_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "tr_vit_forward_train_dense": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,
+                                        _vp, C.POINTER(_i), _i, _vp, _vp, _f, C.POINTER(TrVitDenseTrain)]),
+    "tr_vit_backward_dense": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), _vp, _vp,
+                                   _vp, _vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp]),
 }
 
 _lib = None

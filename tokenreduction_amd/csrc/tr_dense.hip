@@ -10,6 +10,8 @@
 //   tr_dense_index_levels / tr_dense_gather_levels   the same two steps for L levels (the streams after L chosen blocks, each behind its own
 //                     prefix of the stages) in ONE launch each: the index kernel walks the stage table once and writes a level's index where
 //                     its prefix ends; the gather's tile order has the level as its slowest coordinate.
+//   tr_dense_scatter  the gather's adjoint, for the map's gradient in training: dtokens[b, r, :] = the sum of dmap[b, :, p] over the patches
+//                     with index[b, p] == r, fp32 additions in ascending p, every output element written exactly once, no scratch.
 // The gather is the hot path: it writes the largest tensor of the forward once and reads at most as much.  Channels-last is a row copy in
 // the shape of tr_taps.hip (a wave per output row, 16-byte loads).  NCHW transposes a tile of 64 patches x 64 channels through LDS: rows
 // come in with 16-byte loads (a 256-byte piece of each gathered row), leave along p with 16-byte stores (8-byte for bf16) when P % 4 == 0,
@@ -270,6 +272,113 @@ __global__ __launch_bounds__(256) void dense_gather_levels_nchw_kernel(const flo
   gather_tile_nchw<BF16, VEC>(tokens + l * level_stride, index + (size_t)l * B * P, out_l, fill, P, lr.rows[l], D, b, pt * DG_TP, ct * DG_TC, tile);
 }
 
+// ---- the scatter: the gather's adjoint -------------------------------------------------------------------------------------------------
+// dtokens[b, r, :] = the sum of dmap[b, :, p] over the patches p with index[b, p] == r, in fp32, one addition after the other in ascending p
+// starting from +0.  An output row is owned by one wave (channels-last) or by one lane per channel (NCHW) that walks the row's patches in
+// order, so there is nothing to clear, nothing atomic and one set of bits whatever the launch.  The row's patches come from a ballot over the
+// image's index, 64 entries a step: the set bits, lowest first, ARE the ascending list -- no inverse table in memory, no scratch.
+// `index == r` with 0 <= r < n_rows is the whole domain check: -1, -2 and anything >= n_rows equal no row and are never used as an address.
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned int h) { return __builtin_bit_cast(float, h << 16); }
+
+// Channels-last: a wave per output row (b, r), lane l on the 16-byte (bf16 input: 8-byte) chunks l, l + 64, ... of every patch row it sums
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_nhwc_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
+                                                                 void* __restrict__ out, long rows, int P, int n_rows, int D) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                                 // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const long b = row / n_rows;
+  const int r = (int)(row - b * n_rows);
+  const int32_t* idx = index + (size_t)b * P;
+  float4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p0 = 0; p0 < P; p0 += 64) {
+    const int pl = p0 + lane;
+    unsigned long long mask = __ballot(pl < P && idx[pl] == r);
+    while (mask) {
+      const int p = p0 + __ffsll((long long)mask) - 1;     // p < P: only lanes with pl < P vote
+      mask &= mask - 1;
+      const size_t at = ((size_t)b * P + p) * D;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * lane + 256 * j;
+        if (c < D) {
+          float4 v;
+          if (IN_BF16) {
+            const uint2 u = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(dmap) + at + c);
+            v = make_float4(bf16_bits_to_f32(u.x & 0xffffu), bf16_bits_to_f32(u.x >> 16), bf16_bits_to_f32(u.y & 0xffffu), bf16_bits_to_f32(u.y >> 16));
+          } else {
+            v = *reinterpret_cast<const float4*>(static_cast<const float*>(dmap) + at + c);
+          }
+          acc[j].x += v.x;
+          acc[j].y += v.y;
+          acc[j].z += v.z;
+          acc[j].w += v.w;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = 4 * lane + 256 * j;
+    if (c < D) {
+      if (OUT_BF16) {
+        uint2 o;
+        o.x = bf16_rne_bits(acc[j].x) | (bf16_rne_bits(acc[j].y) << 16);
+        o.y = bf16_rne_bits(acc[j].z) | (bf16_rne_bits(acc[j].w) << 16);
+        *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + (size_t)row * D + c) = o;
+      } else {
+        *reinterpret_cast<float4*>(static_cast<float*>(out) + (size_t)row * D + c) = acc[j];
+      }
+    }
+  }
+}
+
+constexpr int DS_TR = 32;            // output rows per tile (8 per wave)
+constexpr int DS_TC = 64;            // channels per tile: a lane per channel
+
+// NCHW: tile (image b, rows r0 ... r0+31, channels c0 ... c0+63); lane l owns channel c0 + l of the rows of its wave and reads the single
+// elements dmap[b, c, p] of the row's patches (stride P between lanes), stores along c.  The image's index sits in LDS.  Wave w takes the rows
+// r0 + w, r0 + w + 4, ...: the four waves work on neighbouring rows -- with a pruning family's index neighbouring patches, the same lines of
+// the map -- at the same time.  The tiles of one image are consecutive logical ids (channel tile fastest) and xcd_remap gives an XCD a
+// contiguous run of them, as in the gather: a line of the image's D x P slab is fetched from HBM once and served by one L2 afterwards.
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_nchw_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
+                                                                 void* __restrict__ out, int P, int n_rows, int D, int rtiles, int ctiles) {
+  __shared__ int sidx[DI_MAX_P];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int ct = id % ctiles, rt = (id / ctiles) % rtiles, b = id / (ctiles * rtiles);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int p = threadIdx.x; p < P; p += 256) sidx[p] = index[(size_t)b * P + p];
+  __syncthreads();
+  const int c = ct * DS_TC + lane;
+  const bool mine = c < D;
+  const size_t col = ((size_t)b * D + (mine ? c : 0)) * P;  // channel c's P elements
+  for (int k = 0; k < DS_TR / 4; ++k) {
+    const int r = rt * DS_TR + wave + 4 * k;
+    if (r >= n_rows) break;                                // (wave-uniform)
+    float acc = 0.f;
+    for (int p0 = 0; p0 < P; p0 += 64) {
+      const int pl = p0 + lane;
+      unsigned long long mask = __ballot(pl < P && sidx[pl] == r);
+      while (mask) {
+        const int p = p0 + __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        if (mine) {
+          if (IN_BF16) acc += bf16_bits_to_f32(static_cast<const uint16_t*>(dmap)[col + p]);
+          else acc += static_cast<const float*>(dmap)[col + p];
+        }
+      }
+    }
+    if (mine) {
+      const size_t at = ((size_t)b * n_rows + r) * D + c;
+      if (OUT_BF16) static_cast<uint16_t*>(out)[at] = (uint16_t)bf16_rne_bits(acc);
+      else static_cast<float*>(out)[at] = acc;
+    }
+  }
+}
+
 }  // namespace
 
 // the stage table checked and copied into `tab` with every stage's n_out (tr_dense_index's rules, for both index entry points)
@@ -440,5 +549,37 @@ extern "C" int tr_dense_gather_levels(const float* tokens, size_t level_stride, 
 #undef DG_LAUNCH
   }
   TR_CHECK_LAUNCH("tr_dense_gather_levels");
+  return TR_OK;
+}
+
+extern "C" int tr_dense_scatter(const void* dmap, const int32_t* index, void* dtokens, int layout, int dmap_is_bf16, int out_is_bf16, int B, int P,
+                                int n_rows, int D, tr_stream_t s) {
+  TR_REQUIRE(dmap && index && dtokens, TR_ERR_NULL, "tr_dense_scatter: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_CONFIG, "tr_dense_scatter: layout %d (TR_LAYOUT_NCHW or TR_LAYOUT_NHWC)", layout);
+  TR_REQUIRE(B > 0 && P >= 1 && P <= DI_MAX_P && n_rows >= 1 && D > 0 && D % 4 == 0 && D <= 1024, TR_ERR_SHAPE,
+             "tr_dense_scatter: need B > 0, 1 <= P <= 1024, n_rows >= 1, D %% 4 == 0, D <= 1024 (B=%d P=%d n_rows=%d D=%d)", B, P, n_rows, D);
+  TR_REQUIRE(tr_aligned16(dmap) && tr_aligned16(index) && tr_aligned16(dtokens), TR_ERR_ALIGN, "tr_dense_scatter: pointers must be 16-byte aligned");
+  const bool ib = dmap_is_bf16 != 0, ob = out_is_bf16 != 0;
+  const long rows = (long)B * n_rows;
+  const int rtiles = (n_rows + DS_TR - 1) / DS_TR, ctiles = (D + DS_TC - 1) / DS_TC;
+  const long blocks = layout == TR_LAYOUT_NHWC ? (rows + 3) / 4 : (long)B * rtiles * ctiles;
+  TR_REQUIRE(blocks <= INT_MAX, TR_ERR_SHAPE, "tr_dense_scatter: %ld workgroups", blocks);
+  hipStream_t st = static_cast<hipStream_t>(s);
+  // required traffic: every element of the map once at most, every output element once, the index
+  tr_prof_note("tr_dense_scatter", 0.0, (double)B * P * D * (ib ? 2.0 : 4.0) + (double)rows * D * (ob ? 2.0 : 4.0) + 4.0 * B * P);
+  const dim3 grid((unsigned)blocks);
+#define DS_LAUNCH(IB, OB)                                                                                                          \
+  do {                                                                                                                             \
+    if (layout == TR_LAYOUT_NHWC)                                                                                                  \
+      hipLaunchKernelGGL((dense_scatter_nhwc_kernel<IB, OB>), grid, dim3(256), 0, st, dmap, index, dtokens, rows, P, n_rows, D);   \
+    else                                                                                                                           \
+      hipLaunchKernelGGL((dense_scatter_nchw_kernel<IB, OB>), grid, dim3(256), 0, st, dmap, index, dtokens, P, n_rows, D, rtiles, ctiles); \
+  } while (0)
+  if (ib && ob) DS_LAUNCH(true, true);
+  else if (ib) DS_LAUNCH(true, false);
+  else if (ob) DS_LAUNCH(false, true);
+  else DS_LAUNCH(false, false);
+#undef DS_LAUNCH
+  TR_CHECK_LAUNCH("tr_dense_scatter");
   return TR_OK;
 }

@@ -196,6 +196,11 @@ struct Bwd {
   size_t drop_off[TR_MAX_DEPTH + 1];      // where block i's masks start
   const float *dlogits, *dpred, *dfeat;
   float* dx;
+  // dense feature maps (tr_vit_backward_dense): the gradient of the final norm of EVERY row (bf16, or fp32 to be rounded) and the stream that
+  // entered the norm, the forward's stream_out; both NULL in every other call
+  const void* dtokens = nullptr;
+  bool dtokens_bf16 = false;
+  const float* dstream = nullptr;
   // The four parameter-gradient products of a block (fc2, fc1, proj, qkv) run as ONE launch after the attention backward, when all four dY
   // exist -- provided nothing has rewritten fc2's dY (the bf16 stream gradient gb) by then: norm2's backward writes its bf16 output into the
   // spare buffer instead and the two trade places.  With DropPath / dropout the scaled dY copies live in scratch that is reused: pairs then.
@@ -338,14 +343,24 @@ struct Bwd {
     TR_TRY(ln_bwd(dxcls, tape<float>(tp.xfinal), w->norm_g, grads->norm_g, grads->norm_b, nullptr, pool ? gpool : g, nullptr, B, cfg->ln_eps,
                   pool ? D : (long)Nl * D));
     if (pool) {
-      if (!walk) return TR_OK;      // the final norm was the lowest parameter
-      TR_TRY(tr_token_pool_bwd(gpool, trplan::pool_weighted(cfg->family) ? size_at(cfg->depth - 1, true) : nullptr, g, B, Nl, D, s));
+      if (!walk && dtokens == nullptr) return TR_OK;      // the final norm was the lowest parameter
+      if (walk) TR_TRY(tr_token_pool_bwd(gpool, trplan::pool_weighted(cfg->family) ? size_at(cfg->depth - 1, true) : nullptr, g, B, Nl, D, s));
     }
     if (dfeat != nullptr) {
       // distillation: gradient wrt the final norm of every row (dyvit.py:252): a second pass of the norm's backward over all rows
       TR_REQUIRE(cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward: dfeat is DyViT's distillation gradient");
       TR_TRY(tr_f32_to_bf16(dfeat, dxn, (size_t)B * Nl * D, s));
       TR_TRY(ln_bwd(dxn, tape<float>(tp.xfin_all), w->norm_g, grads->norm_g, grads->norm_b, g, g, nullptr, B * Nl, cfg->ln_eps, 0, 1));
+    }
+    if (dtokens != nullptr) {
+      // dense map: the same second pass for every family, on the caller's copy of the stream.  It adds into g -- the CLS rows' gradient, or
+      // the pool's spread -- and into the norm's parameter gradients; with a pooled head and no walk g holds nothing and is only scratch
+      const uint16_t* dy = U(dtokens);
+      if (!dtokens_bf16) {
+        TR_TRY(tr_f32_to_bf16(static_cast<const float*>(dtokens), dxn, (size_t)B * Nl * D, s));
+        dy = dxn;
+      }
+      TR_TRY(ln_bwd(dy, dstream, w->norm_g, grads->norm_g, grads->norm_b, (pool && !walk) ? nullptr : g, g, nullptr, B * Nl, cfg->ln_eps, 0, 1));
     }
     if (!walk) return TR_OK;      // the final norm was the lowest parameter
     TR_TRY(tr_f32_to_bf16(g, gb, (size_t)B * Nl * D, s));
@@ -666,8 +681,14 @@ extern "C" size_t tr_vit_backward_workspace_bytes(const tr_vit_config* cfg, int 
 static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
                         const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
                         size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
-                        tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
+                        tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens = nullptr,
+                        int dtokens_is_bf16 = 0, const float* stream = nullptr) {
   TR_REQUIRE(cfg && w && wt && grads && dlogits && tape_ && workspace, TR_ERR_NULL, "tr_vit_backward: null pointer");
+  if (dtokens != nullptr) {
+    TR_REQUIRE(stream != nullptr, TR_ERR_NULL, "tr_vit_backward_dense: dtokens needs the forward's stream_out");
+    TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward_dense: DyViT's feature gradient is dfeat");
+    TR_REQUIRE(tr_aligned16(dtokens) && tr_aligned16(stream), TR_ERR_ALIGN, "tr_vit_backward_dense: dtokens / stream must be 16-byte aligned");
+  }
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_backward: dropout needs the forward's keep mask AND its drop_rate (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
   TR_REQUIRE(cfg->precision == TR_PREC_BF16 && trplan::trainable_family(cfg->family), TR_ERR_CONFIG,
@@ -687,6 +708,9 @@ static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const
   if (blk_hi < stop && blk_hi < cfg->depth - 1) return TR_OK;        // the whole range lies below the stop block
 
   Bwd b(cfg, w, wt, grads, t, tp, bp, fr, B, s, tape_, workspace, accumulate, drop_scale, dropout_keep, drop_rate, dlogits, dpred, dfeat, dx);
+  b.dtokens = dtokens;
+  b.dtokens_bf16 = dtokens_is_bf16 != 0;
+  b.dstream = stream;
   b.rewind_to(blk_hi);
   if (blk_hi == cfg->depth - 1) {
     bool go = false;
@@ -727,4 +751,13 @@ extern "C" int tr_vit_backward_dx(const tr_vit_config* cfg, const tr_vit_weights
                                   tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx) {
   return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
                       s, dropout_keep, drop_rate, dx);
+}
+
+extern "C" int tr_vit_backward_dense(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                                     const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                                     size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                                     tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens,
+                                     int dtokens_is_bf16, const float* stream) {
+  return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
+                      s, dropout_keep, drop_rate, dx, dtokens, dtokens_is_bf16, stream);
 }

@@ -250,6 +250,9 @@ struct Fwd {
   uint32_t level_mask = 0;
   int level_norm = 0, level_i = 0;
   float* level_out = nullptr;
+  // dense feature maps in training (tr_vit_forward_train_dense): the stream entering the final norm and the final norm of every row go to
+  // the caller's buffers -- DyViT's distillation output with the tape's xfin_all slot replaced by a caller-owned one
+  float *dense_stream = nullptr, *dense_tokens = nullptr;
   // ---- the block being enqueued (pre_block, begin_block) ------------------------------------------------------------------------------
   bool have_xn = false;         // norm1(x) already in xn (written by a pre-block reducer)
   bool tail = false;            // this block runs as the CLS tail
@@ -950,6 +953,12 @@ struct Fwd {
       TR_TRY(tr_layernorm_f32(x, D, nullptr, D, w->norm_g, w->norm_b, features_out, B * N, D, cfg->ln_eps, s));
       pending = nullptr;
     }
+    if (train && dense_stream != nullptr) {
+      // the same two launches for a dense map of the last stream: every row's final norm is an output, the whole stream stays for its backward
+      TR_TRY(stream_to(dense_stream, pending, w->norm_g, w->norm_b, xn_shared, cfg->ln_eps));
+      TR_TRY(tr_layernorm_f32(x, D, nullptr, D, w->norm_g, w->norm_b, dense_tokens, B * N, D, cfg->ln_eps, s));
+      pending = nullptr;
+    }
     if (pool) return pooled_norm_head();
     if (train && headless)          // the CLS rows entering the norm stay on the tape (xfinal) for the backward; the tape's xcls is not needed
       return tr_layernorm_bf16_f32(x, ld, slot(tp->xfinal), D, u16(pending), ld, nullptr, 0, w->norm_g, w->norm_b, logits, B, D, cfg->ln_eps, s);
@@ -991,7 +1000,8 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
                             const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s, char* tape,
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
                             const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
-                            const tr_vit_taps* taps = nullptr, const tr_vit_levels* levels = nullptr) {
+                            const tr_vit_taps* taps = nullptr, const tr_vit_levels* levels = nullptr,
+                            const tr_vit_dense_train* dense = nullptr) {
   Plan p;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
@@ -1034,6 +1044,10 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
 
   Fwd f(cfg, w, p, B, s, workspace, tape, tp, img, input_format, pixel_lut, aug, aug_noise, aug_noise_len, logits, kept_idx, compl_idx, soft_out,
         noise_in, features_out, tokens_out, drop_scale, drop_keep, drop_rate, taps, levels);
+  if (dense != nullptr) {          // (validated by vit_forward_train_impl)
+    f.dense_stream = dense->stream_out;
+    f.dense_tokens = dense->tokens_out;
+  }
 
   // patch_embed -> cat(cls) + pos_embed -> depth x Block -> norm -> x[:,0] -> head, with
   // Block: [stage reducer]; x += attn(norm1(x)); [in-block reducer]; x += mlp(norm2(x))
@@ -1145,7 +1159,8 @@ extern "C" int tr_vit_tape_layout(const tr_vit_config* cfg, int B, int blk, size
 static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
                                   float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
                                   float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
-                                  float drop_rate, const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0) {
+                                  float drop_rate, const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
+                                  const tr_vit_dense_train* dense = nullptr) {
   TR_REQUIRE(cfg && tape, TR_ERR_NULL, "tr_vit_forward_train: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_forward_train: dropout needs a keep mask AND 0 < drop_rate < 1 (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
@@ -1159,9 +1174,60 @@ static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights
   for (int i = 0; i < cfg->depth; ++i)
     TR_REQUIRE(t.n_att[i] <= 640, TR_ERR_SHAPE, "tr_vit_forward_train: %d tokens in block %d (the training path holds 640)", t.n_att[i], i);
   TR_REQUIRE(features_out == nullptr || cfg->family == TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_forward_train: features_out is DyViT's distillation output");
-  return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, nullptr, noise_in,
-                          features_out, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate, aug, aug_noise,
-                          aug_noise_len);
+  if (dense == nullptr)
+    return vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, nullptr, noise_in,
+                            features_out, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate, aug, aug_noise,
+                            aug_noise_len);
+  // tr_vit_forward_train_dense: the caller's buffers, checked before any launch
+  const size_t slab = (size_t)B * t.N0;
+  TR_REQUIRE(dense->tokens_out && dense->stream_out, TR_ERR_NULL, "tr_vit_forward_train_dense: tokens_out / stream_out is NULL");
+  TR_REQUIRE((dense->kept_idx != nullptr) == (dense->compl_idx != nullptr), TR_ERR_NULL,
+             "tr_vit_forward_train_dense: kept_idx and compl_idx come together (both or neither)");
+  TR_REQUIRE(dense->rows_elems >= slab * cfg->embed_dim, TR_ERR_SHAPE, "tr_vit_forward_train_dense: tokens_out / stream_out hold %zu elements, [%d, %d, %d] needs %zu",
+             dense->rows_elems, B, t.N0, cfg->embed_dim, slab * cfg->embed_dim);
+  TR_REQUIRE(dense->kept_idx == nullptr || dense->idx_elems >= slab * cfg->depth, TR_ERR_SHAPE,
+             "tr_vit_forward_train_dense: kept_idx / compl_idx hold %zu elements, %d slabs of [%d, %d] need %zu", dense->idx_elems, cfg->depth, B, t.N0,
+             slab * cfg->depth);
+  size_t soft_need = 0;
+  if (trplan::soft_family(cfg->family))
+    for (int i = 0; i < cfg->depth; ++i) soft_need += t.kk[i] > 0 ? (size_t)B * t.kk[i] * (t.n_pre[i] - 1) : 0;
+  TR_REQUIRE(dense->soft_out == nullptr || dense->soft_elems >= soft_need, TR_ERR_SHAPE,
+             "tr_vit_forward_train_dense: soft_out holds %zu elements, the soft stages write %zu", dense->soft_elems, soft_need);
+  TR_REQUIRE(tr_aligned16(dense->tokens_out) && tr_aligned16(dense->stream_out) && tr_aligned16(dense->kept_idx) && tr_aligned16(dense->compl_idx) &&
+                 tr_aligned16(dense->soft_out),
+             TR_ERR_ALIGN, "tr_vit_forward_train_dense: the output buffers must be 16-byte aligned");
+  TR_TRY(vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, dense->soft_out, noise_in,
+                          nullptr, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate, aug, aug_noise,
+                          aug_noise_len, nullptr, nullptr, dense));
+  if (dense->kept_idx == nullptr) return TR_OK;
+  // the decisions stay on the tape for the backward; the slabs take a copy of each deciding block's two slots (a slot IS a slab: B * N0 ints,
+  // written by the kernels that write the eval slabs)
+  hipStream_t st = static_cast<hipStream_t>(s);
+  for (int i = 0; i < cfg->depth; ++i) {
+    if (t.kk[i] <= 0) continue;
+    const char* tb = static_cast<const char*>(tape);
+    TR_REQUIRE(hipMemcpyAsync(dense->kept_idx + i * slab, tb + tp.blk[i].idx, slab * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                   hipMemcpyAsync(dense->compl_idx + i * slab, tb + tp.blk[i].idx2, slab * 4, hipMemcpyDeviceToDevice, st) == hipSuccess,
+               TR_ERR_LAUNCH, "tr_vit_forward_train_dense: copy of block %d's decisions failed", i);
+  }
+  return TR_OK;
+}
+
+extern "C" int tr_vit_forward_train_dense(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format,
+                                          const float* pixel_lut, const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len,
+                                          float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes,
+                                          const float* noise_in, const float* drop_scale, int* tokens_out, int B, tr_stream_t s,
+                                          const uint8_t* dropout_keep, float drop_rate, const tr_vit_dense_train* dense) {
+  TR_REQUIRE(cfg && dense, TR_ERR_NULL, "tr_vit_forward_train_dense: null config or tr_vit_dense_train");
+  TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG,
+             "tr_vit_forward_train_dense: DyViT keeps every token under a policy in training and has its own feature output (features_out)");
+  if (aug != nullptr) {
+    TR_REQUIRE(input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
+               "tr_vit_forward_train_dense: the augmentation runs on uint8 pixels (input_format %d)", input_format);
+    TR_REQUIRE(B > 0 && B % 2 == 0, TR_ERR_SHAPE, "tr_vit_forward_train_dense: an augmented batch must be even, got B = %d", B);
+  }
+  return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in, nullptr,
+                                drop_scale, tokens_out, B, s, dropout_keep, drop_rate, aug, aug_noise, aug_noise_len, dense);
 }
 
 extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,

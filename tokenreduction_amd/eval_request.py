@@ -67,3 +67,16 @@ REFUSALS = {
     "decisions": _refusals("decision taps", "records no decisions", "records", "viz_data already holds Kept_Tokens / Assignment_Maps on the host",
                            _INPUT_FIRST),
     "dense": _refusals("dense feature maps", *_ROWS, _INPUT_FIRST)}
+
+# forward_dense_train, the dense map of a TRAINING forward: the same kind of table, checked in this order by models.forward_dense_train
+# ("args": _dense_arguments).  "dyvit" and "precision" raise NotImplementedError, the others RuntimeError.
+DENSE_TRAIN_REFUSALS = {
+    "eval": "{what} is the dense feature map of a training forward, with a gradient: call model.train() first (in eval mode forward_dense "
+            "returns the same map, without a gradient)",
+    "viz_mode": "{what} and viz_mode do not go together: viz_mode records an eval forward on the host; switch viz_mode off",
+    "cpu": REFUSE_CPU,
+    "dynamic_width": _DYNAMIC_WIDTH,
+    "args": None,
+    "precision": "{what}: the training path is bf16 (fp32 accumulate); set model.precision = 'bf16'",
+    "dyvit": "{what} is not built for DyViT: its training forward keeps every token in the stream under a differentiable policy, so there "
+             "is no reduced stream to put back on the grid, and it has a feature output of its own (dyvit_distillation)"}

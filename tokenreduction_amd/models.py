@@ -34,6 +34,8 @@ forward_dense / forward_async(dense=...) put the final-normed rows of the last b
 forward_dense(blocks=...) / get_intermediate_layers do the same for chosen intermediate blocks: the executor writes every row of those
 blocks while the fast path runs (tr_vit_forward_levels), each level is placed by the stages at or before its block, and one index launch and
 one gather launch serve all levels (tr_dense_index_levels, tr_dense_gather_levels).
+forward_dense_train is the last block's map of a TRAINING forward, a second output of the training autograd node: its gradient reaches the
+backbone through tr_dense_scatter (the gather's adjoint) and tr_vit_backward_dense (training.py).
 """
 from __future__ import annotations
 
@@ -50,7 +52,7 @@ import torch.nn as nn
 
 from . import _lib, pixels
 from .augment import AugmentedBatch
-from .eval_request import REFUSALS, REFUSE_CPU, DenseOutput, EvalRequest, Levels
+from .eval_request import DENSE_TRAIN_REFUSALS, REFUSALS, REFUSE_CPU, DenseOutput, EvalRequest, Levels
 
 
 def _pair(v):
@@ -933,12 +935,38 @@ class VisionTransformer(nn.Module):
         The forward stays on the fast path (tr_vit_forward_levels: one launch per level where its CLS tap would run; the CLS tail stays unless
         the last block is asked for), followed by tr_stage_decisions and ONE tr_dense_index_levels and ONE tr_dense_gather_levels for all
         levels; blocks and norm are part of the graph key.  blocks=None is the call described first, unchanged.
-        A soft-weighted un-merge, following EViT's fused token, training and a gradient are not built.  Refuses train mode, viz_mode,
-        dynamic_width and a block out of range."""
+        A soft-weighted un-merge and following EViT's fused token are not built; in train mode the last block's map, with a gradient, is
+        forward_dense_train's.  Refuses train mode, viz_mode, dynamic_width and a block out of range."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
         dense = dict(output_fmt=output_fmt, dtype=dtype, fill=fill, blocks=blocks, norm=norm)
         return self._forward_eval(x, 0, self._eval_request(x, "forward_dense", dense=dense))
+
+    def forward_dense_train(self, x: torch.Tensor, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
+        """Training forward with a dense feature map that carries a gradient: (out, {"features", "index", "grid"}).  `out` is what model(x)
+        returns in train mode (the logits, or the CLS features of a headless model), bit for bit; the dictionary has the shapes, layouts,
+        dtypes and index / fill semantics of eval's forward_dense (the last block's final-normed rows, single level).  `features` is the
+        second output of the SAME autograd node as `out`: any loss on it, on `out`, or on both drives loss.backward() into the parameters
+        through the HIP backward -- tr_dense_scatter (the gather's adjoint) takes the map's gradient back to the token rows, and
+        tr_vit_backward_dense adds the final norm's backward of every row to the stream gradient.  Gradient accumulation, frozen units, a
+        gradient reducer's block ranges, DropPath and dropout, uint8 and augmented inputs, x.grad and the one-tape guard behave as for
+        model(x).  `index` carries no gradient; a patch without a row shows `fill` and receives none.  The buffers (rows, stream, decision
+        slabs, index, map) are one set per model, like the tape; the map and the index are cloned out.
+        Refuses eval mode (use forward_dense), viz_mode, a CPU input, dynamic_width, a precision other than bf16 and DyViT.  Multi-level maps
+        in training, a differentiable eval forward, a soft-weighted un-merge and following EViT's fused token are not built."""
+        applies = {"eval": not self.training, "viz_mode": self.viz_mode, "cpu": not x.is_cuda, "dynamic_width": self.dynamic_width,
+                   "precision": self.precision != "bf16", "dyvit": self._family == _lib.TR_FAMILY_DYVIT}
+        dense = None
+        for check, message in DENSE_TRAIN_REFUSALS.items():
+            if check == "args":
+                dense, _ = self._dense_arguments(output_fmt=output_fmt, dtype=dtype, fill=fill)
+            elif applies[check]:
+                exc = NotImplementedError if check in ("precision", "dyvit") else RuntimeError
+                raise exc(message.format(what="forward_dense_train", device=x.device))
+        if isinstance(x, AugmentedBatch) and self.pixel_input is None:
+            x = x.float()         # pixel input off: the augmented fp32 image, then the float path (as forward does)
+        from . import training
+        return training.train_forward(self, x, dense)
 
     def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape=False, return_class_token=False, norm=False, dtype=torch.float32, fill=0.0):
         """timm's VisionTransformer.get_intermediate_layers on the fast path: the patch tokens after the last `n` blocks (int n) or after the

@@ -630,6 +630,33 @@ def dense_gather(tokens: torch.Tensor, index: torch.Tensor, layout: str = "NCHW"
     return out.view(shape)
 
 
+def dense_scatter(dmap: torch.Tensor, index: torch.Tensor, n_rows: int, layout: str = "NCHW", dtype=torch.float32,
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """The adjoint of dense_gather (tr_dense_scatter, one launch): dtokens[b, r, :] = the sum of dmap[b, :, p] over the patches p with
+    index[b, p] == r, 0 <= r < n_rows.  dmap [B, D, P] (layout "NCHW") or [B, P, D] ("NHWC"), fp32 or bf16; index int32 [B, P]; the result is
+    [B, n_rows, D], fp32 or bf16 (`dtype`: the fp32 sum rounded once, to nearest even).  The sum is in fp32, in ascending p; a row no patch
+    names is zero; an index entry outside [0, n_rows) owns nothing.  Every element of the result is written once, the same bits every time."""
+    _same_device(dmap, index, out)
+    if layout not in DENSE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(DENSE_LAYOUTS)}, got {layout!r}")
+    if dtype not in (torch.float32, torch.bfloat16) or dmap.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"dmap and dtype must be torch.float32 or torch.bfloat16, got {dmap.dtype} and {dtype}")
+    if dmap.dim() != 3 or index.dim() != 2 or index.shape[0] != dmap.shape[0]:
+        raise ValueError(f"dmap must be [B, D, P] / [B, P, D] and index [B, P], got {tuple(dmap.shape)} and {tuple(index.shape)}")
+    B, P = index.shape
+    D = dmap.shape[1] if layout == "NCHW" else dmap.shape[2]
+    if dmap.numel() != B * D * P:
+        raise ValueError(f"dmap {tuple(dmap.shape)} does not hold [B, D, P] = [{B}, {D}, {P}] in layout {layout}")
+    if out is None:
+        out = torch.empty(B, n_rows, D, dtype=dtype, device=dmap.device)
+    elif out.numel() != B * n_rows * D:
+        raise ValueError(f"out must hold {B * n_rows * D} elements, got {out.numel()}")
+    _lib.check(_lib.load().tr_dense_scatter(_dev(dmap, dmap.dtype, "dmap"), _dev(index, torch.int32, "index"), _dev(out, dtype, "out"),
+                                            DENSE_LAYOUTS[layout], int(dmap.dtype == torch.bfloat16), int(dtype == torch.bfloat16), B, P,
+                                            int(n_rows), D, _stream(dmap)), "tr_dense_scatter")
+    return out.view(B, n_rows, D)
+
+
 def _level_array(values, what):
     vals = [int(v) for v in values]
     if not 1 <= len(vals) <= _lib.TR_MAX_DEPTH:

@@ -12,6 +12,10 @@ pointers, and the backward stops at the lowest block that still has a trainable 
 The input takes a gradient like any autograd leaf: when `x.requires_grad` is set (or a module in front of the model trains) the
 backward runs `tr_vit_backward_dx`, which walks down to the embedding whatever is frozen and folds the patch projection's data gradient
 back into the image; the node returns it in x's slot and autograd accumulates `x.grad`.  Eval mode is not differentiable.
+`model.forward_dense_train(x)` is the same node with a dense request: `tr_vit_forward_train_dense` also leaves the final norm of every row,
+the stream that entered it and the decisions in the eval slabs' format; the eval path's three launches (tr_stage_decisions, tr_dense_index,
+tr_dense_gather) put the rows on the patch grid, and the map is the node's second output.  Its gradient goes through `tr_dense_scatter`
+(the gather's adjoint, bf16 out) into `tr_vit_backward_dense`, which adds the final norm's backward of every row to the stream gradient.
 
 PyTorch is plumbing: memory, the stream, the autograd hook and the loss.  No arithmetic of the model happens in torch.
 """
@@ -103,6 +107,7 @@ class TrainState:
         self._stage_names = {loc: [n for _, n in rows] for loc, rows in self.stage_grads.items() if rows}      # structure, not mask
         self._stage_of = {n: loc for loc, names in self._stage_names.items() for n in names}
         self.gen = 0                 # counts training forwards: the tape belongs to the LAST one (see _VitTrainFn.backward)
+        self.dense = None            # forward_dense_train's buffers (dense_buffers): one set per model, like the tape
 
     def _block_slices(self, model):
         """[(event_index, start, stop)] over the flat buffer: the slice event `e` of tr_vit_backward completes."""
@@ -224,6 +229,25 @@ class TrainState:
             self.B = B
         return self.tape, self.bws
 
+    def dense_buffers(self, model, B, dev):
+        """What forward_dense_train owns beside the tape, for one batch size: the executor's caller-owned outputs (the final norm of every
+        row, the stream entering it, the decision slabs) under their tr_vit_dense_train struct, the decision plan of the eval path
+        (models._decision_plan: the stage table and tr_stage_decisions' record buffers), the index, one map per output dtype and the bf16
+        token gradient tr_dense_scatter writes for the backward."""
+        d = self.dense
+        if d is None or d["B"] != B or d["dev"] != dev:
+            P0, D = model.patch_embed.num_patches, model.embed_dim
+            rows = B * (P0 + 1) * D
+            empty = lambda n, dtype=torch.float32: torch.empty(n, dtype=dtype, device=dev)
+            d = dict(B=B, dev=dev, tokens=empty(rows), stream=empty(rows), kept=empty(model.depth * B * (P0 + 1), torch.int32),
+                     compl=empty(model.depth * B * (P0 + 1), torch.int32), index=empty(B * P0, torch.int32), feat={},
+                     dtok=empty(rows, torch.bfloat16))
+            dec = d["plan"] = model._decision_plan(d, B, dev)          # (keeps itself in d["dec"])
+            d["struct"] = _lib.TrVitDenseTrain(d["tokens"].data_ptr(), d["stream"].data_ptr(), rows, d["kept"].data_ptr(), d["compl"].data_ptr(),
+                                               d["kept"].numel(), dec["soft_ptr"], dec["soft_elems"])
+            self.dense = d
+        return d
+
 
 TAPE_FIELDS = ("x0", "x1", "xn1", "qkv", "ao", "dattn", "x2", "xn2", "pre", "h", "idx", "idx2", "scores", "size",
                "n_pre", "n_att", "n_mlp", "kk")
@@ -307,10 +331,12 @@ def dropout_keep_mask(model, pk, B: int, dev):
 class _VitTrainFn(torch.autograd.Function):
     """logits (+ DyViT's extra outputs) = model(x) with the backward wired to tr_vit_backward.  `anchor` only makes autograd call
     backward.  Outputs: (logits,) or for DyViT (logits, pred_0 .. pred_{S-1} [, features]): pred_j = the stage's hard keep decision
-    [B,P] (straight-through differentiable, dyvit.py:223-225), features = the final norm of the patch tokens [B,P,D]."""
+    [B,P] (straight-through differentiable, dyvit.py:223-225), features = the final norm of the patch tokens [B,P,D].
+    dense (an eval_request.DenseOutput; not DyViT): forward_dense_train's request -- the outputs are (logits, map), the map as eval's
+    forward_dense lays it out; the index stays in TrainState.dense.  Without it the inputs, outputs and launches are those above."""
 
     @staticmethod
-    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None, xe=None):
+    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None, xe=None, dense=None):
         lib = _lib.load()
         pk = model._pack(need_transposed=True)
         cfg = pk["cfg"]
@@ -340,12 +366,19 @@ class _VitTrainFn(torch.autograd.Function):
         noise = model._gumbel_ptr(B, x.device) if dyvit else model._noise_ptr(B, x.device)
         ctx.drop = drop_path_scales(model, B, x.device)
         ctx.keep_mask = dropout_keep_mask(model, pk, B, x.device)
+        dn = st.dense_buffers(model, B, x.device) if dense is not None else None
         with torch.cuda.device(x.device):
             rest = (logits.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], tape.data_ptr(), tape.numel(), noise,
                     None if feats is None else feats.data_ptr(), None if ctx.drop is None else ctx.drop.data_ptr(), tokens, B,
                     torch.cuda.current_stream().cuda_stream, None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(),
                     float(model.drop_rate or 0.0))
-            if aug is not None:      # uint8 pixels + the device-side erase / mixup / cutmix table (augment.py): the columns of the augmented image
+            if dn is not None:       # the superset entry: any of the three inputs below, plus the dense request's caller-owned outputs
+                table, aug_noise = aug if aug is not None else (None, None)
+                rc = lib.tr_vit_forward_train_dense(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut,
+                                                    None if table is None else table.data_ptr(),
+                                                    aug_noise.data_ptr() if aug_noise is not None and aug_noise.numel() else None,
+                                                    0 if aug_noise is None else aug_noise.numel(), *rest[:6], *rest[7:], C.byref(dn["struct"]))
+            elif aug is not None:    # uint8 pixels + the device-side erase / mixup / cutmix table (augment.py): the columns of the augmented image
                 table, aug_noise = aug
                 rc = lib.tr_vit_forward_train_aug(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, table.data_ptr(),
                                                   aug_noise.data_ptr() if aug_noise.numel() else None, aug_noise.numel(), *rest)
@@ -358,8 +391,14 @@ class _VitTrainFn(torch.autograd.Function):
         ctx.model, ctx.B, ctx.pk = model, B, pk
         ctx.keep = (x, aug)
         ctx.n_pred, ctx.distill = 0, distill
+        ctx.dense = dense
+        if dense is not None:
+            ctx.set_materialize_grads(False)      # a loss on one output alone: the other's gradient arrives as None and its path is skipped
         if model._out_width != model._out_cols:          # the padded classifier columns never leave the executor
             logits = logits[:, :model._out_cols].contiguous()
+        if dn is not None:
+            with torch.cuda.device(x.device):
+                return logits, _dense_map(model, dn, dense, list(tokens), B)
         if not dyvit:
             return logits
         preds = []
@@ -393,7 +432,21 @@ class _VitTrainFn(torch.autograd.Function):
             dlp = torch.zeros(B, model._out_width, dtype=torch.float32, device=dev)
             dlp[:, :model._out_cols] = dl
             dl = dlp
-        dpred = dfeat = None
+        dpred = dfeat = dtok = None
+        if ctx.dense is not None and dextra[0] is not None:
+            # the map's gradient back on the token rows: tr_dense_scatter with the forward's index (the gen guard above keeps it the
+            # forward's), bf16 out -- the form the final norm's backward reads
+            dn, P0 = st.dense, model.patch_embed.num_patches
+            dmap = dextra[0].detach()
+            if dmap.dtype not in (torch.float32, torch.bfloat16):
+                dmap = dmap.to(torch.float32)
+            dmap = dmap.contiguous()
+            with torch.cuda.device(dev):
+                _lib.check(lib.tr_dense_scatter(dmap.data_ptr(), dn["index"].data_ptr(), dn["dtok"].data_ptr(),
+                                                _lib.TR_LAYOUT_NCHW if ctx.dense.fmt == "NCHW" else _lib.TR_LAYOUT_NHWC,
+                                                int(dmap.dtype == torch.bfloat16), 1, B, P0, dn["rows"], model.embed_dim,
+                                                torch.cuda.current_stream().cuda_stream), "tr_dense_scatter")
+            dtok = dn["dtok"]
         if ctx.n_pred:
             P = model.patch_embed.num_patches
             gp = [torch.zeros(B, P, dtype=torch.float32, device=dev) if g is None else g.detach().to(torch.float32) for g in dextra[:ctx.n_pred]]
@@ -438,7 +491,10 @@ class _VitTrainFn(torch.autograd.Function):
                         None if dpred is None else dpred.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
                         None if ctx.drop is None else ctx.drop.data_ptr(), st.tape.data_ptr(), st.tape.numel(), st.bws.data_ptr(), st.bws.numel(), accumulate, hi, lo, B, stream,
                         None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(), float(model.drop_rate or 0.0))
-                rc = lib.tr_vit_backward(*args) if dx is None else lib.tr_vit_backward_dx(*args, dx.data_ptr())
+                if dtok is not None:     # every range call takes it; the one with hi == depth - 1 consumes it
+                    rc = lib.tr_vit_backward_dense(*args, None if dx is None else dx.data_ptr(), dtok.data_ptr(), 1, st.dense["stream"].data_ptr())
+                else:
+                    rc = lib.tr_vit_backward(*args) if dx is None else lib.tr_vit_backward_dx(*args, dx.data_ptr())
                 _lib.check(rc, "tr_vit_backward")
                 st.ls_unfold(hi, lo, accumulate, dev)
                 if reduce_now:
@@ -457,10 +513,35 @@ class _VitTrainFn(torch.autograd.Function):
         model._dirty_by_backward = not was_dirty      # dirt that was there before this backward is somebody else's: only a full repack clears it
         if dx is not None and dx.dtype != ctx.x_dtype:
             dx = dx.to(ctx.x_dtype)
-        return None, dx, None, None, None, None, None
+        return None, dx, None, None, None, None, None, None
 
 
-def train_forward(model, x: torch.Tensor) -> torch.Tensor:
+def _dense_map(model, dn, dense, tokens, B):
+    """The eval path's launches behind the training executor (models._launch_outputs): the decision slabs -> record form, the records composed
+    into one row per grid patch, the un-reduce of the final-normed rows.  Returns the map, cloned out of its per-model buffer; the index
+    stays in dn["index"] for the backward."""
+    lib, dec, stream = _lib.load(), dn["plan"], torch.cuda.current_stream().cuda_stream
+    D, P0, n_last = model.embed_dim, model.patch_embed.num_patches, tokens[model.depth - 1]
+    if dec["static"] is None and not dec["checked"]:
+        model._decision_result(dec, B, tokens)                   # the stage table against the training forward's token counts, once
+    if dec["n"]:
+        _lib.check(lib.tr_stage_decisions(dn["kept"].data_ptr(), dn["compl"].data_ptr(), dn["kept"].numel(), dec["soft_ptr"], dec["soft_elems"],
+                                          dec["table"], dec["n"], B, P0 + 1, dec["kept_ptr"], dec["kept_elems"], dec["count_ptr"],
+                                          dec["assign_ptr"], dec["assign_elems"], stream), "tr_stage_decisions")
+    feat = dn["feat"].get(dense.dtype)
+    if feat is None:
+        feat = dn["feat"][dense.dtype] = torch.empty(B * P0 * D, dtype=dense.dtype, device=dn["dev"])
+    _lib.check(lib.tr_dense_index(dec["kept_ptr"], dec["kept_elems"], dec["assign_ptr"], dec["assign_elems"], dec["table"], dec["n"], B, P0,
+                                  n_last, dn["index"].data_ptr(), stream), "tr_dense_index")
+    _lib.check(lib.tr_dense_gather(dn["tokens"].data_ptr(), dn["index"].data_ptr(), feat.data_ptr(),
+                                   _lib.TR_LAYOUT_NCHW if dense.fmt == "NCHW" else _lib.TR_LAYOUT_NHWC, int(dense.dtype == torch.bfloat16),
+                                   dense.fill, B, P0, n_last, D, stream), "tr_dense_gather")
+    dn["rows"] = n_last
+    h, w = model.patch_embed.grid_size
+    return feat.clone().view((B, D, h, w) if dense.fmt == "NCHW" else (B, h, w, D))
+
+
+def train_forward(model, x: torch.Tensor, dense=None):
     if model._family == _lib.TR_FAMILY_DYVIT and model._pool_mode() == _lib.TR_POOL_AVG:
         raise NotImplementedError("global_pool='avg' is not built for DyViT in train mode: training keeps the masked tokens in the stream under a "
                                   "differentiable policy (dyvit.py:221-229), so there is no token set to average over; DyViT eval, where the tokens "
@@ -485,9 +566,13 @@ def train_forward(model, x: torch.Tensor) -> torch.Tensor:
     # tensor, as before
     anchor = torch.empty(0, dtype=torch.float32, device=xe.device, requires_grad=True)
     if fmt == _lib.TR_INPUT_F32 and aug is None and x.requires_grad and torch.is_grad_enabled():
-        out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug, xe)
+        out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug, xe, dense)
     else:
-        out = _VitTrainFn.apply(anchor, xe, model, fmt, lut, aug)
+        out = _VitTrainFn.apply(anchor, xe, model, fmt, lut, aug, None, dense)
+    if dense is not None:            # forward_dense_train: (out, the map); the index is a copy of the per-model buffer and carries no gradient
+        h, w = model.patch_embed.grid_size
+        st = model._train_state()
+        return out[0], {"features": out[1], "index": st.dense["index"].clone().view(x.shape[0], h * w), "grid": (h, w)}
     if model._family != _lib.TR_FAMILY_DYVIT:
         return out
     # dyvit.py:257-261: (x, features, prev_decision.detach(), out_pred_prob) with the DyViT distillation scheme, else (x, out_pred_prob)
