@@ -501,7 +501,8 @@ def test_patch_embed_fused(ops, B, HW, D, C):
 @pytest.mark.parametrize("M,D", [(394, 384), (33, 768), (7, 128), (5, 192)])
 def test_layernorm_with_two_pending_residuals(ops, M, D):
     """The eval executor's lazy norm2: norm2 normalises x + d_attn WITHOUT writing it, the next norm1 takes (x + d_attn) + d_mlp and
-    writes the stream once -- bit for bit what the two eager in-place calls produce (outputs and stream)."""
+    writes the stream once -- bit for bit what the two eager in-place calls produce (outputs and stream).  Both forms against a float64
+    reference at the shape and value edges: tests/test_hip_layernorm_fwd_edges.py::test_layernorm_forms."""
     rng = _rng(700 + M + D)
     x = _randn(rng, M, D) * 2 + 0.3
     d1, d2 = _randn(rng, M, D).bfloat16(), _randn(rng, M, D).bfloat16()
@@ -519,6 +520,8 @@ def test_layernorm_with_two_pending_residuals(ops, M, D):
 # ------------------------------------------------------------------------------------------ LayerNorm
 @pytest.mark.parametrize("M,D", [(7, 128), (394, 384), (33, 768), (5, 192), (3, 1024)])
 def test_layernorm(ops, M, D):
+    """The in-place form at five everyday shapes.  Chunk-count boundaries, workgroup tails, a second eps, the value edges and out-of-range
+    writes are held by tests/test_hip_layernorm_fwd_edges.py."""
     rng = _rng(M + D)
     x, g, b = _randn(rng, M, D) * 3 + 0.5, 1 + _randn(rng, D, scale=0.1), _randn(rng, D, scale=0.1)
     want = torch.nn.functional.layer_norm(x.double(), (D,), g.double(), b.double(), 1e-6).float()
@@ -528,7 +531,8 @@ def test_layernorm(ops, M, D):
 
 @pytest.mark.parametrize("M,D", [(394, 384), (9, 768), (5, 128)])
 def test_layernorm_with_pending_residual(ops, M, D):
-    """x += delta (bf16 Linear output) written back, then LayerNorm: `x = x + drop_path(...)` folded into the next norm."""
+    """x += delta (bf16 Linear output) written back, then LayerNorm: `x = x + drop_path(...)` folded into the next norm.
+    Every residual form at the shape and value edges: tests/test_hip_layernorm_fwd_edges.py::test_layernorm_forms."""
     rng = _rng(M * 3 + D)
     x, d = _randn(rng, M, D), _bf(_randn(rng, M, D, scale=0.3))
     g, b = 1 + _randn(rng, D, scale=0.1), _randn(rng, D, scale=0.1)
@@ -541,6 +545,8 @@ def test_layernorm_with_pending_residual(ops, M, D):
 
 
 def test_layernorm_strided_rows(ops):
+    """The CLS rows of [B, N, D] at stride N D.  Other widths and row counts, and the rows the launch must step over:
+    tests/test_hip_layernorm_fwd_edges.py::test_layernorm_forms (cls_rows)."""
     rng = _rng(9)
     B, N, D = 4, 69, 384
     x, g, b = _randn(rng, B, N, D), 1 + _randn(rng, D, scale=0.1), _randn(rng, D, scale=0.1)
@@ -646,6 +652,8 @@ def test_cls_topk_ties_lowest_index_first(ops):
 @pytest.mark.parametrize("fuse", [False, True])
 @pytest.mark.parametrize("B,N,K,D", [(3, 197, 137, 384), (2, 138, 96, 128), (2, 98, 67, 768), (1, 5, 1, 192)])
 def test_gather_layernorm(ops, fuse, with_delta, B, N, K, D):
+    """The model's shapes (at most 59 dropped tokens).  The four-row tails, the fused row past 256 dropped tokens, the fp32 path and
+    K = N - 1: tests/test_hip_layernorm_fwd_edges.py::test_gather_layernorm_edges and its neighbours."""
     rng = _rng(N + K + D + fuse)
     x = _randn(rng, B, N, D)
     delta = _bf(_randn(rng, B, N, D, scale=0.3)) if with_delta else None

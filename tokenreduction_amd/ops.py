@@ -365,14 +365,37 @@ def mlp_fused_resid_ln(xn: torch.Tensor, packed: torch.Tensor, fc1_b: torch.Tens
     return xn_next
 
 
+def _ln_out(y, shape, dtype, name: str, dev) -> torch.Tensor:
+    """A forward LayerNorm's output: a fresh tensor, or the caller's own contiguous one (a slice of a larger buffer: what lies around it
+    can be watched)."""
+    if y is None:
+        return torch.empty(*shape, dtype=dtype, device=dev)
+    if tuple(y.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(y.shape)}")
+    _dev(y, dtype, name)
+    return y
+
+
+def _ln_rows(t, dtype, name: str, ld: int = None):
+    """(pointer, row stride) of a LayerNorm row operand, or (None, 0): contiguous, or a 2-D column slice of a wider tensor whose row stride is
+    taken from the view; `ld` overrides the stride told to the C ABI."""
+    if t is None:
+        return None, 0 if ld is None else ld
+    if t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == dtype:
+        p, s = t.data_ptr(), t.stride(0)
+    else:
+        p, s = _dev(t, dtype, name), t.shape[-1]
+    return p, s if ld is None else ld
+
+
 def layernorm(x: torch.Tensor, gamma, beta, eps: float, rows: int = None, ldx: int = None, delta: torch.Tensor = None,
-              ldd: int = None) -> torch.Tensor:
+              ldd: int = None, y: torch.Tensor = None) -> torch.Tensor:
     """[x += delta (bf16, written back);] nn.LayerNorm over the last dim of fp32 x -> bf16 [M,D]
-    (optionally only `rows` rows at stride ldx / ldd)."""
+    (optionally only `rows` rows at stride ldx / ldd).  y: the caller's own bf16 [M,D] output."""
     D = x.shape[-1]
     M = rows if rows is not None else x.numel() // D
     ld = ldx if ldx is not None else D
-    y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
+    y = _ln_out(y, (M, D), torch.bfloat16, "y", x.device)
     _lib.check(_lib.load().tr_layernorm_bf16(_dev(x, torch.float32, "x"), ld, _opt(delta, torch.bfloat16, "delta"),
                                              ldd if ldd is not None else D, _dev(gamma, torch.float32, "gamma"),
                                              _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps, _stream()),
@@ -405,19 +428,38 @@ def cls_topk(cls_rows: torch.Tensor, K: int, want_compl: bool = False):
     return idx, compl, scores
 
 
-def gather_layernorm(x: torch.Tensor, idx, compl, scores, gamma, beta, eps: float, delta: torch.Tensor = None):
+def gather_layernorm(x: torch.Tensor, idx, compl, scores, gamma, beta, eps: float, delta: torch.Tensor = None, x_out: torch.Tensor = None,
+                     y: torch.Tensor = None, f32: bool = False):
     """Top-K gather/compact (topk.py:89-93) [+ EViT fused token evit.py:111-123] fused with norm2.
     With delta (bf16 [B,N,D], pending attn.proj output) the gather reads x + delta.
-    x fp32 [B,N,D] -> (x_out fp32 [B,N_out,D], y bf16 [B,N_out,D])."""
+    x fp32 [B,N,D] -> (x_out fp32 [B,N_out,D], y bf16 [B,N_out,D]).  idx None: the plain LayerNorm of all N rows through the gather kernel
+    (x_out None unless the caller passes one).  x_out / y: the caller's own outputs.  f32: tr_gather_layernorm_f32 (fp32 delta and y).
+    compl of shape [B, 0] (everything kept, K = N - 1) still asks for the fused row: an empty weighted sum, exactly zero."""
     B, N, D = x.shape
-    K = idx.shape[1]
-    N_out = K + 1 + (1 if compl is not None else 0)
-    x_out = torch.empty(B, N_out, D, dtype=torch.float32, device=x.device)
-    y = torch.empty(B, N_out, D, dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.load().tr_gather_layernorm_bf16(
-        _dev(x, torch.float32, "x"), _opt(delta, torch.bfloat16, "delta"), _dev(idx, torch.int32, "idx"), _opt(compl, torch.int32, "compl"),
-        _opt(scores, torch.float32, "scores"), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
-        x_out.data_ptr(), y.data_ptr(), B, N, K, D, eps, _stream()), "tr_gather_layernorm_bf16")
+    ydt, ddt = (torch.float32, torch.float32) if f32 else (torch.bfloat16, torch.bfloat16)
+    if idx is None:
+        if compl is not None:
+            raise ValueError("gather_layernorm: compl without idx")
+        K, N_out, pidx, pcompl = 0, N, None, None
+        if x_out is not None:
+            x_out = _ln_out(x_out, (B, N_out, D), torch.float32, "x_out", x.device)
+    else:
+        K = idx.shape[1]
+        N_out = K + 1 + (1 if compl is not None else 0)
+        pidx, pcompl = _dev(idx, torch.int32, "idx"), None
+        if compl is not None:
+            if tuple(compl.shape) != (B, N - 1 - K):
+                raise ValueError(f"gather_layernorm: compl is {tuple(compl.shape)}, expected {(B, N - 1 - K)}")
+            # the C ABI reads "fuse" from compl_idx != NULL, and an empty tensor has no storage (data_ptr() == 0): hand over idx's pointer,
+            # of which the kernel reads no element when the complement is empty
+            pcompl = _dev(compl, torch.int32, "compl") if compl.numel() else pidx
+        x_out = _ln_out(x_out, (B, N_out, D), torch.float32, "x_out", x.device)
+    y = _ln_out(y, (B, N_out, D), ydt, "y", x.device)
+    lib = _lib.load()
+    fn, what = (lib.tr_gather_layernorm_f32, "tr_gather_layernorm_f32") if f32 else (lib.tr_gather_layernorm_bf16, "tr_gather_layernorm_bf16")
+    _lib.check(fn(_dev(x, torch.float32, "x"), _opt(delta, ddt, "delta"), pidx, pcompl,
+                  _opt(scores, torch.float32, "scores"), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+                  None if x_out is None else x_out.data_ptr(), y.data_ptr(), B, N, K, D, eps, _stream()), what)
     return x_out, y
 
 
@@ -444,26 +486,41 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, epilogue: int
     return out
 
 
-def layernorm2(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor, delta2: torch.Tensor = None, write_x: bool = True) -> torch.Tensor:
+def layernorm2(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor, delta2: torch.Tensor = None, write_x: bool = True,
+               y: torch.Tensor = None, x_out: torch.Tensor = None, rows: int = None, ldx: int = None, ldxo: int = None, ldd: int = None,
+               ldd2: int = None) -> torch.Tensor:
     """y = LayerNorm((x + delta) + delta2) -> bf16 [M,D]; the sum is written back to x unless write_x is False (tr_layernorm2_bf16:
-    the eval executor's norm2 without a stream write, and the norm1 that absorbs both pending residuals after it)."""
+    the eval executor's norm2 without a stream write, and the norm1 that absorbs both pending residuals after it).
+    y: the caller's own output; x_out: the sum goes there and x is not written; x, x_out, delta and delta2 may be 2-D column slices
+    (their row stride is told to the C ABI; ldx / ldxo / ldd / ldd2 override it); rows: only that many rows."""
     D = x.shape[-1]
-    M = x.numel() // D
-    y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
-    xp = _dev(x, torch.float32, "x")
-    _lib.check(_lib.load().tr_layernorm2_bf16(xp, D, xp if write_x else None, D, _dev(delta, torch.bfloat16, "delta"), D,
-                                              _opt(delta2, torch.bfloat16, "delta2"), D, _dev(gamma, torch.float32, "gamma"),
+    M = rows if rows is not None else x.numel() // D
+    y = _ln_out(y, (M, D), torch.bfloat16, "y", x.device)
+    xp, sx = _ln_rows(x, torch.float32, "x", ldx)
+    if x_out is not None:
+        if not write_x:
+            raise ValueError("layernorm2: x_out together with write_x=False")
+        po, so = _ln_rows(x_out, torch.float32, "x_out", ldxo)
+    else:
+        po, so = (xp, sx if ldxo is None else ldxo) if write_x else (None, D if ldxo is None else ldxo)
+    pd, sd = _ln_rows(delta, torch.bfloat16, "delta", ldd)
+    pd2, sd2 = _ln_rows(delta2, torch.bfloat16, "delta2", ldd2) if delta2 is not None else (None, D if ldd2 is None else ldd2)
+    _lib.check(_lib.load().tr_layernorm2_bf16(xp, sx, po, so, pd, sd, pd2, sd2, _dev(gamma, torch.float32, "gamma"),
                                               _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps, _stream()), "tr_layernorm2_bf16")
     return y
 
 
-def layernorm_f32(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None) -> torch.Tensor:
+def layernorm_f32(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None, y: torch.Tensor = None, rows: int = None,
+                  ldx: int = None, ldd: int = None) -> torch.Tensor:
+    """tr_layernorm_f32: [x += delta (fp32, written back);] LayerNorm in the reference's arithmetic -> fp32 [M,D].  y: the caller's own
+    output; x and delta may be 2-D column slices (ldx / ldd override the row stride); rows: only that many rows."""
     D = x.shape[-1]
-    M = x.numel() // D
-    y = torch.empty(M, D, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().tr_layernorm_f32(_dev(x, torch.float32, "x"), D, _opt(delta, torch.float32, "delta"), D,
-                                            _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D,
-                                            eps, _stream()), "tr_layernorm_f32")
+    M = rows if rows is not None else x.numel() // D
+    y = _ln_out(y, (M, D), torch.float32, "y", x.device)
+    xp, sx = _ln_rows(x, torch.float32, "x", ldx)
+    pd, sd = _ln_rows(delta, torch.float32, "delta", ldd) if delta is not None else (None, D if ldd is None else ldd)
+    _lib.check(_lib.load().tr_layernorm_f32(xp, sx, pd, sd, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+                                            y.data_ptr(), M, D, eps, _stream()), "tr_layernorm_f32")
     return y
 
 
@@ -1560,30 +1617,38 @@ def _rows2d(t, dtype, name):
     return t.data_ptr(), t.stride(0)
 
 
-def layernorm_to(x: torch.Tensor, x_out: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None) -> torch.Tensor:
+def layernorm_to(x: torch.Tensor, x_out: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None, y: torch.Tensor = None,
+                 ldxo: int = None, ldd: int = None) -> torch.Tensor:
     """layernorm out of place (tr_layernorm_bf16_to): x_out = x + delta, y = LayerNorm(x_out) -> bf16 [M,D]; x is not written.  x, x_out
-    (fp32) and delta (bf16) are [M,D] rows, possibly column slices of wider tensors."""
+    (fp32) and delta (bf16) are [M,D] rows, possibly column slices of wider tensors.  y: the caller's own output; ldxo / ldd override the
+    row strides taken from the views."""
     M, D = x.shape
     _same_device(x, x_out, gamma, beta, delta)
     (px, ldx), (po, ldo) = _rows2d(x, torch.float32, "x"), _rows2d(x_out, torch.float32, "x_out")
-    pd, ldd = _rows2d(delta, torch.bfloat16, "delta") if delta is not None else (None, D)
-    y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.load().tr_layernorm_bf16_to(px, ldx, po, ldo, pd, ldd, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+    pd, sd = _rows2d(delta, torch.bfloat16, "delta") if delta is not None else (None, D)
+    ldo, sd = ldo if ldxo is None else ldxo, sd if ldd is None else ldd
+    y = _ln_out(y, (M, D), torch.bfloat16, "y", x.device)
+    _lib.check(_lib.load().tr_layernorm_bf16_to(px, ldx, po, ldo, pd, sd, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
                                                 y.data_ptr(), M, D, eps, _stream(x)), "tr_layernorm_bf16_to")
     return y
 
 
 def layernorm_bf16_f32(x: torch.Tensor, gamma, beta, eps: float, delta: torch.Tensor = None, delta2: torch.Tensor = None,
-                       x_out: torch.Tensor = None) -> torch.Tensor:
+                       x_out: torch.Tensor = None, y: torch.Tensor = None, rows: int = None, ldx: int = None, ldxo: int = None,
+                       ldd: int = None, ldd2: int = None) -> torch.Tensor:
     """The bf16 path's LayerNorm with fp32 output (tr_layernorm_bf16_f32): y fp32 [M,D] = LayerNorm((x + delta) + delta2); the sum goes to
-    x_out (x itself: in place; None: not written)."""
-    M, D = x.shape
+    x_out (x itself: in place; None: not written).  y: the caller's own output; x, x_out, delta and delta2 may be 2-D column slices (their
+    row stride is told to the C ABI; ldx / ldxo / ldd / ldd2 override it); rows: only that many rows."""
+    D = x.shape[-1]
+    M = rows if rows is not None else x.numel() // D
     _same_device(x, gamma, beta, delta, delta2, x_out)
-    y = torch.empty(M, D, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().tr_layernorm_bf16_f32(_dev(x, torch.float32, "x"), D, _opt(x_out, torch.float32, "x_out"), D,
-                                                 _opt(delta, torch.bfloat16, "delta"), D, _opt(delta2, torch.bfloat16, "delta2"), D,
-                                                 _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps,
-                                                 _stream(x)), "tr_layernorm_bf16_f32")
+    y = _ln_out(y, (M, D), torch.float32, "y", x.device)
+    xp, sx = _ln_rows(x, torch.float32, "x", ldx)
+    po, so = _ln_rows(x_out, torch.float32, "x_out", ldxo) if x_out is not None else (None, D if ldxo is None else ldxo)
+    pd, sd = _ln_rows(delta, torch.bfloat16, "delta", ldd) if delta is not None else (None, D if ldd is None else ldd)
+    pd2, sd2 = _ln_rows(delta2, torch.bfloat16, "delta2", ldd2) if delta2 is not None else (None, D if ldd2 is None else ldd2)
+    _lib.check(_lib.load().tr_layernorm_bf16_f32(xp, sx, po, so, pd, sd, pd2, sd2, _dev(gamma, torch.float32, "gamma"),
+                                                 _dev(beta, torch.float32, "beta"), y.data_ptr(), M, D, eps, _stream(x)), "tr_layernorm_bf16_f32")
     return y
 
 
