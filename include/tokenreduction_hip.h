@@ -232,6 +232,14 @@ int tr_cls_tap(const float* x, long ldx, const void* d1, long ld1, const void* d
                int D, tr_stream_t s);
 int tr_final_tokens_f32(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* gamma, const float* beta, float* y,
                         int M, int D, float eps, tr_stream_t s);
+/* tr_level_tap_norm: both taps of contiguous rows [M, D] in ONE launch, for the level taps of a training forward: sum[row] = (x + d1) + d2 --
+ * the bits of tr_cls_tap at row stride D -- and y[row] = its fp32 LayerNorm -- the bits of tr_final_tokens_f32; x and the pending operands are
+ * read once, two rows are stored.  Operands, alignment and refusals are tr_final_tokens_f32's; sum and y are 16-byte aligned. */
+int tr_level_tap_norm(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* gamma, const float* beta, float* sum,
+                      float* y, int M, int D, float eps, tr_stream_t s);
+/* tr_stream_grad_add: g[i] += d[i] in fp32 and gb[i] = bf16(g[i]) (round to nearest even; gb nullable), n % 4 == 0: the gradient of a level's
+ * rows taken as they stand joins the stream gradient of tr_vit_backward_levels. */
+int tr_stream_grad_add(const float* d, float* g, uint16_t* gb, size_t n, tr_stream_t s);
 /* Average-pooled head (tr_vit_config.global_pool == 1; csrc/tr_pool.hip): timm's global_pool='avg' with fc_norm -- the pool runs BEFORE the
  * final norm.  Pending operands as above (bf16, fp32 when delta_is_f32; d1 / d2 nullable, d2 needs d1), contiguous [B,N,D] like x.
  * tr_token_pool: out[b] = sum_n w[b,n] * v[b,n] / sum_n w[b,n] over the patch rows n = 1 .. N-1 (row 0, the CLS token, is left out), v = (x +
@@ -858,6 +866,18 @@ int tr_dense_gather(const float* tokens, const int32_t* index, void* out, int la
  *   Shapes, alignment and refusals are tr_dense_gather's, each before any launch. */
 int tr_dense_scatter(const void* dmap, const int32_t* index, void* dtokens, int layout, int dmap_is_bf16, int out_is_bf16, int B, int P,
                      int n_rows, int D, tr_stream_t s);
+/* tr_dense_scatter_levels: the adjoint of tr_dense_gather_levels, the scatter of L levels in ONE launch.  dmaps is a HOST array of L device
+ *   pointers (autograd hands over L separate tensors; they travel as kernel arguments, like level_rows), each a map gradient in
+ *   tr_dense_scatter's layouts and dtype (one dtype for all).  A NULL entry is a level without a gradient: its slab of dtokens is not touched
+ *   and none of its tiles is launched; with every entry NULL nothing is launched.  Level l's index is index + l * B * P, its output
+ *   [B, level_rows[l], D] starts at dtokens + l * level_stride elements (fp32, or bf16 when out_is_bf16).  Per level the arithmetic, the
+ *   domain check and the bits are tr_dense_scatter's (the same tile bodies); one launch, so L partial last rounds become one.  The
+ *   logical order runs through the same XCD remap: channels-last has the level slowest; NCHW has the image slowest and the level next, so
+ *   that an XCD's contiguous run holds whole images with all their levels (the levels' tiles do not cost the same under a merge index).  1 <= L <= 32 (TR_ERR_CONFIG); a level's rows must fit level_stride
+ *   (TR_ERR_SHAPE); level_stride must keep every slab 16-byte aligned (a multiple of 4 elements, of 8 for bf16 out: TR_ERR_ALIGN); the
+ *   other refusals are tr_dense_gather_levels', each before any launch. */
+int tr_dense_scatter_levels(const void* const* dmaps, const int32_t* index, void* dtokens, size_t level_stride, const int32_t* level_rows,
+                            int L, int layout, int dmap_is_bf16, int out_is_bf16, int B, int P, int D, tr_stream_t s);
 
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
@@ -958,6 +978,54 @@ int tr_vit_backward_dense(const tr_vit_config* cfg, const tr_vit_weights* w, con
                           size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
                           tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens, int dtokens_is_bf16,
                           const float* stream);
+/* Multi-level dense feature maps in training.  tr_vit_forward_train_levels is tr_vit_forward_train_dense plus level taps (tr_vit_train_levels):
+ * the one entry where level taps and a training tape go together (tr_vit_forward_levels keeps refusing a tape).  After every block of
+ * `blocks` (bit i = block i) the rows of the stream with the residual pending there -- the training forward's DropPath-scaled,
+ * dropout-masked branch -- go to the next slab (level l at l * B * N0 * D elements, holding [B, N_l, D]):
+ *   norm == 0   tokens_out takes the summed rows (tr_cls_tap at row stride D); stream_out is not read
+ *   norm == 1   stream_out takes the summed rows and tokens_out their fp32 final norm, ONE launch per level (tr_level_tap_norm)
+ * The taps run where they run in eval and change nothing else: the logits, the tape and every other launch are tr_vit_forward_train's.
+ * `dense` carries the decision slabs (kept_idx / compl_idx / soft_out) as in tr_vit_forward_train_dense; its tokens_out / stream_out may both
+ * be NULL here (the last block's pair is then not written: a level at block depth-1 serves it).  DyViT: TR_ERR_CONFIG; a NULL struct or
+ * buffer: TR_ERR_NULL; a buffer too small: TR_ERR_SHAPE; not 16-byte aligned: TR_ERR_ALIGN; blocks == 0, a block outside the depth or norm
+ * outside {0, 1}: TR_ERR_CONFIG -- each before any launch.
+ * tr_vit_backward_levels is tr_vit_backward_dense plus the level gradients (tr_vit_level_grads).  `present` has bit l set where level l (the
+ * l-th set bit of `blocks`) has a gradient; dtokens holds level l's token gradient at l * level_stride elements -- bf16 for norm == 1 (the
+ * gradient of the final-normed rows, tr_dense_scatter_levels' output), fp32 for norm == 0 (of the rows as they stand) -- and stream the
+ * forward's stream_out (norm == 1).  A present level at block i < depth-1 is injected in front of block i's Mlp backward, where the stream
+ * gradient is that of the summed stream after block i: norm == 1 runs the final norm's backward over all B * N_i rows (adding into the
+ * stream gradient, rewriting its bf16 copy, adding into the final norm's parameter gradients, reduced at once); norm == 0 runs
+ * tr_stream_grad_add.  The level at block depth-1 enters where tr_vit_backward_dense's dtokens enter (the entry's own dtokens must then be
+ * NULL).  A level below the stop block of a partly frozen model adds nothing to the stream gradient (nobody reads it); with norm == 1 and a
+ * trainable final norm it still adds to the norm's parameter gradients: these passes run in descending block order behind the walk, in the
+ * call whose range holds the stop block (no block walked: in the call with blk_hi == depth-1), so a single call and a pass of range calls
+ * add in the same order.  Every range call takes the same arguments; a level is handled by the call whose range holds its block.  With
+ * lev == NULL or present == 0 the call IS tr_vit_backward_dense. */
+typedef struct {
+  uint32_t blocks;
+  int32_t norm;
+  float* tokens_out;
+  float* stream_out;    /* norm == 1 */
+  size_t level_elems;   /* elements of tokens_out (and of stream_out): at least popcount(blocks) * B * N0 * D */
+} tr_vit_train_levels;
+typedef struct {
+  uint32_t blocks;
+  int32_t norm;
+  uint32_t present;
+  const void* dtokens;
+  const float* stream;
+  size_t level_stride;  /* elements between two levels' slabs, at least B * N0 * D */
+} tr_vit_level_grads;
+int tr_vit_forward_train_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format, const float* pixel_lut,
+                                const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len, float* logits, void* workspace,
+                                size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in, const float* drop_scale,
+                                int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep, float drop_rate,
+                                const tr_vit_dense_train* dense, const tr_vit_train_levels* levels);
+int tr_vit_backward_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                           const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape,
+                           size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                           tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens, int dtokens_is_bf16,
+                           const float* stream, const tr_vit_level_grads* lev);
 size_t tr_vit_dropout_mask_bytes(const tr_vit_config* cfg, int B);
 /* fp32 master parameters -> the bf16 operand copies of the GEMMs, every matrix of a model in ONE launch (an optimizer step changes them
  * all: engine.py:76-91).  Item i: src fp32 [rows, cols] contiguous -> dst bf16 [rows, cols] (nullable) and dst_t bf16 [cols, rows]

@@ -63,6 +63,14 @@ class TrVitDenseTrain(C.Structure):  # tr_vit_dense_train: the caller-owned outp
                 ("soft_out", _vp), ("soft_elems", _sz)]
 
 
+class TrVitTrainLevels(C.Structure):  # tr_vit_train_levels: the level taps of tr_vit_forward_train_levels (32 bytes)
+    _fields_ = [("blocks", C.c_uint32), ("norm", C.c_int32), ("tokens_out", _vp), ("stream_out", _vp), ("level_elems", _sz)]
+
+
+class TrVitLevelGrads(C.Structure):  # tr_vit_level_grads: the level gradients of tr_vit_backward_levels (40 bytes)
+    _fields_ = [("blocks", C.c_uint32), ("norm", C.c_int32), ("present", C.c_uint32), ("dtokens", _vp), ("stream", _vp), ("level_stride", _sz)]
+
+
 class TrDecisionStage(C.Structure):  # tr_decision_stage: one row of tr_stage_decisions' stage table (40 bytes)
     _fields_ = [("block", C.c_int32), ("kind", C.c_int32), ("n_in", C.c_int32), ("k", C.c_int32), ("kept_off", C.c_int64),
                 ("assign_off", C.c_int64), ("soft_off", C.c_int64)]
@@ -248,6 +256,13 @@ SIGNATURES = {
                                         _vp, C.POINTER(_i), _i, _vp, _vp, _f, C.POINTER(TrVitDenseTrain)]),
     "tr_vit_backward_dense": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), _vp, _vp,
                                    _vp, _vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp]),
+    "tr_level_tap_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "tr_stream_grad_add": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tr_dense_scatter_levels": (_i, [C.POINTER(_vp), _vp, _vp, _sz, C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "tr_vit_forward_train_levels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp, _sz, _vp,
+                                         _vp, C.POINTER(_i), _i, _vp, _vp, _f, C.POINTER(TrVitDenseTrain), C.POINTER(TrVitTrainLevels)]),
+    "tr_vit_backward_levels": (_i, [C.POINTER(TrVitConfig), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), C.POINTER(TrVitWeights), _vp, _vp,
+                                    _vp, _vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, C.POINTER(TrVitLevelGrads)]),
 }
 
 _lib = None

@@ -799,6 +799,24 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   *reinterpret_cast<uint2*>(dst + 4 * c) = pk;
 }
 
+// g += d in fp32 and gb = bf16(g): the gradient of a level's rows taken as they stand (no norm) joins the stream gradient
+// (tr_vit_backward_levels); gb nullable
+__global__ __launch_bounds__(256) void stream_grad_add_kernel(const float* __restrict__ d, float* __restrict__ g, uint16_t* __restrict__ gb,
+                                                              size_t nchunks) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nchunks) return;
+  const float4 a = *reinterpret_cast<const float4*>(d + 4 * c);
+  float4 v = *reinterpret_cast<const float4*>(g + 4 * c);
+  v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+  *reinterpret_cast<float4*>(g + 4 * c) = v;
+  if (gb != nullptr) {
+    uint2 pk;
+    pk.x = pack_bf16x2(v.x, v.y);
+    pk.y = pack_bf16x2(v.z, v.w);
+    *reinterpret_cast<uint2*>(gb + 4 * c) = pk;
+  }
+}
+
 // ONE reduce launch for segs[0 .. n) (part, dst, count, S, accumulate filled by the caller), all in the tall or all in the 64 x 4 layout
 template <int L, int N>
 void launch_reduce_table(const RSeg* segs, int n, hipStream_t st) {
@@ -1085,7 +1103,12 @@ struct LnDefer {
 };
 thread_local LnDefer* g_ln_defer = nullptr;
 thread_local LnDefer g_ln_defer_store;
+thread_local bool g_ln_defer_paused = false;
 }  // namespace
+
+// A norm whose parameter gradient is ALSO the destination of another norm of the same context (the final norm under level gradients) must not
+// share a reduce launch with it: two segments of one launch would add into the same d gamma unordered.  Paused, a call reduces at once.
+void tr_ln_defer_pause(bool on) { g_ln_defer_paused = on; }
 
 int tr_ln_defer_flush() {
   LnDefer* c = g_ln_defer;
@@ -1101,7 +1124,7 @@ void tr_ln_defer_begin(float* region, size_t floats, hipStream_t st) {
   c->region = region; c->cap = floats; c->used = 0; c->n = 0; c->st = st;
   g_ln_defer = (region != nullptr && floats > 0) ? c : nullptr;
 }
-void tr_ln_defer_end() { g_ln_defer = nullptr; }           // drops what was not flushed (error paths)
+void tr_ln_defer_end() { g_ln_defer = nullptr; g_ln_defer_paused = false; }           // drops what was not flushed (error paths)
 
 #define TR_TRY_RC(call)             \
   do {                              \
@@ -1140,7 +1163,7 @@ static int layernorm_bwd_impl(const uint16_t* dy, const float* x, long ldx, cons
   }
   LnDefer* dc = g_ln_defer;
   const size_t need = (size_t)grid * 2 * D;
-  const bool defer = dc != nullptr && dc->st == st && grid >= 64 && D <= 4096 && need <= dc->cap;
+  const bool defer = dc != nullptr && !g_ln_defer_paused && dc->st == st && grid >= 64 && D <= 4096 && need <= dc->cap;
   if (defer) {
     if (dc->n + 2 > LN_DEFER_SEGS || dc->used + need > dc->cap) TR_TRY_RC(tr_ln_defer_flush());     // full: reduce what is there, start over
     ws = dc->region + dc->used;
@@ -1243,6 +1266,18 @@ extern "C" int tr_f32_to_bf16(const float* src, uint16_t* dst, size_t n, tr_stre
   const size_t nch = n / 4;
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(s), src, dst, nch);
   TR_CHECK_LAUNCH("tr_f32_to_bf16");
+  return TR_OK;
+}
+
+extern "C" int tr_stream_grad_add(const float* d, float* g, uint16_t* gb, size_t n, tr_stream_t s) {
+  TR_REQUIRE(d && g, TR_ERR_NULL, "tr_stream_grad_add: null pointer");
+  TR_REQUIRE(n > 0 && n % 4 == 0, TR_ERR_SHAPE, "tr_stream_grad_add: element count must be a positive multiple of 4");
+  TR_REQUIRE(tr_aligned16(d) && tr_aligned16(g) && (reinterpret_cast<uintptr_t>(gb) & 7u) == 0, TR_ERR_ALIGN,
+             "tr_stream_grad_add: d / g must be 16-byte, gb 8-byte aligned");
+  const size_t nch = n / 4;
+  TR_REQUIRE((nch + 255) / 256 <= 0x7fffffffu, TR_ERR_SHAPE, "tr_stream_grad_add: %zu elements", n);
+  hipLaunchKernelGGL(stream_grad_add_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(s), d, g, gb, nch);
+  TR_CHECK_LAUNCH("tr_stream_grad_add");
   return TR_OK;
 }
 

@@ -12,6 +12,8 @@
 //                     its prefix ends; the gather's tile order has the level as its slowest coordinate.
 //   tr_dense_scatter  the gather's adjoint, for the map's gradient in training: dtokens[b, r, :] = the sum of dmap[b, :, p] over the patches
 //                     with index[b, p] == r, fp32 additions in ascending p, every output element written exactly once, no scratch.
+//   tr_dense_scatter_levels   the scatter for L levels (the adjoint of tr_dense_gather_levels) in ONE launch: the maps' gradients arrive as L
+//                     separate tensors, a NULL one is a level without a gradient and owns no tile; the tile bodies are tr_dense_scatter's.
 // The gather is the hot path: it writes the largest tensor of the forward once and reads at most as much.  Channels-last is a row copy in
 // the shape of tr_taps.hip (a wave per output row, 16-byte loads).  NCHW transposes a tile of 64 patches x 64 channels through LDS: rows
 // come in with 16-byte loads (a 256-byte piece of each gathered row), leave along p with 16-byte stores (8-byte for bf16) when P % 4 == 0,
@@ -282,10 +284,8 @@ __device__ __forceinline__ float bf16_bits_to_f32(unsigned int h) { return __bui
 
 // Channels-last: a wave per output row (b, r), lane l on the 16-byte (bf16 input: 8-byte) chunks l, l + 64, ... of every patch row it sums
 template <bool IN_BF16, bool OUT_BF16>
-__global__ __launch_bounds__(256) void dense_scatter_nhwc_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
-                                                                 void* __restrict__ out, long rows, int P, int n_rows, int D) {
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;                                 // (wave-uniform)
+__device__ __forceinline__ void scatter_row_nhwc(const void* __restrict__ dmap, const int32_t* __restrict__ index, void* __restrict__ out,
+                                                 long row, int P, int n_rows, int D) {
   const int lane = threadIdx.x & 63;
   const long b = row / n_rows;
   const int r = (int)(row - b * n_rows);
@@ -335,6 +335,43 @@ __global__ __launch_bounds__(256) void dense_scatter_nhwc_kernel(const void* __r
   }
 }
 
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_nhwc_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
+                                                                 void* __restrict__ out, long rows, int P, int n_rows, int D) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                                 // (wave-uniform)
+  scatter_row_nhwc<IN_BF16, OUT_BF16>(dmap, index, out, row, P, n_rows, D);
+}
+
+// The levels of tr_dense_scatter_levels (a kernel argument): a level's map gradient (NULL: no gradient, no workgroup), its rows, and where
+// its workgroups start -- channels-last: in the launch, the level slowest; NCHW: among the tiles of one image; a level without a gradient
+// has start[l] == start[l + 1]
+struct level_scatter_table {
+  const void* dmap[TR_MAX_DEPTH];
+  int rows[TR_MAX_DEPTH];
+  int start[TR_MAX_DEPTH + 1];
+};
+__device__ __forceinline__ int scatter_level_of(const level_scatter_table& lt, int L, int id) {
+  int l = 0;
+  while (l + 1 < L && id >= lt.start[l + 1]) ++l;          // (uniform over the workgroup; an empty level is stepped over)
+  return l;
+}
+template <bool OUT_BF16>
+__device__ __forceinline__ void* scatter_level_out(void* out, size_t elems) {
+  return OUT_BF16 ? static_cast<void*>(static_cast<uint16_t*>(out) + elems) : static_cast<void*>(static_cast<float*>(out) + elems);
+}
+
+// ... for L levels: workgroup id -> (level, four rows of it); a level's index and output are slabs of B * P and level_stride elements
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_levels_nhwc_kernel(level_scatter_table lt, int L, const int32_t* __restrict__ index,
+                                                                        void* __restrict__ out, size_t level_stride, int B, int P, int D) {
+  const int l = scatter_level_of(lt, L, (int)blockIdx.x);
+  const int n_rows = lt.rows[l];
+  const long row = (long)((int)blockIdx.x - lt.start[l]) * 4 + (threadIdx.x >> 6);
+  if (row >= (long)B * n_rows) return;                     // (wave-uniform)
+  scatter_row_nhwc<IN_BF16, OUT_BF16>(lt.dmap[l], index + (size_t)l * B * P, scatter_level_out<OUT_BF16>(out, l * level_stride), row, P, n_rows, D);
+}
+
 constexpr int DS_TR = 32;            // output rows per tile (8 per wave)
 constexpr int DS_TC = 64;            // channels per tile: a lane per channel
 
@@ -344,11 +381,8 @@ constexpr int DS_TC = 64;            // channels per tile: a lane per channel
 // the map -- at the same time.  The tiles of one image are consecutive logical ids (channel tile fastest) and xcd_remap gives an XCD a
 // contiguous run of them, as in the gather: a line of the image's D x P slab is fetched from HBM once and served by one L2 afterwards.
 template <bool IN_BF16, bool OUT_BF16>
-__global__ __launch_bounds__(256) void dense_scatter_nchw_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
-                                                                 void* __restrict__ out, int P, int n_rows, int D, int rtiles, int ctiles) {
-  __shared__ int sidx[DI_MAX_P];
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
-  const int ct = id % ctiles, rt = (id / ctiles) % rtiles, b = id / (ctiles * rtiles);
+__device__ __forceinline__ void scatter_tile_nchw(const void* __restrict__ dmap, const int32_t* __restrict__ index, void* __restrict__ out, int P,
+                                                  int n_rows, int D, int b, int rt, int ct, int* sidx) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int p = threadIdx.x; p < P; p += 256) sidx[p] = index[(size_t)b * P + p];
   __syncthreads();
@@ -377,6 +411,35 @@ __global__ __launch_bounds__(256) void dense_scatter_nchw_kernel(const void* __r
       else static_cast<float*>(out)[at] = acc;
     }
   }
+}
+
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_nchw_kernel(const void* __restrict__ dmap, const int32_t* __restrict__ index,
+                                                                 void* __restrict__ out, int P, int n_rows, int D, int rtiles, int ctiles) {
+  __shared__ int sidx[DI_MAX_P];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int ct = id % ctiles, rt = (id / ctiles) % rtiles, b = id / (ctiles * rtiles);
+  scatter_tile_nchw<IN_BF16, OUT_BF16>(dmap, index, out, P, n_rows, D, b, rt, ct, sidx);
+}
+
+// ... for L levels in one launch.  The logical tile order is (image, level, row tile, channel tile) through the same xcd_remap: inside a level
+// the tiles of an image stay neighbours on one L2, as in the single-level kernel, and an XCD's contiguous run holds whole images with ALL
+// their levels.  With the level slowest an XCD's run would be (part of) one level, and the levels' tiles do not cost the same: under a
+// merge index every level sums all P patches of an image into fewer and fewer rows, so the last level's few tiles carry a quarter of the
+// work on an eighth of the chip (measured: 0.58 ms against 0.33 ms for four launches under ToMe's index; profiles/dense_train_levels_lab.md).
+// A level has its own number of row tiles; lt.start[l] is its first tile inside an image, per_image the tiles of one image
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(256) void dense_scatter_levels_nchw_kernel(level_scatter_table lt, int L, const int32_t* __restrict__ index,
+                                                                        void* __restrict__ out, size_t level_stride, int B, int P, int D,
+                                                                        int ctiles, int per_image) {
+  __shared__ int sidx[DI_MAX_P];
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int b = id / per_image, ti = id - b * per_image;
+  const int l = scatter_level_of(lt, L, ti);
+  const int t = ti - lt.start[l];
+  const int ct = t % ctiles, rt = t / ctiles;
+  scatter_tile_nchw<IN_BF16, OUT_BF16>(lt.dmap[l], index + (size_t)l * B * P, scatter_level_out<OUT_BF16>(out, l * level_stride), P, lt.rows[l], D,
+                                       b, rt, ct, sidx);
 }
 
 }  // namespace
@@ -581,5 +644,67 @@ extern "C" int tr_dense_scatter(const void* dmap, const int32_t* index, void* dt
   else DS_LAUNCH(false, false);
 #undef DS_LAUNCH
   TR_CHECK_LAUNCH("tr_dense_scatter");
+  return TR_OK;
+}
+
+extern "C" int tr_dense_scatter_levels(const void* const* dmaps, const int32_t* index, void* dtokens, size_t level_stride,
+                                       const int32_t* level_rows, int L, int layout, int dmap_is_bf16, int out_is_bf16, int B, int P, int D,
+                                       tr_stream_t s) {
+  TR_REQUIRE(dmaps && level_rows && index && dtokens, TR_ERR_NULL, "tr_dense_scatter_levels: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_CONFIG, "tr_dense_scatter_levels: layout %d (TR_LAYOUT_NCHW or TR_LAYOUT_NHWC)",
+             layout);
+  TR_REQUIRE(L >= 1 && L <= TR_MAX_DEPTH, TR_ERR_CONFIG, "tr_dense_scatter_levels: %d levels (1 ... %d)", L, TR_MAX_DEPTH);
+  TR_REQUIRE(B > 0 && P >= 1 && P <= DI_MAX_P && D > 0 && D % 4 == 0 && D <= 1024, TR_ERR_SHAPE,
+             "tr_dense_scatter_levels: need B > 0, 1 <= P <= 1024, D %% 4 == 0, D <= 1024 (B=%d P=%d D=%d)", B, P, D);
+  const bool ib = dmap_is_bf16 != 0, ob = out_is_bf16 != 0, nhwc = layout == TR_LAYOUT_NHWC;
+  const int ctiles = (D + DS_TC - 1) / DS_TC;
+  level_scatter_table lt;
+  long blocks = 0;
+  bool aligned = true;
+  double bytes = 0.0;
+  for (int l = 0; l < L; ++l) {
+    // a level's rows [B, n_rows, D] lie inside its slab, present or not; slabs start 16-byte aligned
+    TR_REQUIRE(level_rows[l] >= 1 && (size_t)B * level_rows[l] * D <= level_stride, TR_ERR_SHAPE,
+               "tr_dense_scatter_levels: level %d has %d rows: [%d, %d, %d] does not fit a slab of %zu elements", l, level_rows[l], B,
+               level_rows[l], D, level_stride);
+    lt.dmap[l] = dmaps[l];
+    lt.rows[l] = level_rows[l];
+    lt.start[l] = (int)blocks;
+    if (dmaps[l] == nullptr) continue;
+    aligned = aligned && tr_aligned16(dmaps[l]);
+    const long rows = (long)B * level_rows[l];
+    // channels-last: the level's first workgroup in the launch; NCHW: its first tile inside an image
+    blocks += nhwc ? (rows + 3) / 4 : (long)((level_rows[l] + DS_TR - 1) / DS_TR) * ctiles;
+    TR_REQUIRE(blocks * (nhwc ? 1 : B) <= INT_MAX, TR_ERR_SHAPE, "tr_dense_scatter_levels: %ld workgroups", blocks * (nhwc ? 1 : B));
+    bytes += (double)B * P * D * (ib ? 2.0 : 4.0) + (double)rows * D * (ob ? 2.0 : 4.0) + 4.0 * B * P;
+  }
+  for (int l = L; l <= TR_MAX_DEPTH; ++l) lt.start[l] = (int)blocks;
+  for (int l = L; l < TR_MAX_DEPTH; ++l) {
+    lt.dmap[l] = nullptr;
+    lt.rows[l] = 1;
+  }
+  TR_REQUIRE(level_stride % (ob ? 8 : 4) == 0, TR_ERR_ALIGN, "tr_dense_scatter_levels: level_stride %zu does not keep the slabs 16-byte aligned",
+             level_stride);
+  TR_REQUIRE(aligned && tr_aligned16(index) && tr_aligned16(dtokens), TR_ERR_ALIGN, "tr_dense_scatter_levels: pointers must be 16-byte aligned");
+  if (blocks == 0) return TR_OK;                            // no level has a gradient: nothing to write
+  hipStream_t st = static_cast<hipStream_t>(s);
+  // required traffic of the present levels: every element of a map once at most, every output element once, the index
+  tr_prof_note("tr_dense_scatter_levels", 0.0, bytes);
+  const int per_image = (int)blocks;                        // (NCHW)
+  const dim3 grid((unsigned)(nhwc ? blocks : blocks * B));
+#define DS_LAUNCH(IB, OB)                                                                                                                   \
+  do {                                                                                                                                      \
+    if (nhwc)                                                                                                                               \
+      hipLaunchKernelGGL((dense_scatter_levels_nhwc_kernel<IB, OB>), grid, dim3(256), 0, st, lt, L, index, dtokens, level_stride, B, P, D); \
+    else                                                                                                                                    \
+      hipLaunchKernelGGL((dense_scatter_levels_nchw_kernel<IB, OB>), grid, dim3(256), 0, st, lt, L, index, dtokens, level_stride, B, P, D,  \
+                         ctiles, per_image);                                                                                                \
+  } while (0)
+  if (ib && ob) DS_LAUNCH(true, true);
+  else if (ib) DS_LAUNCH(true, false);
+  else if (ob) DS_LAUNCH(false, true);
+  else DS_LAUNCH(false, false);
+#undef DS_LAUNCH
+  TR_CHECK_LAUNCH("tr_dense_scatter_levels");
   return TR_OK;
 }

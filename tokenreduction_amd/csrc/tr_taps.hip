@@ -3,7 +3,9 @@
 //                         (what viz_data["Features"][blk][:, 0] holds: deit_viz.py:199, topk.py:197)
 //   tr_final_tokens_f32   norm(x) of EVERY row after the last block, fp32 (the DyViT teacher's second output, dyvit.py:325-334):
 //                         the residual add(s) and the fp32 LayerNorm in one pass
-// Both are HBM-bound row kernels in the shape of tr_norm.hip: one wave per row, 16-byte accesses, D <= 1024.  The additions are those of
+//   tr_level_tap_norm     both of them for one row read: the summed row AND its fp32 final norm, two stores (the level taps of the
+//                         training forward, tr_vit_forward_train_levels: the backward of the norm needs the row that entered it)
+// All are HBM-bound row kernels in the shape of tr_norm.hip: one wave per row, 16-byte accesses, D <= 1024.  The additions are those of
 // tr_residual_snapshot behind an eager norm2 -- (x + first) + second in fp32 -- and the normalisation is tr_layernorm_f32's (ln_row_store<true>),
 // so the values equal that two-launch sequence bit for bit.
 #include "tr_common.h"
@@ -23,6 +25,25 @@ __device__ __forceinline__ void add_pending(float4 (&v)[NCH], const void* __rest
   }
 }
 
+// (x[row] + d1[row]) + d2[row] in registers: the one summation of every kernel here.  NT: the stream is not read again in this forward
+template <bool DF32, int NCH, bool NT>
+__device__ __forceinline__ void summed_row(float4 (&v)[NCH], const float* __restrict__ xr, const void* __restrict__ d1, size_t off1,
+                                           const void* __restrict__ d2, size_t off2, int lane, int nchunks) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const float* p = xr + 4 * min(lane + 64 * c, nchunks - 1);
+    v[c] = NT ? ln_nt_load4(p) : *reinterpret_cast<const float4*>(p);
+  }
+  if (d1 != nullptr) add_pending<DF32, NCH>(v, d1, off1, lane, nchunks);
+  if (d2 != nullptr) add_pending<DF32, NCH>(v, d2, off2, lane, nchunks);
+}
+template <int NCH>
+__device__ __forceinline__ void store_row(const float4 (&v)[NCH], float* __restrict__ orow, int lane, int nchunks) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (lane + 64 * c < nchunks) *reinterpret_cast<float4*>(orow + 4 * (lane + 64 * c)) = v[c];
+}
+
 // out[b] = (x[b] + d1[b]) + d2[b]: B rows at their own strides (the stream's CLS rows at N * D, compact CLS-tail buffers at D,
 // the destination at n_blocks * D); d1 / d2 nullable
 template <bool DF32, int NCH>
@@ -33,16 +54,9 @@ __global__ __launch_bounds__(256) void cls_tap_kernel(const float* __restrict__ 
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
   const int nchunks = D >> 2;
-  const float* xr = x + (size_t)row * ldx;
   float4 v[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = *reinterpret_cast<const float4*>(xr + 4 * min(lane + 64 * c, nchunks - 1));
-  if (d1 != nullptr) add_pending<DF32, NCH>(v, d1, (size_t)row * ld1, lane, nchunks);
-  if (d2 != nullptr) add_pending<DF32, NCH>(v, d2, (size_t)row * ld2, lane, nchunks);
-  float* orow = out + (size_t)row * ldo;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (lane + 64 * c < nchunks) *reinterpret_cast<float4*>(orow + 4 * (lane + 64 * c)) = v[c];
+  summed_row<DF32, NCH, false>(v, x + (size_t)row * ldx, d1, (size_t)row * ld1, d2, (size_t)row * ld2, lane, nchunks);
+  store_row<NCH>(v, out + (size_t)row * ldo, lane, nchunks);
 }
 
 // y[row] = LayerNorm_f32((x[row] + d1[row]) + d2[row]) over contiguous rows [M, D]; nothing is written back to x.  The stream and the
@@ -55,12 +69,25 @@ __global__ __launch_bounds__(256) void final_tokens_kernel(const float* __restri
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const int nchunks = D >> 2;
-  const float* xr = x + (size_t)row * D;
   float4 v[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = ln_nt_load4(xr + 4 * min(lane + 64 * c, nchunks - 1));
-  if (d1 != nullptr) add_pending<DF32, NCH>(v, d1, (size_t)row * D, lane, nchunks);
-  if (d2 != nullptr) add_pending<DF32, NCH>(v, d2, (size_t)row * D, lane, nchunks);
+  summed_row<DF32, NCH, true>(v, x + (size_t)row * D, d1, (size_t)row * D, d2, (size_t)row * D, lane, nchunks);
+  ln_row_store<true, NCH>(v, nchunks, lane, D, eps, gamma, beta, y + (size_t)row * D);
+}
+
+// sum[row] = (x[row] + d1[row]) + d2[row] and y[row] = LayerNorm_f32(sum[row]) over contiguous rows [M, D]: cls_tap_kernel's row at stride D and
+// final_tokens_kernel's row from ONE read of x and the pending operands.  x is read again by the next norm of a training forward: plain loads
+template <bool DF32, int NCH>
+__global__ __launch_bounds__(256) void level_tap_norm_kernel(const float* __restrict__ x, const void* __restrict__ d1,
+                                                             const void* __restrict__ d2, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float* __restrict__ sum, float* __restrict__ y, int M,
+                                                             int D, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nchunks = D >> 2;
+  float4 v[NCH];
+  summed_row<DF32, NCH, false>(v, x + (size_t)row * D, d1, (size_t)row * D, d2, (size_t)row * D, lane, nchunks);
+  store_row<NCH>(v, sum + (size_t)row * D, lane, nchunks);
   ln_row_store<true, NCH>(v, nchunks, lane, D, eps, gamma, beta, y + (size_t)row * D);
 }
 
@@ -105,5 +132,22 @@ extern "C" int tr_final_tokens_f32(const float* x, const void* d1, const void* d
   if (f32) TR_DISPATCH_NCH(D, hipLaunchKernelGGL((final_tokens_kernel<true, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, d1, d2, gamma, beta, y, M, D, eps));
   else TR_DISPATCH_NCH(D, hipLaunchKernelGGL((final_tokens_kernel<false, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, d1, d2, gamma, beta, y, M, D, eps));
   TR_CHECK_LAUNCH("tr_final_tokens_f32");
+  return TR_OK;
+}
+
+extern "C" int tr_level_tap_norm(const float* x, const void* d1, const void* d2, int delta_is_f32, const float* gamma, const float* beta,
+                                 float* sum, float* y, int M, int D, float eps, tr_stream_t s) {
+  TR_REQUIRE(x && gamma && beta && sum && y, TR_ERR_NULL, "tr_level_tap_norm: null pointer");
+  TR_REQUIRE(d1 != nullptr || d2 == nullptr, TR_ERR_NULL, "tr_level_tap_norm: a second pending operand needs the first");
+  TR_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAX_CHUNKS, TR_ERR_SHAPE, "tr_level_tap_norm: need D %% 4 == 0, D <= 1024 (M=%d D=%d)", M, D);
+  const bool f32 = delta_is_f32 != 0;
+  TR_REQUIRE(operand_ok(d1, D, D, f32) && operand_ok(d2, D, D, f32), TR_ERR_ALIGN, "tr_level_tap_norm: misaligned pending operand");
+  TR_REQUIRE(tr_aligned16(x) && tr_aligned16(gamma) && tr_aligned16(beta) && tr_aligned16(sum) && tr_aligned16(y), TR_ERR_ALIGN,
+             "tr_level_tap_norm: pointers must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  tr_prof_note("tr_level_tap_norm", 0.0, (double)M * D * (12.0 + ((d1 ? 1.0 : 0.0) + (d2 ? 1.0 : 0.0)) * (f32 ? 4.0 : 2.0)));
+  if (f32) TR_DISPATCH_NCH(D, hipLaunchKernelGGL((level_tap_norm_kernel<true, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, d1, d2, gamma, beta, sum, y, M, D, eps));
+  else TR_DISPATCH_NCH(D, hipLaunchKernelGGL((level_tap_norm_kernel<false, NCH>), dim3((M + 3) / 4), dim3(256), 0, st, x, d1, d2, gamma, beta, sum, y, M, D, eps));
+  TR_CHECK_LAUNCH("tr_level_tap_norm");
   return TR_OK;
 }

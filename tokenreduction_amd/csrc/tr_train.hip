@@ -21,6 +21,7 @@ using trplan::align_up;
 void tr_ln_defer_begin(float* region, size_t floats, hipStream_t st);
 int tr_ln_defer_flush();
 void tr_ln_defer_end();
+void tr_ln_defer_pause(bool on);
 
 namespace {
 
@@ -201,6 +202,13 @@ struct Bwd {
   const void* dtokens = nullptr;
   bool dtokens_bf16 = false;
   const float* dstream = nullptr;
+  // multi-level dense maps (tr_vit_backward_levels): per block the token gradient of the level tapped there (bf16 for lev_norm, else fp32)
+  // and, for lev_norm, the stream slab that entered the final norm; NULL where the block has no level or the level no gradient.  The level
+  // of block depth-1 is not here: it travels as dtokens / dstream (lev_norm) or as lev_last (fp32, the rows as they stand)
+  const void* lev_dtok[TR_MAX_DEPTH] = {};
+  const float* lev_stream[TR_MAX_DEPTH] = {};
+  const float* lev_last = nullptr;
+  bool lev_norm = false;
   // The four parameter-gradient products of a block (fc2, fc1, proj, qkv) run as ONE launch after the attention backward, when all four dY
   // exist -- provided nothing has rewritten fc2's dY (the bf16 stream gradient gb) by then: norm2's backward writes its bf16 output into the
   // spare buffer instead and the two trade places.  With DropPath / dropout the scaled dY copies live in scratch that is reused: pairs then.
@@ -363,6 +371,8 @@ struct Bwd {
       TR_TRY(ln_bwd(dy, dstream, w->norm_g, grads->norm_g, grads->norm_b, (pool && !walk) ? nullptr : g, g, nullptr, B * Nl, cfg->ln_eps, 0, 1));
     }
     if (!walk) return TR_OK;      // the final norm was the lowest parameter
+    // the last block's level taken as it stands: its gradient is the stream gradient's own (the bf16 copy is made below)
+    if (lev_last != nullptr) TR_TRY(tr_stream_grad_add(lev_last, g, nullptr, (size_t)B * Nl * D, s));
     TR_TRY(tr_f32_to_bf16(g, gb, (size_t)B * Nl * D, s));
     if (cfg->family == TR_FAMILY_DYVIT) TR_TRY(zero(dpol, (size_t)B * t.N0 * 4));
     *go = true;
@@ -387,6 +397,32 @@ struct Bwd {
     gy_proj = nullptr;
     dcls = nullptr;
     stage_here = false;
+  }
+
+  // A level tapped after block i: its gradient joins g, here the gradient of the summed stream after block i (B * Nm rows), before the block's
+  // first step.  Through the final norm: the norm's backward over all rows, as the last block's second pass -- adds into g, rewrites gb, adds
+  // into the norm's parameter gradients, reduced at once (the deferred table must not hold two segments with one destination).  As it stands:
+  // g += dtok, gb = bf16(g).
+  int level_inject(int i) {
+    if (lev_dtok[i] == nullptr) return TR_OK;
+    if (!lev_norm) return tr_stream_grad_add(static_cast<const float*>(lev_dtok[i]), g, gb, (size_t)M2 * D, s);
+    tr_ln_defer_pause(true);
+    const int rc = ln_bwd(U(lev_dtok[i]), lev_stream[i], w->norm_g, grads->norm_g, grads->norm_b, g, g, gb, M2, cfg->ln_eps, 0, 1);
+    tr_ln_defer_pause(false);
+    return rc;
+  }
+  // The levels below the stop block of a partly frozen model: nobody reads their stream gradient, but a trainable final norm still takes its
+  // parameter gradients from them -- descending block order, g (dead by now) as scratch
+  int levels_below_stop() {
+    if (!lev_norm || !u_norm) return TR_OK;
+    for (int i = (stop < cfg->depth - 1 ? stop : cfg->depth - 1) - 1; i >= 0; --i) {
+      if (lev_dtok[i] == nullptr) continue;
+      tr_ln_defer_pause(true);
+      const int rc = ln_bwd(U(lev_dtok[i]), lev_stream[i], w->norm_g, grads->norm_g, grads->norm_b, nullptr, g, nullptr, B * t.n_mlp[i], cfg->ln_eps, 0, 1);
+      tr_ln_defer_pause(false);
+      TR_TRY(rc);
+    }
+    return TR_OK;
   }
 
   // mlp: x2 -> norm2 -> fc1 -> gelu -> fc2 -> (+ residual), down to norm2's dY in dxn
@@ -682,8 +718,23 @@ static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const
                         const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
                         size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
                         tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens = nullptr,
-                        int dtokens_is_bf16 = 0, const float* stream = nullptr) {
+                        int dtokens_is_bf16 = 0, const float* stream = nullptr, const tr_vit_level_grads* lev = nullptr) {
   TR_REQUIRE(cfg && w && wt && grads && dlogits && tape_ && workspace, TR_ERR_NULL, "tr_vit_backward: null pointer");
+  if (lev != nullptr && lev->present == 0) lev = nullptr;
+  if (lev != nullptr) {
+    const int n_levels = __builtin_popcount(lev->blocks);
+    TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward_levels: DyViT's feature gradient is dfeat");
+    TR_REQUIRE(lev->blocks != 0 && (cfg->depth >= 32 || (lev->blocks >> cfg->depth) == 0) && (lev->norm == 0 || lev->norm == 1) &&
+                   (n_levels >= 32 || (lev->present >> n_levels) == 0),
+               TR_ERR_CONFIG, "tr_vit_backward_levels: blocks 0x%x / norm %d / present 0x%x do not name levels of a depth-%d model", lev->blocks,
+               lev->norm, lev->present, cfg->depth);
+    TR_REQUIRE(lev->dtokens && (lev->norm == 0 || lev->stream), TR_ERR_NULL, "tr_vit_backward_levels: dtokens (norm == 1: or stream) is NULL");
+    TR_REQUIRE(lev->level_stride % 8 == 0 && tr_aligned16(lev->dtokens) && tr_aligned16(lev->stream), TR_ERR_ALIGN,
+               "tr_vit_backward_levels: dtokens / stream must be 16-byte aligned, level_stride a multiple of 8");
+    TR_REQUIRE(dtokens == nullptr || ((lev->blocks >> (cfg->depth - 1)) & 1u) == 0 ||
+                   ((lev->present >> (n_levels - 1)) & 1u) == 0,
+               TR_ERR_CONFIG, "tr_vit_backward_levels: the level of block %d has a gradient AND dtokens is given", cfg->depth - 1);
+  }
   if (dtokens != nullptr) {
     TR_REQUIRE(stream != nullptr, TR_ERR_NULL, "tr_vit_backward_dense: dtokens needs the forward's stream_out");
     TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG, "tr_vit_backward_dense: DyViT's feature gradient is dfeat");
@@ -698,6 +749,8 @@ static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const
   BwdPlan bp;
   TR_REQUIRE(trplan::make_token_plan(cfg, &t) && trplan::make_tape_plan(cfg, B, t, &tp) && make_bwd_plan(cfg, B, t, &bp), TR_ERR_CONFIG,
              "tr_vit_backward: invalid config");
+  TR_REQUIRE(lev == nullptr || lev->level_stride >= (size_t)B * t.N0 * cfg->embed_dim, TR_ERR_SHAPE,
+             "tr_vit_backward_levels: level_stride %zu is below B * N0 * D = %zu", lev ? lev->level_stride : 0, (size_t)B * t.N0 * cfg->embed_dim);
   TR_REQUIRE(tape_bytes >= tp.total && workspace_bytes >= bp.total, TR_ERR_SHAPE, "tr_vit_backward: tape (%zu < %zu) or workspace (%zu < %zu) too small",
              tape_bytes, tp.total, workspace_bytes, bp.total);
   TR_REQUIRE(tr_aligned16(tape_) && tr_aligned16(workspace), TR_ERR_ALIGN, "tr_vit_backward: tape / workspace must be 16-byte aligned");
@@ -711,17 +764,38 @@ static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const
   b.dtokens = dtokens;
   b.dtokens_bf16 = dtokens_is_bf16 != 0;
   b.dstream = stream;
+  if (lev != nullptr) {
+    b.lev_norm = lev->norm != 0;
+    for (int i = 0, l = 0; i < cfg->depth; ++i) {
+      if (((lev->blocks >> i) & 1u) == 0) continue;
+      const int at = l++;
+      if (((lev->present >> at) & 1u) == 0) continue;
+      const void* dt = b.lev_norm ? static_cast<const void*>(static_cast<const uint16_t*>(lev->dtokens) + at * lev->level_stride)
+                                  : static_cast<const void*>(static_cast<const float*>(lev->dtokens) + at * lev->level_stride);
+      if (i < cfg->depth - 1) {
+        b.lev_dtok[i] = dt;
+        b.lev_stream[i] = b.lev_norm ? lev->stream + at * lev->level_stride : nullptr;
+      } else if (b.lev_norm) {     // the last block's level IS the dense map of tr_vit_backward_dense
+        b.dtokens = dt;
+        b.dtokens_bf16 = true;
+        b.dstream = lev->stream + at * lev->level_stride;
+      } else {
+        b.lev_last = static_cast<const float*>(dt);
+      }
+    }
+  }
   b.rewind_to(blk_hi);
   if (blk_hi == cfg->depth - 1) {
     bool go = false;
     TR_TRY(b.head_and_final_norm(&go));
-    if (!go) return TR_OK;
+    if (!go) return stop >= cfg->depth ? b.levels_below_stop() : TR_OK;
   }
   LnDeferScope ln_scope(b.ws<float>(bp.lnpart), bp.lnpart_floats, b.st);
   for (int i = blk_hi; i >= blk_lo && i >= stop; --i) {
     // Block, reversed: x += mlp(norm2(x)); [in-block reducer]; x += attn(norm1(x)); [stage reducer]
     bool done = false;
     b.begin_block(i);
+    TR_TRY(b.level_inject(i));
     TR_TRY(b.mlp_bwd(i));
     TR_TRY(b.norm2_bwd(i));
     TR_TRY(b.proj_bwd(i));
@@ -733,6 +807,7 @@ static int vit_backward(const tr_vit_config* cfg, const tr_vit_weights* w, const
     TR_TRY(b.stage_bwd(i));
   }
   TR_TRY(tr_ln_defer_flush());
+  if (stop >= blk_lo && stop <= blk_hi) TR_TRY(b.levels_below_stop());      // (the walk ended at the stop block in this call)
   if (blk_lo > 0 || stop >= 0) return TR_OK;
   return b.embed_bwd();
 }
@@ -760,4 +835,13 @@ extern "C" int tr_vit_backward_dense(const tr_vit_config* cfg, const tr_vit_weig
                                      int dtokens_is_bf16, const float* stream) {
   return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
                       s, dropout_keep, drop_rate, dx, dtokens, dtokens_is_bf16, stream);
+}
+
+extern "C" int tr_vit_backward_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_weights* wt, const tr_vit_weights* grads,
+                                      const float* dlogits, const float* dpred, const float* dfeat, const float* drop_scale, const void* tape_,
+                                      size_t tape_bytes, void* workspace, size_t workspace_bytes, int accumulate, int blk_hi, int blk_lo, int B,
+                                      tr_stream_t s, const uint8_t* dropout_keep, float drop_rate, float* dx, const void* dtokens,
+                                      int dtokens_is_bf16, const float* stream, const tr_vit_level_grads* lev) {
+  return vit_backward(cfg, w, wt, grads, dlogits, dpred, dfeat, drop_scale, tape_, tape_bytes, workspace, workspace_bytes, accumulate, blk_hi, blk_lo, B,
+                      s, dropout_keep, drop_rate, dx, dtokens, dtokens_is_bf16, stream, lev);
 }

@@ -253,6 +253,9 @@ struct Fwd {
   // dense feature maps in training (tr_vit_forward_train_dense): the stream entering the final norm and the final norm of every row go to
   // the caller's buffers -- DyViT's distillation output with the tape's xfin_all slot replaced by a caller-owned one
   float *dense_stream = nullptr, *dense_tokens = nullptr;
+  // level taps in training (tr_vit_forward_train_levels, norm == 1): the summed rows of a tapped block go to the next slab of level_stream in
+  // the launch that writes their final norm into level_out -- the norm's backward needs the rows that entered it
+  float* level_stream = nullptr;
   // ---- the block being enqueued (pre_block, begin_block) ------------------------------------------------------------------------------
   bool have_xn = false;         // norm1(x) already in xn (written by a pre-block reducer)
   bool tail = false;            // this block runs as the CLS tail
@@ -769,7 +772,10 @@ struct Fwd {
     const void* first = pending_attn != nullptr ? pending_attn : pending;
     const void* second = pending_attn != nullptr ? pending : nullptr;
     float* dst = level_out + (size_t)level_i * B * p.N0 * D;
-    if (level_norm != 0)
+    if (level_stream != nullptr)
+      TR_TRY(tr_level_tap_norm(x, first, second, f32 ? 1 : 0, w->norm_g, w->norm_b, level_stream + (size_t)level_i * B * p.N0 * D, dst, B * N, D,
+                               cfg->ln_eps, s));
+    else if (level_norm != 0)
       TR_TRY(tr_final_tokens_f32(x, first, second, f32 ? 1 : 0, w->norm_g, w->norm_b, dst, B * N, D, cfg->ln_eps, s));
     else
       TR_TRY(tr_cls_tap(x, D, first, D, second, D, f32 ? 1 : 0, dst, D, B * N, D, s));
@@ -1001,7 +1007,7 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
                             const trplan::TapePlan* tp, const float* drop_scale = nullptr, const uint8_t* drop_keep = nullptr, float drop_rate = 0.f,
                             const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
                             const tr_vit_taps* taps = nullptr, const tr_vit_levels* levels = nullptr,
-                            const tr_vit_dense_train* dense = nullptr) {
+                            const tr_vit_dense_train* dense = nullptr, const tr_vit_train_levels* train_levels = nullptr) {
   Plan p;
   TR_REQUIRE(cfg && w && img && logits && workspace, TR_ERR_NULL, "tr_vit_forward: null pointer");
   TR_REQUIRE(make_plan(cfg, B, &p), TR_ERR_CONFIG,
@@ -1047,6 +1053,12 @@ static int vit_forward_impl(const tr_vit_config* cfg, const tr_vit_weights* w, c
   if (dense != nullptr) {          // (validated by vit_forward_train_impl)
     f.dense_stream = dense->stream_out;
     f.dense_tokens = dense->tokens_out;
+  }
+  if (train_levels != nullptr) {   // (validated by vit_forward_train_impl)
+    f.level_mask = train_levels->blocks;
+    f.level_norm = train_levels->norm;
+    f.level_out = train_levels->tokens_out;
+    f.level_stream = train_levels->norm != 0 ? train_levels->stream_out : nullptr;
   }
 
   // patch_embed -> cat(cls) + pos_embed -> depth x Block -> norm -> x[:,0] -> head, with
@@ -1160,7 +1172,7 @@ static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights
                                   float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes, const float* noise_in,
                                   float* features_out, const float* drop_scale, int* tokens_out, int B, tr_stream_t s, const uint8_t* dropout_keep,
                                   float drop_rate, const tr_augment_rec* aug = nullptr, const float* aug_noise = nullptr, long aug_noise_len = 0,
-                                  const tr_vit_dense_train* dense = nullptr) {
+                                  const tr_vit_dense_train* dense = nullptr, const tr_vit_train_levels* levels = nullptr) {
   TR_REQUIRE(cfg && tape, TR_ERR_NULL, "tr_vit_forward_train: null pointer");
   TR_REQUIRE((dropout_keep == nullptr) == (drop_rate == 0.f) && drop_rate >= 0.f && drop_rate < 1.f, TR_ERR_CONFIG,
              "tr_vit_forward_train: dropout needs a keep mask AND 0 < drop_rate < 1 (got mask %p, rate %g)", (const void*)dropout_keep, (double)drop_rate);
@@ -1180,10 +1192,27 @@ static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights
                             aug_noise_len);
   // tr_vit_forward_train_dense: the caller's buffers, checked before any launch
   const size_t slab = (size_t)B * t.N0;
-  TR_REQUIRE(dense->tokens_out && dense->stream_out, TR_ERR_NULL, "tr_vit_forward_train_dense: tokens_out / stream_out is NULL");
+  if (levels == nullptr)
+    TR_REQUIRE(dense->tokens_out && dense->stream_out, TR_ERR_NULL, "tr_vit_forward_train_dense: tokens_out / stream_out is NULL");
+  else {
+    // tr_vit_forward_train_levels: the last block's pair comes as a pair or not at all; the level slabs
+    const int n_levels = __builtin_popcount(levels->blocks);
+    TR_REQUIRE((dense->tokens_out != nullptr) == (dense->stream_out != nullptr), TR_ERR_NULL,
+               "tr_vit_forward_train_levels: dense->tokens_out and dense->stream_out come together (both or neither)");
+    TR_REQUIRE(levels->blocks != 0 && (cfg->depth >= 32 || (levels->blocks >> cfg->depth) == 0), TR_ERR_CONFIG,
+               "tr_vit_forward_train_levels: blocks 0x%x names no block, or one outside 0 ... %d", levels->blocks, cfg->depth - 1);
+    TR_REQUIRE(levels->norm == 0 || levels->norm == 1, TR_ERR_CONFIG, "tr_vit_forward_train_levels: norm %d (0 or 1)", levels->norm);
+    TR_REQUIRE(levels->tokens_out && (levels->norm == 0 || levels->stream_out), TR_ERR_NULL,
+               "tr_vit_forward_train_levels: tokens_out (norm == 1: or stream_out) is NULL");
+    TR_REQUIRE(levels->level_elems >= n_levels * slab * cfg->embed_dim, TR_ERR_SHAPE,
+               "tr_vit_forward_train_levels: the level buffers hold %zu elements, %d levels of [%d, %d, %d] need %zu", levels->level_elems, n_levels, B,
+               t.N0, cfg->embed_dim, n_levels * slab * cfg->embed_dim);
+    TR_REQUIRE(tr_aligned16(levels->tokens_out) && tr_aligned16(levels->stream_out), TR_ERR_ALIGN,
+               "tr_vit_forward_train_levels: the level buffers must be 16-byte aligned");
+  }
   TR_REQUIRE((dense->kept_idx != nullptr) == (dense->compl_idx != nullptr), TR_ERR_NULL,
              "tr_vit_forward_train_dense: kept_idx and compl_idx come together (both or neither)");
-  TR_REQUIRE(dense->rows_elems >= slab * cfg->embed_dim, TR_ERR_SHAPE, "tr_vit_forward_train_dense: tokens_out / stream_out hold %zu elements, [%d, %d, %d] needs %zu",
+  TR_REQUIRE(dense->tokens_out == nullptr || dense->rows_elems >= slab * cfg->embed_dim, TR_ERR_SHAPE, "tr_vit_forward_train_dense: tokens_out / stream_out hold %zu elements, [%d, %d, %d] needs %zu",
              dense->rows_elems, B, t.N0, cfg->embed_dim, slab * cfg->embed_dim);
   TR_REQUIRE(dense->kept_idx == nullptr || dense->idx_elems >= slab * cfg->depth, TR_ERR_SHAPE,
              "tr_vit_forward_train_dense: kept_idx / compl_idx hold %zu elements, %d slabs of [%d, %d] need %zu", dense->idx_elems, cfg->depth, B, t.N0,
@@ -1198,7 +1227,7 @@ static int vit_forward_train_impl(const tr_vit_config* cfg, const tr_vit_weights
              TR_ERR_ALIGN, "tr_vit_forward_train_dense: the output buffers must be 16-byte aligned");
   TR_TRY(vit_forward_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, nullptr, nullptr, dense->soft_out, noise_in,
                           nullptr, tokens_out, B, s, static_cast<char*>(tape), &tp, drop_scale, dropout_keep, drop_rate, aug, aug_noise,
-                          aug_noise_len, nullptr, nullptr, dense));
+                          aug_noise_len, nullptr, nullptr, dense->tokens_out != nullptr ? dense : nullptr, levels));
   if (dense->kept_idx == nullptr) return TR_OK;
   // the decisions stay on the tape for the backward; the slabs take a copy of each deciding block's two slots (a slot IS a slab: B * N0 ints,
   // written by the kernels that write the eval slabs)
@@ -1228,6 +1257,24 @@ extern "C" int tr_vit_forward_train_dense(const tr_vit_config* cfg, const tr_vit
   }
   return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in, nullptr,
                                 drop_scale, tokens_out, B, s, dropout_keep, drop_rate, aug, aug_noise, aug_noise_len, dense);
+}
+
+extern "C" int tr_vit_forward_train_levels(const tr_vit_config* cfg, const tr_vit_weights* w, const void* img, int input_format,
+                                           const float* pixel_lut, const tr_augment_rec* aug, const float* aug_noise, long aug_noise_len,
+                                           float* logits, void* workspace, size_t workspace_bytes, void* tape, size_t tape_bytes,
+                                           const float* noise_in, const float* drop_scale, int* tokens_out, int B, tr_stream_t s,
+                                           const uint8_t* dropout_keep, float drop_rate, const tr_vit_dense_train* dense,
+                                           const tr_vit_train_levels* levels) {
+  TR_REQUIRE(cfg && dense && levels, TR_ERR_NULL, "tr_vit_forward_train_levels: null config, tr_vit_dense_train or tr_vit_train_levels");
+  TR_REQUIRE(cfg->family != TR_FAMILY_DYVIT, TR_ERR_CONFIG,
+             "tr_vit_forward_train_levels: DyViT keeps every token under a policy in training and has its own feature output (features_out)");
+  if (aug != nullptr) {
+    TR_REQUIRE(input_format == TR_INPUT_U8_NCHW || input_format == TR_INPUT_U8_NHWC, TR_ERR_CONFIG,
+               "tr_vit_forward_train_levels: the augmentation runs on uint8 pixels (input_format %d)", input_format);
+    TR_REQUIRE(B > 0 && B % 2 == 0, TR_ERR_SHAPE, "tr_vit_forward_train_levels: an augmented batch must be even, got B = %d", B);
+  }
+  return vit_forward_train_impl(cfg, w, img, input_format, pixel_lut, logits, workspace, workspace_bytes, tape, tape_bytes, noise_in, nullptr,
+                                drop_scale, tokens_out, B, s, dropout_keep, drop_rate, aug, aug_noise, aug_noise_len, dense, levels);
 }
 
 extern "C" int tr_vit_forward_train(const tr_vit_config* cfg, const tr_vit_weights* w, const float* img, float* logits, void* workspace,

@@ -35,7 +35,8 @@ forward_dense(blocks=...) / get_intermediate_layers do the same for chosen inter
 blocks while the fast path runs (tr_vit_forward_levels), each level is placed by the stages at or before its block, and one index launch and
 one gather launch serve all levels (tr_dense_index_levels, tr_dense_gather_levels).
 forward_dense_train is the last block's map of a TRAINING forward, a second output of the training autograd node: its gradient reaches the
-backbone through tr_dense_scatter (the gather's adjoint) and tr_vit_backward_dense (training.py).
+backbone through tr_dense_scatter (the gather's adjoint) and tr_vit_backward_dense (training.py).  forward_dense_train(blocks=...) returns
+the maps of chosen blocks, each a further output of that node (tr_vit_forward_train_levels, tr_dense_scatter_levels, tr_vit_backward_levels).
 """
 from __future__ import annotations
 
@@ -935,14 +936,14 @@ class VisionTransformer(nn.Module):
         The forward stays on the fast path (tr_vit_forward_levels: one launch per level where its CLS tap would run; the CLS tail stays unless
         the last block is asked for), followed by tr_stage_decisions and ONE tr_dense_index_levels and ONE tr_dense_gather_levels for all
         levels; blocks and norm are part of the graph key.  blocks=None is the call described first, unchanged.
-        A soft-weighted un-merge and following EViT's fused token are not built; in train mode the last block's map, with a gradient, is
+        A soft-weighted un-merge and following EViT's fused token are not built; in train mode the same maps, each with a gradient, are
         forward_dense_train's.  Refuses train mode, viz_mode, dynamic_width and a block out of range."""
         if isinstance(x, AugmentedBatch):
             x = x.float()
         dense = dict(output_fmt=output_fmt, dtype=dtype, fill=fill, blocks=blocks, norm=norm)
         return self._forward_eval(x, 0, self._eval_request(x, "forward_dense", dense=dense))
 
-    def forward_dense_train(self, x: torch.Tensor, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
+    def forward_dense_train(self, x: torch.Tensor, blocks=None, norm=True, output_fmt="NCHW", dtype=torch.float32, fill=0.0):
         """Training forward with a dense feature map that carries a gradient: (out, {"features", "index", "grid"}).  `out` is what model(x)
         returns in train mode (the logits, or the CLS features of a headless model), bit for bit; the dictionary has the shapes, layouts,
         dtypes and index / fill semantics of eval's forward_dense (the last block's final-normed rows, single level).  `features` is the
@@ -952,21 +953,35 @@ class VisionTransformer(nn.Module):
         gradient reducer's block ranges, DropPath and dropout, uint8 and augmented inputs, x.grad and the one-tape guard behave as for
         model(x).  `index` carries no gradient; a patch without a row shows `fill` and receives none.  The buffers (rows, stream, decision
         slabs, index, map) are one set per model, like the tape; the map and the index are cloned out.
-        Refuses eval mode (use forward_dense), viz_mode, a CPU input, dynamic_width, a precision other than bf16 and DyViT.  Multi-level maps
-        in training, a differentiable eval forward, a soft-weighted un-merge and following EViT's fused token are not built."""
+        blocks=(...) asks for the maps of chosen blocks (validated as in forward_dense: ints in [-depth, depth), no duplicates, not empty;
+        results in ascending block order): (out, {"features": [L maps], "index": [L int32 [B, h * w]], "blocks", "grid", "cls": fp32 [B, L,
+        D]}).  Level l is the stream after block blocks[l]: every row with the residual pending there -- the training forward's own branch,
+        DropPath-scaled and dropout-masked, summed in fp32 -- through the model's final norm in fp32 arithmetic (norm=True) or as it stands
+        (norm=False), placed on the grid by the decisions of the stages at or before that block.  Every map is a further output of the same
+        autograd node: a loss on any subset of the maps and / or `out` drives ONE loss.backward() -- one tr_dense_scatter_levels launch for
+        the maps that have a gradient, then tr_vit_backward_levels, which injects each level's gradient into the stream gradient in front of
+        its block (norm=True: the final norm's backward over the level's rows, which also adds to norm.weight.grad / norm.bias.grad;
+        norm=False: one add launch).  A map without a gradient costs no scatter work and no injection; with no map gradient at all the
+        backward is model(x)'s.  `index` and `cls` carry no gradient (`cls` is a detached copy of row 0 of each level).  Memory, one set per
+        model and (B, L, norm) beside the tape: with norm=True a level costs two fp32 slabs of B * N0 * D (the summed stream and its norm),
+        with norm=False one (the gather's operand; the backward needs nothing more); plus per level one token-gradient slab (bf16 / fp32),
+        the index and the map.  blocks=None is the call described first, unchanged.
+        Refuses eval mode (use forward_dense), viz_mode, a CPU input, dynamic_width, a precision other than bf16, DyViT and a block out of
+        range.  A gradient through `cls`, a differentiable eval forward, a soft-weighted un-merge and following EViT's fused token are not
+        built."""
         applies = {"eval": not self.training, "viz_mode": self.viz_mode, "cpu": not x.is_cuda, "dynamic_width": self.dynamic_width,
                    "precision": self.precision != "bf16", "dyvit": self._family == _lib.TR_FAMILY_DYVIT}
-        dense = None
+        dense = levels = None
         for check, message in DENSE_TRAIN_REFUSALS.items():
             if check == "args":
-                dense, _ = self._dense_arguments(output_fmt=output_fmt, dtype=dtype, fill=fill)
+                dense, levels = self._dense_arguments(output_fmt=output_fmt, dtype=dtype, fill=fill, blocks=blocks, norm=norm)
             elif applies[check]:
                 exc = NotImplementedError if check in ("precision", "dyvit") else RuntimeError
                 raise exc(message.format(what="forward_dense_train", device=x.device))
         if isinstance(x, AugmentedBatch) and self.pixel_input is None:
             x = x.float()         # pixel input off: the augmented fp32 image, then the float path (as forward does)
         from . import training
-        return training.train_forward(self, x, dense)
+        return training.train_forward(self, x, dense, levels)
 
     def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape=False, return_class_token=False, norm=False, dtype=torch.float32, fill=0.0):
         """timm's VisionTransformer.get_intermediate_layers on the fast path: the patch tokens after the last `n` blocks (int n) or after the

@@ -774,6 +774,66 @@ def dense_gather_levels(tokens: torch.Tensor, level_stride: int, level_rows, ind
     return out.view(shape)
 
 
+def dense_scatter_levels(dmaps, index: torch.Tensor, level_rows, level_stride: int, layout: str = "NCHW", dtype=torch.float32,
+                         out: torch.Tensor = None) -> torch.Tensor:
+    """The adjoint of dense_gather_levels (tr_dense_scatter_levels, one launch for all levels): dmaps is a sequence of L map gradients, each
+    [B, D, P] (layout "NCHW") or [B, P, D] ("NHWC"), all fp32 or all bf16 -- or None for a level without a gradient, whose slab of the result is
+    not touched and which costs no workgroup.  index int32 [L, B, P]; the result is flat, level l's rows [B, level_rows[l], D] at
+    l * level_stride elements, fp32 or bf16 (`dtype`).  Per level the bits of dense_scatter.  With every entry None nothing is launched."""
+    dmaps = list(dmaps)
+    _same_device(index, out, *dmaps)
+    if layout not in DENSE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(DENSE_LAYOUTS)}, got {layout!r}")
+    rows = _level_array(level_rows, "level_rows")
+    L = len(rows)
+    if len(dmaps) != L or index.dim() != 3 or index.shape[0] != L:
+        raise ValueError(f"{L} level rows need {L} maps (or None) and an index [L, B, P], got {len(dmaps)} maps and index {tuple(index.shape)}")
+    _, B, P = index.shape
+    present = [m for m in dmaps if m is not None]
+    in_dtype = present[0].dtype if present else torch.float32
+    if dtype not in (torch.float32, torch.bfloat16) or in_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"the maps and dtype must be torch.float32 or torch.bfloat16, got {in_dtype} and {dtype}")
+    if not present:
+        D = 4
+    else:
+        D = present[0].shape[1] if layout == "NCHW" else present[0].shape[2]
+        for m in present:
+            if m.dim() != 3 or m.dtype != in_dtype or tuple(m.shape) != ((B, D, P) if layout == "NCHW" else (B, P, D)):
+                raise ValueError(f"every map must be {in_dtype} {(B, D, P) if layout == 'NCHW' else (B, P, D)}, got {m.dtype} {tuple(m.shape)}")
+    if out is None:
+        out = torch.empty(L * level_stride, dtype=dtype, device=index.device)
+    elif out.numel() < L * level_stride:
+        raise ValueError(f"out must hold {L * level_stride} elements, got {out.numel()}")
+    ptrs = (ctypes.c_void_p * L)(*[None if m is None else _dev(m, in_dtype, "dmap") for m in dmaps])
+    _lib.check(_lib.load().tr_dense_scatter_levels(ptrs, _dev(index, torch.int32, "index"), _dev(out, dtype, "out"), level_stride, rows, L,
+                                                   DENSE_LAYOUTS[layout], int(in_dtype == torch.bfloat16), int(dtype == torch.bfloat16), B, P, D,
+                                                   _stream(index)), "tr_dense_scatter_levels")
+    return out
+
+
+def level_tap_norm(x: torch.Tensor, gamma, beta, eps: float, d1: torch.Tensor = None, d2: torch.Tensor = None):
+    """(sum, y) of fp32 rows [M, D] in one launch (tr_level_tap_norm): sum = (x + d1) + d2 -- cls_tap's bits at row stride D -- and y its fp32
+    LayerNorm -- final_tokens_f32's bits.  d1 / d2 bf16 or fp32 rows [M, D], both nullable; x is not written."""
+    _same_device(x, d1, d2, gamma, beta)
+    D = x.shape[-1]
+    M = x.numel() // D
+    total, y = torch.empty(M, D, dtype=torch.float32, device=x.device), torch.empty(M, D, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().tr_level_tap_norm(_dev(x, torch.float32, "x"), _pending(d1, "d1"), _pending(d2, "d2"), _pending_f32(d1, d2),
+                                             _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), total.data_ptr(),
+                                             y.data_ptr(), M, D, eps, _stream(x)), "tr_level_tap_norm")
+    return total, y
+
+
+def stream_grad_add(d: torch.Tensor, g: torch.Tensor, gb: torch.Tensor = None):
+    """g += d in fp32 and gb = bf16(g), in place (tr_stream_grad_add): d, g fp32 and gb bf16 (nullable) of one element count, a multiple of 4."""
+    _same_device(d, g, gb)
+    if d.numel() != g.numel() or (gb is not None and gb.numel() != g.numel()):
+        raise ValueError(f"d, g and gb must hold the same number of elements, got {d.numel()}, {g.numel()}, {None if gb is None else gb.numel()}")
+    _lib.check(_lib.load().tr_stream_grad_add(_dev(d, torch.float32, "d"), _dev(g, torch.float32, "g"), _opt(gb, torch.bfloat16, "gb"),
+                                              g.numel(), _stream(g)), "tr_stream_grad_add")
+    return g, gb
+
+
 def attention_f32(qkv: torch.Tensor, B: int, N: int, H: int, want_cls: bool = False, size: torch.Tensor = None,
                   colsum_part: torch.Tensor = None, split: bool = False):
     out = torch.empty(B * N, H * 64, dtype=torch.float32, device=qkv.device)

@@ -16,6 +16,10 @@ back into the image; the node returns it in x's slot and autograd accumulates `x
 the stream that entered it and the decisions in the eval slabs' format; the eval path's three launches (tr_stage_decisions, tr_dense_index,
 tr_dense_gather) put the rows on the patch grid, and the map is the node's second output.  Its gradient goes through `tr_dense_scatter`
 (the gather's adjoint, bf16 out) into `tr_vit_backward_dense`, which adds the final norm's backward of every row to the stream gradient.
+`model.forward_dense_train(x, blocks=...)` asks for the maps of several blocks: `tr_vit_forward_train_levels` taps every chosen block where
+eval's level taps run (one launch per level), `tr_dense_index_levels` and `tr_dense_gather_levels` build all maps, and each map is a further
+output of the node.  In backward ONE `tr_dense_scatter_levels` launch takes the gradients of the maps that have one back to their rows, and
+`tr_vit_backward_levels` injects each level's gradient into the stream gradient in front of its block.
 
 PyTorch is plumbing: memory, the stream, the autograd hook and the loss.  No arithmetic of the model happens in torch.
 """
@@ -108,6 +112,7 @@ class TrainState:
         self._stage_of = {n: loc for loc, names in self._stage_names.items() for n in names}
         self.gen = 0                 # counts training forwards: the tape belongs to the LAST one (see _VitTrainFn.backward)
         self.dense = None            # forward_dense_train's buffers (dense_buffers): one set per model, like the tape
+        self.levels = None           # forward_dense_train(blocks=...)'s buffers (level_buffers): one set per model and (B, L, norm)
 
     def _block_slices(self, model):
         """[(event_index, start, stop)] over the flat buffer: the slice event `e` of tr_vit_backward completes."""
@@ -248,6 +253,31 @@ class TrainState:
             self.dense = d
         return d
 
+    def level_buffers(self, model, B, dev, levels):
+        """What forward_dense_train(blocks=...) owns beside the tape, for one (batch size, number of levels, norm): the level slabs of
+        tr_vit_forward_train_levels (`tokens`: what the gather reads -- the final-normed rows, or with norm=False the summed rows; `stream`,
+        norm=True only: the summed rows the norm's backward needs), the decision slabs and the eval path's decision plan as in dense_buffers,
+        the indices [L, B, P0], one set of maps per output dtype and the token gradients tr_dense_scatter_levels writes (bf16 for norm=True,
+        fp32 for norm=False).  A slab is B * N0 * D elements."""
+        L, norm = len(levels.blocks), bool(levels.norm)
+        d = self.levels
+        if d is None or d["key"] != (B, dev, L, norm):
+            P0, D = model.patch_embed.num_patches, model.embed_dim
+            rows = B * (P0 + 1) * D
+            empty = lambda n, dtype=torch.float32: torch.empty(n, dtype=dtype, device=dev)
+            d = dict(key=(B, dev, L, norm), B=B, dev=dev, stride=rows, tokens=empty(L * rows), stream=empty(L * rows) if norm else None,
+                     kept=empty(model.depth * B * (P0 + 1), torch.int32), compl=empty(model.depth * B * (P0 + 1), torch.int32),
+                     index=empty(L * B * P0, torch.int32), feat={}, dtok=empty(L * rows, torch.bfloat16 if norm else torch.float32))
+            dec = d["plan"] = model._decision_plan(d, B, dev)          # (keeps itself in d["dec"])
+            d["struct"] = _lib.TrVitDenseTrain(None, None, 0, d["kept"].data_ptr(), d["compl"].data_ptr(), d["kept"].numel(), dec["soft_ptr"],
+                                               dec["soft_elems"])
+            self.levels = d
+        mask = sum(1 << b for b in levels.blocks)
+        d["taps"] = _lib.TrVitTrainLevels(mask, int(norm), d["tokens"].data_ptr(), None if d["stream"] is None else d["stream"].data_ptr(),
+                                          d["tokens"].numel())
+        d["mask"] = mask
+        return d
+
 
 TAPE_FIELDS = ("x0", "x1", "xn1", "qkv", "ao", "dattn", "x2", "xn2", "pre", "h", "idx", "idx2", "scores", "size",
                "n_pre", "n_att", "n_mlp", "kk")
@@ -333,10 +363,12 @@ class _VitTrainFn(torch.autograd.Function):
     backward.  Outputs: (logits,) or for DyViT (logits, pred_0 .. pred_{S-1} [, features]): pred_j = the stage's hard keep decision
     [B,P] (straight-through differentiable, dyvit.py:223-225), features = the final norm of the patch tokens [B,P,D].
     dense (an eval_request.DenseOutput; not DyViT): forward_dense_train's request -- the outputs are (logits, map), the map as eval's
-    forward_dense lays it out; the index stays in TrainState.dense.  Without it the inputs, outputs and launches are those above."""
+    forward_dense lays it out; the index stays in TrainState.dense.  Without it the inputs, outputs and launches are those above.
+    levels (an eval_request.Levels, with dense): forward_dense_train(blocks=...) -- the outputs are (logits, map_0, ..., map_{L-1}) in
+    ascending block order; indices and slabs stay in TrainState.levels."""
 
     @staticmethod
-    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None, xe=None, dense=None):
+    def forward(ctx, anchor, x, model, fmt=_lib.TR_INPUT_F32, lut=None, aug=None, xe=None, dense=None, levels=None):
         lib = _lib.load()
         pk = model._pack(need_transposed=True)
         cfg = pk["cfg"]
@@ -366,7 +398,9 @@ class _VitTrainFn(torch.autograd.Function):
         noise = model._gumbel_ptr(B, x.device) if dyvit else model._noise_ptr(B, x.device)
         ctx.drop = drop_path_scales(model, B, x.device)
         ctx.keep_mask = dropout_keep_mask(model, pk, B, x.device)
-        dn = st.dense_buffers(model, B, x.device) if dense is not None else None
+        dn = None
+        if dense is not None:
+            dn = st.dense_buffers(model, B, x.device) if levels is None else st.level_buffers(model, B, x.device, levels)
         with torch.cuda.device(x.device):
             rest = (logits.data_ptr(), ws["buf"].data_ptr(), ws["nbytes"], tape.data_ptr(), tape.numel(), noise,
                     None if feats is None else feats.data_ptr(), None if ctx.drop is None else ctx.drop.data_ptr(), tokens, B,
@@ -374,10 +408,11 @@ class _VitTrainFn(torch.autograd.Function):
                     float(model.drop_rate or 0.0))
             if dn is not None:       # the superset entry: any of the three inputs below, plus the dense request's caller-owned outputs
                 table, aug_noise = aug if aug is not None else (None, None)
-                rc = lib.tr_vit_forward_train_dense(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut,
-                                                    None if table is None else table.data_ptr(),
-                                                    aug_noise.data_ptr() if aug_noise is not None and aug_noise.numel() else None,
-                                                    0 if aug_noise is None else aug_noise.numel(), *rest[:6], *rest[7:], C.byref(dn["struct"]))
+                entry = lib.tr_vit_forward_train_dense if levels is None else lib.tr_vit_forward_train_levels
+                rc = entry(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, None if table is None else table.data_ptr(),
+                           aug_noise.data_ptr() if aug_noise is not None and aug_noise.numel() else None,
+                           0 if aug_noise is None else aug_noise.numel(), *rest[:6], *rest[7:], C.byref(dn["struct"]),
+                           *(() if levels is None else (C.byref(dn["taps"]),)))
             elif aug is not None:    # uint8 pixels + the device-side erase / mixup / cutmix table (augment.py): the columns of the augmented image
                 table, aug_noise = aug
                 rc = lib.tr_vit_forward_train_aug(C.byref(cfg), C.byref(pk["W"]), x.data_ptr(), fmt, lut, table.data_ptr(),
@@ -391,11 +426,14 @@ class _VitTrainFn(torch.autograd.Function):
         ctx.model, ctx.B, ctx.pk = model, B, pk
         ctx.keep = (x, aug)
         ctx.n_pred, ctx.distill = 0, distill
-        ctx.dense = dense
+        ctx.dense, ctx.levels = dense, levels
         if dense is not None:
             ctx.set_materialize_grads(False)      # a loss on one output alone: the other's gradient arrives as None and its path is skipped
         if model._out_width != model._out_cols:          # the padded classifier columns never leave the executor
             logits = logits[:, :model._out_cols].contiguous()
+        if dn is not None and levels is not None:
+            with torch.cuda.device(x.device):
+                return (logits,) + _dense_maps(model, dn, dense, levels, list(tokens), B)
         if dn is not None:
             with torch.cuda.device(x.device):
                 return logits, _dense_map(model, dn, dense, list(tokens), B)
@@ -432,8 +470,26 @@ class _VitTrainFn(torch.autograd.Function):
             dlp = torch.zeros(B, model._out_width, dtype=torch.float32, device=dev)
             dlp[:, :model._out_cols] = dl
             dl = dlp
-        dpred = dfeat = dtok = None
-        if ctx.dense is not None and dextra[0] is not None:
+        dpred = dfeat = dtok = lev = None
+        if ctx.levels is not None and any(g is not None for g in dextra):
+            # the gradients of the maps that have one, back on their levels' rows: ONE tr_dense_scatter_levels launch with the forward's indices
+            # (the gen guard above keeps them the forward's).  A level without a gradient is a NULL entry: no tile, no injection below
+            dn, P0, L = st.levels, model.patch_embed.num_patches, len(ctx.levels.blocks)
+            dmaps = [None if g is None else g.detach() for g in dextra[:L]]
+            kinds = {g.dtype for g in dmaps if g is not None}
+            if kinds != {torch.bfloat16}:          # one dtype per launch: fp32 unless every gradient is bf16
+                dmaps = [None if g is None else g.to(torch.float32) for g in dmaps]
+            dmaps = [None if g is None else g.contiguous() for g in dmaps]
+            ptrs = (C.c_void_p * L)(*[None if g is None else g.data_ptr() for g in dmaps])
+            present = sum(1 << l for l, g in enumerate(dmaps) if g is not None)
+            with torch.cuda.device(dev):
+                _lib.check(lib.tr_dense_scatter_levels(ptrs, dn["index"].data_ptr(), dn["dtok"].data_ptr(), dn["stride"], dn["rows"], L,
+                                                       _lib.TR_LAYOUT_NCHW if ctx.dense.fmt == "NCHW" else _lib.TR_LAYOUT_NHWC,
+                                                       int(kinds == {torch.bfloat16}), int(ctx.levels.norm), B, P0, model.embed_dim,
+                                                       torch.cuda.current_stream().cuda_stream), "tr_dense_scatter_levels")
+            lev = _lib.TrVitLevelGrads(dn["mask"], int(ctx.levels.norm), present, dn["dtok"].data_ptr(),
+                                       None if dn["stream"] is None else dn["stream"].data_ptr(), dn["stride"])
+        elif ctx.levels is None and ctx.dense is not None and dextra[0] is not None:
             # the map's gradient back on the token rows: tr_dense_scatter with the forward's index (the gen guard above keeps it the
             # forward's), bf16 out -- the form the final norm's backward reads
             dn, P0 = st.dense, model.patch_embed.num_patches
@@ -491,7 +547,9 @@ class _VitTrainFn(torch.autograd.Function):
                         None if dpred is None else dpred.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
                         None if ctx.drop is None else ctx.drop.data_ptr(), st.tape.data_ptr(), st.tape.numel(), st.bws.data_ptr(), st.bws.numel(), accumulate, hi, lo, B, stream,
                         None if ctx.keep_mask is None else ctx.keep_mask.data_ptr(), float(model.drop_rate or 0.0))
-                if dtok is not None:     # every range call takes it; the one with hi == depth - 1 consumes it
+                if lev is not None:      # every range call takes the levels; a level is consumed by the call whose range holds its block
+                    rc = lib.tr_vit_backward_levels(*args, None if dx is None else dx.data_ptr(), None, 0, None, C.byref(lev))
+                elif dtok is not None:   # every range call takes it; the one with hi == depth - 1 consumes it
                     rc = lib.tr_vit_backward_dense(*args, None if dx is None else dx.data_ptr(), dtok.data_ptr(), 1, st.dense["stream"].data_ptr())
                 else:
                     rc = lib.tr_vit_backward(*args) if dx is None else lib.tr_vit_backward_dx(*args, dx.data_ptr())
@@ -513,7 +571,34 @@ class _VitTrainFn(torch.autograd.Function):
         model._dirty_by_backward = not was_dirty      # dirt that was there before this backward is somebody else's: only a full repack clears it
         if dx is not None and dx.dtype != ctx.x_dtype:
             dx = dx.to(ctx.x_dtype)
-        return None, dx, None, None, None, None, None, None
+        return None, dx, None, None, None, None, None, None, None
+
+
+def _dense_maps(model, dn, dense, levels, tokens, B):
+    """_dense_map for the levels of forward_dense_train(blocks=...): tr_stage_decisions, then ONE tr_dense_index_levels and ONE
+    tr_dense_gather_levels for all levels (each level behind its own prefix of the stages; tr_dense_index_levels checks the stage table against
+    the token counts the training forward had after each chosen block).  Returns the L maps, cloned out of their per-model buffer; the indices
+    and the rows of every level stay in dn for the backward."""
+    lib, dec, stream = _lib.load(), dn["plan"], torch.cuda.current_stream().cuda_stream
+    D, P0, L = model.embed_dim, model.patch_embed.num_patches, len(levels.blocks)
+    if dec["static"] is None and not dec["checked"]:
+        model._decision_result(dec, B, tokens)                   # the stage table against the training forward's token counts, once
+    if dec["n"]:
+        _lib.check(lib.tr_stage_decisions(dn["kept"].data_ptr(), dn["compl"].data_ptr(), dn["kept"].numel(), dec["soft_ptr"], dec["soft_elems"],
+                                          dec["table"], dec["n"], B, P0 + 1, dec["kept_ptr"], dec["kept_elems"], dec["count_ptr"],
+                                          dec["assign_ptr"], dec["assign_elems"], stream), "tr_stage_decisions")
+    feat = dn["feat"].get(dense.dtype)
+    if feat is None:
+        feat = dn["feat"][dense.dtype] = torch.empty(L * B * P0 * D, dtype=dense.dtype, device=dn["dev"])
+    blocks = (C.c_int32 * L)(*levels.blocks)
+    rows = dn["rows"] = (C.c_int32 * L)(*[tokens[b] for b in levels.blocks])
+    _lib.check(lib.tr_dense_index_levels(dec["kept_ptr"], dec["kept_elems"], dec["assign_ptr"], dec["assign_elems"], dec["table"], dec["n"], B, P0,
+                                         blocks, rows, L, dn["index"].data_ptr(), stream), "tr_dense_index_levels")
+    _lib.check(lib.tr_dense_gather_levels(dn["tokens"].data_ptr(), dn["stride"], rows, L, dn["index"].data_ptr(), feat.data_ptr(),
+                                          _lib.TR_LAYOUT_NCHW if dense.fmt == "NCHW" else _lib.TR_LAYOUT_NHWC, int(dense.dtype == torch.bfloat16),
+                                          dense.fill, B, P0, D, stream), "tr_dense_gather_levels")
+    h, w = model.patch_embed.grid_size
+    return tuple(feat.clone().view((L, B, D, h, w) if dense.fmt == "NCHW" else (L, B, h, w, D)).unbind(0))
 
 
 def _dense_map(model, dn, dense, tokens, B):
@@ -541,7 +626,7 @@ def _dense_map(model, dn, dense, tokens, B):
     return feat.clone().view((B, D, h, w) if dense.fmt == "NCHW" else (B, h, w, D))
 
 
-def train_forward(model, x: torch.Tensor, dense=None):
+def train_forward(model, x: torch.Tensor, dense=None, levels=None):
     if model._family == _lib.TR_FAMILY_DYVIT and model._pool_mode() == _lib.TR_POOL_AVG:
         raise NotImplementedError("global_pool='avg' is not built for DyViT in train mode: training keeps the masked tokens in the stream under a "
                                   "differentiable policy (dyvit.py:221-229), so there is no token set to average over; DyViT eval, where the tokens "
@@ -566,9 +651,16 @@ def train_forward(model, x: torch.Tensor, dense=None):
     # tensor, as before
     anchor = torch.empty(0, dtype=torch.float32, device=xe.device, requires_grad=True)
     if fmt == _lib.TR_INPUT_F32 and aug is None and x.requires_grad and torch.is_grad_enabled():
-        out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug, xe, dense)
+        out = _VitTrainFn.apply(anchor, x, model, fmt, lut, aug, xe, dense, levels)
     else:
-        out = _VitTrainFn.apply(anchor, xe, model, fmt, lut, aug, None, dense)
+        out = _VitTrainFn.apply(anchor, xe, model, fmt, lut, aug, None, dense, levels)
+    if levels is not None:           # forward_dense_train(blocks=...): eval's multi-level dictionary; index and cls carry no gradient
+        (h, w), st, B, D = model.patch_embed.grid_size, model._train_state(), x.shape[0], model.embed_dim
+        dn, L = st.levels, len(levels.blocks)
+        slabs = dn["tokens"].view(L, -1)
+        cls = torch.stack([slabs[l, :B * n * D].view(B, n, D)[:, 0] for l, n in enumerate(dn["rows"])], dim=1)      # (a strided copy)
+        return out[0], {"features": list(out[1:]), "index": list(dn["index"].clone().view(L, B, h * w)), "blocks": levels.blocks,
+                        "grid": (h, w), "cls": cls}
     if dense is not None:            # forward_dense_train: (out, the map); the index is a copy of the per-model buffer and carries no gradient
         h, w = model.patch_embed.grid_size
         st = model._train_state()

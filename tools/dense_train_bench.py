@@ -1,6 +1,7 @@
 """Dense feature maps in training against the plain training step, both in one process on one box (profiles/dense_train_lab.md).
 
     python tools/dense_train_bench.py [--batch 256] [--steps 10] [--rounds 3] [--models topk tome deit] [--fmt NCHW] [--dtype fp32]
+                                       [--levels 2 5 8 11] [--no-norm]
 
 Per model (DeiT-S width, 224 x 224: Top-K kr 0.7, ToMe, dense DeiT-S; reduction at blocks 3 / 6 / 9) one JSON line with ms per step, device
 events around `steps` steps, the two sides alternating within a round (median, min and max over the rounds):
@@ -10,7 +11,11 @@ then the launches the dense step has and the plain step has not, by label, with 
 of each side: the milliseconds since the previous launch's event, so a launch's own time plus its launch gap), and one JSON line per
 (layout, input dtype) of tr_dense_scatter alone on the model's own index: its time (device events around `steps` launches, bf16 out as the
 backward asks for it) and the bytes it must move -- the map once, the token gradient once, the index -- per second, against the rate a
-float4 copy reaches on this part."""
+float4 copy reaches on this part.
+With --levels b0 b1 ... (profiles/dense_train_levels_lab.md) a third side joins the rounds, all three alternating within a round:
+  levels   model.forward_dense_train(x, blocks=(b0, b1, ...)) + a sum loss on every map + backward
+and the scatter section compares ONE tr_dense_scatter_levels launch for all levels with one tr_dense_scatter launch per level on the same
+slabs and indices (the levels step's own), alternating within a round, in time and in bytes per second of the kernel's own traffic."""
 import argparse
 import ctypes as C
 import json
@@ -68,7 +73,7 @@ def _stats(v):
     return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
 
 
-def run(tag, batch, steps, rounds, fmt, dtype):
+def run(tag, batch, steps, rounds, fmt, dtype, levels=None, norm=True):
     import torch
     from tokenreduction_amd import ops
     model = _create(tag)
@@ -84,16 +89,28 @@ def run(tag, batch, steps, rounds, fmt, dtype):
         _, d = model.forward_dense_train(x, output_fmt=fmt, dtype=dtype)
         d["features"].sum().backward()
 
+    def multi():
+        model.zero_grad(set_to_none=True)
+        _, d = model.forward_dense_train(x, blocks=levels, norm=norm, output_fmt=fmt, dtype=dtype)
+        sum(f.sum() for f in d["features"]).backward()
+
+    sides = {"plain": plain, "dense": dense}
+    if levels:
+        sides["levels"] = multi
     for _ in range(2):
-        plain()
-        dense()
-    t = {"plain": [], "dense": []}
+        for fn in sides.values():
+            fn()
+    t = {k: [] for k in sides}
     for _ in range(rounds):
-        t["plain"].append(_event_ms(plain, steps))
-        t["dense"].append(_event_ms(dense, steps))
-    print(json.dumps({"model": tag, "batch": batch, "fmt": fmt, "dtype": str(dtype), "steps": steps, "rounds": rounds,
-                      "plain_ms": _stats(t["plain"]), "dense_ms": _stats(t["dense"]),
-                      "dense_minus_plain_ms": round(statistics.median(t["dense"]) - statistics.median(t["plain"]), 4)}), flush=True)
+        for k, fn in sides.items():
+            t[k].append(_event_ms(fn, steps))
+    line = {"model": tag, "batch": batch, "fmt": fmt, "dtype": str(dtype), "steps": steps, "rounds": rounds,
+            "plain_ms": _stats(t["plain"]), "dense_ms": _stats(t["dense"]),
+            "dense_minus_plain_ms": round(statistics.median(t["dense"]) - statistics.median(t["plain"]), 4)}
+    if levels:
+        line.update(levels=list(levels), norm=norm, levels_ms=_stats(t["levels"]),
+                    levels_minus_plain_ms=round(statistics.median(t["levels"]) - statistics.median(t["plain"]), 4))
+    print(json.dumps(line), flush=True)
     # the launches only the dense step has, with their times
     p, d = _profile(plain), _profile(dense)
     left = {}
@@ -110,7 +127,10 @@ def run(tag, batch, steps, rounds, fmt, dtype):
     print(json.dumps({"model": tag, "launches_plain": len(p), "launches_dense": len(d), "profiled_ms_plain": round(sum(m for _, m in p), 4),
                       "profiled_ms_dense": round(sum(m for _, m in d), 4),
                       "extra_launches": {k: {"count": c, "ms": round(m, 4)} for k, (c, m) in extra.items()}}), flush=True)
+    if levels:
+        _scatter_levels(model, tag, batch, steps, rounds, multi)
     # the scatter alone, on the index of the last dense forward
+    dense()
     st = model._train_state()
     P0, D, n_rows = model.patch_embed.num_patches, model.embed_dim, st.dense["rows"]
     index = st.dense["index"].view(batch, P0)
@@ -127,6 +147,40 @@ def run(tag, batch, steps, rounds, fmt, dtype):
                               "tb_per_s": round(need / med / 1e9, 3), "of_float4_copy": round(need / med / 1e9 / HBM_COPY_TBS, 3)}), flush=True)
 
 
+def _scatter_levels(model, tag, batch, steps, rounds, multi):
+    """One tr_dense_scatter_levels launch against one tr_dense_scatter launch per level, on the levels step's own indices and rows."""
+    import torch
+    from tokenreduction_amd import ops
+    multi()
+    dn = model._train_state().levels
+    P0, D, rows, stride = model.patch_embed.num_patches, model.embed_dim, list(dn["rows"]), dn["stride"]
+    L = len(rows)
+    index = dn["index"].view(L, batch, P0)
+    per_level = [index[l].clone() for l in range(L)]
+    for layout in ("NCHW", "NHWC"):
+        for src in (torch.float32, torch.bfloat16):
+            maps = [torch.randn((batch, D, P0) if layout == "NCHW" else (batch, P0, D), device="cuda").to(src) for _ in range(L)]
+            out = torch.empty(L * stride, dtype=torch.bfloat16, device="cuda")
+            outs = [out[l * stride: l * stride + batch * rows[l] * D] for l in range(L)]
+            one = lambda: ops.dense_scatter_levels(maps, index, rows, stride, layout=layout, dtype=torch.bfloat16, out=out)
+
+            def each():
+                for l in range(L):
+                    ops.dense_scatter(maps[l], per_level[l], rows[l], layout=layout, dtype=torch.bfloat16, out=outs[l])
+            one()
+            each()
+            ms = {"one_launch": [], "per_level": []}
+            for _ in range(rounds):
+                ms["one_launch"].append(_event_ms(one, steps))
+                ms["per_level"].append(_event_ms(each, steps))
+            need = sum(batch * P0 * D * maps[0].element_size() + batch * r * D * 2 + 4 * batch * P0 for r in rows)
+            m1, mL = statistics.median(ms["one_launch"]), statistics.median(ms["per_level"])
+            print(json.dumps({"model": tag, "scatter_levels": layout, "dmap": str(src), "rows": rows, "one_launch_ms": _stats(ms["one_launch"]),
+                              "per_level_ms": _stats(ms["per_level"]), "required_bytes": need, "one_launch_tb_per_s": round(need / m1 / 1e9, 3),
+                              "per_level_tb_per_s": round(need / mL / 1e9, 3), "of_float4_copy": round(need / m1 / 1e9 / HBM_COPY_TBS, 3)}),
+                  flush=True)
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -136,10 +190,12 @@ def main():
     ap.add_argument("--models", nargs="+", default=["topk", "tome", "deit"], choices=sorted(MODELS))
     ap.add_argument("--fmt", default="NCHW", choices=["NCHW", "NHWC"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--levels", type=int, nargs="+", default=None, help="blocks of a multi-level step, e.g. 2 5 8 11")
+    ap.add_argument("--no-norm", action="store_true", help="the levels as they stand (norm=False)")
     a = ap.parse_args()
     dtype = torch.float32 if a.dtype == "fp32" else torch.bfloat16
     for tag in a.models:
-        run(tag, a.batch, a.steps, a.rounds, a.fmt, dtype)
+        run(tag, a.batch, a.steps, a.rounds, a.fmt, dtype, tuple(a.levels) if a.levels else None, not a.no_norm)
 
 
 if __name__ == "__main__":
