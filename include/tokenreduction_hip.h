@@ -69,6 +69,12 @@ int tr_cls_pos_rows(const float* cls_token, const float* pos_embed, float* x, in
 int tr_patch_embed_supported(int C, int HW, int patch, int D);
 int tr_patch_embed_bf16(const float* img, const uint16_t* W, const float* bias, const float* cls_token, const float* pos_embed, float* x,
                         int B, int C, int HW, int patch, int D, tr_stream_t s);
+/* The same launch on a rectangular image, img fp32 [B,C,H,W]: P = (H/16) (W/16) patches in row-major order, patch p = (p / (W/16), p % (W/16)).
+ * The HW entries above are these with H = W = HW (one kernel, the same bits).  tr_patch_embed_hw_supported: patch 16, H and W positive
+ * multiples of 16, D a positive multiple of 384, C * H * W < 2^30 (the kernel's 32-bit source offsets). */
+int tr_patch_embed_hw_supported(int C, int H, int W, int patch, int D);
+int tr_patch_embed_hw_bf16(const float* img, const uint16_t* W_, const float* bias, const float* cls_token, const float* pos_embed, float* x,
+                           int B, int C, int H, int W, int patch, int D, tr_stream_t s);
 
 /* PatchEmbed's data gradient (the gradient of the stride-16 Conv2d with respect to the image): for patch p = (py, px) of image b
  *   dx[b, c, 16 py + iy, 16 px + ix] = sum_k dY[(b, p), k] * W[k, (c, iy, ix)]
@@ -79,6 +85,11 @@ int tr_patch_embed_bf16(const float* img, const uint16_t* W, const float* bias, 
  * anything else is TR_ERR_SHAPE. */
 int tr_patch_embed_dgrad_supported(int C, int HW, int patch, int D);
 int tr_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int HW, int patch, int D, tr_stream_t s);
+/* The same launch on a rectangular image: dx fp32 [B, C, H, W], P = (H/16) (W/16) row-major patches; H and W multiples of 16 up to 4096 each.
+ * tr_patch_embed_dgrad is this with H = W = HW. */
+int tr_patch_embed_dgrad_hw_supported(int C, int H, int W, int patch, int D);
+int tr_patch_embed_dgrad_hw(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int H, int W, int patch, int D,
+                            tr_stream_t s);
 
 /* Raw uint8 pixels: img uint8 [B,C,H,W] (layout TR_LAYOUT_NCHW) or [B,H,W,C] (TR_LAYOUT_NHWC), 16-byte aligned; lut fp32 [C][256] is the
  * normalized value of every pixel value, lut[c][v] = (v / 255 - mean[c]) / std[c] computed by the host (torchvision's ToTensor + Normalize
@@ -90,6 +101,9 @@ int tr_im2col_u8_bf16(const uint8_t* img, const float* lut, int layout, uint16_t
 int tr_im2col_u8_f32(const uint8_t* img, const float* lut, int layout, float* cols, int B, int C, int H, int W, int patch, tr_stream_t s);
 int tr_patch_embed_u8_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls_token,
                            const float* pos_embed, float* x, int B, int C, int HW, int patch, int D, tr_stream_t s);
+/* tr_patch_embed_u8_bf16 on a rectangular image (shapes: tr_patch_embed_hw_supported; NHWC with C = 1 or 3) */
+int tr_patch_embed_u8_hw_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W_, const float* bias, const float* cls_token,
+                              const float* pos_embed, float* x, int B, int C, int H, int W, int patch, int D, tr_stream_t s);
 
 /* Train-time augmentation of a uint8 batch on the device: RandomErasing (datasets.py:93-95, per image, before mixing) and timm's Mixup
  * (mixup / cutmix, engine.py:47-48), applied to the normalized values while the image is unfolded.  The batch B is even and image b's
@@ -644,7 +658,13 @@ typedef struct {
 
 typedef struct {
   int family;                 /* TR_FAMILY_* */
-  int img_size, patch, in_chans;
+  short img_size;             /* image height in pixels, a positive multiple of `patch` */
+  short img_width;            /* image width in pixels; 0 = square, width = img_size.  Otherwise a positive multiple of `patch`; anything else
+                                 is an invalid config.  The grid is gh x gw = (img_size / patch) x (width / patch), P = gh gw patches in row-major
+                                 order, patch p = (p / gw, p % gw): every token count, the tape and the workspace follow from P, and images are
+                                 [B, C, img_size, width].  (Two 16-bit halves of what was `int img_size`: the struct keeps its 80 x 4 bytes and
+                                 every offset, and a caller that wrote the int 224 wrote img_size = 224, img_width = 0.) */
+  int patch, in_chans;
   int embed_dim, depth, num_heads, mlp_hidden, num_classes;   /* num_classes == 0: headless (no classifier; the output is the
                                                                   final-normed CLS row, see tr_vit_forward) */
   float ln_eps;
@@ -691,7 +711,8 @@ size_t tr_vit_workspace_bytes(const tr_vit_config* cfg, int B);
  * it where the logits are consumed. */
 int tr_vit_forward_status(const tr_vit_config* cfg, void* workspace, size_t workspace_bytes, int B, tr_stream_t s);
 
-/* img fp32 [B,C,S,S] -> logits fp32 [B,classes].  Headless (num_classes == 0, deit_viz.py:142,182: head = nn.Identity()): `logits` is
+/* img fp32 [B,C,H,W] (H = cfg->img_size, W = cfg->img_width or, when that is 0, H) -> logits fp32 [B,classes].
+ * Headless (num_classes == 0, deit_viz.py:142,182: head = nn.Identity()): `logits` is
  * fp32 [B,D] and receives pre_logits(norm(x)[:, 0]), the final-normed CLS row; no classifier GEMM runs and w->head_w / head_b may be NULL.
  * In bf16 the row is the final norm's output before its bf16 rounding (tr_layernorm_bf16_f32): bf16(features) is the classifier's operand.
  * cfg->global_pool == 1: the norm and the classifier (or, headless, `logits`) read the weighted average of the patch rows after the last block
@@ -709,8 +730,8 @@ int tr_vit_forward(const tr_vit_config* cfg, const tr_vit_weights* w, const floa
                    void* workspace, size_t workspace_bytes, int32_t* kept_idx, int32_t* compl_idx, float* soft_out,
                    const float* noise_in, float* features_out, int* tokens_out, int B, tr_stream_t s);
 
-/* tr_vit_forward / tr_vit_forward_train with the image in another format: input_format TR_INPUT_F32 = fp32 [B,C,S,S] (the calls above),
- * TR_INPUT_U8_NCHW = uint8 [B,C,S,S], TR_INPUT_U8_NHWC = uint8 [B,S,S,C] (NHWC: C = 1 or 3 where the fused patch embedding runs).  For the
+/* tr_vit_forward / tr_vit_forward_train with the image in another format: input_format TR_INPUT_F32 = fp32 [B,C,H,W] (the calls above),
+ * TR_INPUT_U8_NCHW = uint8 [B,C,H,W], TR_INPUT_U8_NHWC = uint8 [B,H,W,C] (NHWC: C = 1 or 3 where the fused patch embedding runs).  For the
  * uint8 formats pixel_lut is the fp32 [C][256] table of tr_patch_embed_u8_bf16 and the patch embedding normalizes on the way in: outputs
  * and the training tape are bitwise those of the fp32 call on the normalized image.  Any other format, or a uint8 format without a LUT,
  * is TR_ERR_CONFIG.  (Separate entry points rather than fields of tr_vit_config / tr_vit_weights: those layouts are part of the ABI.) */
@@ -881,7 +902,7 @@ int tr_dense_scatter_levels(const void* const* dmaps, const int32_t* index, void
 
 /* ---- training: forward that keeps its activations + backward executor (csrc/tr_vit.hip, csrc/tr_train.hip) ----------------------
  * engine.py:50-76: `output = model(samples)` in train mode, `loss.backward()`.  Every family (bf16 operands, fp32 master weights and
- * gradients), up to 640 tokens (224 x 224 and 384 x 384 inputs).  DyViT (dyvit.py:221-229): noise_in = the Gumbel noise of every stage, fp32 [B,P,2] back to back (torch's
+ * gradients), up to 640 tokens (224 x 224 and 384 x 384 inputs, or any H x W grid of at most 639 patches).  DyViT (dyvit.py:221-229): noise_in = the Gumbel noise of every stage, fp32 [B,P,2] back to back (torch's
  * -log(Exp(1)) draws); the stages' policies stay on the tape (tr_vit_tape_layout); features_out (nullable) fp32 [B,N0,D]: the final
  * norm of every row (the distillation features, dyvit.py:252-258); tr_vit_backward takes dpred fp32 [stages,B,P] (gradient wrt each
  * stage's out_pred_prob) and dfeat fp32 [B,N0,D] (gradient wrt features_out), both nullable.

@@ -44,10 +44,16 @@ class TrVitWeights(C.Structure):
 
 
 class TrVitConfig(C.Structure):
-    _fields_ = [("family", _i), ("img_size", _i), ("patch", _i), ("in_chans", _i), ("embed_dim", _i),
+    _fields_ = [("family", _i), ("img_size", C.c_short), ("img_width", C.c_short), ("patch", _i), ("in_chans", _i), ("embed_dim", _i),
                 ("depth", _i), ("num_heads", _i), ("mlp_hidden", _i), ("num_classes", _i), ("ln_eps", _f),
                 ("keep", _i * TR_MAX_DEPTH), ("precision", _i), ("knn_k", _i), ("cluster_iters", _i), ("sinkhorn_eps", _f),
                 ("kmed_init", _i * TR_MAX_DEPTH), ("ats_dynamic", _i), ("concurrent", C.c_short), ("global_pool", C.c_short)]       # the two 16-bit halves of the last word
+    # img_size / img_width: the two 16-bit halves of what was `int img_size` (height; width, 0 = square)
+
+    @property
+    def image_hw(self):
+        """(H, W) in pixels: img_width == 0 means a square image."""
+        return int(self.img_size), int(self.img_width) or int(self.img_size)
 
 
 class TrVitTaps(C.Structure):        # tr_vit_taps: the output taps of tr_vit_forward_taps
@@ -119,6 +125,11 @@ SIGNATURES = {
     "tr_patch_embed_supported": (_i, [_i, _i, _i, _i]),
     "tr_patch_embed_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_patch_embed_dgrad_supported": (_i, [_i, _i, _i, _i]),
+    "tr_patch_embed_hw_supported": (_i, [_i, _i, _i, _i, _i]),
+    "tr_patch_embed_hw_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "tr_patch_embed_u8_hw_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "tr_patch_embed_dgrad_hw_supported": (_i, [_i, _i, _i, _i, _i]),
+    "tr_patch_embed_dgrad_hw": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "tr_patch_embed_dgrad": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "tr_im2col_u8_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -77,7 +77,7 @@ template <int FMT>
 __global__ __launch_bounds__(512, 1) void patch_embed_kernel(const void* __restrict__ img, const float* __restrict__ lut,
                                                              const uint16_t* __restrict__ W,
                                                              const float* __restrict__ bias, const float* __restrict__ cls,
-                                                             const float* __restrict__ pos, float* __restrict__ x, int C, int HW, int gw,
+                                                             const float* __restrict__ pos, float* __restrict__ x, int C, int H, int IW, int gw,
                                                              int P, int D, int nchunk) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(512, 1) void patch_embed_kernel(const void* __restr
   // uint8: item e -> m = e % rows_pad, r = e / rows_pad, the whole run; offsets in bytes, destination = chunk 2 r (chunk 2 r + 1 is adst ^ 16)
   unsigned aoff[NIT];
   int adst[NIT];
-  const float* ibase = static_cast<const float*>(img) + (FMT == PE_F32 ? (size_t)b * C * HW * HW : 0);
-  const uint8_t* ubase = static_cast<const uint8_t*>(img) + (FMT != PE_F32 ? (size_t)b * C * HW * HW : 0);
+  const float* ibase = static_cast<const float*>(img) + (FMT == PE_F32 ? (size_t)b * C * H * IW : 0);
+  const uint8_t* ubase = static_cast<const uint8_t*>(img) + (FMT != PE_F32 ? (size_t)b * C * H * IW : 0);
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = tid + 512 * it;
@@ -110,14 +110,14 @@ __global__ __launch_bounds__(512, 1) void patch_embed_kernel(const void* __restr
       const bool live = r < 4 && m < rows;
       const int p = min(p0 + m, P - 1);
       const int py = p / gw, px = p - py * gw;
-      aoff[it] = (unsigned)((py * 16 + min(r, 3)) * HW + px * 16 + q * 4);
+      aoff[it] = (unsigned)((py * 16 + min(r, 3)) * IW + px * 16 + q * 4);
       adst[it] = live ? aswz(m, 2 * r + (q >> 1)) + (q & 1) * 8 : -1;
     } else {
       const int r = e / PE_ROWS, m = e - r * PE_ROWS;            // r in 0..4 for e < 1024: r == 4 masked
       const bool live = r < 4 && m < rows;
       const int p = min(p0 + m, P - 1);
       const int py = p / gw, px = p - py * gw;
-      aoff[it] = (unsigned)(((py * 16 + min(r, 3)) * HW + px * 16) * NV);
+      aoff[it] = (unsigned)(((py * 16 + min(r, 3)) * IW + px * 16) * NV);
       adst[it] = live ? aswz(m, 2 * r) : -1;
     }
   }
@@ -144,16 +144,16 @@ __global__ __launch_bounds__(512, 1) void patch_embed_kernel(const void* __restr
 #pragma unroll
     for (int j = 0; j < 6; ++j) dma_piece(W, woff[j] + (unsigned)kt * 128u, wdst + slot * PE_W_BYTES + j * 1024);
     if constexpr (FMT == PE_F32) {
-      const float* src = ibase + (size_t)(kt >> 2) * HW * HW + (size_t)((kt & 3) * 4) * HW;
+      const float* src = ibase + (size_t)(kt >> 2) * H * IW + (size_t)((kt & 3) * 4) * IW;
 #pragma unroll
       for (int it = 0; it < PE_ITEMS; ++it)      // nontemporal: the image is read once -- kept out of the caches the forward lives in (-12 us per forward)
         areg[it] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + aoff[it]));
     } else if constexpr (FMT == PE_U8_NCHW) {    // plain loads: measured 62.7 -> 58.2 us against nontemporal at DeiT-S 224, batch 256
-      const uint8_t* src = ubase + (size_t)(kt >> 2) * HW * HW + (size_t)((kt & 3) * 4) * HW;
+      const uint8_t* src = ubase + (size_t)(kt >> 2) * H * IW + (size_t)((kt & 3) * 4) * IW;
 #pragma unroll
       for (int it = 0; it < NIT; ++it) ureg[it][0] = *reinterpret_cast<const u32x4*>(src + aoff[it]);
     } else {                                     // NHWC: every channel of the run, 3 x 16 B (the next two channels re-read them from L2)
-      const uint8_t* src = ubase + (size_t)((kt & 3) * 4) * HW * 3;
+      const uint8_t* src = ubase + (size_t)((kt & 3) * 4) * IW * 3;
 #pragma unroll
       for (int it = 0; it < NIT; ++it)
 #pragma unroll
@@ -253,35 +253,72 @@ __global__ __launch_bounds__(512, 1) void patch_embed_kernel(const void* __restr
 
 template <int FMT>
 int launch_patch_embed(const void* img, const float* lut, const uint16_t* W, const float* bias, const float* cls, const float* pos, float* x,
-                       int B, int C, int HW, int D, tr_stream_t s, const char* what) {
-  const int gw = HW / 16, P = gw * gw, nchunk = (P + PE_ROWS - 1) / PE_ROWS;
+                       int B, int C, int H, int IW, int D, tr_stream_t s, const char* what) {
+  const int gw = IW / 16, P = (H / 16) * gw, nchunk = (P + PE_ROWS - 1) / PE_ROWS;
   TR_REQUIRE((size_t)D * C * 256 * 2 < ((size_t)1 << 32), TR_ERR_SHAPE, "%s: weight beyond the 32-bit offset range", what);
   const int lds = PE_LDS + (FMT == PE_F32 ? 0 : C * 256 * 4);
   hipStream_t st = static_cast<hipStream_t>(s);
   TR_RESERVE_LDS(reinterpret_cast<const void*>(patch_embed_kernel<FMT>), lds, what);
   tr_prof_note("patch_embed_kernel", 2.0 * B * P * (double)D * C * 256,
-               (double)B * C * HW * HW * (FMT == PE_F32 ? 4.0 : 1.0) + (double)B * (P + 1) * D * 4.0);
-  hipLaunchKernelGGL(patch_embed_kernel<FMT>, dim3(B * nchunk, D / PE_NC), dim3(512), lds, st, img, lut, W, bias, cls, pos, x, C, HW, gw, P, D,
-                     nchunk);
+               (double)B * C * H * IW * (FMT == PE_F32 ? 4.0 : 1.0) + (double)B * (P + 1) * D * 4.0);
+  hipLaunchKernelGGL(patch_embed_kernel<FMT>, dim3(B * nchunk, D / PE_NC), dim3(512), lds, st, img, lut, W, bias, cls, pos, x, C, H, IW, gw, P,
+                     D, nchunk);
   TR_CHECK_LAUNCH(what);
   return TR_OK;
 }
 
 }  // namespace
 
-// 1 when tr_patch_embed_bf16 takes this shape (else the executor runs im2col + GEMM + cls/pos)
+// 1 when tr_patch_embed_hw_bf16 takes this shape (else the executor runs im2col + GEMM + cls/pos).  C * H * W < 2^30 keeps the kernel's 32-bit
+// per-thread source offsets (aoff: bytes of a uint8 NHWC plane at most) in range.
+extern "C" int tr_patch_embed_hw_supported(int C, int H, int W, int patch, int D) {
+  return patch == 16 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0 && C >= 1 && D > 0 && D % PE_NC == 0 && (size_t)C * H * W < ((size_t)1 << 30);
+}
+
+// the square form: H = W = HW
 extern "C" int tr_patch_embed_supported(int C, int HW, int patch, int D) {
   return patch == 16 && HW % 16 == 0 && C >= 1 && D % PE_NC == 0 && (size_t)C * HW * HW < ((size_t)1 << 30);
 }
+
+namespace {
+
+// the checks behind the alignment of every fp32 entry, then the launch
+int patch_embed_f32(const float* img, const uint16_t* W, const float* bias, const float* cls, const float* pos, float* x, int B, int C, int H,
+                    int IW, int D, tr_stream_t s, const char* what) {
+  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(W) && tr_aligned16(bias) && tr_aligned16(cls) && tr_aligned16(pos) && tr_aligned16(x), TR_ERR_ALIGN,
+             "%s: pointers must be 16-byte aligned", what);
+  return launch_patch_embed<PE_F32>(img, nullptr, W, bias, cls, pos, x, B, C, H, IW, D, s, what);
+}
+
+int patch_embed_u8(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls, const float* pos,
+                   float* x, int B, int C, int H, int IW, int D, tr_stream_t s, const char* what) {
+  TR_REQUIRE(PE_LDS + C * 256 * 4 <= 160 * 1024, TR_ERR_SHAPE, "%s: the pixel LUT of %d channels does not fit beside the ring", what, C);
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || C == 1 || C == 3, TR_ERR_SHAPE, "%s: NHWC needs 1 or 3 channels (C=%d)", what, C);
+  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(lut) && tr_aligned16(W) && tr_aligned16(bias) && tr_aligned16(cls) && tr_aligned16(pos) &&
+                 tr_aligned16(x),
+             TR_ERR_ALIGN, "%s: pointers must be 16-byte aligned", what);
+  if (layout == TR_LAYOUT_NCHW || C == 1)        // one channel: NHWC and NCHW are the same bytes
+    return launch_patch_embed<PE_U8_NCHW>(img, lut, W, bias, cls, pos, x, B, C, H, IW, D, s, what);
+  return launch_patch_embed<PE_U8_NHWC3>(img, lut, W, bias, cls, pos, x, B, C, H, IW, D, s, what);
+}
+
+}  // namespace
 
 extern "C" int tr_patch_embed_bf16(const float* img, const uint16_t* W, const float* bias, const float* cls, const float* pos, float* x, int B,
                                    int C, int HW, int patch, int D, tr_stream_t s) {
   TR_REQUIRE(img && W && bias && cls && pos && x, TR_ERR_NULL, "tr_patch_embed_bf16: null pointer");
   TR_REQUIRE(B > 0 && tr_patch_embed_supported(C, HW, patch, D), TR_ERR_SHAPE,
              "tr_patch_embed_bf16: need patch 16, H = W a multiple of 16, embed_dim a multiple of %d (C=%d HW=%d patch=%d D=%d)", PE_NC, C, HW, patch, D);
-  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(W) && tr_aligned16(bias) && tr_aligned16(cls) && tr_aligned16(pos) && tr_aligned16(x), TR_ERR_ALIGN,
-             "tr_patch_embed_bf16: pointers must be 16-byte aligned");
-  return launch_patch_embed<PE_F32>(img, nullptr, W, bias, cls, pos, x, B, C, HW, D, s, "tr_patch_embed_bf16");
+  return patch_embed_f32(img, W, bias, cls, pos, x, B, C, HW, HW, D, s, "tr_patch_embed_bf16");
+}
+
+extern "C" int tr_patch_embed_hw_bf16(const float* img, const uint16_t* W, const float* bias, const float* cls, const float* pos, float* x, int B,
+                                      int C, int H, int IW, int patch, int D, tr_stream_t s) {
+  TR_REQUIRE(img && W && bias && cls && pos && x, TR_ERR_NULL, "tr_patch_embed_hw_bf16: null pointer");
+  TR_REQUIRE(B > 0 && tr_patch_embed_hw_supported(C, H, IW, patch, D), TR_ERR_SHAPE,
+             "tr_patch_embed_hw_bf16: need patch 16, H and W multiples of 16, embed_dim a multiple of %d (C=%d H=%d W=%d patch=%d D=%d)", PE_NC, C, H,
+             IW, patch, D);
+  return patch_embed_f32(img, W, bias, cls, pos, x, B, C, H, IW, D, s, "tr_patch_embed_hw_bf16");
 }
 
 extern "C" int tr_patch_embed_u8_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls,
@@ -292,14 +329,18 @@ extern "C" int tr_patch_embed_u8_bf16(const uint8_t* img, const float* lut, int 
   TR_REQUIRE(B > 0 && tr_patch_embed_supported(C, HW, patch, D), TR_ERR_SHAPE,
              "tr_patch_embed_u8_bf16: need patch 16, H = W a multiple of 16, embed_dim a multiple of %d (C=%d HW=%d patch=%d D=%d)", PE_NC, C, HW,
              patch, D);
-  TR_REQUIRE(PE_LDS + C * 256 * 4 <= 160 * 1024, TR_ERR_SHAPE, "tr_patch_embed_u8_bf16: the pixel LUT of %d channels does not fit beside the ring", C);
-  TR_REQUIRE(layout == TR_LAYOUT_NCHW || C == 1 || C == 3, TR_ERR_SHAPE, "tr_patch_embed_u8_bf16: NHWC needs 1 or 3 channels (C=%d)", C);
-  TR_REQUIRE(tr_aligned16(img) && tr_aligned16(lut) && tr_aligned16(W) && tr_aligned16(bias) && tr_aligned16(cls) && tr_aligned16(pos) &&
-                 tr_aligned16(x),
-             TR_ERR_ALIGN, "tr_patch_embed_u8_bf16: pointers must be 16-byte aligned");
-  if (layout == TR_LAYOUT_NCHW || C == 1)        // one channel: NHWC and NCHW are the same bytes
-    return launch_patch_embed<PE_U8_NCHW>(img, lut, W, bias, cls, pos, x, B, C, HW, D, s, "tr_patch_embed_u8_bf16");
-  return launch_patch_embed<PE_U8_NHWC3>(img, lut, W, bias, cls, pos, x, B, C, HW, D, s, "tr_patch_embed_u8_bf16");
+  return patch_embed_u8(img, lut, layout, W, bias, cls, pos, x, B, C, HW, HW, D, s, "tr_patch_embed_u8_bf16");
+}
+
+extern "C" int tr_patch_embed_u8_hw_bf16(const uint8_t* img, const float* lut, int layout, const uint16_t* W, const float* bias, const float* cls,
+                                         const float* pos, float* x, int B, int C, int H, int IW, int patch, int D, tr_stream_t s) {
+  TR_REQUIRE(img && lut && W && bias && cls && pos && x, TR_ERR_NULL, "tr_patch_embed_u8_hw_bf16: null pointer");
+  TR_REQUIRE(layout == TR_LAYOUT_NCHW || layout == TR_LAYOUT_NHWC, TR_ERR_SHAPE,
+             "tr_patch_embed_u8_hw_bf16: layout %d is neither NCHW (0) nor NHWC (1)", layout);
+  TR_REQUIRE(B > 0 && tr_patch_embed_hw_supported(C, H, IW, patch, D), TR_ERR_SHAPE,
+             "tr_patch_embed_u8_hw_bf16: need patch 16, H and W multiples of 16, embed_dim a multiple of %d (C=%d H=%d W=%d patch=%d D=%d)", PE_NC, C,
+             H, IW, patch, D);
+  return patch_embed_u8(img, lut, layout, W, bias, cls, pos, x, B, C, H, IW, D, s, "tr_patch_embed_u8_hw_bf16");
 }
 
 // ---- PatchEmbed data gradient: d image = fold(dY . W) --------------------------------------------------------------------------------
@@ -318,7 +359,7 @@ namespace {
 
 template <int NK, int R>      // NK = D / 32 K-steps; R units per workgroup
 __global__ __launch_bounds__(256) void patch_embed_dgrad_kernel(const uint16_t* __restrict__ dY, long ldy, const uint16_t* __restrict__ Wt,
-                                                                float* __restrict__ dx, int C, int HW, int gw, int P, int nb, int units) {
+                                                                float* __restrict__ dx, int C, int H, int IW, int gw, int P, int nb, int units) {
   constexpr int D = NK * 32;
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -330,14 +371,15 @@ __global__ __launch_bounds__(256) void patch_embed_dgrad_kernel(const uint16_t* 
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int u = min(u0 + r, units - 1);                    // past the last unit: reads the last one again, stores nothing
-    const int b = u / (gw * nb), rem = u - b * gw * nb;
+    const int upi = (H >> 4) * nb;                           // units of one image: gh patch rows x nb blocks of 16 patches
+    const int b = u / upi, rem = u - b * upi;
     const int py = rem / nb, pb = rem - py * nb;
     const int px = pb * 16 + li;
     const uint16_t* row = dY + ((size_t)b * (P + 1) + 1 + (size_t)py * gw + min(px, gw - 1)) * (size_t)ldy + 8 * g;
 #pragma unroll
     for (int k = 0; k < NK; ++k) yf[r][k] = *reinterpret_cast<const bf16x8*>(row + 32 * k);
     live[r] = u0 + r < units && px < gw;
-    obase[r] = (((size_t)b * C + c) * HW + (size_t)py * 16) * HW + (size_t)px * 16 + 4 * g;
+    obase[r] = (((size_t)b * C + c) * H + (size_t)py * 16) * IW + (size_t)px * 16 + 4 * g;
   }
 #pragma unroll 1
   for (int j = 0; j < 4; ++j) {
@@ -354,27 +396,50 @@ __global__ __launch_bounds__(256) void patch_embed_dgrad_kernel(const uint16_t* 
     }
 #pragma unroll
     for (int r = 0; r < R; ++r)
-      if (live[r]) *reinterpret_cast<f32x4*>(dx + obase[r] + (size_t)iy * HW) = acc[r];
+      if (live[r]) *reinterpret_cast<f32x4*>(dx + obase[r] + (size_t)iy * IW) = acc[r];
   }
 }
 
 template <int NK, int R>
-int launch_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int HW, tr_stream_t s) {
-  const int gw = HW / 16, P = gw * gw, nb = (gw + 15) / 16, units = B * gw * nb;
+int launch_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int H, int IW, tr_stream_t s, const char* what) {
+  const int gh = H / 16, gw = IW / 16, P = gh * gw, nb = (gw + 15) / 16, units = B * gh * nb;
   tr_prof_note("patch_embed_dgrad_kernel", 2.0 * B * P * (double)(NK * 32) * C * 256,
-               (double)B * C * HW * HW * 4.0 + (double)B * P * (NK * 32) * 2.0 + (double)C * 256 * (NK * 32) * 2.0);
+               (double)B * C * H * IW * 4.0 + (double)B * P * (NK * 32) * 2.0 + (double)C * 256 * (NK * 32) * 2.0);
   hipLaunchKernelGGL((patch_embed_dgrad_kernel<NK, R>), dim3((units + R - 1) / R, C), dim3(256), 0, static_cast<hipStream_t>(s), dY, ldy, Wt, dx, C,
-                     HW, gw, P, nb, units);
-  TR_CHECK_LAUNCH("tr_patch_embed_dgrad");
+                     H, IW, gw, P, nb, units);
+  TR_CHECK_LAUNCH(what);
   return TR_OK;
 }
 
 }  // namespace
 
-// 1 when tr_patch_embed_dgrad takes this shape: patch 16, H = W a multiple of 16, 1 or 3 channels, embed_dim 128 / 192 / 384 / 768
+// 1 when tr_patch_embed_dgrad_hw takes this shape: patch 16, H and W multiples of 16 (up to 4096), 1 or 3 channels, embed_dim 128 / 192 / 384 / 768
+extern "C" int tr_patch_embed_dgrad_hw_supported(int C, int H, int W, int patch, int D) {
+  return patch == 16 && H > 0 && H % 16 == 0 && H <= 4096 && W > 0 && W % 16 == 0 && W <= 4096 && (C == 1 || C == 3) &&
+         (D == 128 || D == 192 || D == 384 || D == 768);
+}
+
+// the square form: H = W = HW
 extern "C" int tr_patch_embed_dgrad_supported(int C, int HW, int patch, int D) {
   return patch == 16 && HW > 0 && HW % 16 == 0 && HW <= 4096 && (C == 1 || C == 3) && (D == 128 || D == 192 || D == 384 || D == 768);
 }
+
+namespace {
+
+int patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int H, int IW, int D, tr_stream_t s,
+                      const char* what) {
+  TR_REQUIRE((size_t)B * (H / 16) * ((IW / 16 + 15) / 16) < ((size_t)1 << 30), TR_ERR_SHAPE, "%s: batch %d beyond the launch grid", what, B);
+  TR_REQUIRE(tr_aligned16(dY) && tr_aligned16(Wt) && tr_aligned16(dx) && ldy % 8 == 0, TR_ERR_ALIGN,
+             "%s: pointers and the row stride of dY must be 16-byte aligned", what);
+  switch (D) {
+    case 128: return launch_patch_embed_dgrad<4, 4>(dY, ldy, Wt, dx, B, C, H, IW, s, what);
+    case 192: return launch_patch_embed_dgrad<6, 4>(dY, ldy, Wt, dx, B, C, H, IW, s, what);
+    case 384: return launch_patch_embed_dgrad<12, 4>(dY, ldy, Wt, dx, B, C, H, IW, s, what);
+    default: return launch_patch_embed_dgrad<24, 2>(dY, ldy, Wt, dx, B, C, H, IW, s, what);
+  }
+}
+
+}  // namespace
 
 extern "C" int tr_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int HW, int patch, int D,
                                     tr_stream_t s) {
@@ -382,13 +447,14 @@ extern "C" int tr_patch_embed_dgrad(const uint16_t* dY, long ldy, const uint16_t
   TR_REQUIRE(B > 0 && tr_patch_embed_dgrad_supported(C, HW, patch, D) && ldy >= D, TR_ERR_SHAPE,
              "tr_patch_embed_dgrad: need patch 16, H = W a multiple of 16, 1 or 3 channels, embed_dim 128 / 192 / 384 / 768, ldy >= embed_dim "
              "(C=%d HW=%d patch=%d D=%d ldy=%ld)", C, HW, patch, D, ldy);
-  TR_REQUIRE((size_t)B * (HW / 16) * ((HW / 16 + 15) / 16) < ((size_t)1 << 30), TR_ERR_SHAPE, "tr_patch_embed_dgrad: batch %d beyond the launch grid", B);
-  TR_REQUIRE(tr_aligned16(dY) && tr_aligned16(Wt) && tr_aligned16(dx) && ldy % 8 == 0, TR_ERR_ALIGN,
-             "tr_patch_embed_dgrad: pointers and the row stride of dY must be 16-byte aligned");
-  switch (D) {
-    case 128: return launch_patch_embed_dgrad<4, 4>(dY, ldy, Wt, dx, B, C, HW, s);
-    case 192: return launch_patch_embed_dgrad<6, 4>(dY, ldy, Wt, dx, B, C, HW, s);
-    case 384: return launch_patch_embed_dgrad<12, 4>(dY, ldy, Wt, dx, B, C, HW, s);
-    default: return launch_patch_embed_dgrad<24, 2>(dY, ldy, Wt, dx, B, C, HW, s);
-  }
+  return patch_embed_dgrad(dY, ldy, Wt, dx, B, C, HW, HW, D, s, "tr_patch_embed_dgrad");
+}
+
+extern "C" int tr_patch_embed_dgrad_hw(const uint16_t* dY, long ldy, const uint16_t* Wt, float* dx, int B, int C, int H, int IW, int patch, int D,
+                                       tr_stream_t s) {
+  TR_REQUIRE(dY && Wt && dx, TR_ERR_NULL, "tr_patch_embed_dgrad_hw: null pointer");
+  TR_REQUIRE(B > 0 && tr_patch_embed_dgrad_hw_supported(C, H, IW, patch, D) && ldy >= D, TR_ERR_SHAPE,
+             "tr_patch_embed_dgrad_hw: need patch 16, H and W multiples of 16, 1 or 3 channels, embed_dim 128 / 192 / 384 / 768, ldy >= embed_dim "
+             "(C=%d H=%d W=%d patch=%d D=%d ldy=%ld)", C, H, IW, patch, D, ldy);
+  return patch_embed_dgrad(dY, ldy, Wt, dx, B, C, H, IW, D, s, "tr_patch_embed_dgrad_hw");
 }

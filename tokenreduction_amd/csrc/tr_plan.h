@@ -32,10 +32,23 @@ inline size_t proj_rows(const tr_vit_config* c, const TokenPlan& t, int i) {
   return (size_t)((c->family == TR_FAMILY_ATS && t.kk[i] > 0) ? t.n_mlp[i] : t.n_att[i]);
 }
 
+// image height and width in pixels (tr_vit_config.img_width == 0: square)
+inline int img_h(const tr_vit_config* c) { return c->img_size; }
+inline int img_w(const tr_vit_config* c) { return c->img_width != 0 ? c->img_width : c->img_size; }
+// the patch grid is gh x gw, row-major; false when a side is not a positive multiple of the patch
+inline bool patch_grid(const tr_vit_config* c, int* gh, int* gw) {
+  const int H = img_h(c), W = img_w(c);
+  if (c->patch <= 0 || H <= 0 || W <= 0 || H % c->patch != 0 || W % c->patch != 0) return false;
+  *gh = H / c->patch;
+  *gw = W / c->patch;
+  return true;
+}
+
 inline bool make_token_plan(const tr_vit_config* c, TokenPlan* t) {
   if (c->global_pool != 0 && c->global_pool != 1) return false;      // 0 = the CLS row, 1 = the average of the patch tokens
-  const int g = c->img_size / c->patch;
-  t->P = g * g;
+  int gh, gw;
+  if (!patch_grid(c, &gh, &gw)) return false;
+  t->P = gh * gw;
   t->N0 = t->P + 1;
   int N = t->N0;
   for (int i = 0; i < c->depth; ++i) {

@@ -151,9 +151,9 @@ int frozen_plan(const tr_vit_config* cfg, const tr_vit_weights* w, const tr_vit_
   int stop = (f->u_embed || f->u_patch || dx != nullptr) ? -1 : cfg->depth;
   if (dx != nullptr) {
     TR_REQUIRE(wt->patch_w != nullptr, TR_ERR_NULL, "tr_vit_backward_dx: wt->patch_w (the patch weight transposed) is NULL");
-    TR_REQUIRE(tr_patch_embed_dgrad_supported(cfg->in_chans, cfg->img_size, cfg->patch, cfg->embed_dim), TR_ERR_SHAPE,
-               "tr_vit_backward_dx: no input gradient for in_chans %d, img_size %d, patch %d, embed_dim %d (tr_patch_embed_dgrad)", cfg->in_chans,
-               cfg->img_size, cfg->patch, cfg->embed_dim);
+    TR_REQUIRE(tr_patch_embed_dgrad_hw_supported(cfg->in_chans, trplan::img_h(cfg), trplan::img_w(cfg), cfg->patch, cfg->embed_dim), TR_ERR_SHAPE,
+               "tr_vit_backward_dx: no input gradient for in_chans %d, img_size %d x %d, patch %d, embed_dim %d (tr_patch_embed_dgrad_hw)",
+               cfg->in_chans, trplan::img_h(cfg), trplan::img_w(cfg), cfg->patch, cfg->embed_dim);
     TR_REQUIRE(tr_aligned16(dx), TR_ERR_ALIGN, "tr_vit_backward_dx: dx must be 16-byte aligned");
   }
   for (int i = 0; i < cfg->depth; ++i) {
@@ -667,7 +667,7 @@ struct Bwd {
     if (u_patch)
       TR_TRY(tr_linear_bwd_params(gb, D, t.P, tape<uint16_t>(tp.cols), kcols, F(grads->patch_w), F(grads->patch_b), acc, wsf, wsn, B * t.P, D, kcols, s));
     // the input gradient: the patch projection's data gradient, folded back into the image (every element of dx written once)
-    if (dx != nullptr) TR_TRY(tr_patch_embed_dgrad(gb, D, U(wt->patch_w), dx, B, cfg->in_chans, cfg->img_size, cfg->patch, D, s));
+    if (dx != nullptr) TR_TRY(tr_patch_embed_dgrad_hw(gb, D, U(wt->patch_w), dx, B, cfg->in_chans, trplan::img_h(cfg), trplan::img_w(cfg), cfg->patch, D, s));
     return TR_OK;
   }
 };

@@ -46,13 +46,13 @@ bool make_plan(const tr_vit_config* c, int B, Plan* p) {
   if (!c || B <= 0) return false;
   if (c->precision != TR_PREC_BF16 && c->precision != TR_PREC_FP32 && c->precision != TR_PREC_BF16X3) return false;
   const size_t es = c->precision != TR_PREC_BF16 ? 4 : 2;   // activation element size
-  if (c->patch <= 0 || c->img_size <= 0 || c->img_size % c->patch != 0) return false;
+  int gh, gw;
+  if (!trplan::patch_grid(c, &gh, &gw)) return false;
   if (c->depth <= 0 || c->depth > TR_MAX_DEPTH) return false;
   if (c->num_heads <= 0 || c->embed_dim != c->num_heads * 64) return false;
   if (c->family < TR_FAMILY_DEIT || c->family > TR_FAMILY_HEURISTIC) return false;
   if (c->global_pool != 0 && c->global_pool != 1) return false;
-  const int g = c->img_size / c->patch;
-  p->P = g * g;
+  p->P = gh * gw;
   p->N0 = p->P + 1;
   p->D = c->embed_dim;
   p->H = c->num_heads;
@@ -189,7 +189,7 @@ struct Fwd {
   bool f32, train;              // f32: fp32 activations (TR_PREC_FP32 and TR_PREC_BF16X3)
   char *ws, *tape;
   const trplan::TapePlan* tp;
-  const void* img;              // fp32 [B,C,S,S] (TR_INPUT_F32) or uint8 pixels normalized through pixel_lut by the patch embedding
+  const void* img;              // fp32 [B,C,H,W] (TR_INPUT_F32) or uint8 pixels normalized through pixel_lut by the patch embedding
   int input_format;
   const float *pixel_lut, *aug_noise;
   const tr_augment_rec* aug;
@@ -372,21 +372,21 @@ struct Fwd {
     const uint8_t* u8img = static_cast<const uint8_t*>(img);
     const float* fimg = static_cast<const float*>(img);
     const int layout = input_format == TR_INPUT_U8_NHWC ? TR_LAYOUT_NHWC : TR_LAYOUT_NCHW;
-    const int C = cfg->in_chans, S = cfg->img_size, patch = cfg->patch;
-    if (!train && !f32 && tr_patch_embed_supported(C, S, patch, D)) {
+    const int C = cfg->in_chans, IH = trplan::img_h(cfg), IW = trplan::img_w(cfg), patch = cfg->patch;
+    if (!train && !f32 && tr_patch_embed_hw_supported(C, IH, IW, patch, D)) {
       // eval: unfold + GEMM + cls/pos in one launch (tr_patch.hip), at every batch size (the two paths differ in the last bit: an image's
       // tokens must not depend on its batch); training keeps the column matrix (PatchEmbed's weight-gradient operand)
       if (pixels)
-        TR_TRY(tr_patch_embed_u8_bf16(u8img, pixel_lut, layout, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, S, patch, D, s));
+        TR_TRY(tr_patch_embed_u8_hw_bf16(u8img, pixel_lut, layout, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, IH, IW, patch, D, s));
       else
-        TR_TRY(tr_patch_embed_bf16(fimg, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, S, patch, D, s));
+        TR_TRY(tr_patch_embed_hw_bf16(fimg, u16(w->patch_w), w->patch_b, w->cls_token, w->pos_embed, x, B, C, IH, IW, patch, D, s));
     } else {
       if (pixels && aug != nullptr)      // training on uint8 pixels with the device-side erase / mixup / cutmix: the same columns, of the augmented image
-        TR_TRY(tr_im2col_u8_aug_bf16(u8img, pixel_lut, layout, aug, aug_noise, aug_noise_len, u16(cols), B, C, S, S, patch, s));
+        TR_TRY(tr_im2col_u8_aug_bf16(u8img, pixel_lut, layout, aug, aug_noise, aug_noise_len, u16(cols), B, C, IH, IW, patch, s));
       else if (pixels)
-        TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, C, S, S, patch, s));
+        TR_TRY(op_im2col_u8(f32, u8img, pixel_lut, layout, cols, B, C, IH, IW, patch, s));
       else
-        TR_TRY(op_im2col(f32, fimg, cols, B, C, S, S, patch, s));
+        TR_TRY(op_im2col(f32, fimg, cols, B, C, IH, IW, patch, s));
       TR_TRY(op_gemm(prec, cols, w->patch_w, w->patch_b, x, w->pos_embed, p.P, B * p.P, D, p.kcols, TR_EPI_PATCH_F32, s));
       TR_TRY(tr_cls_pos_rows(w->cls_token, w->pos_embed, x, B, p.N0, D, s));
     }

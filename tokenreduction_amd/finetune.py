@@ -138,11 +138,12 @@ class CosineSchedule:
             self._set(self.lr_at(num_updates))
 
 
-def load_finetune_checkpoint(model, checkpoint):
+def load_finetune_checkpoint(model, checkpoint, src_grid=None):
     """Ingest of a pre-trained checkpoint for fine-tuning (train.py:343-370): `checkpoint` is what torch.load returns for a
     DeiT-layout .pth ({"model": state_dict}) or the state dict itself.  A classifier whose shape does not fit the model is dropped,
     the position embedding is resized to the model's patch grid (class / distillation rows kept, the grid bicubically
-    interpolated -- 14 x 14 -> 24 x 24 for a 224 -> 384 fine-tune), a model with global_pool='avg' takes a checkpoint's fc_norm.* as its
+    interpolated to the model's (gh, gw) -- 14 x 14 -> 24 x 24 for a 224 -> 384 fine-tune, 14 x 14 -> 24 x 40 for a 384 x 640 model; the
+    checkpoint's grid is taken as square unless src_grid=(h, w) names it, and a length that is no square without src_grid raises), a model with global_pool='avg' takes a checkpoint's fc_norm.* as its
     norm.* when the checkpoint has no norm.* of its own (timm's layout of MAE fine-tuned weights), everything else is loaded non-strictly.
     A LayerScale model (init_values) takes a checkpoint's blocks.N.gamma_1 / gamma_2 (the DeiT-III repository's and older timm's names) as
     ls1.gamma / ls2.gamma unless the new names are there; a no_embed_class model's table has no class row, so all of it is the grid.  Returns load_state_dict's
@@ -168,11 +169,23 @@ def load_finetune_checkpoint(model, checkpoint):
             if new not in sd:
                 sd[new] = v
     pos = sd.get("pos_embed")
-    if pos is not None and pos.shape != model.pos_embed.shape:
-        n_patches = model.patch_embed.num_patches
-        n_extra = model.pos_embed.shape[-2] - n_patches
-        old, new = int((pos.shape[-2] - n_extra) ** 0.5), int(n_patches ** 0.5)
-        grid = pos[:, n_extra:].reshape(-1, old, old, pos.shape[-1]).permute(0, 3, 1, 2)
-        grid = F.interpolate(grid, size=(new, new), mode="bicubic", align_corners=False)
+    gh, gw = model.patch_embed.grid_size
+    if src_grid is not None:
+        src_grid = tuple(int(v) for v in src_grid)
+        if len(src_grid) != 2 or min(src_grid) <= 0:
+            raise ValueError(f"src_grid: expected (h, w) of the checkpoint's position grid, got {src_grid}")
+    if pos is not None and (pos.shape != model.pos_embed.shape or (src_grid is not None and src_grid != (gh, gw))):
+        n_extra = model.pos_embed.shape[-2] - gh * gw
+        n_src = pos.shape[-2] - n_extra
+        if src_grid is None:
+            side = int(round(n_src ** 0.5)) if n_src > 0 else 0
+            if side <= 0 or side * side != n_src:
+                raise ValueError(f"pos_embed: the checkpoint's table has {n_src} grid rows (of {pos.shape[-2]}), which is no square grid; "
+                                 "name its grid with src_grid=(h, w)")
+            src_grid = (side, side)
+        elif src_grid[0] * src_grid[1] != n_src:
+            raise ValueError(f"src_grid {src_grid} has {src_grid[0] * src_grid[1]} patches, the checkpoint's table {n_src} grid rows (of {pos.shape[-2]})")
+        grid = pos[:, n_extra:].reshape(-1, src_grid[0], src_grid[1], pos.shape[-1]).permute(0, 3, 1, 2)
+        grid = F.interpolate(grid, size=(gh, gw), mode="bicubic", align_corners=False)
         sd["pos_embed"] = torch.cat((pos[:, :n_extra], grid.permute(0, 2, 3, 1).flatten(1, 2)), dim=1)
     return model.load_state_dict(sd, strict=False)

@@ -15,6 +15,8 @@ There is no CPU path: forward() on a CPU tensor raises.  In train mode forward()
 every factory width, 224 x 224 and 384 x 384; what the training path refuses (attn_drop_rate, the distillation token,
 more than 640 tokens) raises there.  In eval mode every family runs at up to 1024 patch tokens + CLS (448 x 448 and 512 x 512
 inputs) in all three precisions; more tokens raise.
+img_size=(H, W), H and W multiples of 16, is a rectangular input [B, C, H, W]: a gh x gw = H/16 x W/16 grid of row-major patches, through
+every entry a square model runs, with the same limits on the token count; Heuristic, whose distance grid is square, refuses it.
 A headless model (num_classes=0 or reset_classifier(0): head = nn.Identity(), deit_viz.py:142,182) returns the fp32 final-normed CLS row
 [B, embed_dim] wherever a classifier returns logits -- eval in all three precisions, viz_mode, forward_async, training and its backward.
 global_pool='avg' (constructor, create_model, reset_classifier; timm's average-pooled head with fc_norm, the MAE fine-tuning layout): the
@@ -581,8 +583,7 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(dev)
         cfg = _lib.TrVitConfig()
         cfg.family = self._family
-        cfg.img_size, cfg.patch = self.patch_embed.img_size[0], self.patch_embed.patch_size[0]
-        cfg.in_chans = self.patch_embed.proj.in_channels
+        self._cfg_geometry(cfg)
         cfg.embed_dim, cfg.depth, cfg.num_heads = D, self.depth, self.num_heads
         cfg.mlp_hidden = self.blocks[0].mlp.fc1.out_features
         cfg.num_classes = self._classes_padded
@@ -607,6 +608,18 @@ class VisionTransformer(nn.Module):
         if pk.moved or old is None or bytes(old["cfg"]) != bytes(cfg) or bytes(old["W"]) != bytes(W):
             self._ws = {}
         return self._packed
+
+    def _cfg_geometry(self, cfg):
+        """The image side of tr_vit_config: img_size (the height) and img_width, the two 16-bit halves of what was one int -- a square
+        image keeps img_width = 0, the bytes the int wrote -- then patch and in_chans."""
+        (H, W), patch = self.patch_embed.img_size, self.patch_embed.patch_size
+        if patch[0] != patch[1]:
+            raise ValueError(f"patch_size {patch}: the executor takes square patches")
+        if not (0 < H < 32768 and 0 < W < 32768):
+            raise ValueError(f"img_size {(H, W)}: a side is outside 1 ... 32767")
+        cfg.img_size, cfg.img_width, cfg.patch = H, (0 if W == H else W), patch[0]
+        cfg.in_chans = self.patch_embed.proj.in_channels
+        return cfg
 
     def _refresh_mlp_pack(self, dev=None):
         """Rewrite the fragment-major Mlp copies from the (current) bf16 operand copies: one small launch per block, in place -- after every
@@ -804,7 +817,7 @@ class VisionTransformer(nn.Module):
         return self._pixel_input
 
     def set_pixel_input(self, mean=pixels.IMAGENET_DEFAULT_MEAN, std=pixels.IMAGENET_DEFAULT_STD):
-        """Opt-in: a uint8 input [B, C, S, S] -- contiguous (NCHW) or torch.channels_last (NHWC), read in place -- is taken as raw pixels and
+        """Opt-in: a uint8 input [B, C, H, W] -- contiguous (NCHW) or torch.channels_last (NHWC), read in place -- is taken as raw pixels and
         normalized inside the kernels that read the image, bitwise as if the fp32 tensor of torchvision's ToTensor() + Normalize(mean, std)
         had been passed.  Float inputs are unaffected.  set_pixel_input(None) turns it off (a uint8 tensor is then cast to fp32 as before).
         mean and std have in_chans entries.  Not a buffer: state_dict() stays the reference's; copy.deepcopy keeps the setting."""
@@ -1056,8 +1069,8 @@ class VisionTransformer(nn.Module):
             self._refresh_mlp_pack(x.device)
         cfg = pk["cfg"]
         B, Cc, Hh, Ww = x.shape
-        if (Cc, Hh, Ww) != (cfg.in_chans, cfg.img_size, cfg.img_size):
-            raise ValueError(f"expected [B,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(x.shape)}")
+        if (Cc, Hh, Ww) != (cfg.in_chans, *cfg.image_hw):
+            raise ValueError(f"expected [B, C, H, W] = [B,{cfg.in_chans},{cfg.image_hw[0]},{cfg.image_hw[1]}], got {tuple(x.shape)}")
         image = self._executor_input(x)
         x = image[0]
         ws = self._workspace(B, x.device, slot)
@@ -1951,6 +1964,10 @@ class HeuristicVisionTransformer(VisionTransformer):
     def __init__(self, *a, args=None, **kw):
         super().__init__(*a, args=args, **kw)
         self.heuristic_pattern = args.heuristic_pattern
+        gh, gw = self.patch_embed.grid_size
+        if gh != gw:
+            raise ValueError(f"{type(self).__name__}: img_size {self.patch_embed.img_size} gives a {gh} x {gw} patch grid, but the heuristic's "
+                             "distance grid is built on sqrt(num_patches) points per side (heuristic.py:158-162): a square grid only")
         if args.not_contiguous:
             self.reduction_loc = list(args.reduction_loc)
             self.keep_rate = list(args.keep_rate)

@@ -59,13 +59,17 @@ def cls_pos_rows(cls_token, pos_embed, x, B, N, D):
 
 
 def patch_embed(img: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cls_token: torch.Tensor, pos_embed: torch.Tensor, patch: int = 16) -> torch.Tensor:
-    """PatchEmbed + cls_token + pos_embed in one launch (topk.py:181-186): img fp32 [B,C,H,H], w bf16 [D, C*p*p] -> x fp32 [B, P+1, D]."""
-    B, Cc, H, _ = img.shape
+    """PatchEmbed + cls_token + pos_embed in one launch (topk.py:181-186): img fp32 [B,C,H,W], w bf16 [D, C*p*p] -> x fp32 [B, P+1, D],
+    P = (H/p)(W/p) row-major patches.  A square image goes through tr_patch_embed_bf16, any other through tr_patch_embed_hw_bf16."""
+    B, Cc, H, W = img.shape
     D = w.shape[0]
-    x = torch.empty(B, (H // patch) ** 2 + 1, D, dtype=torch.float32, device=img.device)
-    _lib.check(_lib.load().tr_patch_embed_bf16(_dev(img, torch.float32, "img"), _dev(w, torch.bfloat16, "w"), _dev(bias, torch.float32, "bias"),
-                                               _dev(cls_token, torch.float32, "cls_token"), _dev(pos_embed, torch.float32, "pos_embed"), x.data_ptr(),
-                                               B, Cc, H, patch, D, _stream()), "tr_patch_embed_bf16")
+    x = torch.empty(B, (H // patch) * (W // patch) + 1, D, dtype=torch.float32, device=img.device)
+    args = (_dev(img, torch.float32, "img"), _dev(w, torch.bfloat16, "w"), _dev(bias, torch.float32, "bias"),
+            _dev(cls_token, torch.float32, "cls_token"), _dev(pos_embed, torch.float32, "pos_embed"), x.data_ptr(), B, Cc)
+    if H == W:
+        _lib.check(_lib.load().tr_patch_embed_bf16(*args, H, patch, D, _stream()), "tr_patch_embed_bf16")
+    else:
+        _lib.check(_lib.load().tr_patch_embed_hw_bf16(*args, H, W, patch, D, _stream()), "tr_patch_embed_hw_bf16")
     return x
 
 
@@ -130,14 +134,18 @@ def pixels_augment(img: torch.Tensor, lut: torch.Tensor, table: torch.Tensor, no
 
 def patch_embed_u8(img: torch.Tensor, lut: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cls_token: torch.Tensor,
                    pos_embed: torch.Tensor, patch: int = 16) -> torch.Tensor:
-    """patch_embed of raw uint8 pixels (contiguous or channels_last) normalized through `lut`: bitwise patch_embed of the normalized image."""
-    B, Cc, H, _ = img.shape
+    """patch_embed of raw uint8 pixels [B,C,H,W] (contiguous or channels_last) normalized through `lut`: bitwise patch_embed of the
+    normalized image.  A square image goes through tr_patch_embed_u8_bf16, any other through tr_patch_embed_u8_hw_bf16."""
+    B, Cc, H, W = img.shape
     D = w.shape[0]
     ptr, lay, lp = _pixels(img, lut, Cc)
-    x = torch.empty(B, (H // patch) ** 2 + 1, D, dtype=torch.float32, device=img.device)
-    _lib.check(_lib.load().tr_patch_embed_u8_bf16(ptr, lp, lay, _dev(w, torch.bfloat16, "w"), _dev(bias, torch.float32, "bias"),
-                                                  _dev(cls_token, torch.float32, "cls_token"), _dev(pos_embed, torch.float32, "pos_embed"),
-                                                  x.data_ptr(), B, Cc, H, patch, D, _stream(img)), "tr_patch_embed_u8_bf16")
+    x = torch.empty(B, (H // patch) * (W // patch) + 1, D, dtype=torch.float32, device=img.device)
+    args = (ptr, lp, lay, _dev(w, torch.bfloat16, "w"), _dev(bias, torch.float32, "bias"), _dev(cls_token, torch.float32, "cls_token"),
+            _dev(pos_embed, torch.float32, "pos_embed"), x.data_ptr(), B, Cc)
+    if H == W:
+        _lib.check(_lib.load().tr_patch_embed_u8_bf16(*args, H, patch, D, _stream(img)), "tr_patch_embed_u8_bf16")
+    else:
+        _lib.check(_lib.load().tr_patch_embed_u8_hw_bf16(*args, H, W, patch, D, _stream(img)), "tr_patch_embed_u8_hw_bf16")
     return x
 
 
@@ -1131,10 +1139,22 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor = None, accumulat
     return out
 
 
-def patch_embed_dgrad(dy: torch.Tensor, wt: torch.Tensor, B: int, C: int, HW: int, patch: int = 16, out: torch.Tensor = None) -> torch.Tensor:
+def patch_embed_dgrad(dy: torch.Tensor, wt: torch.Tensor, B: int, C: int, HW=None, patch: int = 16, out: torch.Tensor = None, *, H: int = None,
+                      W: int = None) -> torch.Tensor:
     """PatchEmbed's data gradient folded back into the image (tr_patch_embed_dgrad): dy bf16 token rows [B * (P + 1), D] (or a column slice
     of a wider tensor; the CLS row of every image is never read), wt bf16 [C*patch*patch, D] = the patch weight transposed -> dx fp32
-    [B, C, HW, HW], every element written exactly once.  An unsupported shape raises."""
+    [B, C, HW, HW], every element written exactly once.  An unsupported shape raises.  A rectangular image: HW = (H, W) or the keywords
+    H and W -> dx [B, C, H, W] through tr_patch_embed_dgrad_hw (also when H == W); an int HW keeps the square entry."""
+    if H is not None or W is not None or isinstance(HW, (tuple, list)):
+        if isinstance(HW, (tuple, list)):
+            if H is not None or W is not None or len(HW) != 2:
+                raise ValueError(f"patch_embed_dgrad: give the image size once, as HW = (H, W) or as H and W (got HW = {HW}, H = {H}, W = {W})")
+            H, W = HW
+        elif HW is not None or H is None or W is None:
+            raise ValueError(f"patch_embed_dgrad: give either HW or both H and W (got HW = {HW}, H = {H}, W = {W})")
+        return _patch_embed_dgrad_hw(dy, wt, B, C, int(H), int(W), patch, out)
+    if HW is None:
+        raise ValueError("patch_embed_dgrad: the image size is missing (HW, or H and W)")
     D = wt.shape[-1]
     if out is None:
         out = torch.empty(B, C, HW, HW, dtype=torch.float32, device=dy.device)
@@ -1148,6 +1168,24 @@ def patch_embed_dgrad(dy: torch.Tensor, wt: torch.Tensor, B: int, C: int, HW: in
         raise ValueError(f"out: expected {(B, C, HW, HW)}, got {tuple(out.shape)}")
     _lib.check(_lib.load().tr_patch_embed_dgrad(pdy, ldy, _dev(wt, torch.bfloat16, "wt"), _dev(out, torch.float32, "out"), B, C, HW, patch, D,
                                                 _stream(dy)), "tr_patch_embed_dgrad")
+    return out
+
+
+def _patch_embed_dgrad_hw(dy, wt, B, C, H, W, patch, out):
+    """patch_embed_dgrad on [B, C, H, W] (tr_patch_embed_dgrad_hw), the same checks."""
+    D = wt.shape[-1]
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=dy.device)
+    _same_device(dy, wt, out)
+    pdy, ldy = _rows(dy, torch.bfloat16, "dy")
+    if wt.dim() != 2 or wt.shape[0] != C * patch * patch:
+        raise ValueError(f"wt: expected [{C * patch * patch}, D] (the patch weight transposed), got {tuple(wt.shape)}")
+    if dy.dim() != 2 or dy.shape[1] != D or patch <= 0 or H % patch or W % patch or dy.shape[0] != B * ((H // patch) * (W // patch) + 1):
+        raise ValueError(f"dy: expected token rows [B * (P + 1), {D}] for B = {B}, H = {H}, W = {W}, patch = {patch}, got {tuple(dy.shape)}")
+    if out.shape != (B, C, H, W):
+        raise ValueError(f"out: expected {(B, C, H, W)}, got {tuple(out.shape)}")
+    _lib.check(_lib.load().tr_patch_embed_dgrad_hw(pdy, ldy, _dev(wt, torch.bfloat16, "wt"), _dev(out, torch.float32, "out"), B, C, H, W, patch,
+                                                   D, _stream(dy)), "tr_patch_embed_dgrad_hw")
     return out
 
 

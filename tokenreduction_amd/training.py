@@ -227,8 +227,9 @@ class TrainState:
             nb = lib.tr_vit_backward_workspace_bytes(C.byref(pk["cfg"]), B)
             if nt == 0 or nb == 0:
                 raise NotImplementedError(
-                    f"{type(model).__name__}: this configuration has no training path in the HIP executor (built: every family at "
-                    "224x224 and 384x384, up to 640 tokens; bf16); call model.eval() for inference")
+                    f"{type(model).__name__}: this configuration has no training path in the HIP executor (built: every family, square and "
+                    f"rectangular inputs, up to 640 tokens incl. the class token -- this model has {model.patch_embed.num_patches + 1}; bf16); "
+                    "call model.eval() for inference")
             self.tape = torch.empty(nt, dtype=torch.uint8, device=dev)
             self.bws = torch.empty(nb, dtype=torch.uint8, device=dev)
             self.B = B
@@ -377,7 +378,7 @@ class _VitTrainFn(torch.autograd.Function):
         # require one); the executor reads xe, train_forward's detached fp32 contiguous copy of the caller's tensor (made once)
         ctx.want_dx = bool(ctx.needs_input_grad[1]) and fmt == _lib.TR_INPUT_F32 and aug is None
         ctx.x_dtype = x.dtype
-        if ctx.want_dx and not lib.tr_patch_embed_dgrad_supported(cfg.in_chans, cfg.img_size, cfg.patch, cfg.embed_dim):
+        if ctx.want_dx and not lib.tr_patch_embed_dgrad_hw_supported(cfg.in_chans, *cfg.image_hw, cfg.patch, cfg.embed_dim):
             raise NotImplementedError(
                 f"{type(model).__name__}: the input requires a gradient, but the input gradient is built for patch 16, 1 or 3 channels and "
                 f"embed_dim 128 / 192 / 384 / 768 (got patch {cfg.patch}, in_chans {cfg.in_chans}, embed_dim {cfg.embed_dim}); "
@@ -645,6 +646,9 @@ def train_forward(model, x: torch.Tensor, dense=None, levels=None):
             raise ValueError(f"the batch normalizes with (mean, std) = {x.mean_std}, the model with {model.pixel_input}: "
                              "give DeviceAugment the mean and std of model.set_pixel_input")
         aug, x = (x.table, x.noise), x.pixels
+    want = (model.patch_embed.proj.in_channels, *model.patch_embed.img_size)
+    if x.dim() != 4 or tuple(x.shape[1:]) != want:      # before any launch: the executor reads B * C * H * W elements, whatever it is given
+        raise ValueError(f"expected [B, C, H, W] = [B,{want[0]},{want[1]},{want[2]}], got {tuple(x.shape)}")
     xe, fmt, lut = model._executor_input(x)
     # an fp32-format input that takes a gradient goes through autograd as the caller's own tensor (x.grad, a module in front of the model);
     # anything else -- uint8 pixels, an augmented batch, an input without requires_grad, torch.no_grad() -- as the executor's detached

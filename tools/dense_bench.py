@@ -3,6 +3,7 @@
     python tools/dense_bench.py [--batch 256] [--steps 20] [--rounds 3] [--models deit topk tome sit dpcknn] [--fmt NCHW] [--dtype fp32]
     python tools/dense_bench.py --kernels          # the same forwards under rocprofv3 --kernel-trace --stats: the gather's bytes/s
     python tools/dense_bench.py --levels [2 5 8 11] [--no-norm] [--models deit topk tome dpcknn] [--kernels]     # profiles/dense_levels_lab.md
+    python tools/dense_bench.py --size 384 640 --levels 2 5 8 11 --models deit topk      # a rectangular input (profiles/rect_input_lab.md)
 
 Per model (DeiT-S width, 224 x 224: dense DeiT as the identity case, Top-K kr 0.7, ToMe, SiT, DPC-KNN; reduction at blocks 3 / 6 / 9) one
 JSON line with ms per batch, device events around `steps` forwards, the sides alternating within a round:
@@ -40,6 +41,7 @@ sys.path.insert(0, ROOT)
 MODELS = {"deit": "deit_small_patch16_224_local", "topk": "topk_small_patch16_224", "tome": "tome_small_patch16_224", "sit": "sit_small_patch16_224",
           "dpcknn": "dpcknn_small_patch16_224"}
 HBM_COPY_TBS = 6.29          # measured float4 copy on MI355X (8.0 TB/s on paper)
+SIZE = (224, 224)            # --size H W: the input; the factories take a pair (Top-K keeps int(ratio * 196) whatever the grid, topk.py:56)
 
 
 def _args(**kw):
@@ -54,8 +56,8 @@ def _create(tag):
     import tokenreduction_amd as tra
     torch.manual_seed(0)
     args = _args(keep_rate=[1.0], reduction_loc=[]) if tag == "deit" else _args()
-    return tra.create_model(MODELS[tag], pretrained=False, num_classes=1000, drop_rate=0.0, drop_path_rate=0.0, drop_block_rate=None, img_size=224,
-                            args=args).cuda().eval()
+    return tra.create_model(MODELS[tag], pretrained=False, num_classes=1000, drop_rate=0.0, drop_path_rate=0.0, drop_block_rate=None,
+                            img_size=SIZE[0] if SIZE[0] == SIZE[1] else SIZE, args=args).cuda().eval()
 
 
 def _event_ms(fn, steps):
@@ -141,7 +143,7 @@ def run_levels(tag, batch, steps, rounds, fmt, dtype, blocks, norm, child=False)
     m = _create(tag)
     tdtype = torch.bfloat16 if dtype == "bf16" else torch.float32
     g = torch.Generator().manual_seed(1)
-    x = torch.randn(batch, 3, 224, 224, generator=g).cuda()
+    x = torch.randn(batch, 3, *SIZE, generator=g).cuda()
     if tag == "dpcknn":
         m.density_noise = {blk: torch.rand(batch, P, generator=g).cuda() for blk, _, P in m._stage_shapes()}
     blocks = tuple(sorted(blocks))
@@ -180,7 +182,7 @@ def run_levels(tag, batch, steps, rounds, fmt, dtype, blocks, norm, child=False)
     med = {k: statistics.median(v) for k, v in ms.items()}
     out_bytes = 2 if dtype == "bf16" else 4
     tokens = [int(m._last_tokens[b]) for b in blocks]
-    print(json.dumps({"leg": "levels", "model": MODELS[tag], "B": batch, "blocks": blocks, "norm": norm, "fmt": fmt, "dtype": dtype, "steps": steps,
+    print(json.dumps({"leg": "levels", "model": MODELS[tag], "B": batch, "size": list(SIZE), "blocks": blocks, "norm": norm, "fmt": fmt, "dtype": dtype, "steps": steps,
                       "bitwise_equal": same, "level_tokens": tokens, "ms_per_batch": ms, "median_ms_per_batch": med,
                       "images_per_s": {k: round(batch / med[k] * 1e3, 1) for k in med},
                       "extra_ms_over_plain": {k: round(med[k] - med["plain"], 4) for k in ("viz", "levels")},
@@ -199,7 +201,7 @@ def run(tag, batch, steps, rounds, fmt, dtype, only_dense=False):
     m = _create(tag)
     tdtype = torch.bfloat16 if dtype == "bf16" else torch.float32
     g = torch.Generator().manual_seed(1)
-    x = torch.randn(batch, 3, 224, 224, generator=g).cuda()
+    x = torch.randn(batch, 3, *SIZE, generator=g).cuda()
     if tag == "dpcknn":
         m.density_noise = {blk: torch.rand(batch, P, generator=g).cuda() for blk, _, P in m._stage_shapes()}
     dense = lambda: m.forward_dense(x, output_fmt=fmt, dtype=tdtype, fill=0.0)
@@ -225,7 +227,7 @@ def run(tag, batch, steps, rounds, fmt, dtype, only_dense=False):
     m.check_status()
     med = {k: statistics.median(v) for k, v in ms.items()}
     P0, D = m.patch_embed.num_patches, m.embed_dim
-    print(json.dumps({"leg": "forward", "model": MODELS[tag], "B": batch, "fmt": fmt, "dtype": dtype, "steps": steps, "bitwise_equal": same,
+    print(json.dumps({"leg": "forward", "model": MODELS[tag], "B": batch, "size": list(SIZE), "fmt": fmt, "dtype": dtype, "steps": steps, "bitwise_equal": same,
                       "n_last": int(m._last_tokens[-1]), "ms_per_batch": ms, "median_ms_per_batch": med,
                       "extra_ms_over_plain": {k: round(med[k] - med["plain"], 4) for k in ("torch", "dense")},
                       "gather_required_bytes": required_bytes(batch, P0, D, 2 if dtype == "bf16" else 4),
@@ -240,8 +242,8 @@ def kernels_levels(a):
     for tag in a.models:
         with tempfile.TemporaryDirectory() as tmp:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-                   "--child", "--models", tag, "--batch", str(a.batch), "--steps", str(a.steps), "--fmt", a.fmt, "--dtype", a.dtype, "--levels",
-                   *[str(b) for b in a.levels]] + (["--no-norm"] if a.no_norm else [])
+                   "--child", "--models", tag, "--batch", str(a.batch), "--steps", str(a.steps), "--fmt", a.fmt, "--dtype", a.dtype, "--size",
+                   str(SIZE[0]), str(SIZE[1]), "--levels", *[str(b) for b in a.levels]] + (["--no-norm"] if a.no_norm else [])
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
             rows = []
             for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
@@ -263,7 +265,7 @@ def kernels_levels(a):
                     ent[col[:3].lower() + "_us"] = round(float(row[col]) / 1e3, 3)
         for ent in (v for v in out.values() if isinstance(v, dict)):
             ent["average_us"] = round(ent["total_us"] / max(1, ent["calls"]), 3)
-        need = L * required_bytes(a.batch, 196, 384, 2 if a.dtype == "bf16" else 4)
+        need = L * required_bytes(a.batch, (SIZE[0] // 16) * (SIZE[1] // 16), 384, 2 if a.dtype == "bf16" else 4)
         if "gather_levels" in out and "gather_single" in out:
             one, many = out["gather_levels"]["average_us"], out["gather_single"]["average_us"] * L
             out["gather_required_bytes"] = need
@@ -280,13 +282,14 @@ def kernels(a):
     for tag in a.models:
         with tempfile.TemporaryDirectory() as tmp:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-                   "--child", "--models", tag, "--batch", str(a.batch), "--steps", str(a.steps), "--fmt", a.fmt, "--dtype", a.dtype]
+                   "--child", "--models", tag, "--batch", str(a.batch), "--steps", str(a.steps), "--fmt", a.fmt, "--dtype", a.dtype, "--size",
+                   str(SIZE[0]), str(SIZE[1])]
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
             rows = []
             for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
                 rows += list(csv.DictReader(open(path)))
         out = {"leg": "kernels", "model": MODELS[tag], "B": a.batch, "fmt": a.fmt, "dtype": a.dtype}
-        need = required_bytes(a.batch, 196, 384, 2 if a.dtype == "bf16" else 4)
+        need = required_bytes(a.batch, (SIZE[0] // 16) * (SIZE[1] // 16), 384, 2 if a.dtype == "bf16" else 4)
         for row in rows:
             for key in ("dense_gather", "dense_index"):
                 if key in row["Name"]:
@@ -309,11 +312,13 @@ if __name__ == "__main__":
     ap.add_argument("--models", nargs="+", default=list(MODELS), choices=list(MODELS))
     ap.add_argument("--fmt", default="NCHW", choices=["NCHW", "NHWC"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--size", type=int, nargs=2, default=list(SIZE), metavar=("H", "W"), help="input height and width, multiples of 16")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--levels", type=int, nargs="*", default=None, help="the levels mode: the blocks (default 2 5 8 11)")
     ap.add_argument("--no-norm", action="store_true", help="levels mode: the rows as they stand, not their final norm")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    SIZE = tuple(a.size)
     if a.levels is not None:
         a.levels = a.levels or [2, 5, 8, 11]
         if a.models == list(MODELS):
